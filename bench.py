@@ -10,9 +10,14 @@ batch of synthetic pairs (mt19937(12345) stream).
 rh_batch_upload -> rh_batch_compute -> rh_batch_candidates_all x5 (the five threshold scans of
 src/ractip.cpp:557-647, compacted on the device, results on the host); steps alternate between two
 contexts on two host threads so that one context's PCIe legs overlap the other's kernels.  The
-device-resident rate (inputs in HBM, nothing copied back) is reported beside it.
+device-resident rate (inputs in HBM, nothing copied back) is reported beside it by a --full run.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--seqlen 500] [--batch B]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--seqlen 500] [--batch B] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  --full adds everything else this
+benchmark measures: the device-resident rate, the roofline object, dense-result rates, the other BASELINE
+configurations (`also`) and the CPU baselines.  --dump-outputs DIR writes the candidate lists of the last timed step
+(see dump_outputs) so that two builds can be compared output for output.
 
 N > 1: one process per GPU (launched by torch.distributed.run); independent pairs
 are sharded across ranks (weak scaling, the z-score shard of ractip.cpp:1638-1657)
@@ -309,7 +314,7 @@ def timed_steps(ctxs, pairs, steps, body, fence):
     def work(k0):
         try:
             for k in range(k0, steps, len(ctxs)):
-                body(ctxs[k0], pairs)
+                body(ctxs[k0], pairs, k)
         except Exception as e:   # noqa: BLE001 -- re-raised below
             err.append(e)
     fence()
@@ -327,11 +332,40 @@ def timed_steps(ctxs, pairs, steps, body, fence):
     return dt
 
 
-def step_candidates(ctx, pairs):
+def step_candidates(ctx, pairs, k=None, keep=None):
+    """One step; with `keep` (a dict), the five scans' (records, first) are stored in it under their SCAN_NAMES."""
     ctx.batch_upload(pairs)
     ctx.batch_compute()
     for which, th in SCANS:
-        ctx.batch_candidates_all(which, th)
+        rec, first = ctx.batch_candidates_all(which, th)
+        if keep is not None:   # the records are a view of a host buffer that the next scan overwrites
+            keep[SCAN_NAMES[which]] = (rec.copy(), first)
+
+
+SCAN_NAMES = ("bp1", "bp2", "hp", "up1", "up2")
+DUMP_LIMIT_BYTES = 64 * 10 ** 6 - 64 * 1024   # all .npy files of --dump-outputs together, headers included, stay under 64 MB
+
+
+def dump_outputs(out_dir, cands, logz=None, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: DIR/<scan>.npy for the five threshold scans of one step, float64 [K, 4] rows (pair, i, j, p) in the
+    order the path returns them (pair-major), and DIR/logZ.npy (float64 [pairs, 3]) when the step gathered it.  If the
+    whole exceeds `limit`, every scan keeps the same fraction of its rows, a fixed seeded sample in the original order."""
+    os.makedirs(out_dir, exist_ok=True)
+    rows = {}
+    for name in SCAN_NAMES:
+        rec, first = cands[name]
+        pair = np.repeat(np.arange(len(first) - 1), np.diff(first))
+        rows[name] = np.stack([pair, rec["i"], rec["j"], rec["p"]], axis=1).astype(np.float64)
+    fixed = logz.nbytes if logz is not None else 0
+    total = sum(a.nbytes for a in rows.values())
+    frac = min(1.0, (limit - fixed) / total) if total else 1.0
+    for name, a in rows.items():
+        if frac < 1.0:
+            m = int(len(a) * frac)
+            a = a[np.sort(np.random.default_rng(12345).choice(len(a), m, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    if logz is not None:
+        np.save(os.path.join(out_dir, "logZ.npy"), np.asarray(logz, dtype=np.float64))
 
 
 def quick_rates(ractip_amd, torch, device_index, pairs, steps, model="contrafold", hp=None):
@@ -348,7 +382,7 @@ def quick_rates(ractip_amd, torch, device_index, pairs, steps, model="contrafold
             c.batch_upload(pairs)
             c.batch_compute()
         fence = torch.cuda.synchronize
-        dt_res = timed_steps(ctxs[:1], pairs, steps, lambda c, p: c.batch_compute(), fence)
+        dt_res = timed_steps(ctxs[:1], pairs, steps, lambda c, p, k: c.batch_compute(), fence)
         ms, nl = ctxs[0].batch_timings()
         dt_e2e = timed_steps(ctxs, pairs, 2 * steps, step_candidates, fence)
         n = max(len(pairs[0][0]), len(pairs[0][1]))
@@ -386,13 +420,19 @@ def main():
                     help="contrafold: the in-tree engines (parity pinned); vienna: the default CLI path (Vienna-BL, parity unpinned)")
     ap.add_argument("--hp", default=None, choices=["duplex", "cofold"],
                     help="vienna only: hp from pf_duplex (the --duplex branch) or from the two-molecule ensemble (default branch)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="skip the extra n=2000 / z-score / Vienna-BL measurements of the default run")
+    ap.add_argument("--full", action="store_true", help="after the headline steps, also measure the device-resident rate, the roofline "
+                    "object, dense-result rates, the other BASELINE configurations and the CPU baselines (off: headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the candidate lists of the last timed step as DIR/<scan>.npy (float64, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-also", action="store_true", help="--full: skip the extra n=2000 / z-score / Vienna-BL measurements")
     ap.add_argument("--isolate", action="store_true", help="profiling runs: the sweeps of every step run one after the other (no stream overlap), so a "
                     "kernel trace of this command reports the isolated per-kernel durations that roofline.avg_launch_us measures live")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for --gpus > 1 (nccl = RCCL; gloo only for "
                     "rehearsing the multi-rank path on a one-GPU box, where all ranks share cuda:0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     import ractip_amd
@@ -465,11 +505,16 @@ def main():
 
     from ractip_amd import shard
 
-    def step(c, p):
-        step_candidates(c, p)   # host strings -> HBM, all DP kernels, the five threshold scans back on the host
+    last = {}   # --dump-outputs: what the last timed step returned
+
+    def step(c, p, k=None):
+        keep = last if args.dump_outputs and k == args.steps - 1 else None
+        step_candidates(c, p, keep=keep)   # host strings -> HBM, all DP kernels, the five threshold scans back on the host
         if dist is not None:    # the shard's only exchange: per-pair scalars to every rank (ractip.cpp:1655-1663)
-            shard.gather_in_order(c.batch_logz(), total_per_step, dist,
-                                  device=torch.device("cuda", device_index) if args.backend == "nccl" else None)
+            logz = shard.gather_in_order(c.batch_logz(), total_per_step, dist,
+                                         device=torch.device("cuda", device_index) if args.backend == "nccl" else None)
+            if keep is not None:
+                keep["logZ"] = logz
 
     def fence():
         if dist is not None:
@@ -483,26 +528,23 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device="cuda" if args.backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last, last.get("logZ"))
 
-    # device-resident rate (inputs in HBM, nothing copied back): one context, the same number of steps
-    ms_acc = np.zeros(4)
-    nl = [0, 0, 0]
+    if args.full:
+        # device-resident rate (inputs in HBM, nothing copied back): one context, the same number of steps
+        ms_acc = np.zeros(4)
+        nl = [0, 0, 0]
 
-    def resident(c, p):
-        nonlocal nl
-        c.batch_compute()
-        ms, nl = c.batch_timings()
-        ms_acc[:] += np.array(ms)
-    dt_res = timed_steps(ctxs[:1], pairs, args.steps, resident, fence)
+        def resident(c, p, k):
+            nonlocal nl
+            c.batch_compute()
+            ms, nl = c.batch_timings()
+            ms_acc[:] += np.array(ms)
+        dt_res = timed_steps(ctxs[:1], pairs, args.steps, resident, fence)
 
     if rank == 0:
         total_pairs = total_per_step * args.steps
-        roof = measure_roofline(ctx, pairs, args.model, n, batch, vienna, cofold, args.hp, dt_res / args.steps * 1e3, torch, world == 1)
-        if args.isolate:
-            ctx.set_overlap(False)
-        ms_mean = ms_acc / args.steps  # HIP-event ms per step inside the device-resident loop: inside sweep, outside sweep, duplex, whole
-        roof["phases_in_loop"] = {"mccaskill_inside_ms": float(ms_mean[0]), "mccaskill_outside_ms": float(ms_mean[1]), "duplex_ms": float(ms_mean[2]),
-                                  "launches": [int(x) for x in nl], "note": "the duplex stream overlaps the McCaskill stream here"}
         line = {
             "metric": ("sequence-pairs/sec (incl. bp+hp+ap DP; host strings in, thresholded matrices out) at n=%d" % n) if args.workload == "pairs"
                       else "z-score DP stage: shuffled pairs/sec (OxyS/fhlA, bp+hp+ap DP per shuffle; host strings in, thresholded matrices out)",
@@ -517,8 +559,6 @@ def main():
             "vs_baseline": None,
             "dtype": "f64",
             "data": "synthetic",
-            "device_resident_pairs_per_s": len(pairs) * args.steps / dt_res,
-            "device_resident_ms_per_step": dt_res / args.steps * 1e3,
             "config": {"workload": ("synthetic random pairs n=%d/%d, std::mt19937(12345) stream (BASELINE config %s)"
                                     % (n, n, "3" if n == 500 else ("4" if n == 2000 else "-"))) if args.workload == "pairs"
                                    else "OxyS.fa (109) vs fhlA.fa (113), --zscore=12 --seed=1 dinucleotide shuffles (BASELINE config 5, DP stage)",
@@ -529,49 +569,58 @@ def main():
                        "scoring": ("Vienna-BL (BL* tables, ViennaRNA-1.8 semantics, up width 15, hp from %s; parity unpinned)"
                                    % ("co_pf_fold(s1+s2)" if cofold else "pf_duplex")) if vienna
                                   else "CONTRAfold complementary (708 weights)"},
-            "roofline": roof,
         }
-        if world == 1:
-            # dense results instead of the thresholded lists: all five matrices into page-locked host buffers, two contexts
-            bufs = {}
+        if args.full:
+            roof = measure_roofline(ctx, pairs, args.model, n, batch, vienna, cofold, args.hp, dt_res / args.steps * 1e3, torch, world == 1)
+            if args.isolate:
+                ctx.set_overlap(False)
+            ms_mean = ms_acc / args.steps  # HIP-event ms per step inside the device-resident loop: inside sweep, outside sweep, duplex, whole
+            roof["phases_in_loop"] = {"mccaskill_inside_ms": float(ms_mean[0]), "mccaskill_outside_ms": float(ms_mean[1]), "duplex_ms": float(ms_mean[2]),
+                                      "launches": [int(x) for x in nl], "note": "the duplex stream overlaps the McCaskill stream here"}
+            line["device_resident_pairs_per_s"] = len(pairs) * args.steps / dt_res
+            line["device_resident_ms_per_step"] = dt_res / args.steps * 1e3
+            line["roofline"] = roof
+            if world == 1:
+                # dense results instead of the thresholded lists: all five matrices into page-locked host buffers, two contexts
+                bufs = {}
 
-            def step_dense(c, p):
-                c.batch_upload(p)
-                c.batch_compute()
-                bufs[id(c)] = c.batch_results_all_into(bufs.get(id(c)))
+                def step_dense(c, p, k=None):
+                    c.batch_upload(p)
+                    c.batch_compute()
+                    bufs[id(c)] = c.batch_results_all_into(bufs.get(id(c)))
+                for c in ctxs:
+                    step_dense(c, pairs)
+                k_dense = max(2, min(args.steps, 6))
+                dt_dense = timed_steps(ctxs, pairs, k_dense, step_dense, fence)
+                line["pcie_inclusive"] = {"threshold_candidates_pairs_per_s": line["value"],
+                                          "dense_results_pairs_per_s": len(pairs) * k_dense / dt_dense,
+                                          "dense_GB_per_step": sum(a.nbytes for a in bufs[id(ctx)]) / 1e9}
             for c in ctxs:
-                step_dense(c, pairs)
-            k_dense = max(2, min(args.steps, 6))
-            dt_dense = timed_steps(ctxs, pairs, k_dense, step_dense, fence)
-            line["pcie_inclusive"] = {"threshold_candidates_pairs_per_s": line["value"],
-                                      "dense_results_pairs_per_s": len(pairs) * k_dense / dt_dense,
-                                      "dense_GB_per_step": sum(a.nbytes for a in bufs[id(ctx)]) / 1e9}
-        for c in ctxs:
-            c.close()
-        ctxs = []
-        if world == 1 and not args.no_also and args.workload == "pairs" and n == 500 and not vienna:
-            # the other BASELINE configurations, bounded to a few seconds each: config 4 (n = 2000) and config 5 (z-score DP stage)
-            also = {}
-            try:
-                also["n2000"] = quick_rates(ractip_amd, torch, device_index, random_pairs(64, 2000, seed=12345), 3)   # 64 pairs: ~60 GB of tables per context
-                from ractip_amd import shard as _shard
-                fa = [l.strip() for l in open(os.path.join(ROOT, "ractip_amd", "data", "config5_OxyS_fhlA.fa")) if not l.startswith(">")]
-                also["zscore_1000_shuffles"] = quick_rates(ractip_amd, torch, device_index, _shard.zscore_shuffles(fa[0], fa[1], 12, 1000, 1), 10)
-                # the reference's DEFAULT path (Vienna-BL model, parity unpinned): rnafold x2 + accessibility + hp from co_pf_fold / pf_duplex
-                also["vienna_n500_cofold"] = quick_rates(ractip_amd, torch, device_index, random_pairs(256, 500, seed=12345), 3, model="vienna", hp="cofold")
-                also["vienna_n500_duplex"] = quick_rates(ractip_amd, torch, device_index, random_pairs(256, 500, seed=12345), 3, model="vienna", hp="duplex")
-            except Exception as e:   # noqa: BLE001 -- the headline line must still be printed
-                also["error"] = repr(e)
-            line["also"] = also
-        if world == 1 and not args.no_cpu_baseline:
-            if vienna:
-                line["cpu_baseline"] = cpu_baseline_vienna(all_pairs, budget_s=12.0 if n <= 600 else 1.0, cofold=cofold)
+                c.close()
+            ctxs = []
+            if world == 1 and not args.no_also and args.workload == "pairs" and n == 500 and not vienna:
+                # the other BASELINE configurations, bounded to a few seconds each: config 4 (n = 2000) and config 5 (z-score DP stage)
+                also = {}
+                try:
+                    also["n2000"] = quick_rates(ractip_amd, torch, device_index, random_pairs(64, 2000, seed=12345), 3)   # 64 pairs: ~60 GB of tables per context
+                    from ractip_amd import shard as _shard
+                    fa = [l.strip() for l in open(os.path.join(ROOT, "ractip_amd", "data", "config5_OxyS_fhlA.fa")) if not l.startswith(">")]
+                    also["zscore_1000_shuffles"] = quick_rates(ractip_amd, torch, device_index, _shard.zscore_shuffles(fa[0], fa[1], 12, 1000, 1), 10)
+                    # the reference's DEFAULT path (Vienna-BL model, parity unpinned): rnafold x2 + accessibility + hp from co_pf_fold / pf_duplex
+                    also["vienna_n500_cofold"] = quick_rates(ractip_amd, torch, device_index, random_pairs(256, 500, seed=12345), 3, model="vienna", hp="cofold")
+                    also["vienna_n500_duplex"] = quick_rates(ractip_amd, torch, device_index, random_pairs(256, 500, seed=12345), 3, model="vienna", hp="duplex")
+                except Exception as e:   # noqa: BLE001 -- the headline line must still be printed
+                    also["error"] = repr(e)
+                line["also"] = also
+            if world == 1 and not args.no_cpu_baseline:
+                if vienna:
+                    line["cpu_baseline"] = cpu_baseline_vienna(all_pairs, budget_s=12.0 if n <= 600 else 1.0, cofold=cofold)
+                else:
+                    line["cpu_baseline"] = cpu_baseline(all_pairs, budget_s=12.0 if n <= 600 else 1.0)
+                if n <= 600 and args.workload == "pairs":
+                    line["cpu_baseline_all_cores"] = cpu_baseline_all_cores(n, vienna, cofold, per_worker=1 if vienna and cofold else 2)
             else:
-                line["cpu_baseline"] = cpu_baseline(all_pairs, budget_s=12.0 if n <= 600 else 1.0)
-            if n <= 600 and args.workload == "pairs":
-                line["cpu_baseline_all_cores"] = cpu_baseline_all_cores(n, vienna, cofold, per_worker=1 if vienna and cofold else 2)
-        else:
-            line["cpu_baseline"] = None
+                line["cpu_baseline"] = None
         print(json.dumps(line), flush=True)
     if dist is not None:
         dist.barrier()

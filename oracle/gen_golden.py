@@ -46,6 +46,27 @@ if os.environ.get("GOLDEN_ONLY") == "2000b":   # add this block to the existing 
     print("updated", os.path.normpath(dst), os.path.getsize(dst), "bytes")
     sys.exit(0)
 
+if os.environ.get("GOLDEN_ONLY") == "oracle_check":
+    # tests/golden/reference_check.npz: the reference's outputs on the seeded inputs of
+    # tests/test_oracle.py::test_oracle_vs_reference_engines_if_built, so that it runs where oracle/_ref cannot be built
+    out = {}
+    rng = np.random.RandomState(7)
+    for n in (1, 2, 6, 9, 23, 51, 77):
+        seq = "".join(rng.choice(list("ACGU"), n))
+        post = np.zeros((n + 1) * (n + 2) // 2)
+        out["mc/%d/seq" % n] = np.array(seq)
+        out["mc/%d/logZ" % n] = np.array(lib.ref_inference(seq.encode(), 0, post.ctypes.data, None, None))
+        out["mc/%d/post" % n] = post
+    s1 = "".join(rng.choice(list("ACGU"), 37))
+    s2 = "".join(rng.choice(list("ACGU"), 58))
+    post, z2 = np.zeros((len(s1) + 1) * (len(s2) + 1)), np.zeros(2)
+    lib.ref_duplex(s1.encode(), s2.encode(), 0, post.ctypes.data, None, None, z2.ctypes.data)
+    out.update({"dx/s1": np.array(s1), "dx/s2": np.array(s2), "dx/logZ2": z2, "dx/post": post.reshape(len(s1) + 1, len(s2) + 1)})
+    dst = os.path.join(here, "..", "tests", "golden", "reference_check.npz")
+    np.savez_compressed(dst, **out)
+    print("wrote", os.path.normpath(dst), os.path.getsize(dst), "bytes")
+    sys.exit(0)
+
 
 def fasta(path):
     return "".join(l.strip() for l in open(path) if not l.startswith(">"))

@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -19,7 +20,7 @@ def last_json(stdout):
 
 def test_single_gpu_line(hotlib):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--n", "120", "--batch", "8", "--steps", "2",
-                        "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600)
+                        "--warmup", "1", "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = last_json(r.stdout)
     for k in REQUIRED:
@@ -47,6 +48,31 @@ def test_single_gpu_line(hotlib):
     # value is the end-to-end quantity (upload -> compute -> 5 scans on the host); the device-resident rate sits beside it
     assert d["device_resident_pairs_per_s"] > 0 and "rh_batch_upload" in d["config"]["step"]
     assert d["pcie_inclusive"]["dense_results_pairs_per_s"] > 0
+
+
+def test_plain_line_and_dump_outputs(hotlib, tmp_path):
+    """Without --full the line carries the headline only; --dump-outputs writes the five candidate lists of the last timed
+    step as float64 rows (pair, i, j, p), every p above its scan's threshold."""
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--n", "120", "--batch", "8", "--steps", "3",
+                        "--warmup", "1", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = last_json(r.stdout)
+    assert d["steps"] == 3 and d["unit"] == "pairs/s" and d["dtype"] == "f64" and d["higher_is_better"] is True
+    assert abs(d["value"] - 8 * 1e3 / d["ms_per_step"]) < 1e-9 * d["value"]
+    for k in ("roofline", "cpu_baseline", "also", "pcie_inclusive", "device_resident_pairs_per_s"):
+        assert k not in d, k
+    sys.path.insert(0, ROOT)
+    import bench
+    rows = 0
+    for (which, th), name in zip(bench.SCANS, bench.SCAN_NAMES):
+        a = np.load(out / (name + ".npy"))
+        assert a.dtype == np.float64 and a.ndim == 2 and a.shape[1] == 4, name
+        assert (a[:, 0] >= 0).all() and (a[:, 0] < 8).all() and (np.diff(a[:, 0]) >= 0).all(), name
+        assert (a[:, 3] > np.float32(th)).all() and (a[:, 3] <= 1.0 + 1e-6).all(), name
+        rows += len(a)
+    assert rows > 0 and len(np.load(out / "up1.npy")) > 0
+    assert sorted(os.listdir(out)) == sorted(n + ".npy" for n in bench.SCAN_NAMES)
 
 
 def test_traffic_entries_are_bound_to_the_kernel_sources():
@@ -78,7 +104,7 @@ def test_zscore_strong_scaling_line(hotlib):
 
 def test_vienna_model_line(hotlib):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--model", "vienna", "--n", "100", "--batch", "4",
-                        "--steps", "2", "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600)
+                        "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = last_json(r.stdout)
     assert d["value"] > 0 and "Vienna-BL" in d["config"]["scoring"] and d["roofline"]["kernel"].startswith(("vlin_", "dxv_"))
@@ -89,7 +115,7 @@ def test_two_ranks_on_one_gpu_gloo(hotlib):
     port = 29700 + os.getpid() % 200
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--seqlen", "120",
-           "--batch", "8", "--steps", "2", "--warmup", "1"]
+           "--batch", "8", "--steps", "2", "--warmup", "1", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = last_json(r.stdout)

@@ -4,7 +4,6 @@ in this tree -- directly against those engines."""
 import os
 
 import numpy as np
-import pytest
 
 from _oracle import NEG, Reference, assert_log_close, assert_prob_close, tri_offset, tri_size
 
@@ -55,21 +54,28 @@ def test_oracle_n500_vs_golden(oracle, golden):
 
 
 def test_oracle_vs_reference_engines_if_built(oracle):
+    """The reference engines' outputs on seeded inputs: as stored in tests/golden/reference_check.npz (oracle/gen_golden.py,
+    GOLDEN_ONLY=oracle_check), and live as well where oracle/_ref has been built in this tree."""
+    stored = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_check.npz"), allow_pickle=False)
     try:
-        ref = Reference()
+        live = [Reference()]
     except (FileNotFoundError, OSError):
-        pytest.skip("oracle/_ref not built in this tree (reference sources absent)")
+        live = []
     rng = np.random.RandomState(7)
     for n in (1, 2, 6, 9, 23, 51, 77):
         seq = "".join(rng.choice(list("ACGU"), n))
-        a, b = oracle.inference(seq), ref.inference(seq)
-        assert abs(a["logZ"] - b["logZ"]) < 1e-10
-        assert_prob_close(a["post"], b["post"], rel=1e-9, what="n=%d" % n)
+        assert str(stored["mc/%d/seq" % n]) == seq
+        a = oracle.inference(seq)
+        for b in [{"logZ": float(stored["mc/%d/logZ" % n]), "post": stored["mc/%d/post" % n]}] + [r.inference(seq) for r in live]:
+            assert abs(a["logZ"] - b["logZ"]) < 1e-10
+            assert_prob_close(a["post"], b["post"], rel=1e-9, what="n=%d" % n)
     s1 = "".join(rng.choice(list("ACGU"), 37))
     s2 = "".join(rng.choice(list("ACGU"), 58))
-    a, b = oracle.duplex(s1, s2), ref.duplex(s1, s2)
-    assert_log_close(a["logZ2"], b["logZ2"], tol=1e-10)
-    assert_prob_close(a["post"], b["post"], rel=1e-9)
+    assert str(stored["dx/s1"]) == s1 and str(stored["dx/s2"]) == s2
+    a = oracle.duplex(s1, s2)
+    for b in [{"logZ2": stored["dx/logZ2"], "post": stored["dx/post"]}] + [r.duplex(s1, s2) for r in live]:
+        assert_log_close(a["logZ2"], b["logZ2"], tol=1e-10)
+        assert_prob_close(a["post"], b["post"], rel=1e-9)
 
 
 def test_oracle_edge_cases(oracle):

@@ -12,7 +12,7 @@ P2="SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM SQ_INSTS_VMEM_RD SQ_W
 i=0
 for P in "$P1" "$P2"; do
   i=$((i+1))
-  RH_NO_GRAPH=1 rocprofv3 --pmc $P -d $OUT/${TAG}_sq$i -o ${TAG}_sq$i --output-format csv -- python3 $ROOT/bench.py "$@" --steps 1 --warmup 1 --no-cpu-baseline > $OUT/${TAG}_sq$i.log 2>&1 || { tail -5 $OUT/${TAG}_sq$i.log; exit 1; }
+  RH_NO_GRAPH=1 rocprofv3 --pmc $P -d $OUT/${TAG}_sq$i -o ${TAG}_sq$i --output-format csv -- python3 $ROOT/bench.py "$@" --steps 1 --warmup 1 --full --no-cpu-baseline > $OUT/${TAG}_sq$i.log 2>&1 || { tail -5 $OUT/${TAG}_sq$i.log; exit 1; }
   python3 $ROOT/tools/pmc_summary.py $OUT/${TAG}_sq$i >> $OUT/${TAG}_pmc_sq.txt
   rm -rf $OUT/${TAG}_sq$i
 done

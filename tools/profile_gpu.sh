@@ -15,10 +15,10 @@ mkdir -p $OUT
 MODEL=$(echo $KEY | sed 's/_n.*//'); N=$(echo $KEY | sed 's/.*_n\([0-9]*\)_b.*/\1/'); BATCH=$(echo $KEY | sed 's/.*_b\([0-9]*\).*/\1/')
 HP=""; case "$KEY" in *duplex*) HP="--hp duplex";; esac
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_trace -o ${TAG} -- python3 $ROOT/bench.py "$@" --isolate --no-cpu-baseline > $OUT/${TAG}_bench.log 2>&1 || { tail -5 $OUT/${TAG}_bench.log; exit 1; }
+rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_trace -o ${TAG} -- python3 $ROOT/bench.py "$@" --full --isolate --no-cpu-baseline > $OUT/${TAG}_bench.log 2>&1 || { tail -5 $OUT/${TAG}_bench.log; exit 1; }
 grep '^{' $OUT/${TAG}_bench.log | tail -1 > $OUT/${TAG}_bench_under_rocprof.json
 DB=$(ls $OUT/${TAG}_trace/*/*.db $OUT/${TAG}_trace/*.db 2>/dev/null | head -1)
-python3 $ROOT/tools/rocprof_summary.py "$DB" "bench.py $* --isolate --no-cpu-baseline" > $OUT/${TAG}_kernel_stats.txt
+python3 $ROOT/tools/rocprof_summary.py "$DB" "bench.py $* --full --isolate --no-cpu-baseline" > $OUT/${TAG}_kernel_stats.txt
 rm -rf $OUT/${TAG}_trace
 : > $OUT/${TAG}_pmc_traffic.txt
 COMPUTES=3

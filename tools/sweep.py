@@ -5,7 +5,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def run(env, args):
     e = dict(os.environ); e.update(env)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline"] + args,
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline"] + args,
                          env=e, capture_output=True, text=True, timeout=600)
     line = [l for l in out.stdout.split("\n") if l.startswith("{")]
     if not line:
