@@ -3,6 +3,8 @@ been built in this tree, the reference engines (oracle/_ref/libref_contrafold.so
 import ctypes
 import os
 import subprocess
+import threading
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -276,3 +278,116 @@ class ViennaOracle:
         pr = np.zeros((len(s1) + 1, len(s2) + 1))
         z = self.L.vo_bruteforce(self.m, s1.encode(), len(s1), s2.encode(), len(s2), pr.ctypes.data)
         return dict(logZ=z, pr=pr)
+
+
+ORACLE_WORKERS = 8   # threads of OraclePool: a fixed number, never sized by the machine's CPU count
+
+
+class OraclePool:
+    """Memoised oracle calls on a small thread pool.  The ctypes calls release the GIL, so up to `workers` of them run at once.
+    Every method returns a Future, keyed by its inputs (a sequence, or a pair for the two-sequence calls): asking twice costs one
+    call, and asking early lets the oracle run while the GPU computes.  Only unconstrained Vienna calls go to the threads:
+    vienna_oracle.c keeps the allowed-pair mask in one global (vo_allow_mask)."""
+
+    def __init__(self, workers=ORACLE_WORKERS):
+        self.cf = Oracle()
+        self.vo = ViennaOracle()
+        self.pool = ThreadPoolExecutor(max_workers=min(workers, ORACLE_WORKERS))
+        self.cache = {}
+        self.lock = threading.Lock()
+
+    def _get(self, key, fn, *args):
+        with self.lock:
+            f = self.cache.get(key)
+            if f is None:
+                f = self.cache[key] = self.pool.submit(fn, *args)
+        return f
+
+    def inference(self, seq):
+        return self._get(("cf", seq), self.cf.inference, seq)
+
+    def duplex(self, s1, s2):
+        return self._get(("cf-dx", s1, s2), self.cf.duplex, s1, s2)
+
+    def mccaskill(self, seq, max_w=15):
+        return self._get(("vo", seq, max_w), self.vo._mccaskill, seq, max_w, False)
+
+    def cofold(self, s1, s2):
+        return self._get(("vo-co", s1, s2), self.vo._cofold, s1, s2)
+
+    def pf_duplex(self, s1, s2):
+        return self._get(("vo-dx", s1, s2), self.vo.pf_duplex, s1, s2)
+
+    def close(self):
+        self.pool.shutdown(wait=True)
+
+
+def check_pair_properties(s1, s2, r):
+    """Size-independent properties of one pair's results: probabilities in [0,1], every letter pairs with total probability
+    <= 1, up = 1 - row sums, hp row/column sums <= 1, nothing lands on non-complementary letters."""
+    for s, bp, up in ((s1, r["bp1"], r["up1"]), (s2, r["bp2"], r["up2"])):
+        n = len(s)
+        assert np.isfinite(bp).all() and bp.min() >= 0.0 and bp.max() <= 1.0
+        P = np.zeros((n + 1, n + 1))
+        iu = np.triu_indices(n + 1, 0)
+        P[iu] = bp  # reference triangular layout == row-major upper triangle incl. diagonal
+        assert P[0].max() == 0.0 and np.diag(P).max() == 0.0
+        rows = (P + P.T).sum(axis=1)[1:]
+        assert rows.max() <= 1.0 + 1e-9
+        assert np.abs(up - np.maximum(0.0, 1.0 - rows)).max() < 1e-12
+        codes = np.array(["ACGU".index(c) for c in s])
+        ok = np.zeros((4, 4), bool)
+        for x, y in ((0, 3), (3, 0), (1, 2), (2, 1), (2, 3), (3, 2)):
+            ok[x, y] = True
+        bad = ~ok[codes[:, None], codes[None, :]]
+        assert P[1:, 1:][bad & (P[1:, 1:] > 0)].size == 0
+    hp = r["hp"]
+    assert np.isfinite(hp).all() and hp.min() >= 0 and hp.max() <= 1
+    assert hp[0].max() == 0 and hp[:, 0].max() == 0
+    assert hp.sum(axis=1).max() <= 1 + 1e-9 and hp.sum(axis=0).max() <= 1 + 1e-9
+
+
+def check_n2000_golden(r, golden):
+    """The reference's log Z and sparse posteriors of the mt19937(12345) n=2000 pair (oracle/gen_golden.py), on its batch results."""
+    rel = 1e-6
+    assert abs(r["logZ"][0] - float(golden["mc2000/logZ"])) < 1e-7
+    assert abs(r["bp1"].sum() - float(golden["mc2000/post_sum"])) < 1e-5
+    assert_prob_close(r["bp1"][golden["mc2000/idx"]], golden["mc2000/val"], rel=rel, what="bp n=2000")
+    assert abs(r["logZ"][2] - golden["dx2000/logZ2"][0]) < 1e-6
+    hp = r["hp"].ravel()
+    assert abs(hp.sum() - float(golden["dx2000/post_sum"])) < 1e-5
+    assert_prob_close(hp[golden["dx2000/idx"]], golden["dx2000/val"], rel=rel, what="hp n=2000")
+    # the second sequence of the pair (oracle/gen_golden.py, GOLDEN_ONLY=2000b)
+    assert abs(r["logZ"][1] - float(golden["mc2000b/logZ"])) < 1e-7
+    assert abs(r["bp2"].sum() - float(golden["mc2000b/post_sum"])) < 1e-5
+    assert_prob_close(r["bp2"][golden["mc2000b/idx"]], golden["mc2000b/val"], rel=rel, what="bp2 n=2000")
+
+
+def threshold_scans(r, which_th):
+    """The reference's threshold scans (ractip.cpp:557-568, 578-589, 598-608, 621-627) over one pair's dense results, in the
+    record form of rh_batch_candidates_all: (i, j, p) with p narrowed to float, p > threshold in float, row-major order.
+    which: 0 / 1 bp1 / bp2 (1 <= i < j <= n), 2 hp (1 <= i <= n1, 1 <= j <= n2), 3 / 4 up1 / up2 at width 1 (i 0-based, j = 0)."""
+    which, th = which_th
+    th = np.float32(th)
+    if which <= 1:
+        bp = r["bp1" if which == 0 else "bp2"]
+        n = int(round((np.sqrt(8 * len(bp) + 1) - 3) / 2))
+        P = np.zeros((n + 1, n + 1), dtype=np.float32)
+        P[np.triu_indices(n + 1, 0)] = bp.astype(np.float32)
+        hit = np.triu(P > th, 1)
+        hit[0] = False
+        i, j = np.nonzero(hit)
+        p = P[i, j]
+    elif which == 2:
+        H = np.asarray(r["hp"]).astype(np.float32)
+        hit = H > th
+        hit[0] = False
+        hit[:, 0] = False
+        i, j = np.nonzero(hit)
+        p = H[i, j]
+    else:
+        u = np.asarray(r["up1" if which == 3 else "up2"]).astype(np.float32).ravel()
+        i = np.flatnonzero(u > th)
+        j = np.zeros_like(i)
+        p = u[i]
+    return i.astype(np.int64), j.astype(np.int64), p

@@ -7,7 +7,7 @@ log-partition values within 1e-9 absolute (log units)."""
 import numpy as np
 import pytest
 
-from _oracle import NEG, assert_log_close, assert_prob_close, tri_offset, tri_size
+from _oracle import NEG, assert_log_close, assert_prob_close, check_n2000_golden, check_pair_properties, tri_offset, tri_size
 from ractip_amd.seqgen import random_pair, random_pairs
 
 pytestmark = pytest.mark.gpu
@@ -134,38 +134,16 @@ def test_properties_full_size(ctx):
     """n=500 batch and one n=2000 pair (BASELINE.json configs 3 and 4): size-independent checks --
     probabilities in [0,1], every letter pairs with total probability <= 1, up = 1 - row sums,
     hp row/column sums <= 1, nothing lands on non-complementary letters."""
-    def check(s1, s2, r):
-        for s, bp, up in ((s1, r["bp1"], r["up1"]), (s2, r["bp2"], r["up2"])):
-            n = len(s)
-            assert np.isfinite(bp).all() and bp.min() >= 0.0 and bp.max() <= 1.0
-            P = np.zeros((n + 1, n + 1))
-            iu = np.triu_indices(n + 1, 0)
-            P[iu] = bp  # reference triangular layout == row-major upper triangle incl. diagonal
-            assert P[0].max() == 0.0 and np.diag(P).max() == 0.0
-            rows = (P + P.T).sum(axis=1)[1:]
-            assert rows.max() <= 1.0 + 1e-9
-            assert np.abs(up - np.maximum(0.0, 1.0 - rows)).max() < 1e-12
-            codes = np.array(["ACGU".index(c) for c in s])
-            ok = np.zeros((4, 4), bool)
-            for x, y in ((0, 3), (3, 0), (1, 2), (2, 1), (2, 3), (3, 2)):
-                ok[x, y] = True
-            bad = ~ok[codes[:, None], codes[None, :]]
-            assert P[1:, 1:][bad & (P[1:, 1:] > 0)].size == 0
-        hp = r["hp"]
-        assert np.isfinite(hp).all() and hp.min() >= 0 and hp.max() <= 1
-        assert hp[0].max() == 0 and hp[:, 0].max() == 0
-        assert hp.sum(axis=1).max() <= 1 + 1e-9 and hp.sum(axis=0).max() <= 1 + 1e-9
-
     pairs = random_pairs(4, 500)
     ctx.batch_upload(pairs)
     ctx.batch_compute()
     for p, (s1, s2) in enumerate(pairs):
-        check(s1, s2, ctx.batch_results(p))
+        check_pair_properties(s1, s2, ctx.batch_results(p))
     s1, s2 = random_pair(2000)
     ctx.batch_upload([(s1, s2)])
     ctx.batch_compute()
     r = ctx.batch_results(0)
-    check(s1, s2, r)
+    check_pair_properties(s1, s2, r)
     assert abs(r["logZ"][0] - 258.796119) < 1e-5  # SURVEY 8c known answer, InferenceEngine<double>, n=2000
 
 
@@ -176,18 +154,7 @@ def test_n2000_vs_golden(ctx, golden):
     s1, s2 = random_pair(2000)
     ctx.batch_upload([(s1, s2)])
     ctx.batch_compute()
-    r = ctx.batch_results(0)
-    assert abs(r["logZ"][0] - float(golden["mc2000/logZ"])) < 1e-7
-    assert abs(r["bp1"].sum() - float(golden["mc2000/post_sum"])) < 1e-5
-    assert_prob_close(r["bp1"][golden["mc2000/idx"]], golden["mc2000/val"], rel=REL, what="bp n=2000")
-    assert abs(r["logZ"][2] - golden["dx2000/logZ2"][0]) < 1e-6
-    hp = r["hp"].ravel()
-    assert abs(hp.sum() - float(golden["dx2000/post_sum"])) < 1e-5
-    assert_prob_close(hp[golden["dx2000/idx"]], golden["dx2000/val"], rel=REL, what="hp n=2000")
-    # the second sequence of the pair (oracle/gen_golden.py, GOLDEN_ONLY=2000b)
-    assert abs(r["logZ"][1] - float(golden["mc2000b/logZ"])) < 1e-7
-    assert abs(r["bp2"].sum() - float(golden["mc2000b/post_sum"])) < 1e-5
-    assert_prob_close(r["bp2"][golden["mc2000b/idx"]], golden["mc2000b/val"], rel=REL, what="bp2 n=2000")
+    check_n2000_golden(ctx.batch_results(0), golden)
 
 
 def test_linear_path_is_taken_and_falls_back_on_overflow(ctx, oracle):
