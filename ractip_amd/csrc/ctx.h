@@ -1,0 +1,299 @@
+// ctx.h -- the context behind the opaque rh_ctx of include/ractip_hot.h, its device buffers, and the host functions
+// the units of the library share (namespace rh::host).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../include/ractip_hot.h"
+#include "batch.h"
+#include "score_model.h"
+#include "lin_model.h"
+#include "vienna_model.h"
+
+struct rh_ctx;
+
+namespace rh::host {
+
+// grow-only device buffer: freed by its destructor, grown by ensure() (free-then-malloc when too small)
+struct DevBuf {
+    void* p = nullptr;
+    size_t cap = 0;   // bytes
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    template <class T> T* as() const { return static_cast<T*>(p); }
+    explicit operator bool() const { return p != nullptr; }
+};
+
+// one model struct (or weight table) in HBM, allocated once at its exact size
+template <class T>
+struct DevObj : DevBuf {
+    operator T*() const { return as<T>(); }
+    hipError_t upload(const T* host, size_t count = 1)
+    {
+        hipError_t e = hipMalloc(&p, sizeof(T) * count);
+        if (e != hipSuccess) return e;
+        cap = sizeof(T) * count;
+        return hipMemcpy(p, host, cap, hipMemcpyHostToDevice);
+    }
+};
+
+// CONTRAfold linear path: the model at one scale exponent -- host copy, device copy and the transposed, zero-padded single-branch
+// weights wT[l1][t+1] of the strip kernels.  rh_ctx::lin points at the one the next launches use.
+struct LinSet {
+    LinModel h;
+    DevObj<LinModel> d;
+    DevObj<double> wT;
+};
+
+// Vienna-BL linear path: the model at one scale exponent (built on first use, see select_vlin)
+struct VLinSet {
+    VLinModel* h = nullptr;
+    DevObj<VLinModel> d;
+    ~VLinSet() { delete h; }
+};
+
+struct GraphSlot {   // one captured launch sequence (see run_graphed)
+    hipGraphExec_t exec = nullptr;
+    size_t key = 0;
+    int launches = 0, far = 0;
+};
+
+struct Ctx {   // (the fields of rh_ctx, below)
+    int device = 0;
+    int model = 0;
+    std::string err;
+    hipStream_t s_mc = nullptr, s_dx = nullptr;
+    hipEvent_t ev[6] = {};  // mc: start, after inside, after outside ; dx: start, end ; all: end
+    DevObj<ScoreModel> d_model;
+    // other scale exponents of the linear McCaskill path, tried on the problems that leave the double range before the log-space
+    // kernels are (retry_mc_lin_rungs): built on first use from the host copy of the score model
+    static constexpr int kRungs = 3;
+    ScoreModel* h_score = nullptr;
+    LinSet* lin_r = nullptr;                   // [kRungs]
+    int scale_ladder = 1;                      // RH_SCALE_LADDER=0: flagged problems go straight to the log-space kernels
+    int scale_memory = 0;                      // rh_set_scale_memory / RH_SCALE_MEMORY=1: the next batch starts on the exponent most of the last one needed
+                                               // (off by default: a sequence's bits then depend on its own letters only, never on the context's history)
+    // the default exponent's model, the model the next launches use (&lin0 unless a pass runs on a rung: "run on rung k" is
+    // lin = &lin_r[k], and lin = &lin0 afterwards) and the exponent the NEXT batch starts with: -1 = default, k = rung k -- the one
+    // that held more than half of the last batch (a stream of structured RNAs does not pay a failed first pass per batch)
+    LinSet lin0;
+    const LinSet* lin = &lin0;
+    int lin_primary = -1;
+    int rescued_by[kRungs + 1] = {0, 0, 0, 0};  // sequences the last ladder moved to the default exponent [0] / rung k [k + 1]
+    std::vector<int> rescaled_mc;              // sequences the last compute recomputed on the linear path with another exponent (rh_batch_fallbacks which = 2)
+    DevObj<ViennaDx> d_vienna;     // RH_MODEL_VIENNA_BL only
+    int vienna_sem = 0;            // kViennaSem18 / kViennaSem20 (0: CONTRAfold model)
+    VLinModel* d_vlin = nullptr;   // the same model in scaled linear space: the selected entry of vlin_m (not owned)
+    VLinModel* h_vlin = nullptr;
+    // Vienna-BL: other scale exponents of the linear path, tried on the WHOLE batch (single-molecule folds and two-molecule sweeps
+    // together: the latter are seeded from the former) before the log-space kernels; see compute().  Model -1 = the default exponent.
+    static constexpr int kVRungs = 3;
+    ViennaDx* h_vienna = nullptr;              // host copy of the energy tables the rung models are built from
+    VLinSet vlin_m[kVRungs + 1];     // [0] = default, [k + 1] = rung k (owners)
+    int vlin_cur = -1, vlin_primary = -1;      // model selected now / the one a batch starts with
+    bool defer_log = false, deferred = false;  // compute_once: a flagged problem ends the attempt instead of starting the log-space kernels
+    // Vienna-BL, per-pair route of the ladder (round 3): when at most half of the pairs of a batch are flagged, only THOSE pairs are recomputed --
+    // on a helper context of the same model (its own tables, its own whole-batch ladder and log-space fallback) -- and their results are
+    // copied into this batch's result buffers; every other pair keeps the result of the first pass bit for bit
+    rh_ctx* helper = nullptr;
+    bool is_helper = false;
+    int pair_helper = 1;           // RH_PAIR_HELPER=0: the whole batch is run again (round-2 behaviour); 2: helper whenever at most half of the pairs are flagged
+    std::vector<int> flagged_pairs;            // pairs the deferred attempt flagged (folds, two-molecule sweeps or pf_duplex)
+    std::string p_param, p_defaults;           // creation arguments, for the helper
+    bool p_has_param = false, p_has_defaults = false;
+    int p_use_bl = 1, p_sem = 0;
+    bool went_log = false;                     // compute_once (Vienna-BL): the batch was recomputed by the log-space kernels
+    std::vector<int> flagged_mc;               // sequences the deferred attempts flagged
+    DevObj<VLinModel> d_vdxl;      // the same tables at the duplex scale (duplex_vlin.hip)
+    DevObj<VDxLin> d_vdx;
+    double vdx_s = 0.27;           // log Z of pf_duplex per unit of a+b: 0.23 (random ACGU) .. 0.32 (70 % GC)
+    DevObj<DxLinModel> d_dxlin;
+    DxLinModel h_dxlin;
+    DevObj<DxLinModel> d_dxlin_r[4];   // duplex scale-exponent ladder (retry_dx_lin_rungs), built on first use
+    DxLinModel h_dxlin_r[4];
+    std::vector<int> rescaled_dx;              // pairs the last compute recomputed on the linear duplex kernels with another exponent (rh_batch_fallbacks which = 3)
+    DxLinBatch dxl = {};
+    size_t dxl_layout = 0;         // (lda, rows) signature of the zero-padded table image currently in HBM
+    int co_seed = 1;               // Vienna-BL, hp from the two-molecule ensemble: copy the one-strand cells from the single folds (RH_CO_SEED=0: sweep them again)
+    int dx_strip = 1;              // linear duplex: eight anti-diagonals per launch (dxl_strip8); RH_DX_STRIP=0: four (dxl_sweep4)
+    int dx_quad = 1;               // linear duplex: four anti-diagonals per launch (dxl_sweep4, 4 wavefronts per group); RH_DX_QUAD=0: two (dxl_sweep<W>)
+    int dx_w = 4;                  // wavefronts per 64-cell group of the linear duplex kernel
+    int last_dx_path = 0;
+    int far_mfma = 1;              // block products on v_mfma_f64_16x16x4_f64 (BS = 16); RH_FAR_MFMA=0: LDS/FMA kernel
+    int lookahead = 2;             // inside sweep: 2 = two diagonals per launch (lin_inside_diag MODE 3), 1 = look-ahead pairs of launches
+                                   // (MODE 1/2), 0 = one full launch per diagonal; RH_LOOKAHEAD
+    int strip = 3;                 // CONTRAfold linear path: KD = 8 diagonals per launch (mccaskill_strip.hip) with the banded near/far split;
+                                   // RH_STRIP=0: the per-diagonal-pair kernels of mccaskill_lin.hip.  Bit 0 = inside sweep, bit 1 = outside sweep
+    int far2 = -1;                 // two-level block products: -1 = by size (sequences of n >= 384), 0 / 1 forced (RH_FAR2)
+    int far2_next = -1;            // launch-sequence state of far_outside_step
+    int strip_w = 8;               // wavefronts per strip workgroup (RH_STRIP_W = 4 | 8)
+    // short sequences (kSmallMin <= n <= kSmallMax, CONTRAfold model, scaled linear path): one workgroup per sequence, one launch
+    // (mccaskill_small.hip); chosen per sequence by its length alone, so a result does not depend on the rest of the batch.  The sweeps
+    // see these sequences with length 0 (d_n_sweep).  Opt-in (RH_SMALL=1): measured slower than the sweeps (6.1 against 4.9 ms per 1000 pairs of 109 + 53 letters).
+    int small_on = 0;
+    std::vector<int> small_list;
+    DevBuf d_small_list;
+    DevBuf d_n_sweep;
+    int nmax_sweep = 0;
+    // sequences shorter than 40 letters next to longer ones: the sweeps choose their launch organisation by the longest sequence they
+    // see (strips of eight diagonals from 40 letters on), so these get a pass of their own with the organisation they would get alone
+    // (d_n_short: their lengths, 0 for everyone else) -- a result then does not depend on what else is in the batch
+    DevBuf d_n_short;
+    int n_short = 0, nmax_short = 0;
+    int strip_filt = 1;            // single-branch filter of the strip kernels: 1 = factored (A(t) B(|l1-l2|) + sparse residual), 0 = dense (RH_STRIP_FILT)
+    bool strip_filt_ok = false;    // the model's weights have the factored form (strip_weights verifies it entry by entry)
+    int co_cut_min = 0, co_cut_max = 0;   // smallest / largest cut (length of s1) of the two-molecule batch: bounds of the groups its sweeps launch
+    int co_window = 1;             // two-molecule sweeps launch only the groups around the cut (RH_CO_WINDOW=0: all groups, most of which return at once)
+    int acc_final_t = 1;           // Vienna-BL accessibility: vlin_acc_final_t (one thread per letter, all widths; RH_ACC_FINAL_T=0: one thread per letter and width)
+    int acc_wide = 1;              // Vienna-BL accessibility: vlin_acc_gaps_wide for the gap lengths 3..30 (RH_ACC_WIDE=0: vlin_acc_gaps for all)
+    int strip_xcd = 1;             // groups of one sequence consecutive on one XCD (RH_STRIP_XCD=0: sequence-major launch order only)
+    int far_pk = 1;                // ... on packed operand tiles (lin_pack_tiles + lin_far_*_pk); RH_FAR_PK=0: gather per product
+    int use_graphs = 1;            // RH_NO_GRAPH=1 launches every kernel from the host instead
+    GraphSlot g_in, g_out, g_dx;
+    int mode = RH_MODE_AUTO;       // which McCaskill path rh_batch_compute takes
+    int lin_w = 4;                 // wavefronts per 64-cell group of the linear outside kernel (Vienna-BL kernels: 8)
+    int lin_w_in = 4;              // ... of the inside kernel (fewer, longer wavefronts: less per-wavefront scalar overhead)
+    int lin_bs = 16;               // block size of the far/near split of the O(n^3) terms (0 = off)
+    int last_path = 0;             // 1 = linear, 2 = log-space, 3 = linear then log-space fallback
+    int max_w = 1;                 // accessibility widths 1..max_w (src/ractip.cpp:370-375); the CONTRAfold path has width 1 only
+
+    // current batch (host mirror)
+    int np = 0, ns = 0;
+    bool has_mc = false, has_dx = false, computed = false;
+    std::vector<int> n;  // [ns]
+    McBatch mc = {};
+    DxBatch dx = {};
+    // owned device buffers
+    DevBuf d_seq;
+    DevBuf d_n;
+    DevBuf d_mctab;
+    DevBuf d_corowp;
+    DevBuf d_rowp;    // look-ahead partial sums of the next inside diagonal
+    DevBuf d_pk;        // operand tiles of the block products (single-molecule batch)
+    DevBuf d_copk;    // ... of the s1+s2 batch
+    DevBuf d_f5;
+    DevBuf d_bp;
+    DevBuf d_up;
+    DevBuf d_dxtab;
+    DevBuf d_hp;
+    DevBuf d_logz;
+    DevBuf d_scal;
+    DevBuf d_mclogz;
+    DevBuf d_bad;
+    DevBuf d_cnt;
+    DevBuf d_dxbad;
+    DevBuf d_zbar;
+    DevBuf d_zpart;   // per-chunk partial sums of Z~ (+ pairable-cell counts behind them)
+    int lz_chunks = 0;
+    DevBuf d_cand;
+    // compacted sub-batches of the per-problem log-space fallback
+    DevBuf d_subseq;
+    DevBuf d_subn;
+    DevBuf d_subbp;
+    DevBuf d_subup;
+    DevBuf d_subdseq;
+    DevBuf d_subdn;
+    DevBuf d_subdx;
+    bool tables_dirty = false;      // the last compute met values outside the double range: clear the tables before the next batch
+    std::vector<uint8_t> h_codes;   // host mirror of d_seq
+    std::vector<int> fallback_mc, fallback_dx;   // problems the last compute recomputed in log space (rh_batch_fallbacks)
+    DevBuf d_gaps;
+    DevBuf d_allow;   // structure-constraint masks [ns][ld*ld] bytes (Vienna-BL, optional)
+    DevBuf d_coallow;   // the same for the s1+s2 batch
+    DevBuf d_hplen;   // lam^d x hairpin length weight, d = 0..nmax (linear Vienna path)
+    std::vector<double> h_hplen;
+    // two-molecule (co_pf_fold) form of the hybridization matrix: one concatenated sequence s1+s2 per pair
+    int hybrid = RH_HYBRID_DUPLEX;
+    McBatch co = {};
+    DevBuf d_coseq;
+    DevBuf d_con;     // [2][np]: lengths, cuts
+    DevBuf d_cotab;
+    DevBuf d_cof5;    // f5i, f5o, xp, xs, xpo, xso
+    DevBuf d_cobp;
+    DevBuf d_cobad;
+    double ms[4] = {0, 0, 0, 0};
+    int n_launch[3] = {0, 0, 0};
+    int n_far[3] = {0, 0, 0};      // of which block-product launches (mccaskill_far.hip)
+    bool overlap = true;           // false: duplex, inside and outside sweeps run one after the other (isolated phase timings)
+    int time_cls = -1;             // rh_set_kernel_timing: sweep-kernel class whose launches are bracketed by event pairs (-1: none)
+    std::vector<hipEvent_t> tev;   // event pool of the timed class (pairs), tev_n used by the last compute
+    size_t tev_n = 0;
+    Ctx() = default;
+    Ctx(const Ctx&) = delete;
+    ~Ctx() { delete[] lin_r; delete h_score; delete h_vienna; }   // (device buffers free themselves; rh_destroy has set the device)
+};
+
+}  // namespace rh::host
+
+struct rh_ctx : rh::host::Ctx {};   // the opaque context of include/ractip_hot.h
+
+#define HIP_TRY(c, call)                                                                         \
+    do {                                                                                         \
+        hipError_t e_ = (call);                                                                  \
+        if (e_ != hipSuccess)                                                                    \
+            return fail(c, e_ == hipErrorOutOfMemory ? RH_ERR_OOM : RH_ERR_HIP, "%s failed: %s", \
+                        #call, hipGetErrorString(e_));                                           \
+    } while (0)
+
+// launch of one sweep kernel (class = 0 inside, 1 inside block products, 2 outside, 3 outside block products, 4 duplex)
+// Measurement aid (rh_set_kernel_timing): launches of class `time_cls` are bracketed by a HIP event pair on their stream, so that
+// bench.py can report the average duration of ONE kernel class live (what a kernel trace reports per kernel); off by default.
+#define KLAUNCH(c, cls, kern, grid, block, stream, ...)                                                   \
+    do {                                                                                                  \
+        const bool timed_ = (c)->time_cls == (cls) && (c)->tev_n + 2 <= (c)->tev.size();                  \
+        if (timed_) (void)hipEventRecord((c)->tev[(c)->tev_n++], stream);                                 \
+        hipLaunchKernelGGL(kern, grid, block, 0, stream, __VA_ARGS__);                                    \
+        if (timed_) (void)hipEventRecord((c)->tev[(c)->tev_n++], stream);                                 \
+    } while (0)
+
+namespace rh::host {
+
+inline size_t tri_size(int n) { return (size_t)(n + 1) * (n + 2) / 2; }
+
+// rh_api.hip
+int fail(rh_ctx* c, int code, const char* fmt, ...);
+int ensure(rh_ctx* c, DevBuf& buf, size_t bytes, bool zero);
+// staging.hip
+int stage(rh_ctx* c, int ns, const char* const* seqs, const int* lens, bool with_mc, bool with_dx, const char* const* cons = nullptr,
+          const char* const* co_cons = nullptr);
+// launch_contrafold.hip
+int launch_mc_log(rh_ctx* c, int pin, const McBatch& B, double* logz_out);
+int launch_mc_log(rh_ctx* c, int pin);
+int launch_mc_lin_any(rh_ctx* c, int pin, int phase);
+int far_inside_step(rh_ctx* c, const McBatch& B, hipStream_t st, int D, int last_block, int banded = 0);
+int far_outside_begin(rh_ctx* c, const McBatch& B, hipStream_t st, int last_block, int banded = 0, bool repack2 = false);
+int far_outside_step(rh_ctx* c, const McBatch& B, hipStream_t st, int D, int last_block);
+bool strip_inside(const rh_ctx* c, const McBatch& B);
+bool strip_outside(const rh_ctx* c, const McBatch& B);
+std::vector<double> strip_weights(const LinModel& L, bool* ok_out = nullptr);
+// launch_vienna.hip
+int launch_mc_vienna(rh_ctx* c, int pin);
+int launch_mc_vlin(rh_ctx* c, int pin, int phase, bool co);
+int launch_cofold(rh_ctx* c);
+int select_vlin(rh_ctx* c, int model);
+extern const double kVRungS[Ctx::kVRungs];
+// launch_duplex.hip
+int launch_dx_log(rh_ctx* c, const DxBatch& D);
+int launch_dx_log(rh_ctx* c);
+template <int W> int launch_dx_lin_on(rh_ctx* c, DxLinBatch X, const DxLinModel* dm, const DxLinModel& hm, double* logz_out, int* bad);
+int launch_dx_lin_any(rh_ctx* c);
+int launch_dx_vlin(rh_ctx* c);
+int launch_dx_vlog(rh_ctx* c);
+// fallbacks.hip
+int retry_mc_lin_rungs(rh_ctx* c, std::vector<int>* rest);
+int recompute_mc_subset_log(rh_ctx* c, const std::vector<int>& F);
+int retry_dx_lin_rungs(rh_ctx* c, std::vector<int>* rest);
+int recompute_dx_subset_log(rh_ctx* c, const std::vector<int>& F);
+int recompute_pairs_on_helper(rh_ctx* c, const std::vector<int>& P);
+// compute.hip
+int compute(rh_ctx* c);
+
+}  // namespace rh::host
+
+// = create_ctx of rh_api.hip, for the per-pair helper context (C++ linkage, not part of the C ABI)
+rh_ctx* make_ctx_for_helper(int device, int model, const char* param_file, const char* defaults_file, int use_bl, int semantics);

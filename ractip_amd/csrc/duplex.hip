@@ -16,6 +16,7 @@
 #include "batch.h"
 #include "lse.h"
 #include "score_model.h"
+#include "kernels.h"
 
 namespace rh {
 

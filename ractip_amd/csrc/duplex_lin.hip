@@ -18,6 +18,7 @@
 
 #include "batch.h"
 #include "lin_model.h"
+#include "kernels.h"
 
 #ifndef RH_WPE_DX
 #define RH_WPE_DX

@@ -1,0 +1,90 @@
+// kernels.h -- the one declaration of every __global__ kernel and cross-file launch helper of the library.
+// Every .hip file that defines a kernel includes it, and so does every host unit that launches one: the compiler
+// checks each definition (and each explicit instantiation) against the declaration here.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "../../include/ractip_hot.h"
+#include "batch.h"
+#include "score_model.h"
+#include "lin_model.h"
+#include "vienna_model.h"
+
+namespace rh {
+__global__ void mc_init(McBatch B);
+__global__ void mc_inside_diag(McBatch B, const ScoreModel* __restrict__ M, int d, int pin);
+__global__ void mc_outside_diag(McBatch B, const ScoreModel* __restrict__ M, int d, int pin);
+__global__ void mc_unpaired(McBatch B);
+__global__ void dx_sweep_diag(DxBatch B, const ScoreModel* __restrict__ M, int t);
+__global__ void dx_logz(DxBatch B, const ScoreModel* __restrict__ M);
+__global__ void dx_posterior(DxBatch B);
+__global__ void lin_init(McBatch B, const LinModel* __restrict__ L, int* __restrict__ bad);
+template <int W, int BS, int MODE> __global__ void lin_inside_diag(McBatch B, const LinModel* __restrict__ L, int d, double lam_d, int pin);
+template <int W, int BS> __global__ void lin_outside_diag(McBatch B, const LinModel* __restrict__ L, int d, int pin, int* __restrict__ bad);
+template <int W, int BS> __global__ void lin_outside_pair(McBatch B, const LinModel* __restrict__ L, int d, int khi, int pin, int* __restrict__ bad);
+template <int BS> __global__ void lin_far_inside(McBatch B, int D);
+template <int BS> __global__ void lin_far_outside(McBatch B, int D);
+__global__ void lin_far_inside_mfma(McBatch B, int D);
+__global__ void lin_far_outside_mfma(McBatch B, int D);
+template <int SWEEP> __global__ void lin_pack_tiles(McBatch B, int Dblk, int outside, int banded);
+template <int KD, int W, int FILT> __global__ void lin_inside_strip(McBatch B, const LinModel* __restrict__ L, const double* __restrict__ wT, int d0, int f5_lo, double lam_d0, int pin);
+template <int KD, int W, int FILT> __global__ void lin_outside_strip(McBatch B, const LinModel* __restrict__ L, const double* __restrict__ wT, int d0, int f5_hi, int f5_lo, int pin, int* __restrict__ bad);
+__global__ void lin_f5i_tail(McBatch B, const LinModel* __restrict__ L, int jlo);
+void launch_lin_small(const McBatch& B, const LinModel* L, const double* wpad, const int* list, int nlist, int* bad, hipStream_t stream);   // mccaskill_small.hip
+__global__ void lin_f5o_head(McBatch B, const LinModel* __restrict__ L, int khi, int klo);
+__global__ void lin_far_inside_pk(McBatch B, int D, int l2);
+__global__ void lin_far_outside_pk(McBatch B, int D, int l2);
+__global__ void lin_far2_inside(McBatch B, int D2, int l2);
+__global__ void lin_far2_outside(McBatch B, int D2, int l2);
+__global__ void lin_finish(McBatch B, const LinModel* __restrict__ L, double* __restrict__ logz, int* __restrict__ bad);
+template <int W> __global__ void dxl_sweep(DxLinBatch B, const DxLinModel* __restrict__ L, int step, int groups);
+__global__ void dxl_sweep4(DxLinBatch B, const DxLinModel* __restrict__ L, int step, int groups);
+__global__ void dxl_strip8(DxLinBatch B, const DxLinModel* __restrict__ L, int step);
+__global__ void dxvl_sweep4(DxLinBatch B, const VLinModel* __restrict__ L, const VDxLin* __restrict__ D, int step);
+__global__ void dxvl_logz_part(DxLinBatch B, const VLinModel* __restrict__ L, const VDxLin* __restrict__ D, double* __restrict__ zpart,
+                               int* __restrict__ cpart, int nchunk);
+__global__ void dxvl_logz_final(DxLinBatch B, double s, const double* __restrict__ zpart, const int* __restrict__ cpart, int nchunk,
+                                double* __restrict__ zbar, double* __restrict__ logz, int* __restrict__ bad);
+__global__ void dxl_logz_part(DxLinBatch B, const DxLinModel* __restrict__ L, double* __restrict__ zpart, int* __restrict__ cpart, int nchunk);
+__global__ void dxl_logz_final(DxLinBatch B, const DxLinModel* __restrict__ L, const double* __restrict__ zpart, const int* __restrict__ cpart, int nchunk,
+                               double* __restrict__ zbar, double* __restrict__ logz, int* __restrict__ bad);
+__global__ void dxl_posterior(DxLinBatch B, const double* __restrict__ zbar, int* __restrict__ bad);
+__global__ void dxv_sweep_diag(DxBatch B, const ViennaDx* __restrict__ V, int t);
+__global__ void dxv_logz(DxBatch B, const ViennaDx* __restrict__ V);
+__global__ void dxv_posterior(DxBatch B);
+__global__ void mcv_init(McBatch B);
+__global__ void mcv_inside_diag(McBatch B, const ViennaDx* __restrict__ V, int d, int pin);
+__global__ void mcv_outside_diag(McBatch B, const ViennaDx* __restrict__ V, int d, int pin);
+__global__ void mcv_acc_prep(McBatch B, const ViennaDx* __restrict__ V);
+__global__ void mcv_acc_hscan(McBatch B, int slot);
+__global__ void vlin_acc_prep(McBatch B, const VLinModel* __restrict__ L, const double* __restrict__ hplen);
+__global__ void vlin_acc_gaps(McBatch B, const VLinModel* __restrict__ L, double* __restrict__ gaps, int ng, int nchunk, double* __restrict__ part);
+__global__ void vlin_acc_gsum(McBatch B, double* __restrict__ gaps, const double* __restrict__ part, int ng, int nchunk);
+__global__ void vlin_acc_gaps_wide(McBatch B, const VLinModel* __restrict__ L, double* __restrict__ gaps);
+__global__ void vlin_acc_final_t(McBatch B, const VLinModel* __restrict__ L, const double* __restrict__ gaps, int max_w);
+__global__ void vlin_acc_hsum(McBatch B, int max_w);
+__global__ void vlin_acc_gsuf(McBatch B, double* __restrict__ gaps);
+__global__ void vlin_acc_final(McBatch B, const VLinModel* __restrict__ L, const double* __restrict__ gaps, int max_w);
+__global__ void mcv_acc_gaps(McBatch B, const ViennaDx* __restrict__ V, double* __restrict__ gaps);
+__global__ void mcv_acc_final(McBatch B, const ViennaDx* __restrict__ V, const double* __restrict__ gaps, int max_w);
+__global__ void mcv_finish(McBatch B, double* __restrict__ logz);
+__global__ void vlin_init(McBatch B, int* __restrict__ bad);
+__global__ void vlin_co_seed(McBatch B, McBatch S);
+template <int W, int BS, bool CUT, int MODE> __global__ void vlin_inside_diag(McBatch B, const VLinModel* __restrict__ L, int d, double hp_d, int pin);
+template <int W, int BS, bool CUT, int MODE> __global__ void vlin_outside_diag(McBatch B, const VLinModel* __restrict__ L, int d, int pin, int* __restrict__ bad);
+__global__ void vlin_finish(McBatch B, const VLinModel* __restrict__ L, double* __restrict__ logz, int* __restrict__ bad);
+__global__ void mcv_extract_hp(McBatch B, double* __restrict__ hp, size_t hp_stride, int ldd, double* __restrict__ logz, double lin_s, int* __restrict__ bad);
+}  // namespace rh
+
+// defined by the host units (global namespace)
+__global__ void collect_logz(const double* __restrict__ mc_logz, rh::DxBatch D, double* __restrict__ out);                 // rh_api.hip
+__global__ void log_finish(rh::McBatch B, double* __restrict__ logz);                                                       // launch_contrafold.hip
+// candidates.hip
+__global__ void cand_count(const double* __restrict__ base, int kind, int n, int n2, int ld, float th, int nrows, int* __restrict__ counts);
+__global__ void cand_write(const double* __restrict__ base, int kind, int n, int n2, int ld, float th, int nrows, const int* __restrict__ offsets,
+                           rh_cand* __restrict__ out, int cap);
+__global__ void cand_count_all(const double* __restrict__ bp, const double* __restrict__ hp, const double* __restrict__ up, const int* __restrict__ nn,
+                               size_t tri_stride, size_t hp_stride, int up_ld, int hp_ld, int which, int rmax, float th, int* __restrict__ counts);
+__global__ void cand_write_all(const double* __restrict__ bp, const double* __restrict__ hp, const double* __restrict__ up, const int* __restrict__ nn,
+                               size_t tri_stride, size_t hp_stride, int up_ld, int hp_ld, int which, int rmax, float th, const int* __restrict__ offsets,
+                               rh_cand* __restrict__ out, int cap);

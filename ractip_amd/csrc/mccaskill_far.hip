@@ -14,6 +14,7 @@
 
 #include "batch.h"
 #include "lin_model.h"
+#include "kernels.h"
 
 namespace rh {
 

@@ -19,6 +19,7 @@
 
 #include "batch.h"
 #include "lin_model.h"
+#include "kernels.h"
 
 #ifndef RH_WPE_IN
 #define RH_WPE_IN

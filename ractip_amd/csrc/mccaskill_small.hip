@@ -28,11 +28,12 @@
 // they are used unless pinned; (4) what remains is the LDS rate of the DENSE filter, one 512-byte read per FMA: ~1100 reads x 4 cycles
 // per diagonal.  The strips win because their filter is factored (five times fewer operations) and their FM2 far terms run on MFMA;
 // porting the factored filter here (fixed-pitch rows instead of the packed triangle) is the step that would make this the default.
-// Which sequences come here is decided per sequence by its length alone (rh_api.hip), so a result does not depend on the batch.
+// Which sequences come here is decided per sequence by its length alone (staging.hip), so a result does not depend on the batch.
 #include <hip/hip_runtime.h>
 
 #include "batch.h"
 #include "lin_model.h"
+#include "kernels.h"
 
 namespace rh {
 

@@ -30,6 +30,7 @@
 
 #include "batch.h"
 #include "lin_model.h"
+#include "kernels.h"
 
 namespace rh {
 
@@ -117,7 +118,7 @@ extern "C" int rh_debug_trace(unsigned long long* out)
 enum StripTable { S_FC = 0, S_FCX, S_FCA, S_FM1, S_FM, S_FCO, S_FCOX, S_FM2O, S_FMO, S_FM1O, S_FM2F, S_FMOF, S_FM1OF };
 
 // ---------------------------------------------------------------------------------------------------------------
-// FACTORED single-branch filter (FILT = 1; host side: strip_weights in rh_api.hip).  The weight of an interior loop (l1, l2), t = l1+l2,
+// FACTORED single-branch filter (FILT = 1; host side: strip_weights in launch_contrafold.hip).  The weight of an interior loop (l1, l2), t = l1+l2,
 // is A(t) * B(|l1-l2|) up to a sparse residual (bulge ends, centre tap, a few shapes with l1, l2 <= 4: cache_score_single,
 // InferenceEngine.ipp:1161-1197).  For one staged table row x (row rho of the strip: t = rho-1+k on diagonal k) the B-weighted sum
 //   S_t[i] = sum_{l1=1}^{t-1} B(|2 l1 - t|) x[i+1+l1]      obeys      S_{t+2}[i-1] = S_t[i] + B(t) (x[i+1] + x[i+1+t]),

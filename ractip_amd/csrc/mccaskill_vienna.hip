@@ -28,6 +28,7 @@
 #include "batch.h"
 #include "lse.h"
 #include "vienna_model.h"
+#include "kernels.h"
 
 namespace rh {
 

@@ -16,6 +16,7 @@
 
 #include "batch.h"
 #include "vienna_model.h"
+#include "kernels.h"
 
 namespace rh {
 

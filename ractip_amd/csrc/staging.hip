@@ -1,0 +1,290 @@
+// staging.hip -- sequence encoding, structure-constraint masks and the upload of a batch: sizes and allocates
+// every table the batch needs (buffers are kept and reused across batches of equal or smaller shape).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "ctx.h"
+#include "kernels.h"
+
+namespace rh::host {
+
+uint8_t nuc_code(char ch)
+{  // InferenceEngine.ipp:379-384: case-insensitive ACGU, anything else (incl. T, N) is code 4
+    switch (ch) {
+        case 'A': case 'a': return 0;
+        case 'C': case 'c': return 1;
+        case 'G': case 'g': return 2;
+        case 'U': case 'u': return 3;
+        default: return 4;
+    }
+}
+
+uint8_t vienna_code(char ch)
+{  // ViennaRNA encode_char with energy_set 0: A,C,G,U -> 1..4 (T reads as U), anything else 0
+    switch (ch) {
+        case 'A': case 'a': return 1;
+        case 'C': case 'c': return 2;
+        case 'G': case 'g': return 3;
+        case 'U': case 'u': case 'T': case 't': return 4;
+        default: return 0;
+    }
+}
+
+// Allowed-pair mask of pf_fold under fold_constrained (ViennaRNA 1.8 make_ptypes), M[a*ld + b], 1 <= a < b <= n:
+//   'x' the letter never pairs; '<' it pairs only with a later letter, '>' only with an earlier one; a matched '(' ')'
+//   is kept and every pair inconsistent with it (crossing it, or sharing a letter) is removed; '|' and '.' do not
+//   restrict the partition function.  Returns false for unbalanced brackets or a forced pair of non-complementary letters.
+bool build_allow_mask(const char* seq, int n, const char* cons, int ld, uint8_t* M, std::string* why)
+{
+    for (int a = 0; a < ld; a++)
+        for (int b = 0; b < ld; b++) M[(size_t)a * ld + b] = (a >= 1 && a < b && b <= n) ? 1 : 0;
+    const size_t clen = std::strlen(cons);
+    std::vector<int> stack;
+    for (int j = 1; j <= n; j++) {
+        const char ch = (size_t)(j - 1) < clen ? cons[j - 1] : '.';
+        if (ch == 'x') {
+            for (int l = 1; l <= n; l++) { M[(size_t)l * ld + j] = 0; M[(size_t)j * ld + l] = 0; }
+        } else if (ch == '(' || ch == '<') {
+            if (ch == '(') stack.push_back(j);
+            for (int l = 1; l < j; l++) M[(size_t)l * ld + j] = 0;
+        } else if (ch == ')' || ch == '>') {
+            if (ch == ')') {
+                if (stack.empty()) { *why = "unbalanced ')' in the structure constraint"; return false; }
+                const int i = stack.back();
+                stack.pop_back();
+                const uint8_t keep = M[(size_t)i * ld + j];
+                for (int k = i; k <= j; k++) for (int l = j; l <= n; l++) M[(size_t)k * ld + l] = 0;
+                for (int k = 1; k <= i; k++) for (int l = i; l <= j; l++) M[(size_t)k * ld + l] = 0;
+                M[(size_t)i * ld + j] = keep;
+                const uint8_t x = vienna_code(seq[i - 1]), y = vienna_code(seq[j - 1]);
+                static const int T[5][5] = {{0, 0, 0, 0, 0}, {0, 0, 0, 0, 5}, {0, 0, 0, 1, 0}, {0, 0, 2, 0, 3}, {0, 6, 0, 4, 0}};
+                if (keep && !T[x][y]) { *why = "a forced pair of non-complementary letters (pair type 7) is not supported"; return false; }
+            }
+            for (int l = j + 1; l <= n; l++) M[(size_t)j * ld + l] = 0;
+        }
+    }
+    if (!stack.empty()) { *why = "unbalanced '(' in the structure constraint"; return false; }
+    return true;
+}
+
+// Stage `ns` sequences; pairs are (2p, 2p+1) when with_dx.  Allocates what is needed.  cons: per-sequence structure
+// constraints (Vienna-BL, single-molecule batch only) or nullptr.
+int stage(rh_ctx* c, int ns, const char* const* seqs, const int* lens, bool with_mc, bool with_dx, const char* const* cons, const char* const* co_cons)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (ns <= 0) return fail(c, RH_ERR_ARG, "empty batch");
+    int nmax = 0, n1max = 0, n2max = 0;
+    for (int k = 0; k < ns; k++) {
+        if (lens[k] < 1) return fail(c, RH_ERR_ARG, "sequence %d has length %d (must be >= 1)", k, lens[k]);
+        if (!seqs[k]) return fail(c, RH_ERR_ARG, "sequence %d is NULL", k);
+        nmax = std::max(nmax, lens[k]);
+        if (with_dx) { if (k & 1) n2max = std::max(n2max, lens[k]); else n1max = std::max(n1max, lens[k]); }
+    }
+    if (with_dx && (ns & 1)) return fail(c, RH_ERR_ARG, "duplex batch needs an even number of sequences");
+    c->ns = ns; c->np = with_dx ? ns / 2 : 0;
+    c->has_mc = with_mc; c->has_dx = with_dx; c->computed = false;
+    c->n.assign(lens, lens + ns);
+
+    const int lds = (nmax + 3 + 15) & ~15;  // codes 0..n+2 readable
+    const bool vienna = c->model == RH_MODEL_VIENNA_BL;
+    std::vector<uint8_t> codes((size_t)ns * lds, vienna ? 0 : 4);   // sentinel = the model's "no nucleotide" code
+    for (int k = 0; k < ns; k++)
+        for (int i = 0; i < lens[k]; i++) codes[(size_t)k * lds + 1 + i] = vienna ? vienna_code(seqs[k][i]) : nuc_code(seqs[k][i]);
+    int rc;
+    if ((rc = ensure(c, c->d_seq, codes.size(), false))) return rc;
+    if ((rc = ensure(c, c->d_n, sizeof(int) * ns, false))) return rc;
+    c->h_codes = codes;
+    HIP_TRY(c, hipMemcpyAsync(c->d_seq.p, codes.data(), codes.size(), hipMemcpyHostToDevice, c->s_mc));
+    HIP_TRY(c, hipMemcpyAsync(c->d_n.p, lens, sizeof(int) * ns, hipMemcpyHostToDevice, c->s_mc));
+    c->small_list.clear();
+    c->nmax_sweep = nmax;
+    c->n_short = 0; c->nmax_short = 0;
+    if (with_mc && !vienna && !cons) {
+        std::vector<int> nsw(lens, lens + ns), nsh(ns, 0);
+        int nmax_rest = 0;
+        for (int k = 0; k < ns; k++) {
+            if (c->small_on && lens[k] >= kSmallMin && lens[k] <= kSmallMax) { c->small_list.push_back(k); nsw[k] = 0; }
+            else nmax_rest = std::max(nmax_rest, lens[k]);
+        }
+        if (nmax_rest >= kStripMinN)   // some sequence runs in strips: the ones below that length get their own pass
+            for (int k = 0; k < ns; k++)
+                if (nsw[k] > 0 && nsw[k] < kStripMinN) { nsh[k] = nsw[k]; nsw[k] = 0; c->n_short++; c->nmax_short = std::max(c->nmax_short, nsh[k]); }
+        c->nmax_sweep = 0;
+        for (int k = 0; k < ns; k++) c->nmax_sweep = std::max(c->nmax_sweep, nsw[k]);
+        if (!c->small_list.empty() || c->n_short) {
+            // longest first: one workgroup occupies a CU, and workgroups of alternating cost land on alternating CUs
+            std::stable_sort(c->small_list.begin(), c->small_list.end(), [&](int a, int b) { return lens[a] > lens[b]; });
+            if ((rc = ensure(c, c->d_small_list, sizeof(int) * ns, false))) return rc;
+            if ((rc = ensure(c, c->d_n_sweep, sizeof(int) * ns, false))) return rc;
+            if ((rc = ensure(c, c->d_n_short, sizeof(int) * ns, false))) return rc;
+            if (!c->small_list.empty())
+                HIP_TRY(c, hipMemcpyAsync(c->d_small_list.p, c->small_list.data(), sizeof(int) * c->small_list.size(), hipMemcpyHostToDevice, c->s_mc));
+            HIP_TRY(c, hipMemcpyAsync(c->d_n_sweep.p, nsw.data(), sizeof(int) * ns, hipMemcpyHostToDevice, c->s_mc));
+            HIP_TRY(c, hipMemcpyAsync(c->d_n_short.p, nsh.data(), sizeof(int) * ns, hipMemcpyHostToDevice, c->s_mc));
+            HIP_TRY(c, hipStreamSynchronize(c->s_mc));   // (the staging vectors die with this scope)
+        }
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->s_mc));  // host staging buffers die with this scope
+
+    if (with_mc) {
+        McBatch& B = c->mc;
+        B.ns = ns; B.nmax = nmax; B.lds = lds;
+        B.ld = (nmax + 2 + 1) & ~1;
+        B.tab_stride = (size_t)B.ld * B.ld;
+        B.seq_stride = B.tab_stride * (vienna ? (int)kViennaMcTables : (int)T_COUNT);
+        B.tri_stride = (tri_size(nmax) + 1) & ~(size_t)1;
+        if ((rc = ensure(c, c->d_mctab, sizeof(double) * B.seq_stride * ns, false))) return rc;
+        B.nb = (nmax - 1) / 16 + 1;
+        B.pk_stride = (size_t)B.nb * (B.nb + 1) / 2 * 256;
+        if ((rc = ensure(c, c->d_pk, sizeof(double) * B.pk_stride * kPkCopies * ns, false))) return rc;
+        B.pk = c->d_pk.as<double>();
+        if ((rc = ensure(c, c->d_rowp, sizeof(double) * 4 * B.ld * ns, false))) return rc;
+        B.rowp = c->d_rowp.as<double>();
+        if ((rc = ensure(c, c->d_f5, sizeof(double) * 2 * B.ld * ns, false))) return rc;
+        if ((rc = ensure(c, c->d_up, sizeof(double) * B.ld * c->max_w * ns, false))) return rc;
+        // gap probabilities [2 ns][32][ld] + the chunk sums of the gap lengths 1, 2 [8][2 ns][2][ld] (launch_mc_vlin)
+        if (vienna && (rc = ensure(c, c->d_gaps, sizeof(double) * (2 * 32 + 8 * 2 * 2) * B.ld * ns, false))) return rc;
+        if (vienna) {
+            const VLinModel& H = *c->h_vlin;
+            c->h_hplen.resize((size_t)B.ld);
+            for (int d = 0; d < B.ld; d++)   // hairpin of d unpaired letters: length weight (beyond 30 as part_func.c extrapolates) x lam^d
+                c->h_hplen[d] = (d <= 30 ? H.E_hairpin[d] : std::exp(H.hairpin30 - H.lxc * std::log(d / 30.0))) * std::exp(-H.s * d);
+            if ((rc = ensure(c, c->d_hplen, sizeof(double) * B.ld, false))) return rc;
+            HIP_TRY(c, hipMemcpyAsync(c->d_hplen.p, c->h_hplen.data(), sizeof(double) * B.ld, hipMemcpyHostToDevice, c->s_mc));
+            HIP_TRY(c, hipStreamSynchronize(c->s_mc));
+        }
+        if ((rc = ensure(c, c->d_mclogz, sizeof(double) * ns, false))) return rc;
+        if ((rc = ensure(c, c->d_bad, sizeof(int) * ns, false))) return rc;
+        // bp entries outside 1<=i<j<=n are never written by the sweep: keep them zero
+        const size_t bp_bytes = sizeof(double) * B.tri_stride * ns;
+        if ((rc = ensure(c, c->d_bp, bp_bytes, false))) return rc;
+        HIP_TRY(c, hipMemsetAsync(c->d_bp.p, 0, bp_bytes, c->s_mc));
+        B.allow = nullptr;
+        if (cons) {
+            std::vector<uint8_t> M((size_t)ns * B.ld * B.ld);
+            std::string why;
+            for (int k = 0; k < ns; k++)
+                if (!build_allow_mask(seqs[k], lens[k], cons[k] ? cons[k] : "", B.ld, M.data() + (size_t)k * B.ld * B.ld, &why))
+                    return fail(c, RH_ERR_ARG, "sequence %d: %s", k, why.c_str());
+            if ((rc = ensure(c, c->d_allow, M.size(), false))) return rc;
+            HIP_TRY(c, hipMemcpy(c->d_allow.p, M.data(), M.size(), hipMemcpyHostToDevice));
+            B.allow = c->d_allow.as<const uint8_t>();
+        }
+        if (c->tables_dirty) {
+            // a problem of the previous batch overflowed: its tables hold Inf / NaN, which a later batch must never meet even in
+            // cells it masks (0 x Inf).  One clear per such batch; ordinary batches reuse the tables as they are.
+            HIP_TRY(c, hipMemsetAsync(c->d_mctab.p, 0, c->d_mctab.cap, c->s_mc));
+            if (c->d_pk) HIP_TRY(c, hipMemsetAsync(c->d_pk.p, 0, c->d_pk.cap, c->s_mc));
+            if (c->d_cotab) HIP_TRY(c, hipMemsetAsync(c->d_cotab.p, 0, c->d_cotab.cap, c->s_mc));
+            if (c->d_copk) HIP_TRY(c, hipMemsetAsync(c->d_copk.p, 0, c->d_copk.cap, c->s_mc));
+            c->tables_dirty = false;
+        }
+        B.seq = c->d_seq.as<const uint8_t>(); B.n = c->d_n.as<const int>();
+        B.tab = c->d_mctab.as<double>();
+        B.f5i = c->d_f5.as<double>(); B.f5o = c->d_f5.as<double>() + (size_t)B.ld * ns;
+        B.bp = c->d_bp.as<double>(); B.up = c->d_up.as<double>();
+    }
+    if (with_dx) {
+        DxBatch& D = c->dx;
+        D.np = ns / 2; D.n1max = n1max; D.n2max = n2max; D.lds = lds;
+        D.ldd = (n2max + 2 + 1) & ~1;
+        D.tab_stride = (size_t)(n1max + 2) * D.ldd;
+        D.pair_stride = D.tab_stride * 6;   // 4 tables (CONTRAfold model) or 6 (Vienna model: IN/OUT + two decorated copies each)
+        // the linear path keeps anti-diagonal-major tables in the same buffer (sequential use)
+        DxLinBatch& X = c->dxl;
+        X.np = D.np; X.n1max = n1max; X.n2max = n2max; X.lds = lds; X.ldd = D.ldd;
+        X.lda = (n1max + 2 + 2 * kDxPad + 1) & ~1;
+        const size_t rows = (size_t)n1max + n2max + 3;
+        X.tab_stride = rows * X.lda + 128;   // slack: the staged 96-column segments may run past the last row
+        X.pair_stride = X.tab_stride * (vienna ? 6 : (int)DL_COUNT);   // Vienna-BL: raw + two decorated copies per direction
+        const size_t dx_bytes = sizeof(double) * std::max(D.pair_stride, X.pair_stride) * D.np;
+        void* before = c->d_dxtab.p;
+        if ((rc = ensure(c, c->d_dxtab, dx_bytes, false))) return rc;
+        const size_t layout = ((size_t)X.lda << 32) ^ rows ^ ((size_t)D.np << 48);
+        if (c->d_dxtab.p != before || layout != c->dxl_layout || c->last_dx_path != 1) {
+            // pad columns must be zero and a different layout (or the log-space path) leaves arbitrary bytes there
+            HIP_TRY(c, hipMemsetAsync(c->d_dxtab.p, 0, dx_bytes, c->s_dx));
+            c->dxl_layout = layout;
+        }
+        if ((rc = ensure(c, c->d_dxbad, sizeof(int) * D.np, false))) return rc;
+        if ((rc = ensure(c, c->d_zbar, sizeof(double) * D.np, false))) return rc;
+        c->lz_chunks = (n1max + n2max - 1 + 15) / 16;   // kLzRows anti-diagonals per chunk
+        if ((rc = ensure(c, c->d_zpart, (sizeof(double) + sizeof(int)) * (size_t)D.np * c->lz_chunks, false))) return rc;
+        if ((rc = ensure(c, c->d_logz, sizeof(double) * D.np, false))) return rc;
+        const size_t hp_bytes = sizeof(double) * D.tab_stride * D.np;
+        if ((rc = ensure(c, c->d_hp, hp_bytes, false))) return rc;
+        HIP_TRY(c, hipMemsetAsync(c->d_hp.p, 0, hp_bytes, c->s_dx));  // row 0 / column 0 stay zero
+        D.seq = c->d_seq.as<const uint8_t>(); D.n = c->d_n.as<const int>();
+        D.tab = c->d_dxtab.as<double>(); D.hp = c->d_hp.as<double>(); D.logz = c->d_logz.as<double>();
+        if (vienna && c->hybrid == RH_HYBRID_COFOLD) {
+            // concatenated sequences s1+s2, cut after s1
+            McBatch& C = c->co;
+            const int np = ns / 2, cmax = n1max + n2max;
+            C = McBatch{};
+            C.ns = np; C.nmax = cmax;
+            C.lds = (cmax + 3 + 15) & ~15;
+            C.ld = (cmax + 2 + 1) & ~1;
+            C.tab_stride = (size_t)C.ld * C.ld;
+            C.seq_stride = C.tab_stride * kViennaMcTables;
+            C.tri_stride = (tri_size(cmax) + 1) & ~(size_t)1;
+            std::vector<uint8_t> cc((size_t)np * C.lds, 0);
+            std::vector<int> nn(2 * (size_t)np);
+            for (int p = 0; p < np; p++) {
+                const int a = lens[2 * p], b = lens[2 * p + 1];
+                for (int i = 0; i < a; i++) cc[(size_t)p * C.lds + 1 + i] = vienna_code(seqs[2 * p][i]);
+                for (int i = 0; i < b; i++) cc[(size_t)p * C.lds + 1 + a + i] = vienna_code(seqs[2 * p + 1][i]);
+                nn[p] = a + b; nn[np + p] = a;
+                c->co_cut_min = p == 0 ? a : std::min(c->co_cut_min, a);
+                c->co_cut_max = p == 0 ? a : std::max(c->co_cut_max, a);
+            }
+            if ((rc = ensure(c, c->d_coseq, cc.size(), false))) return rc;
+            if ((rc = ensure(c, c->d_con, sizeof(int) * nn.size(), false))) return rc;
+            if ((rc = ensure(c, c->d_cotab, sizeof(double) * C.seq_stride * np, false))) return rc;
+            C.nb = (cmax - 1) / 16 + 1;
+            C.pk_stride = (size_t)C.nb * (C.nb + 1) / 2 * 256;
+            if ((rc = ensure(c, c->d_copk, sizeof(double) * C.pk_stride * kPkCopies * np, false))) return rc;
+            C.pk = c->d_copk.as<double>();
+            if ((rc = ensure(c, c->d_corowp, sizeof(double) * 4 * C.ld * np, false))) return rc;
+            C.rowp = c->d_corowp.as<double>();
+            if ((rc = ensure(c, c->d_cof5, sizeof(double) * 6 * C.ld * np, false))) return rc;
+            if ((rc = ensure(c, c->d_cobp, sizeof(double) * C.tri_stride * np, false))) return rc;
+            if ((rc = ensure(c, c->d_cobad, sizeof(int) * np, false))) return rc;
+            if ((int)c->h_hplen.size() < C.ld) {   // hairpin length weights up to the joint length (see the single-molecule batch)
+                const VLinModel& H = *c->h_vlin;
+                c->h_hplen.resize((size_t)C.ld);
+                for (int d = 0; d < C.ld; d++)
+                    c->h_hplen[d] = (d <= 30 ? H.E_hairpin[d] : std::exp(H.hairpin30 - H.lxc * std::log(d / 30.0))) * std::exp(-H.s * d);
+            }
+            HIP_TRY(c, hipMemcpyAsync(c->d_coseq.p, cc.data(), cc.size(), hipMemcpyHostToDevice, c->s_dx));
+            HIP_TRY(c, hipMemcpyAsync(c->d_con.p, nn.data(), sizeof(int) * nn.size(), hipMemcpyHostToDevice, c->s_dx));
+            HIP_TRY(c, hipStreamSynchronize(c->s_dx));
+            C.seq = c->d_coseq.as<const uint8_t>(); C.n = c->d_con.as<const int>(); C.cut = c->d_con.as<const int>() + np;
+            C.tab = c->d_cotab.as<double>();
+            double* f = c->d_cof5.as<double>();
+            const size_t fs = (size_t)C.ld * np;
+            C.f5i = f; C.f5o = f + fs; C.xp = f + 2 * fs; C.xs = f + 3 * fs; C.xpo = f + 4 * fs; C.xso = f + 5 * fs;
+            C.bp = c->d_cobp.as<double>(); C.up = nullptr;
+            if (co_cons) {   // constraints over the concatenation s1+s2 (one string of length n1+n2 per pair)
+                std::vector<uint8_t> M((size_t)np * C.ld * C.ld);
+                std::string why;
+                for (int p = 0; p < np; p++) {
+                    const std::string joint = std::string(seqs[2 * p], lens[2 * p]) + std::string(seqs[2 * p + 1], lens[2 * p + 1]);
+                    if (!build_allow_mask(joint.c_str(), (int)joint.size(), co_cons[p] ? co_cons[p] : "", C.ld, M.data() + (size_t)p * C.ld * C.ld, &why))
+                        return fail(c, RH_ERR_ARG, "pair %d: %s", p, why.c_str());
+                }
+                if ((rc = ensure(c, c->d_coallow, M.size(), false))) return rc;
+                HIP_TRY(c, hipMemcpy(c->d_coallow.p, M.data(), M.size(), hipMemcpyHostToDevice));
+                C.allow = c->d_coallow.as<const uint8_t>();
+            }
+        }
+        X.seq = D.seq; X.n = D.n; X.tab = D.tab; X.hp = D.hp; X.hp_stride = D.tab_stride;
+    }
+    return RH_OK;
+}
+
+}  // namespace rh::host

@@ -110,7 +110,7 @@ def test_unknown_letters_and_unpairable_inputs(ctx, oracle):
 def test_batch_composition_does_not_change_results(ctx):
     """Results of a problem are bit-identical whether it runs alone or inside a ragged batch.  The sweeps choose their launch
     organisation by the longest sequence they see (strips of eight diagonals from 40 letters on), so sequences shorter than that get
-    a pass of their own next to longer ones (rh_api.hip: launch_mc_lin) -- the second batch below mixes 7 .. 39 letters with 300."""
+    a pass of their own next to longer ones (launch_contrafold.hip: launch_mc_lin) -- the second batch below mixes 7 .. 39 letters with 300."""
     rng = np.random.RandomState(99)
     a, b = rnd(rng, 73), rnd(rng, 58)
     bp_alone, z_alone = ctx.bpp(a)
