@@ -55,7 +55,7 @@ static size_t shape_key(const rh_ctx* c, int which)
                          (size_t)c->dx.ldd, (size_t)c->dx.tab_stride, (size_t)c->dx.n1max, (size_t)c->dx.n2max, (size_t)B.allow, (size_t)B.pk,
                          (size_t)c->far_pk, (size_t)B.rowp, (size_t)c->lookahead, (size_t)B.seeded, (size_t)c->mc.tab, (size_t)c->mc.ld, (size_t)c->d_vlin,
                          // the windowed grid and its pin offset are baked into the captured launches (launch_mc_vlin)
-                         (size_t)c->co_window, (size_t)(c->co_cut_min + 1), (size_t)(c->co_cut_max + 1)})
+                         (size_t)c->co_window, (size_t)(c->co_cut_min + 1), (size_t)(c->co_cut_max + 1), (size_t)(c->far2 + 2)})
             h = mix(h, v);
     } else if (which <= 1) {
         const McBatch& B = c->mc;
@@ -85,6 +85,11 @@ int compute_once(rh_ctx* c)
     c->n_far[0] = c->n_far[1] = c->n_far[2] = 0;
     c->last_path = 0;
     c->fallback_mc.clear(); c->fallback_dx.clear(); c->rescaled_mc.clear(); c->rescaled_dx.clear();
+    // the organisation of each sweep's linear first pass: decided here, on every compute (a replayed graph does not call its launcher),
+    // from switches and shapes that are all part of shape_key
+    const bool vienna = c->model == RH_MODEL_VIENNA_BL;
+    for (int phase = 0; phase < 2; phase++) c->plan[phase] = vienna ? plan_mc_vlin(c, phase, false, c->mc.nmax) : plan_mc_lin(c, phase, c->mc.nmax);
+    c->plan[2] = !vienna ? plan_dx_lin(c, c->dx_w) : c->hybrid == RH_HYBRID_COFOLD ? plan_mc_vlin(c, 0, true, c->co.nmax) : plan_dx_vlin();
     // sequence -> XCD affinity only when the batch spreads evenly over the 8 XCDs (speed only)
     const int pin = (c->has_mc && c->mc.ns % 8 == 0) ? 1 : 0;
     int rc;
@@ -99,8 +104,8 @@ int compute_once(rh_ctx* c)
     auto launch_co_lin = [&]() -> int {   // scaled linear sweeps over s1+s2; out-of-range values send the batch to the log-space kernels
         const int cpin = c->co.ns % 8 == 0 ? 1 : 0;
         return run_graphed(c, c->g_dx, shape_key(c, 3), c->s_dx, &c->n_launch[2], &c->n_far[2], [&] {
-            const int r = launch_mc_vlin(c, cpin, 0, true);
-            return r ? r : launch_mc_vlin(c, cpin, 1, true);
+            const int r = launch_mc_vlin(c, cpin, 0, true, plan_mc_vlin(c, 0, true, c->co.nmax));
+            return r ? r : launch_mc_vlin(c, cpin, 1, true, plan_mc_vlin(c, 1, true, c->co.nmax));
         });
     };
     if (c->has_dx && c->model == RH_MODEL_VIENNA_BL && c->hybrid == RH_HYBRID_COFOLD) {
@@ -125,7 +130,7 @@ int compute_once(rh_ctx* c)
         }
     } else if (c->has_dx) {
         if (c->mode != RH_MODE_LOG) {
-            if ((rc = run_graphed(c, c->g_dx, shape_key(c, 2), c->s_dx, &c->n_launch[2], &c->n_far[2], [&] { return launch_dx_lin_any(c); }))) return rc;
+            if ((rc = run_graphed(c, c->g_dx, shape_key(c, 2), c->s_dx, &c->n_launch[2], &c->n_far[2], [&] { return launch_dx_lin(c, c->plan[2]); }))) return rc;
             dx_lin_launched = true;
         } else {
             if ((rc = launch_dx_log(c))) return rc;
@@ -140,7 +145,7 @@ int compute_once(rh_ctx* c)
     if (c->has_mc && c->model == RH_MODEL_VIENNA_BL) {
         bool log_path = c->mode == RH_MODE_LOG;
         if (!log_path) {   // scaled linear sweeps; a sequence that leaves the double range sends the batch to the log-space kernels
-            if ((rc = run_graphed(c, c->g_in, shape_key(c, 0), c->s_mc, &c->n_launch[0], &c->n_far[0], [&] { return launch_mc_vlin(c, pin, 0, false); }))) return rc;
+            if ((rc = run_graphed(c, c->g_in, shape_key(c, 0), c->s_mc, &c->n_launch[0], &c->n_far[0], [&] { return launch_mc_vlin(c, pin, 0, false, c->plan[0]); }))) return rc;
             HIP_TRY(c, hipEventRecord(c->ev[1], c->s_mc));
             if (co_seed) {   // the inside tables of both molecules are final behind ev[1]
                 HIP_TRY(c, hipStreamWaitEvent(c->s_dx, c->ev[1], 0));
@@ -153,7 +158,7 @@ int compute_once(rh_ctx* c)
             }
             HIP_TRY(c, hipEventRecord(c->ev[5], c->s_mc));   // start of the outside phase (= ev[1] unless the seeded sweeps ran in between)
             out_from_ev5 = true;
-            if ((rc = run_graphed(c, c->g_out, shape_key(c, 1), c->s_mc, &c->n_launch[1], &c->n_far[1], [&] { return launch_mc_vlin(c, pin, 1, false); }))) return rc;
+            if ((rc = run_graphed(c, c->g_out, shape_key(c, 1), c->s_mc, &c->n_launch[1], &c->n_far[1], [&] { return launch_mc_vlin(c, pin, 1, false, c->plan[1]); }))) return rc;
             c->last_path = 1;
             if (c->mode == RH_MODE_AUTO) {
                 std::vector<int> bad(c->mc.ns);
@@ -183,9 +188,9 @@ int compute_once(rh_ctx* c)
         const bool on_rung = c->mode == RH_MODE_AUTO && c->scale_ladder && c->lin_primary >= 0 && c->lin_r;
         if (on_rung) c->lin = &c->lin_r[c->lin_primary];
         struct Back { rh_ctx* c; ~Back() { c->lin = &c->lin0; } } back{c};
-        if ((rc = run_graphed(c, c->g_in, shape_key(c, 0), c->s_mc, &c->n_launch[0], &c->n_far[0], [&] { return launch_mc_lin_any(c, pin, 0); }))) return rc;
+        if ((rc = run_graphed(c, c->g_in, shape_key(c, 0), c->s_mc, &c->n_launch[0], &c->n_far[0], [&] { return launch_mc_lin(c, pin, 0, c->plan[0]); }))) return rc;
         HIP_TRY(c, hipEventRecord(c->ev[1], c->s_mc));
-        if ((rc = run_graphed(c, c->g_out, shape_key(c, 1), c->s_mc, &c->n_launch[1], &c->n_far[1], [&] { return launch_mc_lin_any(c, pin, 1); }))) return rc;
+        if ((rc = run_graphed(c, c->g_out, shape_key(c, 1), c->s_mc, &c->n_launch[1], &c->n_far[1], [&] { return launch_mc_lin(c, pin, 1, c->plan[1]); }))) return rc;
         c->last_path = 1;
         if (c->mode == RH_MODE_AUTO) {  // did every sequence stay inside the double range?
             std::vector<int> bad(c->mc.ns);

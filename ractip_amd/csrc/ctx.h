@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cassert>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -61,6 +62,24 @@ struct GraphSlot {   // one captured launch sequence (see run_graphed)
     hipGraphExec_t exec = nullptr;
     size_t key = 0;
     int launches = 0, far = 0;
+};
+
+// The kernel organisation of one sweep (McCaskill inside, McCaskill outside, hybridization), decided once per compute from the
+// context's switches and the batch shape by plan_mc_lin / plan_mc_vlin / plan_dx_lin / plan_dx_vlin.  The launchers run it and
+// rh_batch_kernels reports it; nothing else reads the organisation switches.
+struct SweepPlan {
+    enum Org { kNone, kStrips, kPairs, kLookahead, kDiagonals, kDxStrip8, kDxSweep4, kDxSweepW };
+    enum Far { kFarNone, kFarLds, kFarGather, kFarPacked };   // block products: LDS/FMA kernel, MFMA with gathered or packed operand tiles
+    Org org = kNone;
+    int W = 0;              // wavefronts per 64-cell group (strips: per workgroup)
+    int BS = 0;             // block size of the far/near split of the O(n^3) terms (0: no block products)
+    int filt = 0;           // strips: the factored single-branch filter
+    Far far = kFarNone;
+    int far2_from = 0;      // packed products: the length from which a sequence takes the two-level form (0: no sequence does)
+    bool banded = false;    // packed products: block diagonal 2 of FM1 / FM is packed masked (the strips' banded near/far split)
+    bool repack2 = false;   // outside sweep: the inside sweep left block diagonal 2 packed in the other form
+    const char* fine = "";       // names rh_batch_kernels reports: the sweep kernel ...
+    const char* far_name = "";   // ... and the block-product kernel
 };
 
 struct Ctx {   // (the fields of rh_ctx, below)
@@ -130,7 +149,6 @@ struct Ctx {   // (the fields of rh_ctx, below)
     int strip = 3;                 // CONTRAfold linear path: KD = 8 diagonals per launch (mccaskill_strip.hip) with the banded near/far split;
                                    // RH_STRIP=0: the per-diagonal-pair kernels of mccaskill_lin.hip.  Bit 0 = inside sweep, bit 1 = outside sweep
     int far2 = -1;                 // two-level block products: -1 = by size (sequences of n >= 384), 0 / 1 forced (RH_FAR2)
-    int far2_next = -1;            // launch-sequence state of far_outside_step
     int strip_w = 8;               // wavefronts per strip workgroup (RH_STRIP_W = 4 | 8)
     // short sequences (kSmallMin <= n <= kSmallMax, CONTRAfold model, scaled linear path): one workgroup per sequence, one launch
     // (mccaskill_small.hip); chosen per sequence by its length alone, so a result does not depend on the rest of the batch.  The sweeps
@@ -160,6 +178,7 @@ struct Ctx {   // (the fields of rh_ctx, below)
     int lin_w_in = 4;              // ... of the inside kernel (fewer, longer wavefronts: less per-wavefront scalar overhead)
     int lin_bs = 16;               // block size of the far/near split of the O(n^3) terms (0 = off)
     int last_path = 0;             // 1 = linear, 2 = log-space, 3 = linear then log-space fallback
+    SweepPlan plan[3];             // of the linear first pass over the batch as uploaded: inside, outside, hybridization (compute_once)
     int max_w = 1;                 // accessibility widths 1..max_w (src/ractip.cpp:370-375); the CONTRAfold path has width 1 only
 
     // current batch (host mirror)
@@ -261,27 +280,53 @@ int ensure(rh_ctx* c, DevBuf& buf, size_t bytes, bool zero);
 // staging.hip
 int stage(rh_ctx* c, int ns, const char* const* seqs, const int* lens, bool with_mc, bool with_dx, const char* const* cons = nullptr,
           const char* const* co_cons = nullptr);
+// a kernel on one line with the name reported for it
+template <class K> struct Named { K kern; const char* name; };
+#define NAMED(...) {__VA_ARGS__, #__VA_ARGS__}
+template <class Row, size_t N, class Pred>
+const Row& row_of(const Row (&rows)[N], Pred&& is)
+{
+    for (const Row& r : rows) if (is(r)) return r;
+    assert(!"the plan names a kernel combination that has no row");
+    return rows[0];
+}
+// sequence-major launch order (sequence -> XCD affinity) or group-major
+inline dim3 seq_grid(int pin, int ns, int groups) { return pin ? dim3(ns, groups) : dim3(groups, ns); }
+// one pass of a McCaskill sweep on the scaled linear kernels: what the schedules and the block-product steps share
+struct SweepPass {
+    rh_ctx* c;
+    const SweepPlan& P;
+    const McBatch& B;    // the sequences of this pass
+    hipStream_t st;
+    int k;               // n_launch[k] / n_far[k] count it
+    int far2_next = -1;  // outside: macro block diagonals whose 64-block products are still to be launched (descending)
+    int last_block() const { return P.BS > 0 ? (B.nmax - 1) / P.BS : 0; }
+};
 // launch_contrafold.hip
 int launch_mc_log(rh_ctx* c, int pin, const McBatch& B, double* logz_out);
 int launch_mc_log(rh_ctx* c, int pin);
-int launch_mc_lin_any(rh_ctx* c, int pin, int phase);
-int far_inside_step(rh_ctx* c, const McBatch& B, hipStream_t st, int D, int last_block, int banded = 0);
-int far_outside_begin(rh_ctx* c, const McBatch& B, hipStream_t st, int last_block, int banded = 0, bool repack2 = false);
-int far_outside_step(rh_ctx* c, const McBatch& B, hipStream_t st, int D, int last_block);
-bool strip_inside(const rh_ctx* c, const McBatch& B);
-bool strip_outside(const rh_ctx* c, const McBatch& B);
+SweepPlan plan_mc_lin(const rh_ctx* c, int phase, int nmax);
+int launch_mc_lin(rh_ctx* c, int pin, int phase, const SweepPlan& P);
+void far_products(const rh_ctx* c, int phase, int nmax, bool mfma, SweepPlan* P);
+const char* far_name(SweepPlan::Far far, int BS, int phase);
+void far_inside_after(const SweepPass& S, int done);
+void far_outside_begin(SweepPass& S, int top);
+void far_outside_before(SweepPass& S, int d);
 std::vector<double> strip_weights(const LinModel& L, bool* ok_out = nullptr);
 // launch_vienna.hip
 int launch_mc_vienna(rh_ctx* c, int pin);
-int launch_mc_vlin(rh_ctx* c, int pin, int phase, bool co);
+SweepPlan plan_mc_vlin(const rh_ctx* c, int phase, bool co, int nmax);
+int launch_mc_vlin(rh_ctx* c, int pin, int phase, bool co, const SweepPlan& P);
 int launch_cofold(rh_ctx* c);
 int select_vlin(rh_ctx* c, int model);
 extern const double kVRungS[Ctx::kVRungs];
 // launch_duplex.hip
 int launch_dx_log(rh_ctx* c, const DxBatch& D);
 int launch_dx_log(rh_ctx* c);
-template <int W> int launch_dx_lin_on(rh_ctx* c, DxLinBatch X, const DxLinModel* dm, const DxLinModel& hm, double* logz_out, int* bad);
-int launch_dx_lin_any(rh_ctx* c);
+SweepPlan plan_dx_lin(const rh_ctx* c, int w);
+SweepPlan plan_dx_vlin();
+int launch_dx_lin_on(rh_ctx* c, const SweepPlan& P, DxLinBatch X, const DxLinModel* dm, const DxLinModel& hm, double* logz_out, int* bad);
+int launch_dx_lin(rh_ctx* c, const SweepPlan& P);
 int launch_dx_vlin(rh_ctx* c);
 int launch_dx_vlog(rh_ctx* c);
 // fallbacks.hip

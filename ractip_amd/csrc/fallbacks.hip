@@ -194,8 +194,8 @@ int retry_mc_lin_rungs(rh_ctx* c, std::vector<int>* rest)
         c->mc = S;
         c->lin = rung < 0 ? &c->lin0 : &c->lin_r[rung];
         const int spin = nsub % 8 == 0 ? 1 : 0;
-        rc = launch_mc_lin_any(c, spin, 0);
-        if (!rc) rc = launch_mc_lin_any(c, spin, 1);
+        rc = launch_mc_lin(c, spin, 0, plan_mc_lin(c, 0, S.nmax));   // (plans of the sub-batch: c->plan keeps the first pass's)
+        if (!rc) rc = launch_mc_lin(c, spin, 1, plan_mc_lin(c, 1, S.nmax));
         if (rc) { restore(); return rc; }
         // flags and log Z of the sub-batch are the first nsub entries of d_bad / d_mclogz
         std::vector<int> sbad(nsub);
@@ -289,7 +289,7 @@ int retry_dx_lin_rungs(rh_ctx* c, std::vector<int>* rest)
         const int saved_chunks = c->lz_chunks;
         c->lz_chunks = (n1max + n2max - 1 + 15) / 16;   // (<= the main batch's: d_zpart / d_zbar are large enough)
         // (always the four-wavefront organisation, whatever RH_DX_W chose for the first pass: see ADVICE.md)
-        rc = launch_dx_lin_on<4>(c, X, c->d_dxlin_r[r], c->h_dxlin_r[r], sub_logz, sub_bad);
+        rc = launch_dx_lin_on(c, plan_dx_lin(c, 4), X, c->d_dxlin_r[r], c->h_dxlin_r[r], sub_logz, sub_bad);
         c->lz_chunks = saved_chunks;
         if (rc) return rc;
         std::vector<int> bad(nsub);

@@ -41,281 +41,288 @@ int launch_mc_log(rh_ctx* c, int pin, const McBatch& B, double* logz_out)
 }
 int launch_mc_log(rh_ctx* c, int pin) { return launch_mc_log(c, pin, c->mc, c->d_mclogz.as<double>()); }
 
-// ---- block products (mccaskill_far.hip, BS = 16) on re-laid operand tiles: the tiles of block diagonal Dblk are packed once,
-// right after their last cell is final, and then read by every product that uses them as two contiguous 2 KB fragments.
+// ---- the kernels of the scaled linear sweeps, each on one line with the name rh_batch_kernels reports for it: plan_mc_lin takes
+// the name and the schedules take the kernel from the same row
+using InsideDiagK = void (*)(McBatch, const LinModel*, int, double, int);
+struct DiagKernels { int W, BS; Named<InsideDiagK> in; Named<decltype(&lin_outside_diag<4, 16>)> out; };   // one launch per diagonal
+#define DIAG(W, BS) {W, BS, NAMED(lin_inside_diag<W, BS, 0>), NAMED(lin_outside_diag<W, BS>)}
+const DiagKernels kDiag[] = {DIAG(8, 0), DIAG(16, 0), DIAG(4, 16), DIAG(8, 16), DIAG(16, 16), DIAG(8, 32), DIAG(16, 32)};
+const Named<InsideDiagK> kInsidePair = NAMED(lin_inside_diag<4, 16, 3>);    // two diagonals per launch
+// look-ahead pairs of launches: the even diagonal also accumulates the sums of the next one, which then needs one wavefront per group
+const Named<InsideDiagK> kInsideAhead[2] = {NAMED(lin_inside_diag<4, 16, 1>), NAMED(lin_inside_diag<4, 16, 2>)};
+struct PairKernels { int W; Named<decltype(&lin_outside_pair<4, 16>)> out; };
+const PairKernels kOutsidePair[] = {{4, NAMED(lin_outside_pair<4, 16>)}, {8, NAMED(lin_outside_pair<8, 16>)}};
+struct StripKernels { int W, filt; Named<decltype(&lin_inside_strip<8, 4, 0>)> in; Named<decltype(&lin_outside_strip<8, 4, 0>)> out; };   // KD = 8 diagonals per launch
+#define STRIP(W, FILT) {W, FILT, NAMED(lin_inside_strip<8, W, FILT>), NAMED(lin_outside_strip<8, W, FILT>)}
+const StripKernels kStrip[] = {STRIP(4, 0), STRIP(8, 1), STRIP(8, 0)};
+// block products: LDS/FMA kernels by block size, MFMA kernels on gathered and on packed operand tiles ([0] inside, [1] outside)
+struct LdsKernels { int BS; Named<decltype(&lin_far_inside<16>)> in, out; };
+const LdsKernels kLds[] = {{16, NAMED(lin_far_inside<16>), NAMED(lin_far_outside<16>)}, {32, NAMED(lin_far_inside<32>), NAMED(lin_far_outside<32>)}};
+const Named<decltype(&lin_far_inside_mfma)> kFarGather[2] = {NAMED(lin_far_inside_mfma), NAMED(lin_far_outside_mfma)};
+const Named<decltype(&lin_far_inside_pk)> kFarPacked[2] = {NAMED(lin_far_inside_pk), NAMED(lin_far_outside_pk)};
+#undef DIAG
+#undef STRIP
+static const DiagKernels& diag_kernels(int W, int BS) { return row_of(kDiag, [&](const DiagKernels& r) { return r.W == W && r.BS == BS; }); }
+static const PairKernels& pair_kernels(int W) { return row_of(kOutsidePair, [&](const PairKernels& r) { return r.W == W; }); }
+static const StripKernels& strip_kernels(int W, int filt) { return row_of(kStrip, [&](const StripKernels& r) { return r.W == W && r.filt == filt; }); }
+static const LdsKernels& lds_kernels(int BS) { return row_of(kLds, [&](const LdsKernels& r) { return r.BS == BS; }); }
+
+// ---- block products on v_mfma_f64_16x16x4_f64 (mccaskill_far.hip, BS = 16), by gather or on re-laid operand tiles: the tiles of
+// block diagonal Dblk are packed once, right after their last cell is final, and then read by every product that uses them as two
+// contiguous 2 KB fragments.
 //   inside : far(D) uses FM1/FM tiles of block diagonals 2..D-2; block diagonal D-2 completes with fine diagonal (D-1)*16-1
 //   outside: far(D) uses FM2o tiles of block diagonals >= D+2 (final before fine diagonal (D+1)*16-1) and FM1/FM tiles of
 //            every block diagonal (the last two are packed when the outside phase starts)
-// returns the number of launches it counts: 1 (the pack launch rides with its product; bench.py adds its traffic to the product's)
-// two-level products (64x64 macro tiles under the 16x16 tile kernels, mccaskill_far.hip) pay from 6 macro blocks per axis on
-// (measured: n = 200, 300 equal, n = 400 +2 %, n = 500 +4 %, n = 2000 +27 %)
-// returns the length from which a SEQUENCE takes the two-level form (0: no sequence of this batch does)
-int far_two_level(const rh_ctx* c, const McBatch& B)
+// Each step counts as one launch: the pack launch rides with its product (bench.py adds its traffic to the product's).
+// Two-level products (64x64 macro tiles under the 16x16 tile kernels) pay from 6 macro blocks per axis on (measured: n = 200, 300
+// equal, n = 400 +2 %, n = 500 +4 %, n = 2000 +27 %): SweepPlan::far2_from is the length from which a SEQUENCE takes that form.
+const char* far_name(SweepPlan::Far far, int BS, int phase)
+{
+    switch (far) {
+        case SweepPlan::kFarLds: return phase == 0 ? lds_kernels(BS).in.name : lds_kernels(BS).out.name;
+        case SweepPlan::kFarGather: return kFarGather[phase].name;
+        case SweepPlan::kFarPacked: return kFarPacked[phase].name;
+        default: return "";
+    }
+}
+// the block-product form of a sweep with block size P->BS (mfma: on the MFMA kernels, BS = 16) and the name reported for it
+void far_products(const rh_ctx* c, int phase, int nmax, bool mfma, SweepPlan* P)
 {
     const int from = c->far2 >= 0 ? (c->far2 ? 1 : 0) : 384;
-    return from > 0 && B.nmax >= from ? from : 0;
+    P->far = P->BS == 0 ? SweepPlan::kFarNone : !mfma ? SweepPlan::kFarLds : c->far_pk ? SweepPlan::kFarPacked : SweepPlan::kFarGather;
+    P->far2_from = P->far == SweepPlan::kFarPacked && from > 0 && nmax >= from ? from : 0;
+    P->far_name = far_name(P->far, P->BS, phase);
 }
 
-int far_inside_step(rh_ctx* c, const McBatch& B, hipStream_t st, int D, int last_block, int banded)
+// schedule of the block products (BS > 0) against the fine diagonals:
+//   inside : far(D) right after fine diagonal (D-1)*BS-1  (its operands are final, tile (I,I+D) starts at (D-1)*BS+1)
+//   outside: far(D) right before fine diagonal (D+1)*BS-1 (operands: spans >= (D+1)*BS+1, already final)
+void far_inside_after(const SweepPass& S, int done)   // done: the fine diagonals 0 .. done-1 are final
 {
-    if (!c->far_pk) { KLAUNCH(c, 1, lin_far_inside_mfma, dim3(last_block - D + 1, B.ns), dim3(256), st, B, D); return 1; }
-    const int l2 = far_two_level(c, B);
-    KLAUNCH(c, 1, lin_pack_tiles<0>, dim3(B.nb - (D - 2), B.ns, 2), dim3(256), st, B, D - 2, 0, banded);
-    if (l2 && (D + 3) % 4 == 0) {   // D = 4*D2-3: every operand tile of macro block diagonal D2 is packed now
-        const int D2 = (D + 3) / 4, last2 = (B.nmax - 1) / 64;
-        if (D2 >= 4 && D2 <= last2) KLAUNCH(c, 1, lin_far2_inside, dim3(last2 - D2 + 1, B.ns), dim3(256), st, B, D2, l2);
+    rh_ctx* c = S.c;
+    const McBatch& B = S.B;
+    const int D = S.P.BS ? done / S.P.BS + 1 : 0, last_block = S.last_block(), l2 = S.P.far2_from;
+    if (S.P.BS == 0 || done % S.P.BS != 0 || D < 4 || D > last_block) return;
+    if (S.P.far == SweepPlan::kFarLds) KLAUNCH(c, 1, (lds_kernels(S.P.BS).in.kern), dim3(last_block - D + 1, B.ns), dim3(256), S.st, B, D);
+    else if (S.P.far == SweepPlan::kFarGather) KLAUNCH(c, 1, (kFarGather[0].kern), dim3(last_block - D + 1, B.ns), dim3(256), S.st, B, D);
+    else {
+        KLAUNCH(c, 1, lin_pack_tiles<0>, dim3(B.nb - (D - 2), B.ns, 2), dim3(256), S.st, B, D - 2, 0, (int)S.P.banded);
+        if (l2 && (D + 3) % 4 == 0) {   // D = 4*D2-3: every operand tile of macro block diagonal D2 is packed now
+            const int D2 = (D + 3) / 4, last2 = (B.nmax - 1) / 64;
+            if (D2 >= 4 && D2 <= last2) KLAUNCH(c, 1, lin_far2_inside, dim3(last2 - D2 + 1, B.ns), dim3(256), S.st, B, D2, l2);
+        }
+        KLAUNCH(c, 1, (kFarPacked[0].kern), dim3(last_block - D + 1, B.ns), dim3(256), S.st, B, D, l2);
     }
-    KLAUNCH(c, 1, lin_far_inside_pk, dim3(last_block - D + 1, B.ns), dim3(256), st, B, D, l2);
-    return 1;
+    c->n_launch[S.k]++;
+    c->n_far[S.k]++;
 }
-// repack2: the inside sweep left block diagonal 2 packed in the other form (masked for the banded split / plain for the block split)
-int far_outside_begin(rh_ctx* c, const McBatch& B, hipStream_t st, int last_block, int banded, bool repack2)
+void far_outside_before(SweepPass& S, int d)
 {
-    if (!c->far_pk) return 0;
-    c->far2_next = (B.nmax - 1) / 64;   // macro block diagonals whose 64-block products are still to be launched (descending)
-    if (repack2 && last_block - 1 > 2) KLAUNCH(c, 3, lin_pack_tiles<1>, dim3(B.nb - 2, B.ns, 2), dim3(256), st, B, 2, 0, banded);
-    for (int Dblk = std::max(2, last_block - 1); Dblk <= last_block; Dblk++)
-        KLAUNCH(c, 3, lin_pack_tiles<1>, dim3(B.nb - Dblk, B.ns, 2), dim3(256), st, B, Dblk, 0, banded);
-    return 0;
-}
-int far_outside_step(rh_ctx* c, const McBatch& B, hipStream_t st, int D, int last_block)
-{
-    if (!c->far_pk) { KLAUNCH(c, 3, lin_far_outside_mfma, dim3(last_block - D + 1, B.ns, 2), dim3(256), st, B, D); return 1; }
-    const int l2 = far_two_level(c, B);
-    if (D + 2 <= last_block) KLAUNCH(c, 3, lin_pack_tiles<1>, dim3(B.nb - (D + 2), B.ns, 1), dim3(256), st, B, D + 2, 1, 0);
-    if (l2) {   // macro block diagonal D2 holds tile block diagonals 4*D2-3 .. 4*D2+3: its products go first, their FM2o tiles (block diagonals >= 4*D2+5) are packed
-        const int last2 = (B.nmax - 1) / 64;
-        for (; c->far2_next >= 0 && 4 * c->far2_next + 3 >= D; c->far2_next--)
-            KLAUNCH(c, 3, lin_far2_outside, dim3(last2 - c->far2_next + 1, B.ns, 2), dim3(256), st, B, c->far2_next, l2);
+    rh_ctx* c = S.c;
+    const McBatch& B = S.B;
+    const int D = S.P.BS ? (d + 1) / S.P.BS - 1 : 0, last_block = S.last_block(), l2 = S.P.far2_from;
+    if (S.P.BS == 0 || (d + 1) % S.P.BS != 0 || D < 0 || D > last_block) return;
+    if (S.P.far == SweepPlan::kFarLds) KLAUNCH(c, 3, (lds_kernels(S.P.BS).out.kern), dim3(last_block - D + 1, B.ns, 2), dim3(256), S.st, B, D);
+    else if (S.P.far == SweepPlan::kFarGather) KLAUNCH(c, 3, (kFarGather[1].kern), dim3(last_block - D + 1, B.ns, 2), dim3(256), S.st, B, D);
+    else {
+        if (D + 2 <= last_block) KLAUNCH(c, 3, lin_pack_tiles<1>, dim3(B.nb - (D + 2), B.ns, 1), dim3(256), S.st, B, D + 2, 1, 0);
+        if (l2) {   // macro block diagonal D2 holds tile block diagonals 4*D2-3 .. 4*D2+3: its products go first, their FM2o tiles (block diagonals >= 4*D2+5) are packed
+            const int last2 = (B.nmax - 1) / 64;
+            for (; S.far2_next >= 0 && 4 * S.far2_next + 3 >= D; S.far2_next--)
+                KLAUNCH(c, 3, lin_far2_outside, dim3(last2 - S.far2_next + 1, B.ns, 2), dim3(256), S.st, B, S.far2_next, l2);
+        }
+        KLAUNCH(c, 3, (kFarPacked[1].kern), dim3(last_block - D + 1, B.ns, 2), dim3(256), S.st, B, D, l2);
     }
-    KLAUNCH(c, 3, lin_far_outside_pk, dim3(last_block - D + 1, B.ns, 2), dim3(256), st, B, D, l2);
-    return 1;
+    c->n_launch[S.k]++;
+    c->n_far[S.k]++;
+}
+// start of the outside sweep at fine diagonal `top`: the last operand tiles are packed, and the tiles whose first cell would come
+// before `top` get their (empty) far sums
+void far_outside_begin(SweepPass& S, int top)
+{
+    if (S.P.BS == 0) return;
+    rh_ctx* c = S.c;
+    const McBatch& B = S.B;
+    const int last_block = S.last_block(), banded = S.P.banded;
+    if (S.P.far == SweepPlan::kFarPacked) {
+        S.far2_next = (B.nmax - 1) / 64;   // macro block diagonals whose 64-block products are still to be launched (descending)
+        if (S.P.repack2 && last_block - 1 > 2) KLAUNCH(c, 3, lin_pack_tiles<1>, dim3(B.nb - 2, B.ns, 2), dim3(256), S.st, B, 2, 0, banded);
+        for (int Dblk = std::max(2, last_block - 1); Dblk <= last_block; Dblk++)
+            KLAUNCH(c, 3, lin_pack_tiles<1>, dim3(B.nb - Dblk, B.ns, 2), dim3(256), S.st, B, Dblk, 0, banded);
+    }
+    for (int d = (last_block + 1) * S.P.BS - 1; d > top; d -= S.P.BS) far_outside_before(S, d);
 }
 
 // ---- McCaskill sweeps, scaled linear-space path (fast; flags sequences that left the double range)
-// BS > 0: block products (mccaskill_far.hip) take the k-terms of complete blocks; schedule:
-//   inside : far(D) right after fine diagonal (D-1)*BS-1  (its operands are final, tile (I,I+D) starts at (D-1)*BS+1)
-//   outside: far(D) right before fine diagonal (D+1)*BS-1 (operands: spans >= (D+1)*BS+1, already final)
-// the strip kernels need the packed block products (masked tiles) and at least one strip behind the 32 bootstrap diagonals
-bool strip_inside(const rh_ctx* c, const McBatch& B) { return (c->strip & 1) && c->far_pk && c->far_mfma && c->lin_bs == 16 && B.nmax >= kStripMinN; }
-bool strip_outside(const rh_ctx* c, const McBatch& B) { return (c->strip & 2) && c->far_pk && c->far_mfma && c->lin_bs == 16 && B.nmax >= kStripMinN; }
-
-// the sweeps of one phase over the sequences B shows (lengths 0 hide a sequence); BR: the batch as uploaded (lin_init / lin_finish /
-// mc_unpaired see every sequence)
-template <int W, int BS>
-int launch_mc_lin_body(rh_ctx* c, int pin, int phase, const McBatch& B, const McBatch& BR, bool init, bool finish)
+// The organisation of one sweep over sequences of up to nmax letters.  W = 4, BS = 16 has every organisation; the others one launch
+// per diagonal (outside, W = 8: diagonal pairs too).  The strip kernels need the packed block products (masked tiles) and at least
+// one strip behind the 32 bootstrap diagonals.
+SweepPlan plan_mc_lin(const rh_ctx* c, int phase, int nmax)
 {
-    int* bad = c->d_bad.as<int>();
-    const int last_block = BS > 0 ? (B.nmax - 1) / BS : 0;
-    if (phase == 0) {
-    if (init) hipLaunchKernelGGL(lin_init, dim3((BR.ns + 63) / 64), dim3(64), 0, c->s_mc, BR, c->lin->d, bad);
-    if constexpr (W == 4 && BS == 16) {
-        if (strip_inside(c, B)) {
-            // diagonals 0..31 by pairs (every row is "near" there), then strips of kStripKD diagonals (mccaskill_strip.hip)
-            constexpr int KD = 8, GS = 64 - (KD - 1);
-            for (int d = 0; d < 32; d += 2) {
-                const int groups = (std::max(B.nmax - 1 - d, 0) + 62) / 63 + 1;
-                KLAUNCH(c, 0, (lin_inside_diag<4, 16, 3>), pin ? dim3(B.ns, groups) : dim3(groups, B.ns), dim3(64 * W), c->s_mc, B, c->lin->d, d,
-                        std::exp(-c->lin->h.s * d), pin);
-                c->n_launch[0]++;
-            }
-            int d0 = 32;
-            for (; d0 <= B.nmax - 2; d0 += KD) {
-                const int groups = (std::max(B.nmax - 1 - d0, 0) + GS - 1) / GS + 1;
-                if (c->strip_w == 4)
-                    KLAUNCH(c, 0, (lin_inside_strip<KD, 4, 0>), pin ? dim3(B.ns, groups) : dim3(groups, B.ns), dim3(256), c->s_mc, B, c->lin->d, c->lin->wT, d0,
-                            d0 == 32 ? 32 : d0 - KD + 2, std::exp(-c->lin->h.s * d0), (pin && c->strip_xcd) ? 2 : pin);
-                else if (c->strip_filt && c->strip_filt_ok)
-                    KLAUNCH(c, 0, (lin_inside_strip<KD, 8, 1>), pin ? dim3(B.ns, groups) : dim3(groups, B.ns), dim3(512), c->s_mc, B, c->lin->d, c->lin->wT, d0,
-                            d0 == 32 ? 32 : d0 - KD + 2, std::exp(-c->lin->h.s * d0), (pin && c->strip_xcd) ? 2 : pin);
-                else
-                    KLAUNCH(c, 0, (lin_inside_strip<KD, 8, 0>), pin ? dim3(B.ns, groups) : dim3(groups, B.ns), dim3(512), c->s_mc, B, c->lin->d, c->lin->wT, d0,
-                            d0 == 32 ? 32 : d0 - KD + 2, std::exp(-c->lin->h.s * d0), (pin && c->strip_xcd) ? 2 : pin);
-                c->n_launch[0]++;
-                if ((d0 + KD) % BS == 0) {
-                    const int D = (d0 + KD) / BS + 1;
-                    if (D >= 4 && D <= last_block) { c->n_launch[0] += far_inside_step(c, B, c->s_mc, D, last_block, 1); c->n_far[0]++; }
-                }
-            }
-            hipLaunchKernelGGL(lin_f5i_tail, dim3(B.ns), dim3(256), 0, c->s_mc, B, c->lin->d, d0 - KD + 2);
-            return RH_OK;
-        }
-        if (c->lookahead == 2) {   // two diagonals per launch (lin_inside_diag MODE 3); the last launch may hold only F5i[nmax]
-            for (int d = 0; d <= B.nmax; d += 2) {
-                const int groups = (std::max(B.nmax - 1 - d, 0) + 62) / 63 + 1;
-                KLAUNCH(c, 0, (lin_inside_diag<4, 16, 3>), pin ? dim3(B.ns, groups) : dim3(groups, B.ns), dim3(64 * W), c->s_mc, B, c->lin->d, d,
-                        std::exp(-c->lin->h.s * d), pin);
-                c->n_launch[0]++;
-                if ((d + 2) % BS == 0) {
-                    const int D = (d + 2) / BS + 1;
-                    if (D >= 4 && D <= last_block) { c->n_launch[0] += far_inside_step(c, B, c->s_mc, D, last_block); c->n_far[0]++; }
-                }
-            }
-            return RH_OK;
-        }
+    SweepPlan P;
+    const int w = phase == 0 ? c->lin_w_in : c->lin_w;
+    P.BS = c->lin_bs == 0 || c->lin_bs == 32 ? c->lin_bs : 16;
+    P.W = w == 16 ? 16 : (w == 4 && P.BS == 16 ? 4 : 8);
+    const bool all_orgs = P.W == 4 && P.BS == 16, strips_ok = c->far_pk && c->far_mfma && c->lin_bs == 16 && nmax >= kStripMinN;
+    const bool strips_on = (c->strip & (phase == 0 ? 1 : 2)) && strips_ok, strips = all_orgs && strips_on;
+    const StripKernels& strip = strip_kernels(c->strip_w, c->strip_w == 8 && c->strip_filt && c->strip_filt_ok);
+    const DiagKernels& diag = diag_kernels(P.W, P.BS);
+    bool mfma = P.BS == 16 && c->far_mfma;
+    P.org = SweepPlan::kDiagonals;
+    P.fine = phase == 0 ? diag.in.name : diag.out.name;
+    if (strips) {
+        P.org = SweepPlan::kStrips;
+        P.W = strip.W;
+        P.filt = strip.filt;
+    } else if (phase == 0 && all_orgs && c->lookahead == 2) {
+        P.org = SweepPlan::kPairs;
+        P.fine = kInsidePair.name;
+        mfma = true;   // (this schedule has the MFMA products whatever RH_FAR_MFMA says)
+    } else if (phase == 0 && all_orgs && c->lookahead) {
+        P.org = SweepPlan::kLookahead;
+        P.fine = kInsideAhead[0].name;
+    } else if (phase == 1 && mfma && (P.W == 4 || P.W == 8) && c->lookahead == 2) {
+        P.org = SweepPlan::kPairs;
+        P.fine = pair_kernels(P.W).out.name;
     }
-    for (int d = 0; d <= B.nmax - 1; d++) {
-        const int groups = (std::max(B.nmax - 1 - d, 0) + 63) / 64 + 1;
-        if constexpr (W == 4 && BS == 16) {
-            if (c->lookahead && (d & 1) == 0)      // even diagonal: also accumulates the look-ahead sums of d+1 ...
-                KLAUNCH(c, 0, (lin_inside_diag<4, 16, 1>), pin ? dim3(B.ns, groups) : dim3(groups, B.ns), dim3(64 * W), c->s_mc, B, c->lin->d, d,
-                        std::exp(-c->lin->h.s * d), pin);
-            else if (c->lookahead)                 // ... which then needs one wavefront per group
-                KLAUNCH(c, 0, (lin_inside_diag<4, 16, 2>), pin ? dim3(B.ns, groups) : dim3(groups, B.ns), dim3(64), c->s_mc, B, c->lin->d, d,
-                        std::exp(-c->lin->h.s * d), pin);
-            else
-                KLAUNCH(c, 0, (lin_inside_diag<W, BS, 0>), pin ? dim3(B.ns, groups) : dim3(groups, B.ns), dim3(64 * W), c->s_mc, B, c->lin->d, d,
-                        std::exp(-c->lin->h.s * d), pin);
-        } else {
-            KLAUNCH(c, 0, (lin_inside_diag<W, BS, 0>), pin ? dim3(B.ns, groups) : dim3(groups, B.ns), dim3(64 * W), c->s_mc, B, c->lin->d, d,
-                    std::exp(-c->lin->h.s * d), pin);
-        }
-        c->n_launch[0]++;
-        if (BS > 0 && (d + 1) % BS == 0) {
-            const int D = (d + 1) / BS + 1;
-            if (D >= 4 && D <= last_block) {
-                if (BS == 16 && c->far_mfma) c->n_launch[0] += far_inside_step(c, B, c->s_mc, D, last_block);
-                else {
-                    KLAUNCH(c, 1, lin_far_inside<(BS > 0 ? BS : 16)>, dim3(last_block - D + 1, B.ns), dim3(256), c->s_mc, B, D);
-                    c->n_launch[0]++;
-                }
-                c->n_far[0]++;
-            }
-        }
-    }
-    return RH_OK;
-    }
-    const bool in_banded = (W == 4 && BS == 16) && strip_inside(c, B);
-    if constexpr (W == 4 && BS == 16) {
-        if (strip_outside(c, B)) {
-            // strips of KD diagonals from the top (mccaskill_strip.hip), banded near/far split: block diagonal 2 of FM1 / FM is packed masked
-            constexpr int KD = 8, GS = 64 - (KD - 1);
-            c->n_launch[1] += far_outside_begin(c, B, c->s_mc, last_block, 1, !in_banded);
-            const int d0_top = (B.nmax - 2) | (KD - 1);
-            for (int D = last_block; D >= 0 && (D + 1) * BS - 1 > d0_top; D--) { c->n_launch[1] += far_outside_step(c, B, c->s_mc, D, last_block); c->n_far[1]++; }
-            hipLaunchKernelGGL(lin_f5o_head, dim3(B.ns), dim3(256), 0, c->s_mc, B, c->lin->d, B.nmax - 1, d0_top - 5);
-            for (int d0 = d0_top; d0 >= KD - 1; d0 -= KD) {
-                if ((d0 + 1) % BS == 0) {
-                    const int D = (d0 + 1) / BS - 1;
-                    if (D >= 0 && D <= last_block) { c->n_launch[1] += far_outside_step(c, B, c->s_mc, D, last_block); c->n_far[1]++; }
-                }
-                const int groups = (std::max(B.nmax - 1 - (d0 - (KD - 1)), 0) + GS - 1) / GS + 1;
-                if (c->strip_w == 4)
-                    KLAUNCH(c, 2, (lin_outside_strip<KD, 4, 0>), pin ? dim3(B.ns, groups) : dim3(groups, B.ns), dim3(256), c->s_mc, B, c->lin->d, c->lin->wT, d0,
-                            d0 - 6, d0 - 13, (pin && c->strip_xcd) ? 2 : pin, bad);
-                else if (c->strip_filt && c->strip_filt_ok)
-                    KLAUNCH(c, 2, (lin_outside_strip<KD, 8, 1>), pin ? dim3(B.ns, groups) : dim3(groups, B.ns), dim3(512), c->s_mc, B, c->lin->d, c->lin->wT, d0,
-                            d0 - 6, d0 - 13, (pin && c->strip_xcd) ? 2 : pin, bad);
-                else
-                    KLAUNCH(c, 2, (lin_outside_strip<KD, 8, 0>), pin ? dim3(B.ns, groups) : dim3(groups, B.ns), dim3(512), c->s_mc, B, c->lin->d, c->lin->wT, d0,
-                            d0 - 6, d0 - 13, (pin && c->strip_xcd) ? 2 : pin, bad);
-                c->n_launch[1]++;
-            }
-            if (finish) hipLaunchKernelGGL(lin_finish, dim3((BR.ns + 63) / 64), dim3(64), 0, c->s_mc, BR, c->lin->d, c->d_mclogz.as<double>(), bad);
-            if (finish) hipLaunchKernelGGL(mc_unpaired, dim3((BR.nmax + 63) / 64, BR.ns), dim3(256), 0, c->s_mc, BR);
-            return RH_OK;
-        }
-    }
-    if (BS == 16 && c->far_mfma) c->n_launch[1] += far_outside_begin(c, B, c->s_mc, last_block, 0, in_banded);
-    if (BS > 0)  // tiles whose first cell would come before the first outside diagonal: their far sums are empty
-        for (int D = last_block; D >= 0 && (D + 1) * BS - 1 > B.nmax - 2; D--) {
-            if (BS == 16 && c->far_mfma) c->n_launch[1] += far_outside_step(c, B, c->s_mc, D, last_block);
-            else {
-                KLAUNCH(c, 3, lin_far_outside<(BS > 0 ? BS : 16)>, dim3(last_block - D + 1, B.ns, 2), dim3(256), c->s_mc, B, D);
-                c->n_launch[1]++;
-            }
-            c->n_far[1]++;
-        }
-    if constexpr (BS == 16 && (W == 8 || W == 4)) {
-        if (c->lookahead == 2 && c->far_mfma) {   // two diagonals per launch (lin_outside_pair)
-            // pairs are (odd, even) whatever the batch: a sequence's results do not depend on its neighbours' lengths
-            for (int d = (B.nmax - 2) | 1; d >= 0; d -= 2) {
-                for (int r = d; r >= d - 1 && r >= 0; r--)   // block products whose tiles start on either diagonal of the pair
-                    if ((r + 1) % BS == 0) {
-                        const int D = (r + 1) / BS - 1;
-                        if (D >= 0 && D <= last_block) { c->n_launch[1] += far_outside_step(c, B, c->s_mc, D, last_block); c->n_far[1]++; }
-                    }
-                const int ncol = B.nmax - 1 - d + 1;          // columns of the longer diagonal d-1 (d = 0: diagonal 0 alone, one less)
-                const int groups = std::max(1, (ncol - 1 + 62) / 63) + 1;
-                KLAUNCH(c, 2, (lin_outside_pair<W, BS>), pin ? dim3(B.ns, groups) : dim3(groups, B.ns), dim3(64 * W), c->s_mc, B, c->lin->d, d,
-                        d, pin, bad);
-                c->n_launch[1]++;
-            }
-            if (finish) hipLaunchKernelGGL(lin_finish, dim3((BR.ns + 63) / 64), dim3(64), 0, c->s_mc, BR, c->lin->d, c->d_mclogz.as<double>(), bad);
-            if (finish) hipLaunchKernelGGL(mc_unpaired, dim3((BR.nmax + 63) / 64, BR.ns), dim3(256), 0, c->s_mc, BR);
-            return RH_OK;
-        }
-    }
-    for (int d = B.nmax - 2; d >= 0; d--) {
-        if (BS > 0 && (d + 1) % BS == 0) {
-            const int D = (d + 1) / BS - 1;
-            if (D >= 0 && D <= last_block) {
-                if (BS == 16 && c->far_mfma) c->n_launch[1] += far_outside_step(c, B, c->s_mc, D, last_block);
-                else {
-                    KLAUNCH(c, 3, lin_far_outside<(BS > 0 ? BS : 16)>, dim3(last_block - D + 1, B.ns, 2), dim3(256), c->s_mc, B, D);
-                    c->n_launch[1]++;
-                }
-                c->n_far[1]++;
-            }
-        }
-        const int groups = (B.nmax - 1 - d + 63) / 64 + 1;
-        KLAUNCH(c, 2, (lin_outside_diag<W, BS>), pin ? dim3(B.ns, groups) : dim3(groups, B.ns), dim3(64 * W), c->s_mc, B,
-                           c->lin->d, d, pin, bad);
-        c->n_launch[1]++;
-    }
-    if (finish) hipLaunchKernelGGL(lin_finish, dim3((BR.ns + 63) / 64), dim3(64), 0, c->s_mc, BR, c->lin->d, c->d_mclogz.as<double>(), bad);
-    if (finish) hipLaunchKernelGGL(mc_unpaired, dim3((BR.nmax + 63) / 64, BR.ns), dim3(256), 0, c->s_mc, BR);
-    return RH_OK;
+    far_products(c, phase, nmax, mfma, &P);
+    // packed tiles of block diagonal 2: masked for the strips' banded near/far split, plain otherwise; the outside sweep packs them
+    // again when the inside sweep left the other form.  (What the inside sweep left is judged with THIS sweep's W, as it always has
+    // been: right unless RH_LIN_W_IN differs from RH_LIN_W while both strip bits are set.)
+    P.banded = strips;
+    P.repack2 = phase == 1 && strips != (all_orgs && (c->strip & 1) && strips_ok);
+    // The strip kernels are reported whenever the strip switches hold: also for W != 4, which runs one launch per diagonal.  With
+    // RH_FAR_MFMA=0 the inside sweep is reported as one launch per diagonal with the LDS products; it runs diagonal pairs with the
+    // MFMA products.  (Kept: the strings are an interface of bench.py and the profiles.)
+    if (strips_on) P.fine = phase == 0 ? strip.in.name : strip.out.name;
+    if (phase == 0 && P.org == SweepPlan::kPairs && !c->far_mfma) { P.fine = diag.in.name; P.far_name = far_name(SweepPlan::kFarLds, 16, 0); }
+    return P;
 }
 
+// ---- the schedules: one function per organisation and sweep, over the sequences B shows (lengths 0 hide a sequence)
+// two diagonals per launch (lin_inside_diag MODE 3 has W = 4: 256 threads) up to diagonal `last`, pairs start even; the last launch
+// may hold only F5i[nmax]
+static void inside_pairs(const SweepPass& S, int pin, int last)
+{
+    for (int d = 0; d <= last; d += 2) {
+        const int groups = (std::max(S.B.nmax - 1 - d, 0) + 62) / 63 + 1;
+        KLAUNCH(S.c, 0, (kInsidePair.kern), seq_grid(pin, S.B.ns, groups), dim3(256), S.st, S.B, S.c->lin->d, d, std::exp(-S.c->lin->h.s * d), pin);
+        S.c->n_launch[0]++;
+        far_inside_after(S, d + 2);   // (the first one is due behind diagonal 47)
+    }
+}
+// diagonals 0..31 by pairs (every row is "near" there), then strips of KD diagonals (mccaskill_strip.hip)
+static void inside_strips(const SweepPass& S, int pin)
+{
+    rh_ctx* c = S.c;
+    const McBatch& B = S.B;
+    constexpr int KD = 8, GS = 64 - (KD - 1);
+    const auto strip = strip_kernels(S.P.W, S.P.filt).in.kern;
+    inside_pairs(S, pin, 30);
+    int d0 = 32;
+    for (; d0 <= B.nmax - 2; d0 += KD) {
+        const int groups = (std::max(B.nmax - 1 - d0, 0) + GS - 1) / GS + 1;
+        KLAUNCH(c, 0, strip, seq_grid(pin, B.ns, groups), dim3(64 * S.P.W), S.st, B, c->lin->d, c->lin->wT, d0, d0 == 32 ? 32 : d0 - KD + 2,
+                std::exp(-c->lin->h.s * d0), (pin && c->strip_xcd) ? 2 : pin);
+        c->n_launch[0]++;
+        far_inside_after(S, d0 + KD);
+    }
+    hipLaunchKernelGGL(lin_f5i_tail, dim3(B.ns), dim3(256), 0, S.st, B, c->lin->d, d0 - KD + 2);
+}
+// one launch per diagonal, or (ahead) look-ahead pairs of launches
+static void inside_diagonals(const SweepPass& S, int pin, bool ahead)
+{
+    const InsideDiagK full = diag_kernels(S.P.W, S.P.BS).in.kern;
+    for (int d = 0; d <= S.B.nmax - 1; d++) {
+        const int groups = (std::max(S.B.nmax - 1 - d, 0) + 63) / 64 + 1;
+        const bool odd = ahead && (d & 1);
+        KLAUNCH(S.c, 0, (!ahead ? full : kInsideAhead[odd].kern), seq_grid(pin, S.B.ns, groups), dim3(odd ? 64 : 64 * S.P.W), S.st, S.B, S.c->lin->d, d,
+                std::exp(-S.c->lin->h.s * d), pin);
+        S.c->n_launch[0]++;
+        far_inside_after(S, d + 1);
+    }
+}
 
-// Which sequences run where is decided per sequence, by its length alone: 8..109 letters by their own workgroup when RH_SMALL=1
-// (mccaskill_small.hip), fewer than kStripMinN letters next to longer ones in a pass of their own (the organisation they would get
-// alone), everyone else in the sweeps.  Sub-batches of the scale ladder (c->mc.n is not the upload's length array) run as they are.
-template <int W, int BS>
-int launch_mc_lin(rh_ctx* c, int pin, int phase)
+// strips of KD diagonals from the top, aligned so that a sequence's strips do not depend on the batch
+static void outside_strips(SweepPass& S, int pin)
+{
+    rh_ctx* c = S.c;
+    const McBatch& B = S.B;
+    constexpr int KD = 8, GS = 64 - (KD - 1);
+    const auto strip = strip_kernels(S.P.W, S.P.filt).out.kern;
+    const int d0_top = (B.nmax - 2) | (KD - 1);
+    far_outside_begin(S, d0_top);
+    hipLaunchKernelGGL(lin_f5o_head, dim3(B.ns), dim3(256), 0, S.st, B, c->lin->d, B.nmax - 1, d0_top - 5);
+    for (int d0 = d0_top; d0 >= KD - 1; d0 -= KD) {
+        far_outside_before(S, d0);
+        const int groups = (std::max(B.nmax - 1 - (d0 - (KD - 1)), 0) + GS - 1) / GS + 1;
+        KLAUNCH(c, 2, strip, seq_grid(pin, B.ns, groups), dim3(64 * S.P.W), S.st, B, c->lin->d, c->lin->wT, d0, d0 - 6, d0 - 13,
+                (pin && c->strip_xcd) ? 2 : pin, c->d_bad.as<int>());
+        c->n_launch[1]++;
+    }
+}
+// two diagonals per launch (lin_outside_pair); pairs are (odd, even) whatever the batch: a sequence's results do not depend on
+// its neighbours' lengths
+static void outside_pairs(SweepPass& S, int pin)
+{
+    const auto pair = pair_kernels(S.P.W).out.kern;
+    far_outside_begin(S, S.B.nmax - 2);
+    for (int d = (S.B.nmax - 2) | 1; d >= 0; d -= 2) {
+        for (int r = d; r >= d - 1 && r >= 0; r--) far_outside_before(S, r);   // block products whose tiles start on either diagonal of the pair
+        const int ncol = S.B.nmax - 1 - d + 1;          // columns of the longer diagonal d-1 (d = 0: diagonal 0 alone, one less)
+        const int groups = std::max(1, (ncol - 1 + 62) / 63) + 1;
+        KLAUNCH(S.c, 2, pair, seq_grid(pin, S.B.ns, groups), dim3(64 * S.P.W), S.st, S.B, S.c->lin->d, d, d, pin, S.c->d_bad.as<int>());
+        S.c->n_launch[1]++;
+    }
+}
+static void outside_diagonals(SweepPass& S, int pin)
+{
+    const auto diag = diag_kernels(S.P.W, S.P.BS).out.kern;
+    far_outside_begin(S, S.B.nmax - 2);
+    for (int d = S.B.nmax - 2; d >= 0; d--) {
+        far_outside_before(S, d);
+        const int groups = (S.B.nmax - 1 - d + 63) / 64 + 1;
+        KLAUNCH(S.c, 2, diag, seq_grid(pin, S.B.ns, groups), dim3(64 * S.P.W), S.st, S.B, S.c->lin->d, d, pin, S.c->d_bad.as<int>());
+        S.c->n_launch[1]++;
+    }
+}
+
+// One phase (0 inside, 1 outside) over the batch c->mc, whose plan is P.  Which sequences run where is decided per sequence, by
+// its length alone: 8..109 letters by their own workgroup when RH_SMALL=1 (mccaskill_small.hip), fewer than kStripMinN letters next
+// to longer ones in a pass of their own (the organisation they would get alone, a plan of its own), everyone else in the sweeps.
+// Sub-batches of the scale ladder (c->mc.n is not the upload's length array) run as they are.  lin_init / lin_finish / mc_unpaired
+// see every sequence.
+int launch_mc_lin(rh_ctx* c, int pin, int phase, const SweepPlan& P)
 {
     const McBatch BR = c->mc;
     const bool routed = (const void*)BR.n == c->d_n.p && (!c->small_list.empty() || c->n_short > 0);
-    if (!routed) return launch_mc_lin_body<W, BS>(c, pin, phase, BR, BR, true, true);
     int* bad = c->d_bad.as<int>();
-    McBatch BL = BR, BSH = BR;
-    BL.n = c->d_n_sweep.as<const int>(); BL.nmax = c->nmax_sweep;
-    BSH.n = c->d_n_short.as<const int>(); BSH.nmax = c->nmax_short;
-    int rc;
+    const auto sweep = [&](const McBatch& B, const SweepPlan& Q) {
+        SweepPass S{c, Q, B, c->s_mc, phase};
+        if (Q.org == SweepPlan::kStrips) return phase == 0 ? inside_strips(S, pin) : outside_strips(S, pin);
+        if (Q.org == SweepPlan::kPairs) return phase == 0 ? inside_pairs(S, pin, B.nmax) : outside_pairs(S, pin);
+        return phase == 0 ? inside_diagonals(S, pin, Q.org == SweepPlan::kLookahead) : outside_diagonals(S, pin);
+    };
     if (phase == 0) {
         hipLaunchKernelGGL(lin_init, dim3((BR.ns + 63) / 64), dim3(64), 0, c->s_mc, BR, c->lin->d, bad);
-        if (!c->small_list.empty()) {
+        if (routed && !c->small_list.empty()) {
             launch_lin_small(BR, c->lin->d, c->lin->wT + kStripFiltOff + kStripFiltLen, c->d_small_list.as<const int>(), (int)c->small_list.size(), bad, c->s_mc);
             c->n_launch[0]++;
         }
-        if (BL.nmax > 0 && (rc = launch_mc_lin_body<W, BS>(c, pin, 0, BL, BR, false, false))) return rc;
-        if (c->n_short > 0 && (rc = launch_mc_lin_body<W, BS>(c, pin, 0, BSH, BR, false, false))) return rc;
-        return RH_OK;
     }
-    if (BL.nmax > 0 && (rc = launch_mc_lin_body<W, BS>(c, pin, 1, BL, BR, false, false))) return rc;
-    if (c->n_short > 0 && (rc = launch_mc_lin_body<W, BS>(c, pin, 1, BSH, BR, false, false))) return rc;
-    hipLaunchKernelGGL(lin_finish, dim3((BR.ns + 63) / 64), dim3(64), 0, c->s_mc, BR, c->lin->d, c->d_mclogz.as<double>(), bad);
-    hipLaunchKernelGGL(mc_unpaired, dim3((BR.nmax + 63) / 64, BR.ns), dim3(256), 0, c->s_mc, BR);
+    if (routed) {
+        McBatch BL = BR, BSH = BR;
+        BL.n = c->d_n_sweep.as<const int>(); BL.nmax = c->nmax_sweep;
+        BSH.n = c->d_n_short.as<const int>(); BSH.nmax = c->nmax_short;
+        if (BL.nmax > 0) sweep(BL, plan_mc_lin(c, phase, BL.nmax));
+        if (c->n_short > 0) sweep(BSH, plan_mc_lin(c, phase, BSH.nmax));
+    } else
+        sweep(BR, P);
+    if (phase == 1) {
+        hipLaunchKernelGGL(lin_finish, dim3((BR.ns + 63) / 64), dim3(64), 0, c->s_mc, BR, c->lin->d, c->d_mclogz.as<double>(), bad);
+        hipLaunchKernelGGL(mc_unpaired, dim3((BR.nmax + 63) / 64, BR.ns), dim3(256), 0, c->s_mc, BR);
+    }
     return RH_OK;
-}
-
-template <int BS>
-int launch_mc_lin_w(rh_ctx* c, int pin, int phase)
-{
-    switch (phase == 0 ? c->lin_w_in : c->lin_w) {
-        case 16: return launch_mc_lin<16, BS>(c, pin, phase);
-        case 4: if (BS == 16) return launch_mc_lin<4, 16>(c, pin, phase); else return launch_mc_lin<8, BS>(c, pin, phase);
-        default: return launch_mc_lin<8, BS>(c, pin, phase);
-    }
-}
-int launch_mc_lin_any(rh_ctx* c, int pin, int phase)
-{
-    switch (c->lin_bs) {
-        case 0: return launch_mc_lin_w<0>(c, pin, phase);
-        case 32: return launch_mc_lin_w<32>(c, pin, phase);
-        default: return launch_mc_lin_w<16>(c, pin, phase);
-    }
 }
 
 // single-branch weights of the strip kernels: wT[l1*40 + t+1] = shape_w(l1, t-l1), zero where the shape does not exist (the dense

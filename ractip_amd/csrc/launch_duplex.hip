@@ -27,37 +27,60 @@ int launch_dx_log(rh_ctx* c, const DxBatch& D)
 }
 int launch_dx_log(rh_ctx* c) { return launch_dx_log(c, c->dx); }
 
-// ---- duplex sweeps, scaled linear path
+// ---- duplex sweeps, scaled linear path: eight (dxl_strip8), four (dxl_sweep4) or two (dxl_sweep<W>) anti-diagonals per launch;
+// W = 4 has all three, W = 2 and 8 the last.  Each kernel on one line with the name reported for it.
+using DxSweepK = void (*)(DxLinBatch, const DxLinModel*, int, int);
+const Named<void (*)(DxLinBatch, const DxLinModel*, int)> kDxStrip8 = NAMED(dxl_strip8);
+const Named<DxSweepK> kDxSweep4 = NAMED(dxl_sweep4);
+struct DxSweepKernels { int W; Named<DxSweepK> k; };
+const DxSweepKernels kDxSweepW[] = {{4, NAMED(dxl_sweep<4>)}, {2, NAMED(dxl_sweep<2>)}, {8, NAMED(dxl_sweep<8>)}};
+static const DxSweepKernels& dx_sweep_kernels(int W) { return row_of(kDxSweepW, [&](const DxSweepKernels& r) { return r.W == W; }); }
+const Named<void (*)(DxLinBatch, const VLinModel*, const VDxLin*, int)> kDxvlSweep4 = NAMED(dxvl_sweep4);
+
+SweepPlan plan_dx_lin(const rh_ctx* c, int w)
+{
+    SweepPlan P;
+    P.W = w == 2 || w == 8 ? w : 4;
+    P.org = !(P.W == 4 && c->dx_quad) ? SweepPlan::kDxSweepW : c->dx_strip ? SweepPlan::kDxStrip8 : SweepPlan::kDxSweep4;
+    P.fine = P.org == SweepPlan::kDxStrip8 ? kDxStrip8.name : P.org == SweepPlan::kDxSweep4 ? kDxSweep4.name : dx_sweep_kernels(P.W).k.name;
+    return P;
+}
+SweepPlan plan_dx_vlin()   // (one organisation)
+{
+    SweepPlan P;
+    P.org = SweepPlan::kDxSweep4;
+    P.fine = kDxvlSweep4.name;
+    return P;
+}
+
 // X: the batch (the whole one, or a compacted sub-batch of the scale-exponent ladder with its own tables); dm / hm: the model at the
 // scale exponent of this pass; logz_out / bad: per pair of X
-template <int W>
-int launch_dx_lin_on(rh_ctx* c, DxLinBatch X, const DxLinModel* dm, const DxLinModel& hm, double* logz_out, int* bad)
+int launch_dx_lin_on(rh_ctx* c, const SweepPlan& P, DxLinBatch X, const DxLinModel* dm, const DxLinModel& hm, double* logz_out, int* bad)
 {
     const int smax = X.n1max + X.n2max;
     const int steps = smax / 2;
     const int groups = (X.n1max + 2 + 63) / 64;
     const double leu = hm.lam_eu, l2 = hm.lam_pow[2];
-    if (W == 4 && c->dx_quad && c->dx_strip) {   // eight anti-diagonals per launch (dxl_strip8)
+    if (P.org == SweepPlan::kDxStrip8) {
         const int groups8 = (X.n1max + 2 + 57) / 58;
         for (int t = 0; 8 * t < smax - 1; t++) {
             for (int k = 0; k < 8; k++) X.pw8[k] = std::pow(leu, 8.0 * t + k) * l2;
-            KLAUNCH(c, 4, dxl_strip8, dim3(groups8, X.np, 2), dim3(512), c->s_dx, X, dm, t);
+            KLAUNCH(c, 4, (kDxStrip8.kern), dim3(groups8, X.np, 2), dim3(512), c->s_dx, X, dm, t);
             c->n_launch[2]++;
         }
-    } else
-    if (W == 4 && c->dx_quad) {   // four anti-diagonals per launch (dxl_sweep4)
+    } else if (P.org == SweepPlan::kDxSweep4) {
         const int groups4 = (X.n1max + 2 + 61) / 62;
         for (int t = 0; 4 * t < smax - 1; t++) {
             for (int k = 0; k < 4; k++) X.pw4[k] = std::pow(leu, 4.0 * t + k) * l2;
-            KLAUNCH(c, 4, dxl_sweep4, dim3(groups4, X.np, 2), dim3(256), c->s_dx, X, dm, t, groups4);
+            KLAUNCH(c, 4, (kDxSweep4.kern), dim3(groups4, X.np, 2), dim3(256), c->s_dx, X, dm, t, groups4);
             c->n_launch[2]++;
         }
     } else
-    for (int t = 0; t < steps; t++) {
+    for (int t = 0; t < steps; t++) {   // two anti-diagonals per launch
         // inside diagonal sd = 2+2t+k: (lam e^eu)^(sd-2) lam^2 ; outside sd = Smax-2t-1+k: (lam e^eu)^(2t+1-k) lam^2
         X.pw_in[0] = std::pow(leu, 2.0 * t) * l2;      X.pw_in[1] = X.pw_in[0] * leu;
         X.pw_out[1] = std::pow(leu, 2.0 * t) * l2;     X.pw_out[0] = X.pw_out[1] * leu;
-        KLAUNCH(c, 4, dxl_sweep<W>, dim3(groups, X.np, 2), dim3(64 * W), c->s_dx, X, dm, t, groups);
+        KLAUNCH(c, 4, (dx_sweep_kernels(P.W).k.kern), dim3(groups, X.np, 2), dim3(64 * P.W), c->s_dx, X, dm, t, groups);
         c->n_launch[2]++;
     }
     double* zpart = c->d_zpart.as<double>();
@@ -68,9 +91,7 @@ int launch_dx_lin_on(rh_ctx* c, DxLinBatch X, const DxLinModel* dm, const DxLinM
     hipLaunchKernelGGL(dxl_posterior, dim3((X.n1max + 31) / 32, (smax - 1 + 31) / 32, X.np), dim3(256), 0, c->s_dx, X, c->d_zbar.as<const double>(), bad);
     return RH_OK;
 }
-template int launch_dx_lin_on<4>(rh_ctx*, DxLinBatch, const DxLinModel*, const DxLinModel&, double*, int*);   // (fallbacks.hip: retry_dx_lin_rungs)
-template <int W>
-int launch_dx_lin(rh_ctx* c) { return launch_dx_lin_on<W>(c, c->dxl, c->d_dxlin, c->h_dxlin, c->d_logz.as<double>(), c->d_dxbad.as<int>()); }
+int launch_dx_lin(rh_ctx* c, const SweepPlan& P) { return launch_dx_lin_on(c, P, c->dxl, c->d_dxlin, c->h_dxlin, c->d_logz.as<double>(), c->d_dxbad.as<int>()); }
 
 // Vienna-BL pf_duplex, scaled linear space (duplex_vlin.hip)
 int launch_dx_vlin(rh_ctx* c)
@@ -81,7 +102,7 @@ int launch_dx_vlin(rh_ctx* c)
     const double lam = std::exp(-c->vdx_s);
     for (int t = 0; 4 * t < smax - 1; t++) {
         for (int k = 0; k < 4; k++) X.pw4[k] = std::pow(lam, 2.0 + 4.0 * t + k);
-        KLAUNCH(c, 4, dxvl_sweep4, dim3(groups4, X.np, 2), dim3(256), c->s_dx, X, c->d_vdxl, c->d_vdx, t);
+        KLAUNCH(c, 4, (kDxvlSweep4.kern), dim3(groups4, X.np, 2), dim3(256), c->s_dx, X, c->d_vdxl, c->d_vdx, t);
         c->n_launch[2]++;
     }
     double* zpart = c->d_zpart.as<double>();
@@ -105,14 +126,6 @@ int launch_dx_vlog(rh_ctx* c)
     hipLaunchKernelGGL(dxv_logz, dim3(D.np), dim3(1024), 0, c->s_dx, D, c->d_vienna);
     hipLaunchKernelGGL(dxv_posterior, dim3((D.n1max * D.n2max + 255) / 256, D.np), dim3(256), 0, c->s_dx, D);
     return RH_OK;
-}
-int launch_dx_lin_any(rh_ctx* c)
-{
-    switch (c->dx_w) {
-        case 2: return launch_dx_lin<2>(c);
-        case 8: return launch_dx_lin<8>(c);
-        default: return launch_dx_lin<4>(c);
-    }
 }
 
 }  // namespace rh::host

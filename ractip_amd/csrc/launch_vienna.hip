@@ -43,108 +43,80 @@ int launch_mc_vienna(rh_ctx* c, int pin)
 // ---- Vienna-BL McCaskill sweeps, scaled linear-space path (mccaskill_vlin.hip) with the block products of mccaskill_far.hip.
 // co = false: the single-molecule batch on the McCaskill stream (+ accessibility); co = true: the s1+s2 batch of the
 // two-molecule hybridization matrix on the duplex stream (two more groups per launch for the exterior halves XS / XP)
-template <int BS>
-int launch_mc_vlin_bs(rh_ctx* c, int pin, int phase, bool co)
+using VInsideK = void (*)(McBatch, const VLinModel*, int, double, int);
+using VOutsideK = void (*)(McBatch, const VLinModel*, int, int, int*);
+// the kernels of one <W = 8, BS, CUT> by MODE (0: one launch per diagonal; 1, 2: the full and the one-wavefront launch of a
+// look-ahead pair, BS = 16 only), on one line with the names reported for them
+struct VlinKernels { int BS; bool cut; VInsideK in[3]; VOutsideK out[3]; const char *in_name, *out_name; };
+#define VLIN_NAMES(BS, CUT) "vlin_inside_diag<8, " #BS ", " #CUT ">", "vlin_outside_diag<8, " #BS ", " #CUT ">"
+#define VLIN(BS, CUT) {BS, CUT, {vlin_inside_diag<8, BS, CUT, 0>}, {vlin_outside_diag<8, BS, CUT, 0>}, VLIN_NAMES(BS, CUT)}
+#define VLIN_AHEAD(BS, CUT) {BS, CUT, {vlin_inside_diag<8, BS, CUT, 0>, vlin_inside_diag<8, BS, CUT, 1>, vlin_inside_diag<8, BS, CUT, 2>}, \
+                             {vlin_outside_diag<8, BS, CUT, 0>, vlin_outside_diag<8, BS, CUT, 1>, vlin_outside_diag<8, BS, CUT, 2>}, VLIN_NAMES(BS, CUT)}
+const VlinKernels kVlin[] = {VLIN(0, false), VLIN(0, true), VLIN_AHEAD(16, false), VLIN_AHEAD(16, true)};
+#undef VLIN_NAMES
+#undef VLIN
+#undef VLIN_AHEAD
+static const VlinKernels& vlin_kernels(int BS, bool cut) { return row_of(kVlin, [&](const VlinKernels& r) { return r.BS == BS && r.cut == cut; }); }
+
+SweepPlan plan_mc_vlin(const rh_ctx* c, int phase, bool co, int nmax)
 {
-    constexpr int W = 8;
-    const McBatch& B = co ? c->co : c->mc;
-    hipStream_t st = co ? c->s_dx : c->s_mc;
-    int* bad = (int*)(co ? c->d_cobad.p : c->d_bad.p);
-    int* nl = co ? &c->n_launch[2] : (phase == 0 ? &c->n_launch[0] : &c->n_launch[1]);
-    int* nf = co ? &c->n_far[2] : (phase == 0 ? &c->n_far[0] : &c->n_far[1]);
-    const int extra = co ? 3 : 1;   // F5 (+ XP, XS)
-    const int last_block = BS > 0 ? (B.nmax - 1) / BS : 0;
-    // two-molecule sweeps: the groups of diagonal dd with a cell on both strands are 1 + 64 slot <= cut < 1 + 64 slot + 64 + dd; the
-    // union over the batch's cuts is launched behind the three F5 / XP / XS groups (window_slot_vl); cells = all cell groups of the launch
-    const bool window = co && c->co_window && c->co_cut_min >= 1;
-    const auto windowed = [&](int dd, int cells, int* pin_arg) -> int {
+    SweepPlan P;
+    P.W = 8;
+    P.BS = c->lin_bs != 0 ? 16 : 0;
+    P.org = P.BS == 16 && c->lookahead ? SweepPlan::kLookahead : SweepPlan::kDiagonals;
+    far_products(c, phase, nmax, true, &P);
+    const VlinKernels& k = vlin_kernels(P.BS, co);
+    P.fine = phase == 0 ? k.in_name : k.out_name;
+    // Reported as before where the report has never named what runs (the strings are an interface of bench.py and the profiles):
+    // RH_LIN_BS=32 as block size 32 and RH_FAR_MFMA=0 as the LDS products (these kernels have BS = 16 on the MFMA products only);
+    // the two-molecule sweeps as one descriptive string, BS = 16 whatever RH_LIN_BS says, and without a block-product name.
+    if (c->lin_bs == 32) P.fine = phase == 0 ? "vlin_inside_diag<8, 32, false>" : "vlin_outside_diag<8, 32, false>";
+    if (P.BS && (c->lin_bs == 32 || !c->far_mfma)) P.far_name = far_name(SweepPlan::kFarLds, c->lin_bs == 32 ? 32 : 16, phase);
+    if (co) { P.fine = "vlin_inside_diag<8, 16, true> + vlin_outside_diag<8, 16, true> (s1+s2)"; P.far_name = ""; }
+    return P;
+}
+
+// The grid of one launch over `cells` groups of 64 cells: behind them F5 (+ XP, XS for the two-molecule sweeps).  window: of the
+// two-molecule sweeps, only the groups of diagonal dd with a cell on both strands, 1 + 64 slot <= cut < 1 + 64 slot + 64 + dd --
+// the union over the batch's cuts -- are launched, behind the three F5 / XP / XS groups (window_slot_vl); the kernel finds its
+// group through the pin argument
+struct VlinGrid { dim3 grid; int pin; };
+static VlinGrid vlin_grid(const rh_ctx* c, const McBatch& B, bool co, bool window, int pin, int dd, int cells)
+{
+    int groups = cells + (co ? 3 : 1), pin_k = pin;
+    if (window) {
         const int t = c->co_cut_min - 65 - dd;
         const int lo = std::max(0, (t >= 0 ? t / 64 : -((-t + 63) / 64)) + 1), hi = std::min(cells - 1, (c->co_cut_max - 1) / 64);
-        *pin_arg = pin | 128 | (lo << 8);
-        return 3 + std::max(0, hi - lo + 1);
-    };
-    if (phase == 0) {
-        hipLaunchKernelGGL(vlin_init, dim3((B.ns + 63) / 64), dim3(64), 0, st, B, bad);
-        if (co && B.seeded) hipLaunchKernelGGL(vlin_co_seed, dim3(c->mc.nmax, B.ns), dim3(256), 0, st, B, c->mc);
-        for (int d = 0; d <= B.nmax - 1; d++) {
-            const int cells = (std::max(B.nmax - 1 - d, 0) + 63) / 64;
-            const bool la1 = BS == 16 && c->lookahead && (d & 1) == 0;   // this launch also feeds diagonal d+1
-            int pin_k = pin;
-            const int groups = (window && B.seeded) ? windowed(la1 ? d + 1 : d, cells, &pin_k) : cells + extra;
-            const double hp_d = c->h_hplen[d];
-            const dim3 grid = pin ? dim3(B.ns, groups) : dim3(groups, B.ns);
-            bool done = false;
-            if constexpr (BS == 16) {
-                if (c->lookahead) {   // look-ahead pairs: even diagonal = full launch that also accumulates d+1's sums, odd = one wavefront per group
-                    done = true;
-                    if ((d & 1) == 0) {
-                        if (co) KLAUNCH(c, 0, (vlin_inside_diag<W, 16, true, 1>), grid, dim3(64 * W), st, B, c->d_vlin, d, hp_d, pin_k);
-                        else KLAUNCH(c, 0, (vlin_inside_diag<W, 16, false, 1>), grid, dim3(64 * W), st, B, c->d_vlin, d, hp_d, pin);
-                    } else {
-                        if (co) KLAUNCH(c, 0, (vlin_inside_diag<W, 16, true, 2>), grid, dim3(64), st, B, c->d_vlin, d, hp_d, pin_k);
-                        else KLAUNCH(c, 0, (vlin_inside_diag<W, 16, false, 2>), grid, dim3(64), st, B, c->d_vlin, d, hp_d, pin);
-                    }
-                }
-            }
-            if (!done) {
-                if (co) KLAUNCH(c, 0, (vlin_inside_diag<W, BS, true, 0>), grid, dim3(64 * W), st, B, c->d_vlin, d, hp_d, pin_k);
-                else KLAUNCH(c, 0, (vlin_inside_diag<W, BS, false, 0>), grid, dim3(64 * W), st, B, c->d_vlin, d, hp_d, pin);
-            }
-            (*nl)++;
-            if (BS > 0 && (d + 1) % BS == 0) {
-                const int D = (d + 1) / BS + 1;
-                if (D >= 4 && D <= last_block) { (*nl) += far_inside_step(c, B, st, D, last_block); (*nf)++; }
-            }
-        }
-        return RH_OK;
+        pin_k = pin | 128 | (lo << 8);
+        groups = 3 + std::max(0, hi - lo + 1);
     }
-    if (BS > 0) {
-        (*nl) += far_outside_begin(c, B, st, last_block);
-        for (int D = last_block; D >= 0 && (D + 1) * BS - 1 > B.nmax - 2; D--) { (*nl) += far_outside_step(c, B, st, D, last_block); (*nf)++; }
+    return {seq_grid(pin, B.ns, groups), pin_k};
+}
+
+// one launch per diagonal, or look-ahead pairs: the even diagonal is a full launch that also accumulates the sums of d+1, which then
+// needs one wavefront per group
+static void vlin_inside(const SweepPass& S, int pin, bool co)
+{
+    rh_ctx* c = S.c;
+    const McBatch& B = S.B;
+    const VlinKernels& K = vlin_kernels(S.P.BS, co);
+    const bool ahead = S.P.org == SweepPlan::kLookahead, window = co && c->co_window && c->co_cut_min >= 1 && B.seeded;
+    hipLaunchKernelGGL(vlin_init, dim3((B.ns + 63) / 64), dim3(64), 0, S.st, B, (int*)(co ? c->d_cobad.p : c->d_bad.p));
+    if (co && B.seeded) hipLaunchKernelGGL(vlin_co_seed, dim3(c->mc.nmax, B.ns), dim3(256), 0, S.st, B, c->mc);
+    for (int d = 0; d <= B.nmax - 1; d++) {
+        const int mode = !ahead ? 0 : (d & 1) ? 2 : 1;
+        const int cells = (std::max(B.nmax - 1 - d, 0) + 63) / 64;
+        const VlinGrid G = vlin_grid(c, B, co, window, pin, mode == 1 ? d + 1 : d, cells);   // (mode 1 also feeds diagonal d+1)
+        KLAUNCH(c, 0, (K.in[mode]), G.grid, dim3(mode == 2 ? 64 : 64 * S.P.W), S.st, B, c->d_vlin, d, c->h_hplen[d], G.pin);
+        c->n_launch[S.k]++;
+        far_inside_after(S, d + 1);
     }
-    const bool la = BS == 16 && c->lookahead;   // look-ahead pairs (odd diagonal: full launch + the sums of the next, even: one wavefront per group)
-    for (int d = la ? ((B.nmax - 2) | 1) : B.nmax - 2; d >= 0; d--) {
-        if (BS > 0 && (d + 1) % BS == 0 && d <= B.nmax - 2) {
-            const int D = (d + 1) / BS - 1;
-            if (D >= 0 && D <= last_block) { (*nl) += far_outside_step(c, B, st, D, last_block); (*nf)++; }
-        }
-        bool done = false;
-        if constexpr (BS == 16) {
-            if (la) {
-                done = true;
-                int pin_k = pin;
-                if (d & 1) {
-                    const int cells = (B.nmax - d + 63) / 64;   // cells of diagonal d-1
-                    const int groups = window ? windowed(d, cells, &pin_k) : cells + extra;
-                    const dim3 grid = pin ? dim3(B.ns, groups) : dim3(groups, B.ns);
-                    if (co) KLAUNCH(c, 2, (vlin_outside_diag<W, 16, true, 1>), grid, dim3(64 * W), st, B, c->d_vlin, d, pin_k, bad);
-                    else KLAUNCH(c, 2, (vlin_outside_diag<W, 16, false, 1>), grid, dim3(64 * W), st, B, c->d_vlin, d, pin, bad);
-                } else {
-                    const int cells = (B.nmax - 1 - d + 63) / 64;
-                    const int groups = window ? windowed(d, cells, &pin_k) : cells + extra;
-                    const dim3 grid = pin ? dim3(B.ns, groups) : dim3(groups, B.ns);
-                    if (co) KLAUNCH(c, 2, (vlin_outside_diag<W, 16, true, 2>), grid, dim3(64), st, B, c->d_vlin, d, pin_k, bad);
-                    else KLAUNCH(c, 2, (vlin_outside_diag<W, 16, false, 2>), grid, dim3(64), st, B, c->d_vlin, d, pin, bad);
-                }
-            }
-        }
-        if (!done) {
-            const int cells = (B.nmax - 1 - d + 63) / 64;
-            int pin_k = pin;
-            const int groups = window ? windowed(d, cells, &pin_k) : cells + extra;
-            if (co) KLAUNCH(c, 2, (vlin_outside_diag<W, BS, true, 0>), pin ? dim3(B.ns, groups) : dim3(groups, B.ns), dim3(64 * W), st, B, c->d_vlin, d, pin_k, bad);
-            else KLAUNCH(c, 2, (vlin_outside_diag<W, BS, false, 0>), pin ? dim3(B.ns, groups) : dim3(groups, B.ns), dim3(64 * W), st, B, c->d_vlin, d, pin, bad);
-        }
-        (*nl)++;
-    }
-    if (co) {
-        const DxBatch& D = c->dx;
-        hipLaunchKernelGGL(mcv_extract_hp, dim3((D.n1max * D.n2max + 255) / 256, B.ns), dim3(256), 0, st, B, D.hp, D.tab_stride, D.ldd, D.logz,
-                           c->h_vlin->s, bad);
-        return RH_OK;
-    }
-    hipLaunchKernelGGL(vlin_finish, dim3((B.ns + 63) / 64), dim3(64), 0, st, B, c->d_vlin, c->d_mclogz.as<double>(), bad);
-    // accessibility P(i..i+w unpaired), w < max_w
+}
+
+// accessibility P(i..i+w unpaired), w < max_w, behind the single-molecule sweeps
+static void vlin_finish_acc(rh_ctx* c, const McBatch& B, hipStream_t st)
+{
+    hipLaunchKernelGGL(vlin_finish, dim3((B.ns + 63) / 64), dim3(64), 0, st, B, c->d_vlin, c->d_mclogz.as<double>(), c->d_bad.as<int>());
     const int tiles = (B.ld + 31) / 32;
     hipLaunchKernelGGL(vlin_acc_prep, dim3(tiles * tiles, B.ns), dim3(256), 0, st, B, c->d_vlin, c->d_hplen.as<const double>());
     hipLaunchKernelGGL(mcv_acc_hscan, dim3((B.nmax + 1 + 255) / 256, B.ns), dim3(256), 0, st, B, 10 /* VL_FM2F */);
@@ -166,12 +138,39 @@ int launch_mc_vlin_bs(rh_ctx* c, int pin, int phase, bool co)
     else
         hipLaunchKernelGGL(vlin_acc_final, dim3((B.nmax + 255) / 256, B.ns, c->max_w), dim3(256), 0, st, B, c->d_vlin, c->d_gaps.as<const double>(), c->max_w);
     c->n_launch[1] += 6;
-    return RH_OK;
 }
 
-int launch_mc_vlin(rh_ctx* c, int pin, int phase, bool co)
+// the same from the top; look-ahead pairs: the odd diagonal is the full launch (+ the sums of the next), the even one a wavefront per group
+static void vlin_outside(SweepPass& S, int pin, bool co)
 {
-    return c->lin_bs != 0 ? launch_mc_vlin_bs<16>(c, pin, phase, co) : launch_mc_vlin_bs<0>(c, pin, phase, co);
+    rh_ctx* c = S.c;
+    const McBatch& B = S.B;
+    const VlinKernels& K = vlin_kernels(S.P.BS, co);
+    const bool ahead = S.P.org == SweepPlan::kLookahead, window = co && c->co_window && c->co_cut_min >= 1;
+    int* bad = (int*)(co ? c->d_cobad.p : c->d_bad.p);
+    far_outside_begin(S, B.nmax - 2);
+    for (int d = ahead ? ((B.nmax - 2) | 1) : B.nmax - 2; d >= 0; d--) {
+        if (d <= B.nmax - 2) far_outside_before(S, d);
+        const int mode = !ahead ? 0 : (d & 1) ? 1 : 2;
+        const int cells = mode == 1 ? (B.nmax - d + 63) / 64 : (B.nmax - 1 - d + 63) / 64;   // (mode 1: the cells of diagonal d-1)
+        const VlinGrid G = vlin_grid(c, B, co, window, pin, d, cells);
+        KLAUNCH(c, 2, (K.out[mode]), G.grid, dim3(mode == 2 ? 64 : 64 * S.P.W), S.st, B, c->d_vlin, d, G.pin, bad);
+        c->n_launch[S.k]++;
+    }
+    if (co) {
+        const DxBatch& D = c->dx;
+        hipLaunchKernelGGL(mcv_extract_hp, dim3((D.n1max * D.n2max + 255) / 256, B.ns), dim3(256), 0, S.st, B, D.hp, D.tab_stride, D.ldd, D.logz,
+                           c->h_vlin->s, bad);
+    } else
+        vlin_finish_acc(c, B, S.st);
+}
+
+int launch_mc_vlin(rh_ctx* c, int pin, int phase, bool co, const SweepPlan& P)
+{
+    SweepPass S{c, P, co ? c->co : c->mc, co ? c->s_dx : c->s_mc, co ? 2 : phase};
+    if (phase == 0) vlin_inside(S, pin, co);
+    else vlin_outside(S, pin, co);
+    return RH_OK;
 }
 
 // ---- hybridization matrix from the two-molecule ensemble (co_pf_fold semantics): the same sweeps over s1+s2 with a cut

@@ -469,29 +469,20 @@ int rh_batch_kernels(rh_ctx* c, const char* fine[3], const char* far[3], int n_f
 {
     if (!c) return RH_ERR_ARG;
     if (!c->computed) return fail(c, RH_ERR_ARG, "no computed batch");
-    static thread_local std::string names[6];
-    const bool vienna0 = c->model == RH_MODEL_VIENNA_BL;
-    const std::string w = std::to_string(c->lin_w == 16 ? 16 : (!vienna0 && c->lin_w == 4 && c->lin_bs != 0 && c->lin_bs != 32 ? 4 : 8)), w_in = std::to_string(c->lin_w_in == 16 ? 16 : (c->lin_w_in == 4 && c->lin_bs != 0 && c->lin_bs != 32 ? 4 : 8)), bs = std::to_string(c->lin_bs == 0 || c->lin_bs == 32 ? c->lin_bs : 16);
-    const bool vienna = c->model == RH_MODEL_VIENNA_BL, lin = c->last_path == 1;
-    const bool pairs = !vienna && lin && c->lookahead == 2 && c->far_mfma && c->lin_bs == 16;   // two diagonals per launch
-    const std::string pre = vienna ? "vlin_" : "lin_";
-    const std::string targs = vienna ? bs + ", false" : bs;
-    names[0] = !c->has_mc ? "" : lin ? pre + "inside_diag<" + (vienna ? "8" : w_in) + ", " + targs + (vienna ? "" : (pairs && c->lin_w_in == 4) ? ", 3" : (c->lookahead == 1 && c->lin_w_in == 4 && c->lin_bs == 16) ? ", 1" : ", 0") + ">"
-                                     : vienna ? "mcv_inside_diag" : "mc_inside_diag";
-    if (c->has_mc && lin && !vienna && strip_inside(c, c->mc)) names[0] = c->strip_w == 4 ? "lin_inside_strip<8, 4, 0>" : ((c->strip_filt && c->strip_filt_ok) ? "lin_inside_strip<8, 8, 1>" : "lin_inside_strip<8, 8, 0>");
-    const bool ostrip = c->has_mc && lin && !vienna && strip_outside(c, c->mc);
-    names[1] = ostrip ? (c->strip_w == 4 ? "lin_outside_strip<8, 4, 0>" : ((c->strip_filt && c->strip_filt_ok) ? "lin_outside_strip<8, 8, 1>" : "lin_outside_strip<8, 8, 0>")) : !c->has_mc ? "" : lin ? ((pairs && (c->lin_w == 4 || c->lin_w == 8)) ? "lin_outside_pair<" + w + ", " + targs + ">" : pre + "outside_diag<" + (vienna ? "8" : w) + ", " + targs + ">")
-                                     : vienna ? "mcv_outside_diag" : "mc_outside_diag";
-    names[2] = !c->has_dx ? "" : vienna ? (c->hybrid == RH_HYBRID_COFOLD ? (c->last_dx_path == 1 ? "vlin_inside_diag<8, 16, true> + vlin_outside_diag<8, 16, true> (s1+s2)"
-                                                                                         : "mcv_inside_diag + mcv_outside_diag (s1+s2)") : (c->last_dx_path == 1 ? "dxvl_sweep4" : "dxv_sweep_diag")) : c->last_dx_path == 1 ? ((c->dx_quad && c->dx_w != 2 && c->dx_w != 8) ? std::string(c->dx_strip ? "dxl_strip8" : "dxl_sweep4") : "dxl_sweep<" + std::to_string(c->dx_w == 2 || c->dx_w == 8 ? c->dx_w : 4) + ">") : "dx_sweep_diag";
-    const bool mfma = c->far_mfma && c->lin_bs != 0 && c->lin_bs != 32;
-    const std::string fsuf = c->far_pk ? "_pk" : "_mfma";
-    names[3] = (c->has_mc && lin && c->n_far[0]) ? (mfma ? "lin_far_inside" + fsuf : "lin_far_inside<" + bs + ">") : "";
-    names[4] = (c->has_mc && lin && c->n_far[1]) ? (mfma ? "lin_far_outside" + fsuf : "lin_far_outside<" + bs + ">") : "";
-    names[5] = "";
+    // the plans of the linear first pass (compute_once) where it stood; the fixed names of the log-space kernels where it did not
+    const bool vienna = c->model == RH_MODEL_VIENNA_BL, lin = c->last_path == 1, dx_lin = c->last_dx_path == 1;
+    const char* names[6] = {"", "", "", "", "", ""};
+    if (c->has_mc) {
+        names[0] = lin ? c->plan[0].fine : vienna ? "mcv_inside_diag" : "mc_inside_diag";
+        names[1] = lin ? c->plan[1].fine : vienna ? "mcv_outside_diag" : "mc_outside_diag";
+        if (lin && c->n_far[0]) names[3] = c->plan[0].far_name;
+        if (lin && c->n_far[1]) names[4] = c->plan[1].far_name;
+    }
+    if (c->has_dx)
+        names[2] = dx_lin ? c->plan[2].fine : !vienna ? "dx_sweep_diag" : c->hybrid == RH_HYBRID_COFOLD ? "mcv_inside_diag + mcv_outside_diag (s1+s2)" : "dxv_sweep_diag";
     for (int k = 0; k < 3; k++) {
-        if (fine) fine[k] = names[k].c_str();
-        if (far) far[k] = names[3 + k].c_str();
+        if (fine) fine[k] = names[k];
+        if (far) far[k] = names[3 + k];
         if (n_far) n_far[k] = c->n_far[k];
     }
     return RH_OK;
