@@ -101,6 +101,32 @@ struct DxBatch {
 
 // ---- duplex, scaled linear path: anti-diagonal-major tables [sd*lda + kDxPad + a], a = i, sd = i + (L2+1-j)
 constexpr int kDxPad = 32;   // zero columns on both sides of every row (>= 29: the longest window reach)
+// How far from its cells a row is ever read.  Row sd has cells at columns alo(sd) = max(1, sd-L2) .. ahi(sd) = min(L1, sd-1); both grow
+// with sd, by at most one per row.  A kept cell (sd, a), alo(sd) <= a <= ahi(sd), reads, with dir = -1 (inside) / +1 (outside):
+//   * row sd + dir*(2+t), t = 0..28, at columns a + dir*(1..t+1)   (windows: win_pass8 / win_pass4 / win_pass; t <= 2: dx_cell_loads;
+//     rows of the same strip: finish);
+// Inside, that row r = sd-2-t has alo(r) <= alo(sd) and ahi(r) >= ahi(sd)-2-t, and the columns are a-1-t .. a-1: not below
+// alo(sd)-1-t >= alo(r)-29 and not above ahi(sd)-1 <= ahi(r)+t+1 <= ahi(r)+29.  Outside, r = sd+2+t has alo(r) <= alo(sd)+2+t and
+// ahi(r) >= ahi(sd), and the columns are a+1 .. a+1+t: not below alo(sd)+1 >= alo(r)-t-1 >= alo(r)-29 and not above ahi(sd)+1+t <=
+// ahi(r)+29.  So every read of a kept cell lies in [alo(r)-29, ahi(r)+29] of the row it reads (tests/test_gpu_stale_tables.py enumerates it);
+// a row kept correct on [alo-kDxBand, ahi+kDxBand] serves every reader, and the zero pad columns are that band where it leaves the row.
+constexpr int kDxBand = 32;
+static_assert(kDxBand >= 30 && kDxBand <= kDxPad, "the band covers every read and ends inside the pad columns");
+// dxl_strip8: the groups of 58 columns that [lo - kDxBand, hi + kDxBand] can touch when lo..hi spans the cells of the eight rows of launch `step`, for any
+// pair with L1 <= n1max, L2 <= n2max: a row has at most min(L1, L2, sd-1, L1+L2-sd+1) cells, the first row of the launch (inside
+// sd = 2+8 step, outside sd = L1+L2-8 step-7) so at most cnt = min(n1max, n2max, 8 step+8, n1max+n2max-8 step-1), the eight rows together
+// span at most cnt+7 columns, and an interval of n columns meets at most (n-1)/58 + 2 groups
+inline int dxl_strip8_groups(int n1max, int n2max, int step)
+{
+    const int all = (n1max + 2 + 57) / 58;
+    int cnt = n1max < n2max ? n1max : n2max;
+    if (8 * step + 8 < cnt) cnt = 8 * step + 8;
+    const int rest = n1max + n2max - 8 * step - 1;
+    if ((rest > 1 ? rest : 1) < cnt) cnt = rest > 1 ? rest : 1;
+    const int g = (cnt + 7 + 2 * kDxBand - 1) / 58 + 2;
+    return g < all ? g : all;
+}
+
 enum DxLinTable { DL_IN = 0, DL_INX, DL_OUT, DL_OUTX, DL_COUNT };
 
 struct DxLinBatch {

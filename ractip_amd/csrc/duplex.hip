@@ -221,4 +221,23 @@ __global__ __launch_bounds__(256) void dx_posterior(DxBatch B)
     B.hp[(size_t)pr * B.tab_stride + ij] = e > kNeg / 2 ? exp(e) : 0.0;
 }
 
+// What no posterior kernel of the CONTRAfold model writes of hp[(n1max+2) x ldd]: row 0, column 0 and everything beyond L1 / L2.  dx_posterior
+// above and dxl_posterior (duplex_lin.hip) store every entry 1 <= i <= L1, 1 <= j <= L2 of every pair whatever its value (zeros
+// included, no holes), and a pair recomputed as a sub-batch gets its whole matrix copied over; so the upload zeroes only the rest.
+// blockIdx.x deals the rows of a pair's matrix round-robin (a workgroup per row is a quarter of a million nearly empty workgroups).
+__global__ __launch_bounds__(256) void dx_hp_clear_rest(DxBatch B)
+{
+    const int pr = blockIdx.y;
+    const int L1 = B.n[2 * pr], L2 = B.n[2 * pr + 1];
+    for (int i = blockIdx.x; i < B.n1max + 2; i += gridDim.x) {
+        double* __restrict__ row = B.hp + (size_t)pr * B.tab_stride + (size_t)i * B.ldd;
+        if (i == 0 || i > L1) {
+            for (int j = threadIdx.x; j < B.ldd; j += 256) row[j] = 0.0;
+        } else {
+            if (threadIdx.x == 0) row[0] = 0.0;
+            for (int j = L2 + 1 + threadIdx.x; j < B.ldd; j += 256) row[j] = 0.0;
+        }
+    }
+}
+
 }  // namespace rh

@@ -447,7 +447,19 @@ __global__ __launch_bounds__(256) RH_WPE_DX void dxl_sweep4(DxLinBatch B, const 
 //   * X_k also reads the strip's own rows k' <= k-2 (kept in LDS, raw and decorated): four time slots, two diagonals each
 //     (wavefronts 2s, 2s+1), an LDS-only barrier in between;
 //   * X_k reaches k-1-k' columns into row k': the valid lanes shrink by up to 6 from the `dir` side, groups advance by 58 columns
-//     and the overlap is recomputed.  Every column 0..n1max+1 of the 8 rows is written (0 where there is no cell).
+//     and the overlap is recomputed.
+// What a launch leaves behind (the band invariant).  Row sd has cells at columns alo(sd) = max(1, sd-L2) .. ahi(sd) = min(L1, sd-1).
+// After the launch each of its rows is correct -- the cell's value, 0 where there is no cell -- on [alo-kDxBand, ahi+kDxBand] clipped
+// to the columns 0..n1max+1 of the row, and UNSPECIFIED beyond (whatever an earlier batch of the same table layout left there,
+// Inf / NaN included).  That is all anyone reads, see the proof at kDxBand (batch.h): a kept cell reads a row only within 30 columns
+// of that row's cells, and dxl_logz_part / dxl_posterior read cells only.  A lane outside [alo, ahi] of its diagonal may load and sum
+// such stale values, but none of them reaches a stored value: `pairable` (dx_cell_weights) is false for it, so its operands are
+// selected to 0 and finish() stores 0 for it, and windows, partial sums and the strip's own rows are per lane -- a kept lane takes
+// from srow only lanes that are themselves kept cells or zeros.  Hence no clear of these tables after an overflowed batch either.
+//   * a group with cells on none of the eight diagonals stores zeros where its columns meet the band of a row, and nothing else;
+//   * a group with cells stores its 58 columns of all eight rows (a superset);
+//   * the grid holds only as many groups as the bands of one launch can touch: blockIdx.x counts from the first group of this
+//     pair's band (dxl_strip8_groups is the bound, a function of the batch shape and the step alone: the launches are captured).
 __device__ __forceinline__ void lds_barrier_dx() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 template <int WV>
@@ -516,10 +528,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
     const int sdA = outside ? smax - KD * step : 2 + KD * step;
     if (outside ? sdA < 2 : sdA > smax) return;                 // none of the eight diagonals exists
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    // the cells of the launch's rows span columns lo..hi (alo and ahi both grow with sd); the first group that meets their band
+    const int sd_lo = outside ? (sdA - (KD - 1) > 2 ? sdA - (KD - 1) : 2) : sdA, sd_hi = outside ? sdA : (sdA + (KD - 1) < smax ? sdA + (KD - 1) : smax);
+    const int lo = sd_lo - L2 > 1 ? sd_lo - L2 : 1;
+    const int grp = (lo > kDxBand ? lo - kDxBand : 0) / GS + (int)blockIdx.x;
+    if (grp * GS > B.n1max + 1) return;
     // own lanes: inside (sources at smaller columns) lanes 6..63, outside lanes 0..57
-    const int a0 = outside ? (int)blockIdx.x * GS : (int)blockIdx.x * GS - 6;
+    const int a0 = outside ? grp * GS : grp * GS - 6;
     const int a = a0 + lane;
-    const bool own = outside ? (lane < GS || a0 + GS > B.n1max + 1) : (lane >= 6 || blockIdx.x == 0);
+    const bool own = outside ? (lane < GS || a0 + GS > B.n1max + 1) : (lane >= 6 || grp == 0);
     const int lda = B.lda;
     const size_t ts = B.tab_stride;
     double* __restrict__ tab = B.tab + (size_t)pr * B.pair_stride;
@@ -528,7 +545,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
     const double* __restrict__ rawt = tab + (outside ? DL_OUT : DL_IN) * ts + kDxPad;
     const double* __restrict__ dect = tab + (outside ? DL_OUTX : DL_INX) * ts + kDxPad;
 
-    {   // does this group hold a cell [max(1, sd-L2), min(L1, sd-1)] of any of the eight diagonals?  If not: clear its columns and leave
+    {   // does this group hold a cell [max(1, sd-L2), min(L1, sd-1)] of any of the eight diagonals?  If not: zero what it owns of the rows' bands and leave
         bool has = false;
 #pragma unroll
         for (int k = 0; k < KD; k++) {
@@ -540,7 +557,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
 #pragma unroll
                 for (int q = 0; q < 2; q++) {
                     const int r = w + 8 * q, tbl = r >> 3, sd = sdA + (r & 7) * fwd;
-                    if (sd >= 2 && sd <= smax) tab[(tbl ? (outside ? DL_OUTX : DL_INX) : (outside ? DL_OUT : DL_IN)) * ts + (size_t)sd * lda + kDxPad + a] = 0.0;
+                    const int blo = (sd - L2 > 1 ? sd - L2 : 1) - kDxBand, bhi = (sd - 1 < L1 ? sd - 1 : L1) + kDxBand;
+                    if (sd >= 2 && sd <= smax && a >= blo && a <= bhi) tab[(tbl ? (outside ? DL_OUTX : DL_INX) : (outside ? DL_OUT : DL_IN)) * ts + (size_t)sd * lda + kDxPad + a] = 0.0;
                 }
             }
             return;
@@ -640,7 +658,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
         lds_barrier_dx();
     }
     RH_DSTAMP(7);   // chain (four slots)
-    // ---- the 2 x 8 rows go to HBM: row (table, k) by wavefront; every column of the row is rewritten
+    // ---- the 2 x 8 rows go to HBM: row (table, k) by wavefront; all columns of the group, which covers what it owns of the rows' bands
     if (own && a >= 0 && a <= B.n1max + 1) {
 #pragma unroll
         for (int q = 0; q < 2; q++) {
@@ -657,28 +675,64 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
 // workgroup, read along the rows of the table (coalesced), then one thread per pair adds the chunks in order.
 // zpart: [NP][nchunk] partial sums, cpart: pairable-cell counts
 constexpr int kLzRows = 16;
+// A streaming reduction: the work of a chunk is the list of items (row, k), row = 0..kLzRows-1, k = 0..nk-1, item (row, k) being
+// column alo + 256 k + thread of the row; nk covers the longest row the batch shape allows, so the list is the same for every
+// workgroup and every thread adds its items in the order (sd, a + 256 k) whatever the pair.  Eight items at a time: all their loads
+// (letters and table value, from an address clamped into the row) are issued before anything is tested, and an item that is no cell or
+// no complementary pair is dropped by SELECT -- a load behind `if (!pairs) continue` is only issued once the letters have arrived.
+// The row factor is the same for the whole row: one pow() per row and workgroup, through LDS.
 __global__ __launch_bounds__(256) void dxl_logz_part(DxLinBatch B, const DxLinModel* __restrict__ L, double* __restrict__ zpart, int* __restrict__ cpart, int nchunk)
 {
+    constexpr int U = 8;
     __shared__ double sm[4];
     __shared__ int sc[4];
+    __shared__ double srowf[kLzRows];
     const int pr = blockIdx.y, chunk = blockIdx.x;
     const int L1 = B.n[2 * pr], L2 = B.n[2 * pr + 1];
+    const int smax = L1 + L2, sd0 = 2 + chunk * kLzRows;
     const uint8_t* __restrict__ s1 = B.seq + (size_t)(2 * pr) * B.lds;
     const uint8_t* __restrict__ s2 = B.seq + (size_t)(2 * pr + 1) * B.lds;
     const double* __restrict__ in = B.tab + (size_t)pr * B.pair_stride + DL_IN * B.tab_stride + kDxPad;
+    if (sd0 > smax) {   // (no row of this pair: the chunk's sums are zero)
+        if (threadIdx.x == 0) { zpart[(size_t)pr * nchunk + chunk] = 0.0; cpart[(size_t)pr * nchunk + chunk] = 0; }
+        return;
+    }
+    if (threadIdx.x < kLzRows) {
+        // close~ = (lam*e^eu)^(L1+L2-sd) * lam^2 * dangles * helix_closing
+        const int sd = sd0 + threadIdx.x;
+        srowf[threadIdx.x] = pow(L->lam_eu, (double)(L1 + L2 - sd)) * L->lam_pow[2];
+    }
+    __syncthreads();
+    const int nmin = B.n1max < B.n2max ? B.n1max : B.n2max;
+    const int nk = (nmin + 255) / 256;                 // a row has at most min(L1, L2) cells
+    const int nitem = kLzRows * nk;                    // (a multiple of U)
     double acc = 0.0;
     int npair = 0;
-    for (int sd = 2 + chunk * kLzRows; sd < 2 + (chunk + 1) * kLzRows && sd <= L1 + L2; sd++) {
-        // close~ = (lam*e^eu)^(L1+L2-sd) * lam^2 * dangles * helix_closing
-        const double rowf = pow(L->lam_eu, (double)(L1 + L2 - sd)) * L->lam_pow[2];
-        const int alo = sd - L2 > 1 ? sd - L2 : 1, ahi = sd - 1 < L1 ? sd - 1 : L1;
-        for (int a = alo + threadIdx.x; a <= ahi; a += 256) {
-            const int i = a, j = L2 + 1 - (sd - a);
-            const int x = s1[i], y = s2[j];
-            if (!pairs(x, y)) continue;
-            npair++;
-            const double cl = rowf * L->E_dl[x * 25 + y * 5 + s1[i + 1]] * L->E_dr[x * 25 + y * 5 + s2[j - 1]] * L->E_hc[x * 5 + y];
-            acc = fma(in[(size_t)sd * B.lda + a], cl, acc);
+    int row = 0, k = 0;                                // item m = row * nk + k (wave-uniform)
+    for (int m0 = 0; m0 < nitem; m0 += U) {
+        double v[U], rowf[U];
+        int x[U], y[U], xp[U], ym[U];
+        bool live[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const int sd = sd0 + row;
+            const int sdc = sd <= smax ? sd : smax;
+            const int alo = sdc - L2 > 1 ? sdc - L2 : 1, ahi = sdc - 1 < L1 ? sdc - 1 : L1;
+            const int a = alo + 256 * k + (int)threadIdx.x;
+            live[u] = sd <= smax && a <= ahi;
+            const int i = live[u] ? a : alo, j = L2 + 1 - (sdc - i);
+            x[u] = s1[i]; xp[u] = s1[i + 1]; y[u] = s2[j]; ym[u] = s2[j - 1];
+            v[u] = in[(size_t)sdc * B.lda + i];
+            rowf[u] = srowf[row];
+            if (++k == nk) { k = 0; row++; }
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const bool on = live[u] && pairs(x[u], y[u]);
+            const double cl = rowf[u] * L->E_dl[x[u] * 25 + y[u] * 5 + xp[u]] * L->E_dr[x[u] * 25 + y[u] * 5 + ym[u]] * L->E_hc[x[u] * 5 + y[u]];
+            const double next = fma(v[u], cl, acc);
+            acc = on ? next : acc;
+            npair += on ? 1 : 0;
         }
     }
     for (int o = 32; o > 0; o >>= 1) { acc += __shfl_xor(acc, o, 64); npair += __shfl_xor(npair, o, 64); }

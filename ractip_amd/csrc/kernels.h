@@ -18,6 +18,7 @@ __global__ void mc_unpaired(McBatch B);
 __global__ void dx_sweep_diag(DxBatch B, const ScoreModel* __restrict__ M, int t);
 __global__ void dx_logz(DxBatch B, const ScoreModel* __restrict__ M);
 __global__ void dx_posterior(DxBatch B);
+__global__ void dx_hp_clear_rest(DxBatch B);
 __global__ void lin_init(McBatch B, const LinModel* __restrict__ L, int* __restrict__ bad);
 template <int W, int BS, int MODE> __global__ void lin_inside_diag(McBatch B, const LinModel* __restrict__ L, int d, double lam_d, int pin);
 template <int W, int BS> __global__ void lin_outside_diag(McBatch B, const LinModel* __restrict__ L, int d, int pin, int* __restrict__ bad);

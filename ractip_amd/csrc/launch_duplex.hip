@@ -62,10 +62,10 @@ int launch_dx_lin_on(rh_ctx* c, const SweepPlan& P, DxLinBatch X, const DxLinMod
     const int groups = (X.n1max + 2 + 63) / 64;
     const double leu = hm.lam_eu, l2 = hm.lam_pow[2];
     if (P.org == SweepPlan::kDxStrip8) {
-        const int groups8 = (X.n1max + 2 + 57) / 58;
         for (int t = 0; 8 * t < smax - 1; t++) {
             for (int k = 0; k < 8; k++) X.pw8[k] = std::pow(leu, 8.0 * t + k) * l2;
-            KLAUNCH(c, 4, (kDxStrip8.kern), dim3(groups8, X.np, 2), dim3(512), c->s_dx, X, dm, t);
+            // (only the groups the bands of this step's rows can touch; the kernel places them per pair)
+            KLAUNCH(c, 4, (kDxStrip8.kern), dim3(dxl_strip8_groups(X.n1max, X.n2max, t), X.np, 2), dim3(512), c->s_dx, X, dm, t);
             c->n_launch[2]++;
         }
     } else if (P.org == SweepPlan::kDxSweep4) {

@@ -218,9 +218,13 @@ int stage(rh_ctx* c, int ns, const char* const* seqs, const int* lens, bool with
         if ((rc = ensure(c, c->d_logz, sizeof(double) * D.np, false))) return rc;
         const size_t hp_bytes = sizeof(double) * D.tab_stride * D.np;
         if ((rc = ensure(c, c->d_hp, hp_bytes, false))) return rc;
-        HIP_TRY(c, hipMemsetAsync(c->d_hp.p, 0, hp_bytes, c->s_dx));  // row 0 / column 0 stay zero
         D.seq = c->d_seq.as<const uint8_t>(); D.n = c->d_n.as<const int>();
         D.tab = c->d_dxtab.as<double>(); D.hp = c->d_hp.as<double>(); D.logz = c->d_logz.as<double>();
+        // row 0, column 0 and what lies beyond L1 / L2 stay zero.  CONTRAfold model: every path stores all of 1..L1 x 1..L2 (see
+        // dx_hp_clear_rest), so only the rest is zeroed.  Vienna-BL keeps the whole clear: its hp also comes from the two-molecule
+        // ensemble (cofold) and from the helper context, which copy or store parts of the matrix only.
+        if (vienna) HIP_TRY(c, hipMemsetAsync(c->d_hp.p, 0, hp_bytes, c->s_dx));
+        else hipLaunchKernelGGL(dx_hp_clear_rest, dim3(16, D.np), dim3(256), 0, c->s_dx, D);
         if (vienna && c->hybrid == RH_HYBRID_COFOLD) {
             // concatenated sequences s1+s2, cut after s1
             McBatch& C = c->co;
