@@ -13,13 +13,18 @@
 
 namespace rh::host {
 
-// ---- hipGraph replay of the fast path.  The launch sequence of a batch depends only on its shape (and on the
-// buffer addresses baked into the kernel arguments), so it is captured once per shape and replayed: the ~1000
-// launches per sweep then cost the GPU-side ~1.5 us boundary instead of a host launch each.
-template <class F>
-int run_graphed(rh_ctx* c, GraphSlot& g, size_t key, hipStream_t stream, int* launch_counter, int* far_counter, F&& launch)
+// ---- hipGraph replay of the fast path.  A launch sequence depends only on its argument(s) (ctx.h), so it is captured once per
+// value of them and replayed: the ~1000 launches per sweep then cost the GPU-side ~1.5 us boundary instead of a host launch each.
+// The key of slot g is a hash of the arguments' bytes; k: the n_launch / n_far entry that counts the sequence.
+template <class L, class... Args>
+int run_graphed(rh_ctx* c, GraphSlot& g, hipStream_t stream, int k, L launcher, const Args&... args)
 {
+    const auto launch = [&] { int rc = RH_OK; ((rc = rc ? rc : launcher(c, args)), ...); return rc; };
     if (!c->use_graphs || c->time_cls >= 0) return launch();   // (timed launches are host launches: events between graph nodes would be captured)
+    size_t key = 1469598103934665603ull + (sizeof(Args) + ...);
+    const auto mix = [&](const void* p, size_t n) { for (size_t q = 0; q < n; q++) key = (key ^ ((const unsigned char*)p)[q]) * 0x100000001b3ull; };
+    (mix(&args, sizeof(Args)), ...);
+    int *launch_counter = &c->n_launch[k], *far_counter = &c->n_far[k];
     if (!g.exec || g.key != key) {
         if (g.exec) { HIP_TRY(c, hipGraphExecDestroy(g.exec)); g.exec = nullptr; }
         hipGraph_t graph = nullptr;
@@ -44,35 +49,73 @@ int run_graphed(rh_ctx* c, GraphSlot& g, size_t key, hipStream_t stream, int* la
     return RH_OK;
 }
 
-static size_t shape_key(const rh_ctx* c, int which)
+// ---- the arguments of the launchers, from the context
+// One phase over the sequences B on the model `lin`.  routed: B is the batch as uploaded, whose short and small sequences have passes
+// of their own (stage() has written their lists and length arrays).
+McLinArgs mc_lin_args(const rh_ctx* c, int phase, const McBatch& B, const LinSet* lin, bool routed)
 {
-    auto mix = [](size_t h, size_t v) { return (h ^ v) * 0x100000001b3ull + 0x9e3779b97f4a7c15ull; };
-    size_t h = 1469598103934665603ull + which;
-    if (which == 3) {
-        const McBatch& B = c->co;
-        for (size_t v : {(size_t)B.ns, (size_t)B.nmax, (size_t)B.ld, (size_t)B.lds, (size_t)B.tab, (size_t)B.seq, (size_t)B.n, (size_t)B.f5i,
-                         (size_t)B.bp, (size_t)c->d_cobad.p, (size_t)c->lin_bs, (size_t)B.tri_stride, (size_t)c->dx.hp, (size_t)c->dx.logz,
-                         (size_t)c->dx.ldd, (size_t)c->dx.tab_stride, (size_t)c->dx.n1max, (size_t)c->dx.n2max, (size_t)B.allow, (size_t)B.pk,
-                         (size_t)c->far_pk, (size_t)B.rowp, (size_t)c->lookahead, (size_t)B.seeded, (size_t)c->mc.tab, (size_t)c->mc.ld, (size_t)c->d_vlin,
-                         // the windowed grid and its pin offset are baked into the captured launches (launch_mc_vlin)
-                         (size_t)c->co_window, (size_t)(c->co_cut_min + 1), (size_t)(c->co_cut_max + 1), (size_t)(c->far2 + 2)})
-            h = mix(h, v);
-    } else if (which <= 1) {
-        const McBatch& B = c->mc;
-        for (size_t v : {(size_t)B.ns, (size_t)B.nmax, (size_t)B.ld, (size_t)B.lds, (size_t)B.tab, (size_t)B.seq, (size_t)B.n,
-                         (size_t)B.f5i, (size_t)B.bp, (size_t)B.up, (size_t)c->d_bad.p, (size_t)c->d_mclogz.p, (size_t)c->lin_w, (size_t)c->lin_w_in,
-                         (size_t)c->lin_bs, (size_t)B.tri_stride, (size_t)c->far_mfma, (size_t)c->max_w, (size_t)c->d_gaps.p,
-                         (size_t)c->d_hplen.p, (size_t)B.allow, (size_t)B.pk, (size_t)c->far_pk, (size_t)B.rowp, (size_t)c->lookahead, (size_t)c->strip, (size_t)c->lin->wT.p, (size_t)c->strip_w, (size_t)(c->strip_filt && c->strip_filt_ok), (size_t)c->strip_xcd, (size_t)(c->far2 + 2), (size_t)c->acc_wide, (size_t)c->acc_final_t, (size_t)c->d_vlin,
-                         (size_t)c->small_on, c->small_list.size(), (size_t)c->nmax_sweep, (size_t)c->d_small_list.p, (size_t)c->d_n_sweep.p,
-                         (size_t)c->n_short, (size_t)c->nmax_short, (size_t)c->d_n_short.p})
-            h = mix(h, v);
-    } else {
-        const DxLinBatch& X = c->dxl;
-        for (size_t v : {(size_t)X.np, (size_t)X.n1max, (size_t)X.n2max, (size_t)X.lda, (size_t)X.ldd, (size_t)X.tab, (size_t)X.hp,
-                         (size_t)X.seq, (size_t)X.n, (size_t)c->d_zbar.p, (size_t)c->d_logz.p, (size_t)c->d_dxbad.p, (size_t)c->dx_w, (size_t)c->d_zpart.p, (size_t)c->dx_quad, (size_t)c->dx_strip})
-            h = mix(h, v);
+    McLinArgs A;
+    A.B = B; A.lin = lin; A.phase = phase;
+    A.logz = c->d_mclogz.as<double>(); A.bad = c->d_bad.as<int>();
+    A.plan = plan_mc_lin(c, phase, B.nmax);
+    if (routed && (!c->small_list.empty() || c->n_short > 0)) {
+        A.routed = 1;
+        A.small_list = c->d_small_list.as<const int>(); A.n_small = (int)c->small_list.size();
+        A.n_sweep = c->d_n_sweep.as<const int>(); A.nmax_sweep = c->nmax_sweep;
+        A.n_short = c->d_n_short.as<const int>(); A.nmax_short = c->nmax_short; A.short_count = c->n_short;
+        A.plan_sweep = plan_mc_lin(c, phase, A.nmax_sweep);
+        A.plan_short = plan_mc_lin(c, phase, A.nmax_short);
     }
-    return h;
+    A.pin = B.ns % 8 == 0 ? 1 : 0;   // sequence -> XCD affinity only when the batch spreads evenly over the 8 XCDs (speed only)
+    A.strip_xcd = c->strip_xcd;
+    return A;
+}
+
+// One phase over the staged single-molecule batch or (co) the s1+s2 batch, on the model select_vlin selected last
+static McVlinArgs mc_vlin_args(const rh_ctx* c, int phase, bool co)
+{
+    McVlinArgs A;
+    A.B = co ? c->co : c->mc; A.phase = phase; A.co = co;
+    A.pin = A.B.ns % 8 == 0 ? 1 : 0;
+    A.plan = plan_mc_vlin(c, phase, co, A.B.nmax);
+    A.d_vlin = c->d_vlin; A.h_vlin = c->h_vlin; A.hplen = c->h_hplen.data(); A.d_hplen = c->d_hplen.as<const double>();
+    A.bad = co ? c->d_cobad.as<int>() : c->d_bad.as<int>();
+    if (co) {
+        const DxBatch& D = c->dx;
+        if (A.B.seeded) A.from = c->mc;
+        A.hp = D.hp; A.hp_logz = D.logz; A.hp_stride = D.tab_stride; A.hp_ldd = D.ldd; A.n1max = D.n1max; A.n2max = D.n2max;
+        A.cut_min = c->co_cut_min; A.cut_max = c->co_cut_max;
+        A.window = c->co_window && c->co_cut_min >= 1 && (phase == 1 || A.B.seeded);   // (an unseeded inside sweep computes every group)
+    } else {
+        A.logz = c->d_mclogz.as<double>(); A.gaps = c->d_gaps.as<double>(); A.max_w = c->max_w;
+        // (vlin_acc_gaps_wide addresses a sequence's tables with 32-bit offsets; vlin_acc_final_t has up to fifteen widths)
+        A.acc_wide = c->acc_wide && (size_t)kViennaMcTables * A.B.tab_stride * sizeof(double) < ((size_t)1 << 32);
+        A.acc_final_t = c->acc_final_t && c->max_w <= 15;
+    }
+    return A;
+}
+
+// The hybridization sweeps over the staged batch of pairs, either model
+DxLinArgs dx_lin_args(const rh_ctx* c)
+{
+    DxLinArgs A;
+    A.X = c->dxl; A.plan = c->plan[2]; A.lz_chunks = c->lz_chunks;
+    if (c->model == RH_MODEL_VIENNA_BL) A.vdx_s = c->vdx_s;
+    else { A.dm = c->d_dxlin; A.hm = &c->h_dxlin; }
+    A.zpart = c->d_zpart.as<double>(); A.zbar = c->d_zbar.as<double>();
+    A.logz = c->d_logz.as<double>(); A.bad = c->d_dxbad.as<int>();
+    return A;
+}
+
+// the indices of the set ones among the n flags at d_flags, read behind everything `st` holds
+int flagged(rh_ctx* c, const int* d_flags, int n, hipStream_t st, std::vector<int>* set)
+{
+    std::vector<int> flags(n);
+    HIP_TRY(c, hipMemcpyAsync(flags.data(), d_flags, sizeof(int) * n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    set->clear();
+    for (int k = 0; k < n; k++) if (flags[k]) set->push_back(k);
+    return RH_OK;
 }
 
 int compute_once(rh_ctx* c)
@@ -85,14 +128,14 @@ int compute_once(rh_ctx* c)
     c->n_far[0] = c->n_far[1] = c->n_far[2] = 0;
     c->last_path = 0;
     c->fallback_mc.clear(); c->fallback_dx.clear(); c->rescaled_mc.clear(); c->rescaled_dx.clear();
-    // the organisation of each sweep's linear first pass: decided here, on every compute (a replayed graph does not call its launcher),
-    // from switches and shapes that are all part of shape_key
+    // the organisation of each sweep's linear first pass: decided here, on every compute (a replayed graph does not call its launcher);
+    // the arguments below carry the same plans to the launchers
     const bool vienna = c->model == RH_MODEL_VIENNA_BL;
     for (int phase = 0; phase < 2; phase++) c->plan[phase] = vienna ? plan_mc_vlin(c, phase, false, c->mc.nmax) : plan_mc_lin(c, phase, c->mc.nmax);
     c->plan[2] = !vienna ? plan_dx_lin(c, c->dx_w) : c->hybrid == RH_HYBRID_COFOLD ? plan_mc_vlin(c, 0, true, c->co.nmax) : plan_dx_vlin();
-    // sequence -> XCD affinity only when the batch spreads evenly over the 8 XCDs (speed only)
-    const int pin = (c->has_mc && c->mc.ns % 8 == 0) ? 1 : 0;
+    const int pin = (c->has_mc && c->mc.ns % 8 == 0) ? 1 : 0;   // (of the log-space sweeps; the linear ones: see their arguments)
     int rc;
+    std::vector<int> bad;
     // duplex first on its own stream: it is independent of the McCaskill sweeps and overlaps them
     HIP_TRY(c, hipEventRecord(c->ev[3], c->s_dx));
     bool dx_lin_launched = false, co_lin_launched = false, co_seed_bad = false, out_from_ev5 = false;
@@ -102,11 +145,7 @@ int compute_once(rh_ctx* c)
                          c->co_seed && !c->mc.allow && !c->co.allow && c->mc.ns == 2 * c->co.ns;
     c->co.seeded = co_seed ? 1 : 0;
     auto launch_co_lin = [&]() -> int {   // scaled linear sweeps over s1+s2; out-of-range values send the batch to the log-space kernels
-        const int cpin = c->co.ns % 8 == 0 ? 1 : 0;
-        return run_graphed(c, c->g_dx, shape_key(c, 3), c->s_dx, &c->n_launch[2], &c->n_far[2], [&] {
-            const int r = launch_mc_vlin(c, cpin, 0, true, plan_mc_vlin(c, 0, true, c->co.nmax));
-            return r ? r : launch_mc_vlin(c, cpin, 1, true, plan_mc_vlin(c, 1, true, c->co.nmax));
-        });
+        return run_graphed(c, c->g_dx, c->s_dx, 2, launch_mc_vlin, mc_vlin_args(c, 0, true), mc_vlin_args(c, 1, true));   // (one graph of both)
     };
     if (c->has_dx && c->model == RH_MODEL_VIENNA_BL && c->hybrid == RH_HYBRID_COFOLD) {
         HIP_TRY(c, hipMemsetAsync(c->d_cobp.p, 0, sizeof(double) * c->co.tri_stride * c->co.ns, c->s_dx));
@@ -122,7 +161,7 @@ int compute_once(rh_ctx* c)
         }
     } else if (c->has_dx && c->model == RH_MODEL_VIENNA_BL) {
         if (c->mode != RH_MODE_LOG) {   // scaled linear sweeps; pairs outside the double range send the batch to the log-space kernels
-            if ((rc = run_graphed(c, c->g_dx, shape_key(c, 2), c->s_dx, &c->n_launch[2], &c->n_far[2], [&] { return launch_dx_vlin(c); }))) return rc;
+            if ((rc = run_graphed(c, c->g_dx, c->s_dx, 2, launch_dx_vlin, dx_lin_args(c)))) return rc;
             dx_lin_launched = true;
         } else {
             if ((rc = launch_dx_vlog(c))) return rc;
@@ -130,10 +169,10 @@ int compute_once(rh_ctx* c)
         }
     } else if (c->has_dx) {
         if (c->mode != RH_MODE_LOG) {
-            if ((rc = run_graphed(c, c->g_dx, shape_key(c, 2), c->s_dx, &c->n_launch[2], &c->n_far[2], [&] { return launch_dx_lin(c, c->plan[2]); }))) return rc;
+            if ((rc = run_graphed(c, c->g_dx, c->s_dx, 2, launch_dx_lin, dx_lin_args(c)))) return rc;
             dx_lin_launched = true;
         } else {
-            if ((rc = launch_dx_log(c))) return rc;
+            if ((rc = launch_dx_log(c, c->dx))) return rc;
             c->last_dx_path = 2;
         }
     }
@@ -145,7 +184,7 @@ int compute_once(rh_ctx* c)
     if (c->has_mc && c->model == RH_MODEL_VIENNA_BL) {
         bool log_path = c->mode == RH_MODE_LOG;
         if (!log_path) {   // scaled linear sweeps; a sequence that leaves the double range sends the batch to the log-space kernels
-            if ((rc = run_graphed(c, c->g_in, shape_key(c, 0), c->s_mc, &c->n_launch[0], &c->n_far[0], [&] { return launch_mc_vlin(c, pin, 0, false, c->plan[0]); }))) return rc;
+            if ((rc = run_graphed(c, c->g_in, c->s_mc, 0, launch_mc_vlin, mc_vlin_args(c, 0, false)))) return rc;
             HIP_TRY(c, hipEventRecord(c->ev[1], c->s_mc));
             if (co_seed) {   // the inside tables of both molecules are final behind ev[1]
                 HIP_TRY(c, hipStreamWaitEvent(c->s_dx, c->ev[1], 0));
@@ -158,16 +197,14 @@ int compute_once(rh_ctx* c)
             }
             HIP_TRY(c, hipEventRecord(c->ev[5], c->s_mc));   // start of the outside phase (= ev[1] unless the seeded sweeps ran in between)
             out_from_ev5 = true;
-            if ((rc = run_graphed(c, c->g_out, shape_key(c, 1), c->s_mc, &c->n_launch[1], &c->n_far[1], [&] { return launch_mc_vlin(c, pin, 1, false, c->plan[1]); }))) return rc;
+            if ((rc = run_graphed(c, c->g_out, c->s_mc, 1, launch_mc_vlin, mc_vlin_args(c, 1, false)))) return rc;
             c->last_path = 1;
             if (c->mode == RH_MODE_AUTO) {
-                std::vector<int> bad(c->mc.ns);
-                HIP_TRY(c, hipMemcpyAsync(bad.data(), c->d_bad.p, sizeof(int) * c->mc.ns, hipMemcpyDeviceToHost, c->s_mc));
-                HIP_TRY(c, hipStreamSynchronize(c->s_mc));
-                for (int b : bad) log_path |= (b != 0);
+                if ((rc = flagged(c, c->d_bad.as<int>(), c->mc.ns, c->s_mc, &bad))) return rc;
+                log_path = !bad.empty();
                 if (log_path) { c->last_path = 3; c->tables_dirty = true; co_seed_bad = co_seed; }
                 if (log_path && c->defer_log) {   // another exponent first (compute): this attempt ends here
-                    for (int k = 0; k < c->mc.ns; k++) if (bad[k]) { c->flagged_mc.push_back(k); if (c->has_dx) c->flagged_pairs.push_back(k / 2); }
+                    for (int k : bad) { c->flagged_mc.push_back(k); if (c->has_dx) c->flagged_pairs.push_back(k / 2); }
                     c->deferred = true;
                     log_path = false;
                 }
@@ -184,23 +221,19 @@ int compute_once(rh_ctx* c)
             if (c->last_path == 0) c->last_path = 2;
         }
     } else if (c->has_mc && c->mode != RH_MODE_LOG) {
-        // the exponent most of the last batch needed (scale-exponent ladder); c->lin is the default's again afterwards
+        // on the exponent most of the last batch needed (scale-exponent ladder), or the default one
         const bool on_rung = c->mode == RH_MODE_AUTO && c->scale_ladder && c->lin_primary >= 0 && c->lin_r;
-        if (on_rung) c->lin = &c->lin_r[c->lin_primary];
-        struct Back { rh_ctx* c; ~Back() { c->lin = &c->lin0; } } back{c};
-        if ((rc = run_graphed(c, c->g_in, shape_key(c, 0), c->s_mc, &c->n_launch[0], &c->n_far[0], [&] { return launch_mc_lin(c, pin, 0, c->plan[0]); }))) return rc;
+        const LinSet* lin = on_rung ? &c->lin_r[c->lin_primary] : &c->lin0;
+        if ((rc = run_graphed(c, c->g_in, c->s_mc, 0, launch_mc_lin, mc_lin_args(c, 0, c->mc, lin, true)))) return rc;
         HIP_TRY(c, hipEventRecord(c->ev[1], c->s_mc));
-        if ((rc = run_graphed(c, c->g_out, shape_key(c, 1), c->s_mc, &c->n_launch[1], &c->n_far[1], [&] { return launch_mc_lin(c, pin, 1, c->plan[1]); }))) return rc;
+        if ((rc = run_graphed(c, c->g_out, c->s_mc, 1, launch_mc_lin, mc_lin_args(c, 1, c->mc, lin, true)))) return rc;
         c->last_path = 1;
         if (c->mode == RH_MODE_AUTO) {  // did every sequence stay inside the double range?
-            std::vector<int> bad(c->mc.ns);
-            HIP_TRY(c, hipMemcpyAsync(bad.data(), c->d_bad.p, sizeof(int) * c->mc.ns, hipMemcpyDeviceToHost, c->s_mc));
-            HIP_TRY(c, hipStreamSynchronize(c->s_mc));
-            for (int k = 0; k < c->mc.ns; k++) if (bad[k]) c->fallback_mc.push_back(k);
+            if ((rc = flagged(c, c->d_bad.as<int>(), c->mc.ns, c->s_mc, &c->fallback_mc))) return rc;
             if (!c->fallback_mc.empty()) {
                 c->last_path = 3;
                 c->tables_dirty = true;
-                if ((rc = retry_mc_lin_rungs(c, &c->fallback_mc))) return rc;   // another exponent first; what is left goes to log space
+                if ((rc = retry_mc_lin_rungs(c, lin, &c->fallback_mc))) return rc;   // another exponent first; what is left goes to log space
                 for (int q = 0; q <= rh_ctx::kRungs; q++)   // more than half of the batch on one exponent: the next batch starts there
                     if (c->scale_memory && c->mc.ns >= 8 && 2 * c->rescued_by[q] > c->mc.ns) c->lin_primary = q - 1;   // (a batch, not a single call)
                 if (c->fallback_mc.empty()) { }
@@ -216,19 +249,16 @@ int compute_once(rh_ctx* c)
         c->n_far[0] = c->n_far[1] = 0;
         HIP_TRY(c, hipEventRecord(c->ev[0], c->s_mc));
         HIP_TRY(c, hipMemsetAsync(c->d_bp.p, 0, sizeof(double) * c->mc.tri_stride * c->mc.ns, c->s_mc));
-        if ((rc = launch_mc_log(c, pin))) return rc;
+        if ((rc = launch_mc_log(c, pin, c->mc, c->d_mclogz.as<double>()))) return rc;
         if (c->last_path == 0) c->last_path = 2;
     }
     HIP_TRY(c, hipEventRecord(c->ev[2], c->s_mc));
     if (co_lin_launched && c->mode == RH_MODE_AUTO) {
-        std::vector<int> bad(c->co.ns);
-        HIP_TRY(c, hipMemcpyAsync(bad.data(), c->d_cobad.p, sizeof(int) * c->co.ns, hipMemcpyDeviceToHost, c->s_dx));
-        HIP_TRY(c, hipStreamSynchronize(c->s_dx));
-        bool redo = co_seed_bad;   // a molecule left the double range on its own: what was copied from its fold is not usable
-        for (int b : bad) redo |= (b != 0);
+        if ((rc = flagged(c, c->d_cobad.as<int>(), c->co.ns, c->s_dx, &bad))) return rc;
+        const bool redo = co_seed_bad || !bad.empty();   // (a molecule left the double range on its own: what was copied from its fold is not usable)
         if (redo && c->defer_log) {
             c->tables_dirty = true; c->deferred = true;
-            for (int k = 0; k < c->co.ns; k++) if (bad[k]) c->flagged_pairs.push_back(k);
+            c->flagged_pairs.insert(c->flagged_pairs.end(), bad.begin(), bad.end());
         }
         else if (redo) {   // some pair left the double range: recompute the two-molecule sweeps in log space
             c->went_log = true;
@@ -244,11 +274,8 @@ int compute_once(rh_ctx* c)
     if (dx_lin_launched) {
         c->last_dx_path = 1;
         if (c->mode == RH_MODE_AUTO) {
-            std::vector<int> bad(c->dx.np);
-            HIP_TRY(c, hipMemcpyAsync(bad.data(), c->d_dxbad.p, sizeof(int) * c->dx.np, hipMemcpyDeviceToHost, c->s_dx));
-            HIP_TRY(c, hipStreamSynchronize(c->s_dx));
-            bool redo = false;
-            for (int k = 0; k < c->dx.np; k++) if (bad[k]) { redo = true; c->fallback_dx.push_back(k); }
+            if ((rc = flagged(c, c->d_dxbad.as<int>(), c->dx.np, c->s_dx, &c->fallback_dx))) return rc;
+            const bool redo = !c->fallback_dx.empty();
             if (redo && c->model != RH_MODEL_VIENNA_BL && 2 * c->fallback_dx.size() <= (size_t)c->dx.np) {
                 // only the flagged pairs, as a compacted sub-batch with its own tables: another scale exponent on the linear kernels
                 // first (retry_dx_lin_rungs), the log-space kernels for what is left
@@ -263,7 +290,7 @@ int compute_once(rh_ctx* c)
             } else if (redo) {  // most pairs (or the Vienna-BL model): recompute the batch with the log-space kernels
                 c->n_launch[2] = 0;
                 HIP_TRY(c, hipEventRecord(c->ev[3], c->s_dx));
-                if ((rc = (c->model == RH_MODEL_VIENNA_BL ? launch_dx_vlog(c) : launch_dx_log(c)))) return rc;
+                if ((rc = (c->model == RH_MODEL_VIENNA_BL ? launch_dx_vlog(c) : launch_dx_log(c, c->dx)))) return rc;
                 HIP_TRY(c, hipEventRecord(c->ev[4], c->s_dx));
                 c->last_dx_path = 3;
             }

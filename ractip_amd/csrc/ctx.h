@@ -5,7 +5,9 @@
 
 #include <cassert>
 #include <cstdint>
+#include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/ractip_hot.h"
@@ -44,7 +46,7 @@ struct DevObj : DevBuf {
 };
 
 // CONTRAfold linear path: the model at one scale exponent -- host copy, device copy and the transposed, zero-padded single-branch
-// weights wT[l1][t+1] of the strip kernels.  rh_ctx::lin points at the one the next launches use.
+// weights wT[l1][t+1] of the strip kernels.  McLinArgs::lin names the one a pass runs on.
 struct LinSet {
     LinModel h;
     DevObj<LinModel> d;
@@ -60,7 +62,7 @@ struct VLinSet {
 
 struct GraphSlot {   // one captured launch sequence (see run_graphed)
     hipGraphExec_t exec = nullptr;
-    size_t key = 0;
+    size_t key = 0;   // hash of the argument(s) it was captured with
     int launches = 0, far = 0;
 };
 
@@ -76,11 +78,74 @@ struct SweepPlan {
     int filt = 0;           // strips: the factored single-branch filter
     Far far = kFarNone;
     int far2_from = 0;      // packed products: the length from which a sequence takes the two-level form (0: no sequence does)
-    bool banded = false;    // packed products: block diagonal 2 of FM1 / FM is packed masked (the strips' banded near/far split)
-    bool repack2 = false;   // outside sweep: the inside sweep left block diagonal 2 packed in the other form
+    int banded = 0;         // packed products: block diagonal 2 of FM1 / FM is packed masked (the strips' banded near/far split)
+    int repack2 = 0;        // outside sweep: the inside sweep left block diagonal 2 packed in the other form
     const char* fine = "";       // names rh_batch_kernels reports: the sweep kernel ...
     const char* far_name = "";   // ... and the block-product kernel
 };
+
+// ---- The argument of each captured launch sequence.  A launcher takes (rh_ctx*, const Args&), and everything that can differ between
+// two computes on one context reaches it through the argument: run_graphed keys the captured graph by a hash of the argument's
+// bytes, so a value a launcher took from anywhere else would be one a stale graph replays.  Inside a launcher the context serves
+// only for the streams and events, the KLAUNCH timing state, the n_launch / n_far counters, fail(), and the objects that are fixed
+// from rh_create* to rh_destroy (d_model, d_vienna, d_vdx, d_vdxl, d_dxlin).  The arguments are built outside the capture
+// (mc_lin_args, mc_vlin_args, dx_lin_args), plans and variants decided.  Equal fields give equal bytes: an argument starts as zeroed
+// storage, and what is copied into it whole has no padding of its own.
+static_assert(std::has_unique_object_representations_v<SweepPlan> && std::has_unique_object_representations_v<McBatch>);
+static_assert(sizeof(DxLinBatch) == 4 * sizeof(void*) + 6 * sizeof(int) + 3 * sizeof(size_t) + 16 * sizeof(double), "no padding");
+
+struct McLinArgs {   // launch_mc_lin: one phase (0 inside, 1 outside) of the CONTRAfold-model sweeps on the scaled linear kernels
+    McBatch B;                 // every sequence of the pass
+    const LinSet* lin;         // the model at the scale exponent of this pass
+    double* logz;              // per sequence of B
+    int* bad;
+    SweepPlan plan;            // of the pass over B as it is (not routed)
+    // per-sequence routing (the batch as uploaded only; see launch_mc_lin): the sequences of the small list have a workgroup each,
+    // the sweeps see the lengths n_sweep, the short pass n_short (0 hides a sequence), each with a plan of its own
+    const int* small_list;     // device
+    const int* n_sweep;
+    const int* n_short;
+    SweepPlan plan_sweep, plan_short;
+    int routed, n_small, nmax_sweep, short_count, nmax_short;
+    int phase, pin, strip_xcd;
+    McLinArgs() { std::memset(this, 0, sizeof *this); }
+};
+
+struct McVlinArgs {   // launch_mc_vlin: one phase of the Vienna-BL sweeps over the single-molecule batch or (co) the s1+s2 batch
+    McBatch B;
+    McBatch from;              // seeded two-molecule sweeps: the single-molecule batch whose inside tables they copy
+    SweepPlan plan;
+    const VLinModel* d_vlin;   // the model at the scale exponent of this pass, device and host (select_vlin) ...
+    const VLinModel* h_vlin;
+    const double* hplen;       // ... its hairpin length weights x lam^d: host (kernel argument of inside diagonal d) and device
+    const double* d_hplen;
+    int* bad;
+    double* logz;              // single-molecule batch: log Z, the gap probabilities of the accessibility and its widths
+    double* gaps;
+    double* hp;                // two-molecule sweeps: where hp and its log Z go (DxBatch::hp, logz, tab_stride, ldd, n1max, n2max)
+    double* hp_logz;
+    size_t hp_stride;
+    int hp_ldd, n1max, n2max;
+    int window, cut_min, cut_max;   // ... and the window of groups around the cuts they launch
+    int max_w, acc_wide, acc_final_t;   // accessibility variants: vlin_acc_gaps_wide, vlin_acc_final_t
+    int phase, pin, co;
+    McVlinArgs() { std::memset(this, 0, sizeof *this); }
+};
+
+struct DxLinArgs {   // launch_dx_lin (CONTRAfold model: dm, hm) and launch_dx_vlin (Vienna-BL: vdx_s)
+    DxLinBatch X;              // the whole batch, or a compacted sub-batch of the scale-exponent ladder with its own tables
+    SweepPlan plan;
+    const DxLinModel* dm;      // the model at the scale exponent of this pass: device, host
+    const DxLinModel* hm;
+    double vdx_s;
+    double* zpart;             // [lz_chunks][np] partial sums of Z~ (+ cell counts behind them)
+    double* zbar;
+    double* logz;              // per pair of X
+    int* bad;
+    int lz_chunks;
+    DxLinArgs() { std::memset(this, 0, sizeof *this); }
+};
+static_assert(std::is_trivially_copyable_v<McLinArgs> && std::is_trivially_copyable_v<McVlinArgs> && std::is_trivially_copyable_v<DxLinArgs>);
 
 struct Ctx {   // (the fields of rh_ctx, below)
     int device = 0;
@@ -97,11 +162,9 @@ struct Ctx {   // (the fields of rh_ctx, below)
     int scale_ladder = 1;                      // RH_SCALE_LADDER=0: flagged problems go straight to the log-space kernels
     int scale_memory = 0;                      // rh_set_scale_memory / RH_SCALE_MEMORY=1: the next batch starts on the exponent most of the last one needed
                                                // (off by default: a sequence's bits then depend on its own letters only, never on the context's history)
-    // the default exponent's model, the model the next launches use (&lin0 unless a pass runs on a rung: "run on rung k" is
-    // lin = &lin_r[k], and lin = &lin0 afterwards) and the exponent the NEXT batch starts with: -1 = default, k = rung k -- the one
-    // that held more than half of the last batch (a stream of structured RNAs does not pay a failed first pass per batch)
+    // the default exponent's model and the exponent the NEXT batch starts with: -1 = default, k = rung k -- the one that held more
+    // than half of the last batch (a stream of structured RNAs does not pay a failed first pass per batch)
     LinSet lin0;
-    const LinSet* lin = &lin0;
     int lin_primary = -1;
     int rescued_by[kRungs + 1] = {0, 0, 0, 0};  // sequences the last ladder moved to the default exponent [0] / rung k [k + 1]
     std::vector<int> rescaled_mc;              // sequences the last compute recomputed on the linear path with another exponent (rh_batch_fallbacks which = 2)
@@ -304,9 +367,8 @@ struct SweepPass {
 };
 // launch_contrafold.hip
 int launch_mc_log(rh_ctx* c, int pin, const McBatch& B, double* logz_out);
-int launch_mc_log(rh_ctx* c, int pin);
 SweepPlan plan_mc_lin(const rh_ctx* c, int phase, int nmax);
-int launch_mc_lin(rh_ctx* c, int pin, int phase, const SweepPlan& P);
+int launch_mc_lin(rh_ctx* c, const McLinArgs& A);
 void far_products(const rh_ctx* c, int phase, int nmax, bool mfma, SweepPlan* P);
 const char* far_name(SweepPlan::Far far, int BS, int phase);
 void far_inside_after(const SweepPass& S, int done);
@@ -316,27 +378,28 @@ std::vector<double> strip_weights(const LinModel& L, bool* ok_out = nullptr);
 // launch_vienna.hip
 int launch_mc_vienna(rh_ctx* c, int pin);
 SweepPlan plan_mc_vlin(const rh_ctx* c, int phase, bool co, int nmax);
-int launch_mc_vlin(rh_ctx* c, int pin, int phase, bool co, const SweepPlan& P);
+int launch_mc_vlin(rh_ctx* c, const McVlinArgs& A);
 int launch_cofold(rh_ctx* c);
 int select_vlin(rh_ctx* c, int model);
 extern const double kVRungS[Ctx::kVRungs];
 // launch_duplex.hip
 int launch_dx_log(rh_ctx* c, const DxBatch& D);
-int launch_dx_log(rh_ctx* c);
 SweepPlan plan_dx_lin(const rh_ctx* c, int w);
 SweepPlan plan_dx_vlin();
-int launch_dx_lin_on(rh_ctx* c, const SweepPlan& P, DxLinBatch X, const DxLinModel* dm, const DxLinModel& hm, double* logz_out, int* bad);
-int launch_dx_lin(rh_ctx* c, const SweepPlan& P);
-int launch_dx_vlin(rh_ctx* c);
+int launch_dx_lin(rh_ctx* c, const DxLinArgs& A);
+int launch_dx_vlin(rh_ctx* c, const DxLinArgs& A);
 int launch_dx_vlog(rh_ctx* c);
 // fallbacks.hip
-int retry_mc_lin_rungs(rh_ctx* c, std::vector<int>* rest);
+int retry_mc_lin_rungs(rh_ctx* c, const LinSet* first, std::vector<int>* rest);
 int recompute_mc_subset_log(rh_ctx* c, const std::vector<int>& F);
 int retry_dx_lin_rungs(rh_ctx* c, std::vector<int>* rest);
 int recompute_dx_subset_log(rh_ctx* c, const std::vector<int>& F);
 int recompute_pairs_on_helper(rh_ctx* c, const std::vector<int>& P);
 // compute.hip
 int compute(rh_ctx* c);
+McLinArgs mc_lin_args(const rh_ctx* c, int phase, const McBatch& B, const LinSet* lin, bool routed);
+DxLinArgs dx_lin_args(const rh_ctx* c);
+int flagged(rh_ctx* c, const int* d_flags, int n, hipStream_t st, std::vector<int>* set);
 
 }  // namespace rh::host
 

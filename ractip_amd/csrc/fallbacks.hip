@@ -145,37 +145,32 @@ int ensure_rungs(rh_ctx* c)
     return RH_OK;
 }
 
-// `rest`: the sequences the main pass flagged; on return those that no rung could hold (for the log-space kernels)
-int retry_mc_lin_rungs(rh_ctx* c, std::vector<int>* rest)
+// `first`: the model of the main pass; `rest`: the sequences it flagged, on return those that no rung could hold (for the log-space
+// kernels)
+int retry_mc_lin_rungs(rh_ctx* c, const LinSet* first, std::vector<int>* rest)
 {
     if (!c->scale_ladder || rest->empty()) return RH_OK;
     int rc;
     if ((rc = ensure_rungs(c))) return rc;
-    const McBatch B = c->mc;
+    const McBatch& B = c->mc;
     // direction: log Z = log(Z~) + s n of the failed pass is +Inf / NaN / large after an overflow, -Inf or below s n after an underflow
     std::vector<double> lz(B.ns);
     HIP_TRY(c, hipMemcpyAsync(lz.data(), c->d_mclogz.p, sizeof(double) * B.ns, hipMemcpyDeviceToHost, c->s_mc));
     HIP_TRY(c, hipStreamSynchronize(c->s_mc));
     std::vector<int> over, under;
-    for (int k : *rest) ((lz[k] == lz[k] && lz[k] < c->lin->h.s * c->n[k]) ? under : over).push_back(k);
-    const LinSet* const saved_lin = c->lin;   // (a rung when the batch started on one, compute_once)
+    for (int k : *rest) ((lz[k] == lz[k] && lz[k] < first->h.s * c->n[k]) ? under : over).push_back(k);
     for (int& q : c->rescued_by) q = 0;
     // the exponents to try: larger ones in ascending order for the overflows, smaller ones in descending order for the underflows
-    // (model -1 = the default exponent, when this pass ran on a rung)
+    // (model -1 = the default exponent, when the main pass ran on a rung)
     struct Try { int model; bool up; };
     std::vector<Try> tries;
     {
         std::vector<std::pair<double, int>> all = {{c->lin0.h.s, -1}};
         for (int r = 0; r < rh_ctx::kRungs; r++) all.push_back({kRungS[r], r});
         std::sort(all.begin(), all.end());
-        for (const auto& e : all) if (e.first > saved_lin->h.s + 1e-12) tries.push_back({e.second, true});
-        for (auto it = all.rbegin(); it != all.rend(); ++it) if (it->first < saved_lin->h.s - 1e-12) tries.push_back({it->second, false});
+        for (const auto& e : all) if (e.first > first->h.s + 1e-12) tries.push_back({e.second, true});
+        for (auto it = all.rbegin(); it != all.rend(); ++it) if (it->first < first->h.s - 1e-12) tries.push_back({it->second, false});
     }
-    const int saved_nl[3] = {c->n_launch[0], c->n_launch[1], c->n_launch[2]}, saved_nf[3] = {c->n_far[0], c->n_far[1], c->n_far[2]};
-    const auto restore = [&] {
-        c->mc = B; c->lin = saved_lin;
-        for (int q = 0; q < 3; q++) { c->n_launch[q] = saved_nl[q]; c->n_far[q] = saved_nf[q]; }
-    };
     for (const Try& t : tries) {
         const int rung = t.model;
         std::vector<int>& F = t.up ? over : under;
@@ -189,31 +184,28 @@ int retry_mc_lin_rungs(rh_ctx* c, std::vector<int>* rest)
         HIP_TRY(c, hipMemsetAsync(c->d_mctab.p, 0, sizeof(double) * B.seq_stride * nsub, c->s_mc));
         if (c->d_pk) HIP_TRY(c, hipMemsetAsync(c->d_pk.p, 0, sizeof(double) * B.pk_stride * kPkCopies * nsub, c->s_mc));
         HIP_TRY(c, hipStreamSynchronize(c->s_mc));   // (the uploads of `sub`)
-        // the launch code reads the batch and the model from the context: c->mc.n is not the upload's length array any more, so the
-        // sub-batch runs as it is, without the per-sequence routing of launch_mc_lin
-        c->mc = S;
-        c->lin = rung < 0 ? &c->lin0 : &c->lin_r[rung];
-        const int spin = nsub % 8 == 0 ? 1 : 0;
-        rc = launch_mc_lin(c, spin, 0, plan_mc_lin(c, 0, S.nmax));   // (plans of the sub-batch: c->plan keeps the first pass's)
-        if (!rc) rc = launch_mc_lin(c, spin, 1, plan_mc_lin(c, 1, S.nmax));
-        if (rc) { restore(); return rc; }
+        // the sub-batch runs as it is, with plans of its own and without the per-sequence routing of launch_mc_lin;
+        // its launches are not counted
+        const LinSet* lin = rung < 0 ? &c->lin0 : &c->lin_r[rung];
+        const int saved_nl[2] = {c->n_launch[0], c->n_launch[1]}, saved_nf[2] = {c->n_far[0], c->n_far[1]};
+        rc = launch_mc_lin(c, mc_lin_args(c, 0, S, lin, false));
+        if (!rc) rc = launch_mc_lin(c, mc_lin_args(c, 1, S, lin, false));
+        for (int q = 0; q < 2; q++) { c->n_launch[q] = saved_nl[q]; c->n_far[q] = saved_nf[q]; }
+        if (rc) return rc;
         // flags and log Z of the sub-batch are the first nsub entries of d_bad / d_mclogz
-        std::vector<int> sbad(nsub);
+        std::vector<int> sbad, still;
         std::vector<double> slz(nsub);
-        hipError_t e = hipMemcpyAsync(sbad.data(), c->d_bad.p, sizeof(int) * nsub, hipMemcpyDeviceToHost, c->s_mc);
-        if (e == hipSuccess) e = hipMemcpyAsync(slz.data(), c->d_mclogz.p, sizeof(double) * nsub, hipMemcpyDeviceToHost, c->s_mc);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->s_mc);
-        if (e != hipSuccess) { restore(); return fail(c, RH_ERR_HIP, "scale ladder: %s", hipGetErrorString(e)); }
-        std::vector<int> still;
+        HIP_TRY(c, hipMemcpyAsync(slz.data(), c->d_mclogz.p, sizeof(double) * nsub, hipMemcpyDeviceToHost, c->s_mc));
+        if ((rc = flagged(c, c->d_bad.as<int>(), nsub, c->s_mc, &sbad))) return rc;
+        size_t b = 0;
         for (int k = 0; k < nsub; k++) {
-            if (sbad[k]) { still.push_back(F[k]); continue; }
-            if ((e = scatter_mc(c, k, F[k])) != hipSuccess) { restore(); return fail(c, RH_ERR_HIP, "scale ladder: %s", hipGetErrorString(e)); }
+            if (b < sbad.size() && sbad[b] == k) { b++; still.push_back(F[k]); continue; }
+            HIP_TRY(c, scatter_mc(c, k, F[k]));
             lz[F[k]] = slz[k];
             c->rescaled_mc.push_back(F[k]);
             c->rescued_by[rung + 1]++;
         }
         F.swap(still);
-        restore();   // (every early return below finds the context as it was)
     }
     HIP_TRY(c, hipMemcpyAsync(c->d_mclogz.p, lz.data(), sizeof(double) * B.ns, hipMemcpyHostToDevice, c->s_mc));
     HIP_TRY(c, hipStreamSynchronize(c->s_mc));   // (lz dies with this scope)
@@ -266,11 +258,12 @@ int retry_dx_lin_rungs(rh_ctx* c, std::vector<int>* rest)
             HIP_TRY(c, c->d_dxlin_r[r].upload(&c->h_dxlin_r[r]));
         }
     }
-    std::vector<int> F = *rest;
+    std::vector<int> F = *rest, bad;
     for (int r = 0; r < kDxRungs && !F.empty(); r++) {
         const SubBatch sub = gather(c, F, 2, D.lds);
         const int nsub = sub.nsub, n1max = sub.nmax[0], n2max = sub.nmax[1];
-        DxLinBatch X = c->dxl;   // lds, ldd, hp_stride as in the main batch: results scatter back row for row
+        DxLinArgs A = dx_lin_args(c);   // (d_zpart / d_zbar of the main batch: large enough, the sub-batch has no more chunks)
+        DxLinBatch& X = A.X;   // lds, ldd, hp_stride as in the main batch: results scatter back row for row
         X.np = nsub; X.n1max = n1max; X.n2max = n2max;
         X.lda = (n1max + 2 + 2 * kDxPad + 1) & ~1;
         const size_t rows = (size_t)n1max + n2max + 3;
@@ -286,18 +279,16 @@ int retry_dx_lin_rungs(rh_ctx* c, std::vector<int>* rest)
         HIP_TRY(c, hipMemsetAsync(c->d_subdx.p, 0, own_bytes, c->s_dx));   // pad columns, row 0 / column 0 of hp
         HIP_TRY(c, hipStreamSynchronize(c->s_dx));   // (the uploads of `sub`)
         X.seq = c->d_subdseq.as<const uint8_t>(); X.n = c->d_subdn.as<const int>(); X.tab = sub_tab; X.hp = sub_hp;
-        const int saved_chunks = c->lz_chunks;
-        c->lz_chunks = (n1max + n2max - 1 + 15) / 16;   // (<= the main batch's: d_zpart / d_zbar are large enough)
-        // (always the four-wavefront organisation, whatever RH_DX_W chose for the first pass: see ADVICE.md)
-        rc = launch_dx_lin_on(c, plan_dx_lin(c, 4), X, c->d_dxlin_r[r], c->h_dxlin_r[r], sub_logz, sub_bad);
-        c->lz_chunks = saved_chunks;
-        if (rc) return rc;
-        std::vector<int> bad(nsub);
-        HIP_TRY(c, hipMemcpyAsync(bad.data(), sub_bad, sizeof(int) * nsub, hipMemcpyDeviceToHost, c->s_dx));
-        HIP_TRY(c, hipStreamSynchronize(c->s_dx));
+        A.plan = plan_dx_lin(c, 4);   // (always the four-wavefront organisation, whatever RH_DX_W chose for the first pass: see ADVICE.md)
+        A.dm = c->d_dxlin_r[r]; A.hm = &c->h_dxlin_r[r];
+        A.lz_chunks = (n1max + n2max - 1 + 15) / 16;
+        A.logz = sub_logz; A.bad = sub_bad;
+        if ((rc = launch_dx_lin(c, A))) return rc;
+        if ((rc = flagged(c, sub_bad, nsub, c->s_dx, &bad))) return rc;
         std::vector<int> still;
+        size_t b = 0;
         for (int k = 0; k < nsub; k++) {
-            if (bad[k]) { still.push_back(F[k]); continue; }
+            if (b < bad.size() && bad[b] == k) { b++; still.push_back(F[k]); continue; }
             HIP_TRY(c, scatter_dx(c, sub_hp, sub_logz, k, F[k]));
             c->rescaled_dx.push_back(F[k]);
         }

@@ -39,7 +39,6 @@ int launch_mc_log(rh_ctx* c, int pin, const McBatch& B, double* logz_out)
     hipLaunchKernelGGL(mc_unpaired, dim3((B.nmax + 63) / 64, B.ns), dim3(256), 0, c->s_mc, B);
     return RH_OK;
 }
-int launch_mc_log(rh_ctx* c, int pin) { return launch_mc_log(c, pin, c->mc, c->d_mclogz.as<double>()); }
 
 // ---- the kernels of the scaled linear sweeps, each on one line with the name rh_batch_kernels reports for it: plan_mc_lin takes
 // the name and the schedules take the kernel from the same row
@@ -202,49 +201,49 @@ SweepPlan plan_mc_lin(const rh_ctx* c, int phase, int nmax)
 // ---- the schedules: one function per organisation and sweep, over the sequences B shows (lengths 0 hide a sequence)
 // two diagonals per launch (lin_inside_diag MODE 3 has W = 4: 256 threads) up to diagonal `last`, pairs start even; the last launch
 // may hold only F5i[nmax]
-static void inside_pairs(const SweepPass& S, int pin, int last)
+static void inside_pairs(const SweepPass& S, const McLinArgs& A, int last)
 {
     for (int d = 0; d <= last; d += 2) {
         const int groups = (std::max(S.B.nmax - 1 - d, 0) + 62) / 63 + 1;
-        KLAUNCH(S.c, 0, (kInsidePair.kern), seq_grid(pin, S.B.ns, groups), dim3(256), S.st, S.B, S.c->lin->d, d, std::exp(-S.c->lin->h.s * d), pin);
+        KLAUNCH(S.c, 0, (kInsidePair.kern), seq_grid(A.pin, S.B.ns, groups), dim3(256), S.st, S.B, A.lin->d, d, std::exp(-A.lin->h.s * d), A.pin);
         S.c->n_launch[0]++;
         far_inside_after(S, d + 2);   // (the first one is due behind diagonal 47)
     }
 }
 // diagonals 0..31 by pairs (every row is "near" there), then strips of KD diagonals (mccaskill_strip.hip)
-static void inside_strips(const SweepPass& S, int pin)
+static void inside_strips(const SweepPass& S, const McLinArgs& A)
 {
     rh_ctx* c = S.c;
     const McBatch& B = S.B;
     constexpr int KD = 8, GS = 64 - (KD - 1);
     const auto strip = strip_kernels(S.P.W, S.P.filt).in.kern;
-    inside_pairs(S, pin, 30);
+    inside_pairs(S, A, 30);
     int d0 = 32;
     for (; d0 <= B.nmax - 2; d0 += KD) {
         const int groups = (std::max(B.nmax - 1 - d0, 0) + GS - 1) / GS + 1;
-        KLAUNCH(c, 0, strip, seq_grid(pin, B.ns, groups), dim3(64 * S.P.W), S.st, B, c->lin->d, c->lin->wT, d0, d0 == 32 ? 32 : d0 - KD + 2,
-                std::exp(-c->lin->h.s * d0), (pin && c->strip_xcd) ? 2 : pin);
+        KLAUNCH(c, 0, strip, seq_grid(A.pin, B.ns, groups), dim3(64 * S.P.W), S.st, B, A.lin->d, A.lin->wT, d0, d0 == 32 ? 32 : d0 - KD + 2,
+                std::exp(-A.lin->h.s * d0), (A.pin && A.strip_xcd) ? 2 : A.pin);
         c->n_launch[0]++;
         far_inside_after(S, d0 + KD);
     }
-    hipLaunchKernelGGL(lin_f5i_tail, dim3(B.ns), dim3(256), 0, S.st, B, c->lin->d, d0 - KD + 2);
+    hipLaunchKernelGGL(lin_f5i_tail, dim3(B.ns), dim3(256), 0, S.st, B, A.lin->d, d0 - KD + 2);
 }
 // one launch per diagonal, or (ahead) look-ahead pairs of launches
-static void inside_diagonals(const SweepPass& S, int pin, bool ahead)
+static void inside_diagonals(const SweepPass& S, const McLinArgs& A, bool ahead)
 {
     const InsideDiagK full = diag_kernels(S.P.W, S.P.BS).in.kern;
     for (int d = 0; d <= S.B.nmax - 1; d++) {
         const int groups = (std::max(S.B.nmax - 1 - d, 0) + 63) / 64 + 1;
         const bool odd = ahead && (d & 1);
-        KLAUNCH(S.c, 0, (!ahead ? full : kInsideAhead[odd].kern), seq_grid(pin, S.B.ns, groups), dim3(odd ? 64 : 64 * S.P.W), S.st, S.B, S.c->lin->d, d,
-                std::exp(-S.c->lin->h.s * d), pin);
+        KLAUNCH(S.c, 0, (!ahead ? full : kInsideAhead[odd].kern), seq_grid(A.pin, S.B.ns, groups), dim3(odd ? 64 : 64 * S.P.W), S.st, S.B, A.lin->d, d,
+                std::exp(-A.lin->h.s * d), A.pin);
         S.c->n_launch[0]++;
         far_inside_after(S, d + 1);
     }
 }
 
 // strips of KD diagonals from the top, aligned so that a sequence's strips do not depend on the batch
-static void outside_strips(SweepPass& S, int pin)
+static void outside_strips(SweepPass& S, const McLinArgs& A)
 {
     rh_ctx* c = S.c;
     const McBatch& B = S.B;
@@ -252,18 +251,18 @@ static void outside_strips(SweepPass& S, int pin)
     const auto strip = strip_kernels(S.P.W, S.P.filt).out.kern;
     const int d0_top = (B.nmax - 2) | (KD - 1);
     far_outside_begin(S, d0_top);
-    hipLaunchKernelGGL(lin_f5o_head, dim3(B.ns), dim3(256), 0, S.st, B, c->lin->d, B.nmax - 1, d0_top - 5);
+    hipLaunchKernelGGL(lin_f5o_head, dim3(B.ns), dim3(256), 0, S.st, B, A.lin->d, B.nmax - 1, d0_top - 5);
     for (int d0 = d0_top; d0 >= KD - 1; d0 -= KD) {
         far_outside_before(S, d0);
         const int groups = (std::max(B.nmax - 1 - (d0 - (KD - 1)), 0) + GS - 1) / GS + 1;
-        KLAUNCH(c, 2, strip, seq_grid(pin, B.ns, groups), dim3(64 * S.P.W), S.st, B, c->lin->d, c->lin->wT, d0, d0 - 6, d0 - 13,
-                (pin && c->strip_xcd) ? 2 : pin, c->d_bad.as<int>());
+        KLAUNCH(c, 2, strip, seq_grid(A.pin, B.ns, groups), dim3(64 * S.P.W), S.st, B, A.lin->d, A.lin->wT, d0, d0 - 6, d0 - 13,
+                (A.pin && A.strip_xcd) ? 2 : A.pin, A.bad);
         c->n_launch[1]++;
     }
 }
 // two diagonals per launch (lin_outside_pair); pairs are (odd, even) whatever the batch: a sequence's results do not depend on
 // its neighbours' lengths
-static void outside_pairs(SweepPass& S, int pin)
+static void outside_pairs(SweepPass& S, const McLinArgs& A)
 {
     const auto pair = pair_kernels(S.P.W).out.kern;
     far_outside_begin(S, S.B.nmax - 2);
@@ -271,55 +270,53 @@ static void outside_pairs(SweepPass& S, int pin)
         for (int r = d; r >= d - 1 && r >= 0; r--) far_outside_before(S, r);   // block products whose tiles start on either diagonal of the pair
         const int ncol = S.B.nmax - 1 - d + 1;          // columns of the longer diagonal d-1 (d = 0: diagonal 0 alone, one less)
         const int groups = std::max(1, (ncol - 1 + 62) / 63) + 1;
-        KLAUNCH(S.c, 2, pair, seq_grid(pin, S.B.ns, groups), dim3(64 * S.P.W), S.st, S.B, S.c->lin->d, d, d, pin, S.c->d_bad.as<int>());
+        KLAUNCH(S.c, 2, pair, seq_grid(A.pin, S.B.ns, groups), dim3(64 * S.P.W), S.st, S.B, A.lin->d, d, d, A.pin, A.bad);
         S.c->n_launch[1]++;
     }
 }
-static void outside_diagonals(SweepPass& S, int pin)
+static void outside_diagonals(SweepPass& S, const McLinArgs& A)
 {
     const auto diag = diag_kernels(S.P.W, S.P.BS).out.kern;
     far_outside_begin(S, S.B.nmax - 2);
     for (int d = S.B.nmax - 2; d >= 0; d--) {
         far_outside_before(S, d);
         const int groups = (S.B.nmax - 1 - d + 63) / 64 + 1;
-        KLAUNCH(S.c, 2, diag, seq_grid(pin, S.B.ns, groups), dim3(64 * S.P.W), S.st, S.B, S.c->lin->d, d, pin, S.c->d_bad.as<int>());
+        KLAUNCH(S.c, 2, diag, seq_grid(A.pin, S.B.ns, groups), dim3(64 * S.P.W), S.st, S.B, A.lin->d, d, A.pin, A.bad);
         S.c->n_launch[1]++;
     }
 }
 
-// One phase (0 inside, 1 outside) over the batch c->mc, whose plan is P.  Which sequences run where is decided per sequence, by
-// its length alone: 8..109 letters by their own workgroup when RH_SMALL=1 (mccaskill_small.hip), fewer than kStripMinN letters next
-// to longer ones in a pass of their own (the organisation they would get alone, a plan of its own), everyone else in the sweeps.
-// Sub-batches of the scale ladder (c->mc.n is not the upload's length array) run as they are.  lin_init / lin_finish / mc_unpaired
-// see every sequence.
-int launch_mc_lin(rh_ctx* c, int pin, int phase, const SweepPlan& P)
+// One phase (0 inside, 1 outside) over the batch A.B.  A routed pass (the batch as uploaded) decides per sequence, by its length
+// alone, what runs it: 8..109 letters their own workgroup when RH_SMALL=1 (mccaskill_small.hip), fewer than kStripMinN letters next to
+// longer ones a pass of their own (the organisation they would get alone, a plan of its own), everyone else the sweeps.  Sub-batches
+// of the scale ladder run as they are (not routed: see ADVICE.md).  lin_init / lin_finish / mc_unpaired see every sequence.
+int launch_mc_lin(rh_ctx* c, const McLinArgs& A)
 {
-    const McBatch BR = c->mc;
-    const bool routed = (const void*)BR.n == c->d_n.p && (!c->small_list.empty() || c->n_short > 0);
-    int* bad = c->d_bad.as<int>();
+    const McBatch& BR = A.B;
+    const int phase = A.phase;
     const auto sweep = [&](const McBatch& B, const SweepPlan& Q) {
         SweepPass S{c, Q, B, c->s_mc, phase};
-        if (Q.org == SweepPlan::kStrips) return phase == 0 ? inside_strips(S, pin) : outside_strips(S, pin);
-        if (Q.org == SweepPlan::kPairs) return phase == 0 ? inside_pairs(S, pin, B.nmax) : outside_pairs(S, pin);
-        return phase == 0 ? inside_diagonals(S, pin, Q.org == SweepPlan::kLookahead) : outside_diagonals(S, pin);
+        if (Q.org == SweepPlan::kStrips) return phase == 0 ? inside_strips(S, A) : outside_strips(S, A);
+        if (Q.org == SweepPlan::kPairs) return phase == 0 ? inside_pairs(S, A, B.nmax) : outside_pairs(S, A);
+        return phase == 0 ? inside_diagonals(S, A, Q.org == SweepPlan::kLookahead) : outside_diagonals(S, A);
     };
     if (phase == 0) {
-        hipLaunchKernelGGL(lin_init, dim3((BR.ns + 63) / 64), dim3(64), 0, c->s_mc, BR, c->lin->d, bad);
-        if (routed && !c->small_list.empty()) {
-            launch_lin_small(BR, c->lin->d, c->lin->wT + kStripFiltOff + kStripFiltLen, c->d_small_list.as<const int>(), (int)c->small_list.size(), bad, c->s_mc);
+        hipLaunchKernelGGL(lin_init, dim3((BR.ns + 63) / 64), dim3(64), 0, c->s_mc, BR, A.lin->d, A.bad);
+        if (A.routed && A.n_small > 0) {
+            launch_lin_small(BR, A.lin->d, A.lin->wT + kStripFiltOff + kStripFiltLen, A.small_list, A.n_small, A.bad, c->s_mc);
             c->n_launch[0]++;
         }
     }
-    if (routed) {
+    if (A.routed) {
         McBatch BL = BR, BSH = BR;
-        BL.n = c->d_n_sweep.as<const int>(); BL.nmax = c->nmax_sweep;
-        BSH.n = c->d_n_short.as<const int>(); BSH.nmax = c->nmax_short;
-        if (BL.nmax > 0) sweep(BL, plan_mc_lin(c, phase, BL.nmax));
-        if (c->n_short > 0) sweep(BSH, plan_mc_lin(c, phase, BSH.nmax));
+        BL.n = A.n_sweep; BL.nmax = A.nmax_sweep;
+        BSH.n = A.n_short; BSH.nmax = A.nmax_short;
+        if (BL.nmax > 0) sweep(BL, A.plan_sweep);
+        if (A.short_count > 0) sweep(BSH, A.plan_short);
     } else
-        sweep(BR, P);
+        sweep(BR, A.plan);
     if (phase == 1) {
-        hipLaunchKernelGGL(lin_finish, dim3((BR.ns + 63) / 64), dim3(64), 0, c->s_mc, BR, c->lin->d, c->d_mclogz.as<double>(), bad);
+        hipLaunchKernelGGL(lin_finish, dim3((BR.ns + 63) / 64), dim3(64), 0, c->s_mc, BR, A.lin->d, A.logz, A.bad);
         hipLaunchKernelGGL(mc_unpaired, dim3((BR.nmax + 63) / 64, BR.ns), dim3(256), 0, c->s_mc, BR);
     }
     return RH_OK;

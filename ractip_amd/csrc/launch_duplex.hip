@@ -25,7 +25,6 @@ int launch_dx_log(rh_ctx* c, const DxBatch& D)
     hipLaunchKernelGGL(dx_posterior, dim3((cells + 255) / 256, D.np), dim3(256), 0, c->s_dx, D);
     return RH_OK;
 }
-int launch_dx_log(rh_ctx* c) { return launch_dx_log(c, c->dx); }
 
 // ---- duplex sweeps, scaled linear path: eight (dxl_strip8), four (dxl_sweep4) or two (dxl_sweep<W>) anti-diagonals per launch;
 // W = 4 has all three, W = 2 and 8 the last.  Each kernel on one line with the name reported for it.
@@ -53,14 +52,16 @@ SweepPlan plan_dx_vlin()   // (one organisation)
     return P;
 }
 
-// X: the batch (the whole one, or a compacted sub-batch of the scale-exponent ladder with its own tables); dm / hm: the model at the
-// scale exponent of this pass; logz_out / bad: per pair of X
-int launch_dx_lin_on(rh_ctx* c, const SweepPlan& P, DxLinBatch X, const DxLinModel* dm, const DxLinModel& hm, double* logz_out, int* bad)
+// A.X: the whole batch, or a compacted sub-batch of the scale-exponent ladder with its own tables
+int launch_dx_lin(rh_ctx* c, const DxLinArgs& A)
 {
+    DxLinBatch X = A.X;
+    const SweepPlan& P = A.plan;
+    const DxLinModel* dm = A.dm;
     const int smax = X.n1max + X.n2max;
     const int steps = smax / 2;
     const int groups = (X.n1max + 2 + 63) / 64;
-    const double leu = hm.lam_eu, l2 = hm.lam_pow[2];
+    const double leu = A.hm->lam_eu, l2 = A.hm->lam_pow[2];
     if (P.org == SweepPlan::kDxStrip8) {
         for (int t = 0; 8 * t < smax - 1; t++) {
             for (int k = 0; k < 8; k++) X.pw8[k] = std::pow(leu, 8.0 * t + k) * l2;
@@ -83,35 +84,31 @@ int launch_dx_lin_on(rh_ctx* c, const SweepPlan& P, DxLinBatch X, const DxLinMod
         KLAUNCH(c, 4, (dx_sweep_kernels(P.W).k.kern), dim3(groups, X.np, 2), dim3(64 * P.W), c->s_dx, X, dm, t, groups);
         c->n_launch[2]++;
     }
-    double* zpart = c->d_zpart.as<double>();
-    int* cpart = (int*)(zpart + (size_t)X.np * c->lz_chunks);
-    hipLaunchKernelGGL(dxl_logz_part, dim3(c->lz_chunks, X.np), dim3(256), 0, c->s_dx, X, dm, zpart, cpart, c->lz_chunks);
-    hipLaunchKernelGGL(dxl_logz_final, dim3((X.np + 63) / 64), dim3(64), 0, c->s_dx, X, dm, (const double*)zpart, (const int*)cpart,
-                       c->lz_chunks, c->d_zbar.as<double>(), logz_out, bad);
-    hipLaunchKernelGGL(dxl_posterior, dim3((X.n1max + 31) / 32, (smax - 1 + 31) / 32, X.np), dim3(256), 0, c->s_dx, X, c->d_zbar.as<const double>(), bad);
+    int* cpart = (int*)(A.zpart + (size_t)X.np * A.lz_chunks);
+    hipLaunchKernelGGL(dxl_logz_part, dim3(A.lz_chunks, X.np), dim3(256), 0, c->s_dx, X, dm, A.zpart, cpart, A.lz_chunks);
+    hipLaunchKernelGGL(dxl_logz_final, dim3((X.np + 63) / 64), dim3(64), 0, c->s_dx, X, dm, (const double*)A.zpart, (const int*)cpart,
+                       A.lz_chunks, A.zbar, A.logz, A.bad);
+    hipLaunchKernelGGL(dxl_posterior, dim3((X.n1max + 31) / 32, (smax - 1 + 31) / 32, X.np), dim3(256), 0, c->s_dx, X, (const double*)A.zbar, A.bad);
     return RH_OK;
 }
-int launch_dx_lin(rh_ctx* c, const SweepPlan& P) { return launch_dx_lin_on(c, P, c->dxl, c->d_dxlin, c->h_dxlin, c->d_logz.as<double>(), c->d_dxbad.as<int>()); }
 
 // Vienna-BL pf_duplex, scaled linear space (duplex_vlin.hip)
-int launch_dx_vlin(rh_ctx* c)
+int launch_dx_vlin(rh_ctx* c, const DxLinArgs& A)
 {
-    DxLinBatch X = c->dxl;
+    DxLinBatch X = A.X;
     const int smax = X.n1max + X.n2max;
     const int groups4 = (X.n1max + 2 + 61) / 62;
-    const double lam = std::exp(-c->vdx_s);
+    const double lam = std::exp(-A.vdx_s);
     for (int t = 0; 4 * t < smax - 1; t++) {
         for (int k = 0; k < 4; k++) X.pw4[k] = std::pow(lam, 2.0 + 4.0 * t + k);
         KLAUNCH(c, 4, (kDxvlSweep4.kern), dim3(groups4, X.np, 2), dim3(256), c->s_dx, X, c->d_vdxl, c->d_vdx, t);
         c->n_launch[2]++;
     }
-    double* zpart = c->d_zpart.as<double>();
-    int* cpart = (int*)(zpart + (size_t)X.np * c->lz_chunks);
-    hipLaunchKernelGGL(dxvl_logz_part, dim3(c->lz_chunks, X.np), dim3(256), 0, c->s_dx, X, c->d_vdxl, c->d_vdx, zpart, cpart, c->lz_chunks);
-    hipLaunchKernelGGL(dxvl_logz_final, dim3((X.np + 63) / 64), dim3(64), 0, c->s_dx, X, c->vdx_s, (const double*)zpart, (const int*)cpart,
-                       c->lz_chunks, c->d_zbar.as<double>(), c->d_logz.as<double>(), c->d_dxbad.as<int>());
-    hipLaunchKernelGGL(dxl_posterior, dim3((X.n1max + 31) / 32, (smax - 1 + 31) / 32, X.np), dim3(256), 0, c->s_dx, X, c->d_zbar.as<const double>(),
-                       c->d_dxbad.as<int>());
+    int* cpart = (int*)(A.zpart + (size_t)X.np * A.lz_chunks);
+    hipLaunchKernelGGL(dxvl_logz_part, dim3(A.lz_chunks, X.np), dim3(256), 0, c->s_dx, X, c->d_vdxl, c->d_vdx, A.zpart, cpart, A.lz_chunks);
+    hipLaunchKernelGGL(dxvl_logz_final, dim3((X.np + 63) / 64), dim3(64), 0, c->s_dx, X, A.vdx_s, (const double*)A.zpart, (const int*)cpart,
+                       A.lz_chunks, A.zbar, A.logz, A.bad);
+    hipLaunchKernelGGL(dxl_posterior, dim3((X.n1max + 31) / 32, (smax - 1 + 31) / 32, X.np), dim3(256), 0, c->s_dx, X, (const double*)A.zbar, A.bad);
     return RH_OK;
 }
 int launch_dx_vlog(rh_ctx* c)

@@ -81,95 +81,95 @@ SweepPlan plan_mc_vlin(const rh_ctx* c, int phase, bool co, int nmax)
 // the union over the batch's cuts -- are launched, behind the three F5 / XP / XS groups (window_slot_vl); the kernel finds its
 // group through the pin argument
 struct VlinGrid { dim3 grid; int pin; };
-static VlinGrid vlin_grid(const rh_ctx* c, const McBatch& B, bool co, bool window, int pin, int dd, int cells)
+static VlinGrid vlin_grid(const McVlinArgs& A, int dd, int cells)
 {
-    int groups = cells + (co ? 3 : 1), pin_k = pin;
-    if (window) {
-        const int t = c->co_cut_min - 65 - dd;
-        const int lo = std::max(0, (t >= 0 ? t / 64 : -((-t + 63) / 64)) + 1), hi = std::min(cells - 1, (c->co_cut_max - 1) / 64);
-        pin_k = pin | 128 | (lo << 8);
+    int groups = cells + (A.co ? 3 : 1), pin_k = A.pin;
+    if (A.window) {
+        const int t = A.cut_min - 65 - dd;
+        const int lo = std::max(0, (t >= 0 ? t / 64 : -((-t + 63) / 64)) + 1), hi = std::min(cells - 1, (A.cut_max - 1) / 64);
+        pin_k = A.pin | 128 | (lo << 8);
         groups = 3 + std::max(0, hi - lo + 1);
     }
-    return {seq_grid(pin, B.ns, groups), pin_k};
+    return {seq_grid(A.pin, A.B.ns, groups), pin_k};
 }
 
 // one launch per diagonal, or look-ahead pairs: the even diagonal is a full launch that also accumulates the sums of d+1, which then
 // needs one wavefront per group
-static void vlin_inside(const SweepPass& S, int pin, bool co)
+static void vlin_inside(const SweepPass& S, const McVlinArgs& A)
 {
     rh_ctx* c = S.c;
     const McBatch& B = S.B;
-    const VlinKernels& K = vlin_kernels(S.P.BS, co);
-    const bool ahead = S.P.org == SweepPlan::kLookahead, window = co && c->co_window && c->co_cut_min >= 1 && B.seeded;
-    hipLaunchKernelGGL(vlin_init, dim3((B.ns + 63) / 64), dim3(64), 0, S.st, B, (int*)(co ? c->d_cobad.p : c->d_bad.p));
-    if (co && B.seeded) hipLaunchKernelGGL(vlin_co_seed, dim3(c->mc.nmax, B.ns), dim3(256), 0, S.st, B, c->mc);
+    const VlinKernels& K = vlin_kernels(S.P.BS, A.co);
+    const bool ahead = S.P.org == SweepPlan::kLookahead;
+    hipLaunchKernelGGL(vlin_init, dim3((B.ns + 63) / 64), dim3(64), 0, S.st, B, A.bad);
+    if (A.co && B.seeded) hipLaunchKernelGGL(vlin_co_seed, dim3(A.from.nmax, B.ns), dim3(256), 0, S.st, B, A.from);
     for (int d = 0; d <= B.nmax - 1; d++) {
         const int mode = !ahead ? 0 : (d & 1) ? 2 : 1;
         const int cells = (std::max(B.nmax - 1 - d, 0) + 63) / 64;
-        const VlinGrid G = vlin_grid(c, B, co, window, pin, mode == 1 ? d + 1 : d, cells);   // (mode 1 also feeds diagonal d+1)
-        KLAUNCH(c, 0, (K.in[mode]), G.grid, dim3(mode == 2 ? 64 : 64 * S.P.W), S.st, B, c->d_vlin, d, c->h_hplen[d], G.pin);
+        const VlinGrid G = vlin_grid(A, mode == 1 ? d + 1 : d, cells);   // (mode 1 also feeds diagonal d+1)
+        KLAUNCH(c, 0, (K.in[mode]), G.grid, dim3(mode == 2 ? 64 : 64 * S.P.W), S.st, B, A.d_vlin, d, A.hplen[d], G.pin);
         c->n_launch[S.k]++;
         far_inside_after(S, d + 1);
     }
 }
 
 // accessibility P(i..i+w unpaired), w < max_w, behind the single-molecule sweeps
-static void vlin_finish_acc(rh_ctx* c, const McBatch& B, hipStream_t st)
+static void vlin_finish_acc(rh_ctx* c, const McVlinArgs& A, hipStream_t st)
 {
-    hipLaunchKernelGGL(vlin_finish, dim3((B.ns + 63) / 64), dim3(64), 0, st, B, c->d_vlin, c->d_mclogz.as<double>(), c->d_bad.as<int>());
+    const McBatch& B = A.B;
+    const VLinModel* d_vlin = A.d_vlin;
+    hipLaunchKernelGGL(vlin_finish, dim3((B.ns + 63) / 64), dim3(64), 0, st, B, d_vlin, A.logz, A.bad);
     const int tiles = (B.ld + 31) / 32;
-    hipLaunchKernelGGL(vlin_acc_prep, dim3(tiles * tiles, B.ns), dim3(256), 0, st, B, c->d_vlin, c->d_hplen.as<const double>());
+    hipLaunchKernelGGL(vlin_acc_prep, dim3(tiles * tiles, B.ns), dim3(256), 0, st, B, d_vlin, A.d_hplen);
     hipLaunchKernelGGL(mcv_acc_hscan, dim3((B.nmax + 1 + 255) / 256, B.ns), dim3(256), 0, st, B, 10 /* VL_FM2F */);
-    hipLaunchKernelGGL(vlin_acc_hsum, dim3((B.nmax + 3) / 4, B.ns), dim3(256), 0, st, B, c->max_w);
-    if (c->acc_wide && (size_t)kViennaMcTables * B.tab_stride * sizeof(double) < ((size_t)1 << 32)) {   // (vlin_acc_gaps_wide addresses a sequence's tables with 32-bit offsets)
+    hipLaunchKernelGGL(vlin_acc_hsum, dim3((B.nmax + 3) / 4, B.ns), dim3(256), 0, st, B, A.max_w);
+    if (A.acc_wide) {
         // gap lengths 1, 2 (the tabulated shapes: six times the loads of a generic length): one thread per letter and length, the inner
         // spans in 8 chunks; 3..30: the lanes over the gap length (vlin_acc_gaps_wide)
         constexpr int NG = 2, NCH = 8;
-        double* part = c->d_gaps.as<double>() + (size_t)2 * 32 * B.ld * B.ns;
+        double* part = A.gaps + (size_t)2 * 32 * B.ld * B.ns;
         // (one wavefront per workgroup: the loop runs to the longest inner span of the workgroup's letters, which differ by the block width)
-        hipLaunchKernelGGL(vlin_acc_gaps, dim3((B.nmax + 63) / 64, B.ns, 2 * NG * NCH), dim3(64), 0, st, B, c->d_vlin, c->d_gaps.as<double>(), NG, NCH, part);
-        hipLaunchKernelGGL(vlin_acc_gsum, dim3((B.nmax + 255) / 256, B.ns, 2 * NG), dim3(256), 0, st, B, c->d_gaps.as<double>(), (const double*)part, NG, NCH);
-        hipLaunchKernelGGL(vlin_acc_gaps_wide, dim3((B.nmax + 3) / 4, B.ns, 2), dim3(256), 0, st, B, c->d_vlin, c->d_gaps.as<double>());
+        hipLaunchKernelGGL(vlin_acc_gaps, dim3((B.nmax + 63) / 64, B.ns, 2 * NG * NCH), dim3(64), 0, st, B, d_vlin, A.gaps, NG, NCH, part);
+        hipLaunchKernelGGL(vlin_acc_gsum, dim3((B.nmax + 255) / 256, B.ns, 2 * NG), dim3(256), 0, st, B, A.gaps, (const double*)part, NG, NCH);
+        hipLaunchKernelGGL(vlin_acc_gaps_wide, dim3((B.nmax + 3) / 4, B.ns, 2), dim3(256), 0, st, B, d_vlin, A.gaps);
     } else
-        hipLaunchKernelGGL(vlin_acc_gaps, dim3((B.nmax + 255) / 256, B.ns, 60), dim3(256), 0, st, B, c->d_vlin, c->d_gaps.as<double>(), 30, 1, (double*)nullptr);
-    hipLaunchKernelGGL(vlin_acc_gsuf, dim3((B.nmax + 255) / 256, B.ns, 2), dim3(256), 0, st, B, c->d_gaps.as<double>());
-    if (c->acc_final_t && c->max_w <= 15)   // one thread per letter, all widths (the operands of the fifteen widths overlap)
-        hipLaunchKernelGGL(vlin_acc_final_t, dim3((B.nmax + 255) / 256, B.ns), dim3(256), 0, st, B, c->d_vlin, c->d_gaps.as<const double>(), c->max_w);
+        hipLaunchKernelGGL(vlin_acc_gaps, dim3((B.nmax + 255) / 256, B.ns, 60), dim3(256), 0, st, B, d_vlin, A.gaps, 30, 1, (double*)nullptr);
+    hipLaunchKernelGGL(vlin_acc_gsuf, dim3((B.nmax + 255) / 256, B.ns, 2), dim3(256), 0, st, B, A.gaps);
+    if (A.acc_final_t)   // one thread per letter, all widths (the operands of the fifteen widths overlap)
+        hipLaunchKernelGGL(vlin_acc_final_t, dim3((B.nmax + 255) / 256, B.ns), dim3(256), 0, st, B, d_vlin, (const double*)A.gaps, A.max_w);
     else
-        hipLaunchKernelGGL(vlin_acc_final, dim3((B.nmax + 255) / 256, B.ns, c->max_w), dim3(256), 0, st, B, c->d_vlin, c->d_gaps.as<const double>(), c->max_w);
+        hipLaunchKernelGGL(vlin_acc_final, dim3((B.nmax + 255) / 256, B.ns, A.max_w), dim3(256), 0, st, B, d_vlin, (const double*)A.gaps, A.max_w);
     c->n_launch[1] += 6;
 }
 
 // the same from the top; look-ahead pairs: the odd diagonal is the full launch (+ the sums of the next), the even one a wavefront per group
-static void vlin_outside(SweepPass& S, int pin, bool co)
+static void vlin_outside(SweepPass& S, const McVlinArgs& A)
 {
     rh_ctx* c = S.c;
     const McBatch& B = S.B;
-    const VlinKernels& K = vlin_kernels(S.P.BS, co);
-    const bool ahead = S.P.org == SweepPlan::kLookahead, window = co && c->co_window && c->co_cut_min >= 1;
-    int* bad = (int*)(co ? c->d_cobad.p : c->d_bad.p);
+    const VlinKernels& K = vlin_kernels(S.P.BS, A.co);
+    const bool ahead = S.P.org == SweepPlan::kLookahead;
     far_outside_begin(S, B.nmax - 2);
     for (int d = ahead ? ((B.nmax - 2) | 1) : B.nmax - 2; d >= 0; d--) {
         if (d <= B.nmax - 2) far_outside_before(S, d);
         const int mode = !ahead ? 0 : (d & 1) ? 1 : 2;
         const int cells = mode == 1 ? (B.nmax - d + 63) / 64 : (B.nmax - 1 - d + 63) / 64;   // (mode 1: the cells of diagonal d-1)
-        const VlinGrid G = vlin_grid(c, B, co, window, pin, d, cells);
-        KLAUNCH(c, 2, (K.out[mode]), G.grid, dim3(mode == 2 ? 64 : 64 * S.P.W), S.st, B, c->d_vlin, d, G.pin, bad);
+        const VlinGrid G = vlin_grid(A, d, cells);
+        KLAUNCH(c, 2, (K.out[mode]), G.grid, dim3(mode == 2 ? 64 : 64 * S.P.W), S.st, B, A.d_vlin, d, G.pin, A.bad);
         c->n_launch[S.k]++;
     }
-    if (co) {
-        const DxBatch& D = c->dx;
-        hipLaunchKernelGGL(mcv_extract_hp, dim3((D.n1max * D.n2max + 255) / 256, B.ns), dim3(256), 0, S.st, B, D.hp, D.tab_stride, D.ldd, D.logz,
-                           c->h_vlin->s, bad);
-    } else
-        vlin_finish_acc(c, B, S.st);
+    if (A.co)
+        hipLaunchKernelGGL(mcv_extract_hp, dim3((A.n1max * A.n2max + 255) / 256, B.ns), dim3(256), 0, S.st, B, A.hp, A.hp_stride, A.hp_ldd, A.hp_logz,
+                           A.h_vlin->s, A.bad);
+    else
+        vlin_finish_acc(c, A, S.st);
 }
 
-int launch_mc_vlin(rh_ctx* c, int pin, int phase, bool co, const SweepPlan& P)
+int launch_mc_vlin(rh_ctx* c, const McVlinArgs& A)
 {
-    SweepPass S{c, P, co ? c->co : c->mc, co ? c->s_dx : c->s_mc, co ? 2 : phase};
-    if (phase == 0) vlin_inside(S, pin, co);
-    else vlin_outside(S, pin, co);
+    SweepPass S{c, A.plan, A.B, A.co ? c->s_dx : c->s_mc, A.co ? 2 : A.phase};
+    if (A.phase == 0) vlin_inside(S, A);
+    else vlin_outside(S, A);
     return RH_OK;
 }
 

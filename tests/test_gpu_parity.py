@@ -750,6 +750,101 @@ def test_vienna_bl_two_molecule_graph_is_rekeyed_when_the_shortest_cut_changes(h
         assert r["hp"].max() > 1e-3   # the short-cut pair's cross-strand cells were really computed
 
 
+def test_captured_launches_follow_every_quantity_they_bake_in(hotlib, monkeypatch):
+    """The captured launch graphs of a context are keyed by everything their launches bake in.  Chains of uploads on ONE context,
+    consecutive ones differing in exactly one such quantity (buffers, counts and leading dimensions stay): every result equals,
+    bit for bit, that of the same batch on a fresh context, which has no graph to replay.
+    With the scale memory on, a result depends on the exponent the context has moved to (that is what the switch is); there the
+    fresh context is brought to the same exponent by a batch of ANOTHER shape, so that it has no graph of the compared shape either."""
+    import ractip_amd
+    rng = np.random.default_rng(80)
+    rs = lambda n: "".join(rng.choice(list("ACGU"), size=n))
+    comp = {"G": "C", "C": "G"}
+
+    def hairpins(n):
+        s = ""
+        while len(s) < n:
+            stem = "".join(rng.choice(list("GC"), size=10))
+            s += stem + "AAAA" + "".join(comp[ch] for ch in reversed(stem)) + "AA"
+        return s[:n]
+    keys = ("bp1", "bp2", "up1", "up2", "hp", "logZ")
+
+    def compute(c, pairs, state={}):
+        if state.get("memory"):
+            c.set_scale_memory(True)
+        if "hybrid" in state:
+            c.set_hybrid(state["hybrid"])
+        if "max_w" in state:
+            c.set_max_w(state["max_w"])
+        c.batch_upload(pairs)
+        c.batch_compute()
+        return [c.batch_results(p) for p in range(len(pairs))]
+
+    def chain(model, steps, prepare={}):
+        """steps: (what, pairs, the settings that change with it); prepare[what]: what a fresh context runs before that step"""
+        c = ractip_amd.Context(device=0, model=model)
+        state = {}
+        try:
+            for what, pairs, settings in steps:
+                state.update(settings)
+                got = compute(c, pairs, state)
+                f = ractip_amd.Context(device=0, model=model)
+                try:
+                    if what in prepare:
+                        prepare[what](f, state)
+                    want = compute(f, pairs, state)
+                finally:
+                    f.close()
+                for p, (r, r0) in enumerate(zip(got, want)):
+                    for k in keys:
+                        assert np.array_equal(r[k], r0[k]), (what, p, k)
+        finally:
+            c.close()
+
+    def batch(l1, l2):
+        return [(rs(a), rs(b)) for a, b in zip(l1, l2)]
+    CF, VBL = ractip_amd.hot.RH_MODEL_CONTRAFOLD, ractip_amd.hot.RH_MODEL_VIENNA_BL
+
+    # ---- CONTRAfold model
+    l1, l2 = [99, 80, 70, 60, 90, 50, 45, 64], [55, 88, 41, 48, 77, 66, 52, 40]
+    structured = [(hairpins(1100), hairpins(1000)) for _ in range(4)]
+    chain(CF, [
+        ("longest sequence 99", batch(l1, l2), {}),
+        ("longest sequence 100, the same leading dimension", batch([100] + l1[1:], l2), {}),
+        ("longest sequence 99 again", batch(l1, l2), {}),
+        ("a sequence under 40 letters: the short pass", batch(l1, l2[:3] + [30] + l2[4:]), {}),
+        ("no short sequence again", batch(l1, l2), {}),
+        ("chains of hairpins move the exponent", structured, {"memory": True}),
+        ("ordinary sequences of the same shape on the moved exponent", batch([1100] * 4, [1000] * 4), {}),
+    ], prepare={"ordinary sequences of the same shape on the moved exponent":
+                lambda f, state: compute(f, structured + [(hairpins(1100), hairpins(1000))], state)})
+    monkeypatch.setenv("RH_SMALL", "1")   # (read when a context is created)
+    try:
+        chain(CF, [
+            ("three sequences of 8..109 letters", batch([150, 120, 130, 60, 140, 111, 125, 118], [140, 100, 115, 122, 9, 133, 127, 110]), {}),
+            ("six of them", batch([150, 120, 109, 60, 140, 111, 80, 118], [140, 100, 115, 122, 9, 133, 127, 8]), {}),
+            ("three again", batch([150, 120, 130, 60, 140, 111, 125, 118], [140, 100, 115, 122, 9, 133, 127, 110]), {}),
+        ])
+    finally:
+        monkeypatch.delenv("RH_SMALL")
+
+    # ---- Vienna-BL model, hp from the two-molecule ensemble unless a step says otherwise
+    v1, v2 = [70, 190, 100, 120, 150, 95, 130, 110], [180, 90, 200, 60, 140, 75, 160, 85]   # cuts 70..190, longest s1+s2 = 300
+    same = batch(v1, v2)
+    ladder = [(hairpins(900), rs(300)), (rs(420), rs(800)), (rs(350), rs(500)), (rs(850), rs(700))]
+    chain(VBL, [
+        ("cuts 70..190", batch(v1, v2), {"hybrid": True, "max_w": 1}),
+        ("another shortest cut", batch([90] + v1[1:], v2), {}),
+        ("another longest cut", batch([90, 170] + v1[2:], v2), {}),
+        ("accessibility width 1", same, {"max_w": 1}),
+        ("accessibility widths 1..8", same, {"max_w": 8}),
+        ("a chain of hairpins moves the whole batch to another exponent", ladder, {}),
+        ("ordinary sequences of the same shape", batch([900, 420, 350, 850], [300, 800, 500, 700]), {}),
+        ("hp from pf_duplex", same, {"hybrid": False}),
+        ("hp from the two-molecule ensemble, the same pairs", same, {"hybrid": True}),
+    ])
+
+
 def test_vienna_bl_scale_exponent_ladder(hotlib, monkeypatch):
     """Vienna-BL model: a batch with sequences outside the double range of the default exponent (chains of stable hairpins, log Z
     0.87 per nucleotide at 900 nt) is run again on the linear kernels with another exponent -- whole batch: folds, accessibility and
