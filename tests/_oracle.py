@@ -294,6 +294,7 @@ class OraclePool:
         self.vo = ViennaOracle()
         self.pool = ThreadPoolExecutor(max_workers=min(workers, ORACLE_WORKERS))
         self.cache = {}
+        self.constrained_cache = {}
         self.lock = threading.Lock()
 
     def _get(self, key, fn, *args):
@@ -317,6 +318,22 @@ class OraclePool:
 
     def pf_duplex(self, s1, s2):
         return self._get(("vo-dx", s1, s2), self.vo.pf_duplex, s1, s2)
+
+    def wait(self):
+        """Returns when every call queued so far has ended."""
+        with self.lock:
+            queued = list(self.cache.values())
+        for f in queued:
+            f.exception()
+
+    def constrained(self, call, *args, constraint):
+        """A constrained Vienna call ('mccaskill' or 'cofold'; memoised, its result and not a Future): on the calling thread with
+        the pool idle, because the allowed-pair mask is one global that a call on another thread would read or reset."""
+        key = (call, args, constraint)
+        if key not in self.constrained_cache:
+            self.wait()
+            self.constrained_cache[key] = getattr(self.vo, call)(*args, constraint=constraint)
+        return self.constrained_cache[key]
 
     def close(self):
         self.pool.shutdown(wait=True)

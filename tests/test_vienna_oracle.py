@@ -70,6 +70,28 @@ def test_mccaskill_equals_bruteforce_enumeration(vo):
         assert np.abs(a["up"] - b["up"]).max() < 1e-11, s
 
 
+WIDE_WIDTH_CASES = [   # 40-50 letters, few of them pairable (the enumeration stays small), accessibility wider than any interior-loop side (30)
+    ("GGG" + "A" * 31 + "CCC" + "AAGC", 36),
+    ("GCG" + "A" * 12 + "GGC" + "A" * 20 + "GCC" + "A" * 3 + "CGC", 40),
+    ("A" * 5 + "GGAC" + "A" * 33 + "GUCC", 34),
+    ("GGG" + "A" * 31 + "CCC" + "AAGC", 31),
+]
+
+
+@pytest.mark.parametrize("s,W", WIDE_WIDTH_CASES, ids=["%d-w%d" % (len(s), W) for s, W in WIDE_WIDTH_CASES])
+def test_mccaskill_wide_widths_equal_bruteforce_enumeration(vo, s, W):
+    """P(region unpaired) at widths above 30, where no interior loop can hold the region in one side and the gap sums of the DP
+    vanish: log Z, bp and every up column of the DP == explicit enumeration (PARITY UNPINNED against ViennaRNA; this pins the
+    restatement the GPU tests compare the wide widths with).  The columns from 30 on are not all zero, so the comparison means something."""
+    assert 40 <= len(s) <= 50 and W > 30
+    a, b = vo.mccaskill(s, max_w=W), vo.fold_bruteforce(s, max_w=W)
+    assert abs(a["logZ"] - b["logZ"]) < 1e-11
+    assert np.abs(a["post"] - b["post"]).max() < 1e-11
+    assert a["up"].shape == (len(s), W) and np.abs(a["up"] - b["up"]).max() < 1e-11
+    wide = b["up"][:, 30:]
+    assert ((wide > 0) & (wide < 1)).any(), "the columns of widths above 30 are all 0 or 1"
+
+
 def test_mccaskill_invariants_on_bundled_sequences(vo, golden):
     for name in ("DIS", "CopA", "CopT", "OxyS", "fhlA"):
         s = str(golden["mc/%s/seq" % name])
