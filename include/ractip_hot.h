@@ -58,7 +58,8 @@ rh_ctx* rh_create(int device, int model, const char* param_file);
  *   RH_VIENNA_SEM_18: ViennaRNA-1.8 LoopEnergy + dangle sums, the 1.8 branch of src/pf_duplex.c:209-433 (all kernels);
  *   RH_VIENNA_SEM_20: ViennaRNA-2.x E_IntLoop / E_ExtLoop / E_MLstem / E_Hairpin, the HAVE_VIENNA20 branch the reference's
  *     CMake selects (src/pf_duplex.c:128-206; CMakeLists.txt:28): mismatch_interior_1n / _23, mismatch_exterior / _multi,
- *     tri/tetra/hexaloop energies replacing the hairpin energy.  Log-space kernels only (rh_set_mode(LINEAR) is refused);
+ *     tri/tetra/hexaloop energies replacing the hairpin energy.  Log-space kernels, except pf_duplex on request:
+ *     rh_set_mode(LINEAR) is refused, rh_set_duplex_mode(AUTO or LINEAR) moves the pf_duplex sweeps to the linear kernels;
  *   RH_VIENNA_SEM_AUTO: 2.x if defaults_file or param_file is a v2.0 parameter file, else 1.8.
  * PARITY UNPINNED in both semantics. */
 #define RH_VIENNA_SEM_AUTO 0
@@ -83,6 +84,18 @@ int rh_set_mode(rh_ctx* ctx, int mode);
 int rh_last_path(const rh_ctx* ctx);
 /* the same for the sweeps that produced hp (duplex or two-molecule ensemble) */
 int rh_last_hybrid_path(const rh_ctx* ctx);
+/* Arithmetic path of the pf_duplex sweeps alone: the sweeps that produce hp under RH_HYBRID_DUPLEX (rh_duplex, the batched
+ * form, the pf_duplex shim), either model, either semantics, independently of the McCaskill sweeps.  RH_MODE_INHERIT
+ * (default): as rh_set_mode says.  AUTO / LOG / LINEAR: as for rh_set_mode, for these sweeps only -- AUTO recomputes by the
+ * log-space kernels what left the double range (rh_last_hybrid_path = 3, rh_batch_fallbacks which = 1), LINEAR never does.
+ * Under RH_VIENNA_SEM_20 this is how pf_duplex (src/pf_duplex.c:128-206) reaches the scaled linear kernels: AUTO and LINEAR run
+ * them, LOG and INHERIT stay on the log-space kernels.  Ignored under RH_HYBRID_COFOLD: the two-molecule sweeps follow
+ * rh_set_mode.  Takes effect at the next compute, with or without a new upload (the linear and the log-space kernels share the
+ * pair's tables; a compute that changes from one to the other clears them first).  A RH_VIENNA_SEM_20 context keeps ten
+ * linear tables per pair instead of six whether or not it ever calls this. */
+#define RH_MODE_INHERIT (-1)
+int rh_set_duplex_mode(rh_ctx* ctx, int mode);
+int rh_get_duplex_mode(const rh_ctx* ctx);
 
 /* Base-pairing probabilities of one sequence.  Replaces the body of
  * RactIP::contrafold up to GetPosterior (src/ractip.cpp:199-211:

@@ -100,6 +100,7 @@ struct DxBatch {
 };
 
 // ---- duplex, scaled linear path: anti-diagonal-major tables [sd*lda + kDxPad + a], a = i, sd = i + (L2+1-j)
+constexpr int kVdTables18 = 6, kVdTables20 = 10;   // tables per pair of the Vienna-BL linear duplex (DxvLinTable, duplex_vlin.hip): 1.8 / 2.x semantics
 constexpr int kDxPad = 32;   // zero columns on both sides of every row (>= 29: the longest window reach)
 // How far from its cells a row is ever read.  Row sd has cells at columns alo(sd) = max(1, sd-L2) .. ahi(sd) = min(L1, sd-1); both grow
 // with sd, by at most one per row.  A kept cell (sd, a), alo(sd) <= a <= ahi(sd), reads, with dir = -1 (inside) / +1 (outside):

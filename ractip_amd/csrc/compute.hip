@@ -100,7 +100,7 @@ DxLinArgs dx_lin_args(const rh_ctx* c)
 {
     DxLinArgs A;
     A.X = c->dxl; A.plan = c->plan[2]; A.lz_chunks = c->lz_chunks;
-    if (c->model == RH_MODEL_VIENNA_BL) A.vdx_s = c->vdx_s;
+    if (c->model == RH_MODEL_VIENNA_BL) { A.vdx_s = c->vdx_s; A.sem20 = c->vienna_sem == kViennaSem20; }
     else { A.dm = c->d_dxlin; A.hm = &c->h_dxlin; }
     A.zpart = c->d_zpart.as<double>(); A.zbar = c->d_zbar.as<double>();
     A.logz = c->d_logz.as<double>(); A.bad = c->d_dxbad.as<int>();
@@ -132,10 +132,18 @@ int compute_once(rh_ctx* c)
     // the arguments below carry the same plans to the launchers
     const bool vienna = c->model == RH_MODEL_VIENNA_BL;
     for (int phase = 0; phase < 2; phase++) c->plan[phase] = vienna ? plan_mc_vlin(c, phase, false, c->mc.nmax) : plan_mc_lin(c, phase, c->mc.nmax);
-    c->plan[2] = !vienna ? plan_dx_lin(c, c->dx_w) : c->hybrid == RH_HYBRID_COFOLD ? plan_mc_vlin(c, 0, true, c->co.nmax) : plan_dx_vlin();
+    c->plan[2] = !vienna ? plan_dx_lin(c, c->dx_w) : c->hybrid == RH_HYBRID_COFOLD ? plan_mc_vlin(c, 0, true, c->co.nmax) : plan_dx_vlin(c->vienna_sem == kViennaSem20);
     const int pin = (c->has_mc && c->mc.ns % 8 == 0) ? 1 : 0;   // (of the log-space sweeps; the linear ones: see their arguments)
+    // the path of the pf_duplex sweeps (RH_HYBRID_DUPLEX): rh_set_duplex_mode, or what rh_set_mode says
+    const int dx_mode = c->duplex_mode == RH_MODE_INHERIT ? c->mode : c->duplex_mode;
     int rc;
     std::vector<int> bad;
+    // the linear duplex kernels share d_dxtab with the log-space ones and read zero pad columns: after a log-space compute on this
+    // upload (another mode since, or a fallback) the image stage() left is gone
+    if (c->has_dx && c->dxtab_log && dx_mode != RH_MODE_LOG && !(c->model == RH_MODEL_VIENNA_BL && c->hybrid == RH_HYBRID_COFOLD)) {
+        HIP_TRY(c, hipMemsetAsync(c->d_dxtab.p, 0, c->dx_bytes, c->s_dx));
+        c->dxtab_log = false;
+    }
     // duplex first on its own stream: it is independent of the McCaskill sweeps and overlaps them
     HIP_TRY(c, hipEventRecord(c->ev[3], c->s_dx));
     bool dx_lin_launched = false, co_lin_launched = false, co_seed_bad = false, out_from_ev5 = false;
@@ -160,19 +168,21 @@ int compute_once(rh_ctx* c)
             if (c->last_dx_path != 3) c->last_dx_path = 2;
         }
     } else if (c->has_dx && c->model == RH_MODEL_VIENNA_BL) {
-        if (c->mode != RH_MODE_LOG) {   // scaled linear sweeps; pairs outside the double range send the batch to the log-space kernels
+        if (dx_mode != RH_MODE_LOG) {   // scaled linear sweeps; pairs outside the double range send the batch to the log-space kernels
             if ((rc = run_graphed(c, c->g_dx, c->s_dx, 2, launch_dx_vlin, dx_lin_args(c)))) return rc;
             dx_lin_launched = true;
         } else {
             if ((rc = launch_dx_vlog(c))) return rc;
+            c->dxtab_log = true;
             c->last_dx_path = 2;
         }
     } else if (c->has_dx) {
-        if (c->mode != RH_MODE_LOG) {
+        if (dx_mode != RH_MODE_LOG) {
             if ((rc = run_graphed(c, c->g_dx, c->s_dx, 2, launch_dx_lin, dx_lin_args(c)))) return rc;
             dx_lin_launched = true;
         } else {
             if ((rc = launch_dx_log(c, c->dx))) return rc;
+            c->dxtab_log = true;
             c->last_dx_path = 2;
         }
     }
@@ -273,7 +283,7 @@ int compute_once(rh_ctx* c)
     }
     if (dx_lin_launched) {
         c->last_dx_path = 1;
-        if (c->mode == RH_MODE_AUTO) {
+        if (dx_mode == RH_MODE_AUTO) {
             if ((rc = flagged(c, c->d_dxbad.as<int>(), c->dx.np, c->s_dx, &c->fallback_dx))) return rc;
             const bool redo = !c->fallback_dx.empty();
             if (redo && c->model != RH_MODEL_VIENNA_BL && 2 * c->fallback_dx.size() <= (size_t)c->dx.np) {
@@ -291,6 +301,7 @@ int compute_once(rh_ctx* c)
                 c->n_launch[2] = 0;
                 HIP_TRY(c, hipEventRecord(c->ev[3], c->s_dx));
                 if ((rc = (c->model == RH_MODEL_VIENNA_BL ? launch_dx_vlog(c) : launch_dx_log(c, c->dx)))) return rc;
+                c->dxtab_log = true;
                 HIP_TRY(c, hipEventRecord(c->ev[4], c->s_dx));
                 c->last_dx_path = 3;
             }

@@ -143,6 +143,7 @@ struct DxLinArgs {   // launch_dx_lin (CONTRAfold model: dm, hm) and launch_dx_v
     double* logz;              // per pair of X
     int* bad;
     int lz_chunks;
+    int sem20;                 // Vienna-BL: the 2.x instantiations (dxvl_sweep4<true>, four more tables per pair)
     DxLinArgs() { std::memset(this, 0, sizeof *this); }
 };
 static_assert(std::is_trivially_copyable_v<McLinArgs> && std::is_trivially_copyable_v<McVlinArgs> && std::is_trivially_copyable_v<DxLinArgs>);
@@ -201,6 +202,9 @@ struct Ctx {   // (the fields of rh_ctx, below)
     std::vector<int> rescaled_dx;              // pairs the last compute recomputed on the linear duplex kernels with another exponent (rh_batch_fallbacks which = 3)
     DxLinBatch dxl = {};
     size_t dxl_layout = 0;         // (lda, rows) signature of the zero-padded table image currently in HBM
+    size_t dx_bytes = 0;           // bytes of d_dxtab the staged batch uses
+    bool dxtab_log = false;        // the log-space duplex kernels wrote d_dxtab since its last clear: the linear kernels, which share
+                                   // the buffer and need zero pad columns, clear it first (a change of mode without a new upload)
     int co_seed = 1;               // Vienna-BL, hp from the two-molecule ensemble: copy the one-strand cells from the single folds (RH_CO_SEED=0: sweep them again)
     int dx_strip = 1;              // linear duplex: eight anti-diagonals per launch (dxl_strip8); RH_DX_STRIP=0: four (dxl_sweep4)
     int dx_quad = 1;               // linear duplex: four anti-diagonals per launch (dxl_sweep4, 4 wavefronts per group); RH_DX_QUAD=0: two (dxl_sweep<W>)
@@ -237,6 +241,7 @@ struct Ctx {   // (the fields of rh_ctx, below)
     int use_graphs = 1;            // RH_NO_GRAPH=1 launches every kernel from the host instead
     GraphSlot g_in, g_out, g_dx;
     int mode = RH_MODE_AUTO;       // which McCaskill path rh_batch_compute takes
+    int duplex_mode = RH_MODE_INHERIT;   // rh_set_duplex_mode: the path of the pf_duplex sweeps alone (INHERIT: as `mode`)
     int lin_w = 4;                 // wavefronts per 64-cell group of the linear outside kernel (Vienna-BL kernels: 8)
     int lin_w_in = 4;              // ... of the inside kernel (fewer, longer wavefronts: less per-wavefront scalar overhead)
     int lin_bs = 16;               // block size of the far/near split of the O(n^3) terms (0 = off)
@@ -385,7 +390,7 @@ extern const double kVRungS[Ctx::kVRungs];
 // launch_duplex.hip
 int launch_dx_log(rh_ctx* c, const DxBatch& D);
 SweepPlan plan_dx_lin(const rh_ctx* c, int w);
-SweepPlan plan_dx_vlin();
+SweepPlan plan_dx_vlin(bool sem20);
 int launch_dx_lin(rh_ctx* c, const DxLinArgs& A);
 int launch_dx_vlin(rh_ctx* c, const DxLinArgs& A);
 int launch_dx_vlog(rh_ctx* c);

@@ -11,6 +11,14 @@
 //   * the seven tabulated shapes (stack, 1-bulges, 1x1, 1x2, 2x1, 2x2) are gathered per cell in the epilogue; X_2 / X_3 take the
 //     ones that lie on X_0 / X_1 (stack; stack + 1-bulges) from LDS, where wavefronts 0 / 1 leave their rows.
 // A pair whose scaled partition function leaves the double range is flagged and recomputed by the log-space kernels.
+// S20 = true: ViennaRNA-2.x loop energies (kViennaSem20, pf_duplex.c:128-206), the arithmetic of duplex_vienna.hip's kinds 3 / 4:
+//   * the ends are the E_ExtLoop terms E_dxE (open :146, close :158, 185, 200) instead of the dangle products;
+//   * 1xn loops (n >= 3) are the two taps l1 = 1 and l1 = tw-1 of a fourth copy of the source table, decorated with mismatch1nI,
+//     weighted W1N[tw]; 2x3 loops the two taps l1 = 2, 3 at tw = 5 of a fifth copy (mismatch23I), weighted W23.  shape_w holds 0
+//     for those shapes, so the generic filter leaves them out.  The taps come straight from global memory next to the
+//     TerminalAU bulge taps of the same row (same branch, one wait for both): three loads per row and diagonal are too thin to
+//     stage.  LDS: 24 KiB staged rows + 26 KiB partial sums + 1 KiB hand-over = 51 KiB of the 53.3 KiB that three workgroups
+//     per CU allow; two more staged row sets (12 KiB) would make it 63 KiB, two workgroups.
 #include <hip/hip_runtime.h>
 
 #include "batch.h"
@@ -19,7 +27,9 @@
 
 namespace rh {
 
-enum DxvLinTable { VD_IN = 0, VD_INX, VD_OUT, VD_OUTX, VD_INT, VD_OUTT, VD_COUNT };   // IN / OUT at DL_IN / DL_OUT: dxl_posterior reads them
+enum DxvLinTable { VD_IN = 0, VD_INX, VD_OUT, VD_OUTX, VD_INT, VD_OUTT, VD_IN1N, VD_OUT1N, VD_IN23, VD_OUT23, VD_COUNT20, VD_COUNT = VD_IN1N };   // IN / OUT at DL_IN / DL_OUT: dxl_posterior reads them
+
+static_assert(VD_COUNT == kVdTables18 && VD_COUNT20 == kVdTables20, "staging.hip sizes a pair's tables by these");
 
 namespace {
 typedef const volatile __attribute__((address_space(3))) double* lds_vp;
@@ -39,9 +49,13 @@ __device__ __forceinline__ double small_wd(const VLinModel* L, int l1, int l2, i
 // all staged rows of wavefront WV: t = WV, WV+4, ... <= 30 (row A + dir*(2+t)); lengths and weight offsets are compile-time.
 // seg0[q*96 + k]: inside column a-4-t+skip+k with skip = max(0, t-27) (X_k reads tap l1 at a-1-l1), outside column a+1+k
 // (tap l1 at a+1+l1).  accg[k]: generic loops of X_k (x shape_w), accb[k]: long bulges (x WB), taken from the TerminalAU rows
-template <int WV>
-__device__ __forceinline__ void vwin_pass4(const double* seg0, const VLinModel* __restrict__ L, const double* __restrict__ taurows, int lda,
-                                           bool outside, int sdA, int smax, int a, double accg[4], double accb[4])
+// S20: acc1n[k]: 1xn loops of X_k (x W1N) from the mismatch1nI rows; acc23: the 2x3 loops (x W23) of the one diagonal X_(WV^1)
+// whose loops of length 5 lie on a row of this wavefront (t = 5-k: 4, 5, 2, 3 for WV = 0..3), from the mismatch23I rows
+template <int WV, bool S20>
+__device__ __forceinline__ void vwin_pass4(const double* seg0, const VLinModel* __restrict__ L, const VDxLin* __restrict__ D,
+                                           const double* __restrict__ taurows, const double* __restrict__ rows1n,
+                                           const double* __restrict__ rows23, int lda, bool outside, int sdA, int smax, int a,
+                                           double accg[4], double accb[4], double acc1n[4], double& acc23)
 {
     if constexpr (WV < 4) {
 #pragma unroll
@@ -55,12 +69,22 @@ __device__ __forceinline__ void vwin_pass4(const double* seg0, const VLinModel* 
                 const int dir = outside ? 1 : -1;
                 const double* __restrict__ trow = taurows + (size_t)row * lda + a;
                 const double near = trow[dir];                                   // bulge with l1 = 0
+                const double* __restrict__ nrow = rows1n + (size_t)row * lda + a;
+                double near1 = 0.0;
+                if constexpr (S20) near1 = nrow[2 * dir];                         // 1xn loop with l1 = 1
 #pragma unroll
                 for (int k = 0; k < 4; k++) {
                     const int tw = t + k;
                     if (tw < 2 || tw > kMaxSingle) continue;
                     accb[k] = fma(L->WB[tw], near + trow[dir * (1 + tw)], accb[k]);   // ... and with l1 = tw
                     if (tw < 4) continue;                                        // generic loops: l1, l2 >= 1, t >= 4
+                    if constexpr (S20) {
+                        acc1n[k] = fma(D->W1N[tw], near1 + nrow[dir * tw], acc1n[k]);   // ... and with l1 = tw-1
+                        if (tw == 5) {                                           // l1 = 2, 3
+                            const double* __restrict__ r23 = rows23 + (size_t)row * lda + a;
+                            acc23 = D->W23 * (r23[3 * dir] + r23[4 * dir]);
+                        }
+                    }
                     const double* __restrict__ wt = L->shape_w + tw * (tw + 1) / 2;
                     double g0 = 0.0, g1 = 0.0;
 #pragma unroll
@@ -76,10 +100,11 @@ __device__ __forceinline__ void vwin_pass4(const double* seg0, const VLinModel* 
 }
 }  // namespace
 
+template <bool S20>
 __global__ __launch_bounds__(256) void dxvl_sweep4(DxLinBatch B, const VLinModel* __restrict__ L, const VDxLin* __restrict__ D, int step)
 {
     __shared__ double buf[4][8][96];
-    __shared__ double part[8][4][64];
+    __shared__ double part[S20 ? 13 : 8][4][64];   // S20: [8 + k] the 1xn sums, [12][k] the 2x3 sum of X_k
     __shared__ double hand[2][64];      // raw X_0, raw X_1 of this group's columns
     const int pr = blockIdx.y;
     const int L1 = B.n[2 * pr], L2 = B.n[2 * pr + 1];
@@ -109,8 +134,12 @@ __global__ __launch_bounds__(256) void dxvl_sweep4(DxLinBatch B, const VLinModel
     const bool mine = sdw >= 2 && sdw <= smax;
     const size_t at = (size_t)sdw * lda + kDxPad + a;
     const int T_RAW = outside ? VD_OUT : VD_IN, T_MM = outside ? VD_OUTX : VD_INX, T_TAU = outside ? VD_OUTT : VD_INT;
+    const int T_1N = outside ? VD_OUT1N : VD_IN1N, T_23 = outside ? VD_OUT23 : VD_IN23;   // (S20: the pair has VD_COUNT20 tables)
     if (!has) {   // only clear the columns of the rows
-        if (mine && a <= B.n1max + 1 && (w < 2 || owns23)) { tab[T_RAW * ts + at] = 0.0; tab[T_MM * ts + at] = 0.0; tab[T_TAU * ts + at] = 0.0; }
+        if (mine && a <= B.n1max + 1 && (w < 2 || owns23)) {
+            tab[T_RAW * ts + at] = 0.0; tab[T_MM * ts + at] = 0.0; tab[T_TAU * ts + at] = 0.0;
+            if constexpr (S20) { tab[T_1N * ts + at] = 0.0; tab[T_23 * ts + at] = 0.0; }
+        }
         return;
     }
 
@@ -137,14 +166,20 @@ __global__ __launch_bounds__(256) void dxvl_sweep4(DxLinBatch B, const VLinModel
             if (lane < 32) buf[w][q][64 + lane] = v1[q];
         }
     }
-    double accg[4] = {0.0, 0.0, 0.0, 0.0}, accb[4] = {0.0, 0.0, 0.0, 0.0};
+    double accg[4] = {0.0, 0.0, 0.0, 0.0}, accb[4] = {0.0, 0.0, 0.0, 0.0}, acc1n[4] = {0.0, 0.0, 0.0, 0.0}, acc23 = 0.0;
     switch (w) {
-#define X(V) case V: vwin_pass4<V>(&buf[w][0][lane], L, tab + T_TAU * ts + kDxPad, lda, outside, sdA, smax, a, accg, accb); break;
+#define X(V) case V: vwin_pass4<V, S20>(&buf[w][0][lane], L, D, tab + T_TAU * ts + kDxPad, tab + (S20 ? T_1N : T_TAU) * ts + kDxPad, \
+                                        tab + (S20 ? T_23 : T_TAU) * ts + kDxPad, lda, outside, sdA, smax, a, accg, accb, acc1n, acc23); break;
         X(0) X(1) X(2) X(3)
 #undef X
     }
 #pragma unroll
     for (int k = 0; k < 4; k++) { part[k][w][lane] = accg[k]; part[4 + k][w][lane] = accb[k]; }
+    if constexpr (S20) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) part[8 + k][w][lane] = acc1n[k];
+        part[12][w ^ 1][lane] = acc23;
+    }
 
     // ---- epilogue of X_w: letters, pair type, the tabulated shapes whose rows are final (before the barrier)
     const int b = sdw - a, i = a, j = L2 + 1 - b;
@@ -166,11 +201,20 @@ __global__ __launch_bounds__(256) void dxvl_sweep4(DxLinBatch B, const VLinModel
     const bool pairable = type != 0;
     const double* __restrict__ rawt = tab + T_RAW * ts + kDxPad;
     double sm7 = 0.0, e_tau = 1.0, mm_up = 0.0, mm_dn = 0.0, ends = 0.0;
+    double m1n_up = 0.0, m1n_dn = 0.0, m23_up = 0.0, m23_dn = 0.0;   // S20: this pair's mismatch1nI / mismatch23I as either end
     double c_st = 0.0, c_b01 = 0.0, c_b10 = 0.0;   // weights of the shapes of X_2 / X_3 whose source row belongs to this launch
     {
         const int rt = vienna_rtype(type);
         const double l_tau = L->E_tau[type], l_up = D->E_mmI[type * 25 + xp * 5 + ym], l_dn = D->E_mmI[rt * 25 + yp * 5 + xm];
         const double l_d5i = D->E_d5[type * 5 + xm], l_d3i = D->E_d3[type * 5 + yp], l_d3o = D->E_d3[rt * 5 + xp], l_d5o = D->E_d5[rt * 5 + ym];
+        // S20: the E_ExtLoop end term, index convention of duplex_vienna.hip (5 = no neighbour); loaded unconditionally like the rest
+        double l_end = 0.0, l_1u = 0.0, l_1d = 0.0, l_2u = 0.0, l_2d = 0.0;
+        if constexpr (S20) {
+            l_end = !outside ? D->E_dxE[type * 36 + (i > 1 ? xm : 5) * 6 + (j < L2 ? yp : 5)]     // pf_duplex.c:146
+                             : D->E_dxE[rt * 36 + (j > 1 ? ym : 5) * 6 + (i < L1 ? xp : 5)];     // pf_duplex.c:158, 185, 200
+            l_1u = D->E_mm1n[type * 25 + xp * 5 + ym]; l_1d = D->E_mm1n[rt * 25 + yp * 5 + xm];
+            l_2u = D->E_mm23[type * 25 + xp * 5 + ym]; l_2d = D->E_mm23[rt * 25 + yp * 5 + xm];
+        }
         double sv[7], sw[7];
         bool sok[7];
 #pragma unroll
@@ -193,7 +237,11 @@ __global__ __launch_bounds__(256) void dxvl_sweep4(DxLinBatch B, const VLinModel
         }
         if (pairable) {
             e_tau = l_tau; mm_up = l_up; mm_dn = l_dn;
-            if (!outside) ends = D->E_init * (i > 1 ? l_d5i : 1.0) * (j < L2 ? l_d3i : 1.0) * e_tau;   // pf_duplex.c:321-326
+            if constexpr (S20) {
+                m1n_up = l_1u; m1n_dn = l_1d; m23_up = l_2u; m23_dn = l_2d;
+                ends = outside ? l_end : D->E_init * l_end;
+            }
+            else if (!outside) ends = D->E_init * (i > 1 ? l_d5i : 1.0) * (j < L2 ? l_d3i : 1.0) * e_tau;   // pf_duplex.c:321-326
             else ends = (i < L1 ? l_d3o : 1.0) * (j > 1 ? l_d5o : 1.0) * e_tau;                         // pf_duplex.c:361-365
         }
 #pragma unroll
@@ -218,10 +266,20 @@ __global__ __launch_bounds__(256) void dxvl_sweep4(DxLinBatch B, const VLinModel
     double g = 0.0, gb = b2;
 #pragma unroll
     for (int k = 0; k < 4; k++) { g += part[w][k][lane]; gb += part[4 + w][k][lane]; }
+    double x20 = 0.0;   // S20: the 1xn and 2x3 loops, each family times this cell's own mismatch factor
+    if constexpr (S20) {
+        double g1n = 0.0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) g1n += part[8 + w][k][lane];
+        x20 = (outside ? m1n_up : m1n_dn) * g1n + (outside ? m23_up : m23_dn) * part[12][w][lane];
+    }
     const double pw = B.pw4[w];         // lam^(sd) inside / lam^(L1+L2+2-sd) outside: the scale of the open / close term
     double v = 0.0;
     if (w < 2) {
-        if (pairable) v = pw * ends + (outside ? mm_up : mm_dn) * g + e_tau * gb + sm7;
+        if (pairable) {
+            v = pw * ends + (outside ? mm_up : mm_dn) * g + e_tau * gb + sm7;
+            if constexpr (S20) v += x20;
+        }
         hand[w][lane] = v;
     }
     __syncthreads();
@@ -236,16 +294,24 @@ __global__ __launch_bounds__(256) void dxvl_sweep4(DxLinBatch B, const VLinModel
                 sm7 = fma(in2 ? hand[0][l2] : 0.0, c_b10, sm7);
             }
             v = pw * ends + (outside ? mm_up : mm_dn) * g + e_tau * gb + sm7;
+            if constexpr (S20) v += x20;
         }
     } else if (!mine) return;
     if (a <= B.n1max + 1) {  // every column of the row is rewritten: stale values of other shapes never survive
         tab[T_RAW * ts + at] = v;
         tab[T_MM * ts + at] = v * (outside ? mm_dn : mm_up);   // decorated as the other end of a later generic loop
         tab[T_TAU * ts + at] = v * e_tau;
+        if constexpr (S20) {
+            tab[T_1N * ts + at] = v * (outside ? m1n_dn : m1n_up);
+            tab[T_23 * ts + at] = v * (outside ? m23_dn : m23_up);
+        }
     }
 }
+template __global__ void dxvl_sweep4<false>(DxLinBatch, const VLinModel*, const VDxLin*, int);
+template __global__ void dxvl_sweep4<true>(DxLinBatch, const VLinModel*, const VDxLin*, int);
 
 // Z~ = sum IN~[a,b] * close(a,b) * lam^(L1+L2+2-a-b)   (pf_duplex.c:337-341); same two deterministic stages as dxl_logz_part
+template <bool S20>
 __global__ __launch_bounds__(256) void dxvl_logz_part(DxLinBatch B, const VLinModel* __restrict__ L, const VDxLin* __restrict__ D,
                                                      double* __restrict__ zpart, int* __restrict__ cpart, int nchunk)
 {
@@ -267,7 +333,9 @@ __global__ __launch_bounds__(256) void dxvl_logz_part(DxLinBatch B, const VLinMo
             if (!type) continue;
             npair++;
             const int rt = vienna_rtype(type);
-            const double cl = rowf * (i < L1 ? D->E_d3[rt * 5 + s1[i + 1]] : 1.0) * (j > 1 ? D->E_d5[rt * 5 + s2[j - 1]] : 1.0) * L->E_tau[type];
+            double cl;
+            if constexpr (S20) cl = rowf * D->E_dxE[rt * 36 + (j > 1 ? s2[j - 1] : 5) * 6 + (i < L1 ? s1[i + 1] : 5)];   // pf_duplex.c:158
+            else cl = rowf * (i < L1 ? D->E_d3[rt * 5 + s1[i + 1]] : 1.0) * (j > 1 ? D->E_d5[rt * 5 + s2[j - 1]] : 1.0) * L->E_tau[type];
             acc = fma(in[(size_t)sd * B.lda + a], cl, acc);
         }
     }
@@ -279,6 +347,8 @@ __global__ __launch_bounds__(256) void dxvl_logz_part(DxLinBatch B, const VLinMo
         cpart[(size_t)pr * nchunk + chunk] = sc[0] + sc[1] + sc[2] + sc[3];
     }
 }
+template __global__ void dxvl_logz_part<false>(DxLinBatch, const VLinModel*, const VDxLin*, double*, int*, int);
+template __global__ void dxvl_logz_part<true>(DxLinBatch, const VLinModel*, const VDxLin*, double*, int*, int);
 __global__ void dxvl_logz_final(DxLinBatch B, double s, const double* __restrict__ zpart, const int* __restrict__ cpart, int nchunk,
                                 double* __restrict__ zbar, double* __restrict__ logz, int* __restrict__ bad)
 {

@@ -311,7 +311,7 @@ int recompute_pairs_on_helper(rh_ctx* c, const std::vector<int>& P)
         c->helper->is_helper = true;
     }
     rh_ctx* h = c->helper;
-    h->max_w = c->max_w; h->hybrid = c->hybrid; h->mode = RH_MODE_AUTO; h->scale_ladder = c->scale_ladder; h->scale_memory = 0;
+    h->max_w = c->max_w; h->hybrid = c->hybrid; h->mode = RH_MODE_AUTO; h->duplex_mode = c->duplex_mode; h->scale_ladder = c->scale_ladder; h->scale_memory = 0;
     h->vlin_primary = c->vlin_primary < 0 ? 0 : -1;   // the exponent of the first pass is known to fail for these pairs: start on the next one
     const int nsub = (int)P.size();
     const int lds = c->mc.lds;

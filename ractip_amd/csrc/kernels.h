@@ -41,8 +41,8 @@ __global__ void lin_finish(McBatch B, const LinModel* __restrict__ L, double* __
 template <int W> __global__ void dxl_sweep(DxLinBatch B, const DxLinModel* __restrict__ L, int step, int groups);
 __global__ void dxl_sweep4(DxLinBatch B, const DxLinModel* __restrict__ L, int step, int groups);
 __global__ void dxl_strip8(DxLinBatch B, const DxLinModel* __restrict__ L, int step);
-__global__ void dxvl_sweep4(DxLinBatch B, const VLinModel* __restrict__ L, const VDxLin* __restrict__ D, int step);
-__global__ void dxvl_logz_part(DxLinBatch B, const VLinModel* __restrict__ L, const VDxLin* __restrict__ D, double* __restrict__ zpart,
+template <bool S20> __global__ void dxvl_sweep4(DxLinBatch B, const VLinModel* __restrict__ L, const VDxLin* __restrict__ D, int step);
+template <bool S20> __global__ void dxvl_logz_part(DxLinBatch B, const VLinModel* __restrict__ L, const VDxLin* __restrict__ D, double* __restrict__ zpart,
                                int* __restrict__ cpart, int nchunk);
 __global__ void dxvl_logz_final(DxLinBatch B, double s, const double* __restrict__ zpart, const int* __restrict__ cpart, int nchunk,
                                 double* __restrict__ zbar, double* __restrict__ logz, int* __restrict__ bad);

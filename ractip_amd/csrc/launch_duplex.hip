@@ -34,7 +34,8 @@ const Named<DxSweepK> kDxSweep4 = NAMED(dxl_sweep4);
 struct DxSweepKernels { int W; Named<DxSweepK> k; };
 const DxSweepKernels kDxSweepW[] = {{4, NAMED(dxl_sweep<4>)}, {2, NAMED(dxl_sweep<2>)}, {8, NAMED(dxl_sweep<8>)}};
 static const DxSweepKernels& dx_sweep_kernels(int W) { return row_of(kDxSweepW, [&](const DxSweepKernels& r) { return r.W == W; }); }
-const Named<void (*)(DxLinBatch, const VLinModel*, const VDxLin*, int)> kDxvlSweep4 = NAMED(dxvl_sweep4);
+// Vienna-BL: [0] ViennaRNA-1.8 loop energies, [1] 2.x (four more tables per pair)
+const Named<void (*)(DxLinBatch, const VLinModel*, const VDxLin*, int)> kDxvlSweep4[2] = {NAMED(dxvl_sweep4<false>), NAMED(dxvl_sweep4<true>)};
 
 SweepPlan plan_dx_lin(const rh_ctx* c, int w)
 {
@@ -44,11 +45,11 @@ SweepPlan plan_dx_lin(const rh_ctx* c, int w)
     P.fine = P.org == SweepPlan::kDxStrip8 ? kDxStrip8.name : P.org == SweepPlan::kDxSweep4 ? kDxSweep4.name : dx_sweep_kernels(P.W).k.name;
     return P;
 }
-SweepPlan plan_dx_vlin()   // (one organisation)
+SweepPlan plan_dx_vlin(bool sem20)   // (one organisation, an instantiation per semantics)
 {
     SweepPlan P;
     P.org = SweepPlan::kDxSweep4;
-    P.fine = kDxvlSweep4.name;
+    P.fine = kDxvlSweep4[sem20 ? 1 : 0].name;
     return P;
 }
 
@@ -101,11 +102,12 @@ int launch_dx_vlin(rh_ctx* c, const DxLinArgs& A)
     const double lam = std::exp(-A.vdx_s);
     for (int t = 0; 4 * t < smax - 1; t++) {
         for (int k = 0; k < 4; k++) X.pw4[k] = std::pow(lam, 2.0 + 4.0 * t + k);
-        KLAUNCH(c, 4, (kDxvlSweep4.kern), dim3(groups4, X.np, 2), dim3(256), c->s_dx, X, c->d_vdxl, c->d_vdx, t);
+        KLAUNCH(c, 4, (kDxvlSweep4[A.sem20 ? 1 : 0].kern), dim3(groups4, X.np, 2), dim3(256), c->s_dx, X, c->d_vdxl, c->d_vdx, t);
         c->n_launch[2]++;
     }
     int* cpart = (int*)(A.zpart + (size_t)X.np * A.lz_chunks);
-    hipLaunchKernelGGL(dxvl_logz_part, dim3(A.lz_chunks, X.np), dim3(256), 0, c->s_dx, X, c->d_vdxl, c->d_vdx, A.zpart, cpart, A.lz_chunks);
+    if (A.sem20) hipLaunchKernelGGL(dxvl_logz_part<true>, dim3(A.lz_chunks, X.np), dim3(256), 0, c->s_dx, X, c->d_vdxl, c->d_vdx, A.zpart, cpart, A.lz_chunks);
+    else hipLaunchKernelGGL(dxvl_logz_part<false>, dim3(A.lz_chunks, X.np), dim3(256), 0, c->s_dx, X, c->d_vdxl, c->d_vdx, A.zpart, cpart, A.lz_chunks);
     hipLaunchKernelGGL(dxvl_logz_final, dim3((X.np + 63) / 64), dim3(64), 0, c->s_dx, X, A.vdx_s, (const double*)A.zpart, (const int*)cpart,
                        A.lz_chunks, A.zbar, A.logz, A.bad);
     hipLaunchKernelGGL(dxl_posterior, dim3((X.n1max + 31) / 32, (smax - 1 + 31) / 32, X.np), dim3(256), 0, c->s_dx, X, (const double*)A.zbar, A.bad);

@@ -195,7 +195,7 @@ static rh_ctx* create_ctx(int device, int model, const char* param_file, const c
     c->device = device; c->model = model;
     c->max_w = model == RH_MODEL_VIENNA_BL ? 15 : 1;   // RactIP's default --max-w (src/cmdline.c:151-186) / contrafold's width 1
     c->vienna_sem = host_vienna ? host_vienna->semantics : 0;
-    if (c->vienna_sem == kViennaSem20) c->mode = RH_MODE_LOG;   // the scaled linear kernels hold the 1.8 semantics only
+    if (c->vienna_sem == kViennaSem20) c->mode = RH_MODE_LOG;   // the scaled linear kernels hold the 1.8 semantics only (pf_duplex: rh_set_duplex_mode)
     // scale exponent of the linear fast path: log Z per nucleotide of typical sequences under this model
     // (random ACGU: 0.107..0.129 for n = 200..2000); deviations only cost dynamic range, never accuracy
     build_lin_model(host_model, 0.12, &c->lin0.h);
@@ -461,6 +461,15 @@ int rh_set_mode(rh_ctx* c, int mode)
     c->mode = mode;
     return RH_OK;
 }
+
+int rh_set_duplex_mode(rh_ctx* c, int mode)
+{
+    if (!c) return RH_ERR_ARG;
+    if (mode < RH_MODE_INHERIT || mode > RH_MODE_LINEAR) return fail(c, RH_ERR_ARG, "unknown duplex mode %d", mode);
+    c->duplex_mode = mode;
+    return RH_OK;
+}
+int rh_get_duplex_mode(const rh_ctx* c) { return c ? c->duplex_mode : RH_ERR_ARG; }
 
 int rh_last_path(const rh_ctx* c) { return c ? c->last_path : RH_ERR_ARG; }
 int rh_last_hybrid_path(const rh_ctx* c) { return c ? c->last_dx_path : RH_ERR_ARG; }

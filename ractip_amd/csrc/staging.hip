@@ -201,7 +201,10 @@ int stage(rh_ctx* c, int ns, const char* const* seqs, const int* lens, bool with
         X.lda = (n1max + 2 + 2 * kDxPad + 1) & ~1;
         const size_t rows = (size_t)n1max + n2max + 3;
         X.tab_stride = rows * X.lda + 128;   // slack: the staged 96-column segments may run past the last row
-        X.pair_stride = X.tab_stride * (vienna ? 6 : (int)DL_COUNT);   // Vienna-BL: raw + two decorated copies per direction
+        // Vienna-BL: raw + two decorated copies per direction; 2.x semantics: two more copies each (mismatch1nI, mismatch23I) -- sized
+        // by the context, not by rh_set_duplex_mode, which may change between upload and compute: a 2.x context that stays on the
+        // log-space kernels pays for it with a larger buffer and clear (10 linear tables against the 6 log-space ones, whichever is larger)
+        X.pair_stride = X.tab_stride * (!vienna ? (int)DL_COUNT : c->vienna_sem == kViennaSem20 ? kVdTables20 : kVdTables18);
         const size_t dx_bytes = sizeof(double) * std::max(D.pair_stride, X.pair_stride) * D.np;
         void* before = c->d_dxtab.p;
         if ((rc = ensure(c, c->d_dxtab, dx_bytes, false))) return rc;
@@ -210,7 +213,9 @@ int stage(rh_ctx* c, int ns, const char* const* seqs, const int* lens, bool with
             // pad columns must be zero and a different layout (or the log-space path) leaves arbitrary bytes there
             HIP_TRY(c, hipMemsetAsync(c->d_dxtab.p, 0, dx_bytes, c->s_dx));
             c->dxl_layout = layout;
+            c->dxtab_log = false;
         }
+        c->dx_bytes = dx_bytes;
         if ((rc = ensure(c, c->d_dxbad, sizeof(int) * D.np, false))) return rc;
         if ((rc = ensure(c, c->d_zbar, sizeof(double) * D.np, false))) return rc;
         c->lz_chunks = (n1max + n2max - 1 + 15) / 16;   // kLzRows anti-diagonals per chunk

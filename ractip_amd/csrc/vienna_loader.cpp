@@ -21,6 +21,9 @@ namespace {
 
 constexpr int kInf = 1000000;   // INF of the parameter files
 
+// position of (l1, l2) in the row-major shape list of ViennaDx (l1 + l2 <= 30), as build_vienna_dx fills it
+inline int shape_index(int l1, int l2) { return l1 * 31 - l1 * (l1 - 1) / 2 + l2; }
+
 // every table of either file layout, in the files' 10 cal/mol integers, indexed as ViennaRNA indexes them
 struct ViennaInts {
     int stack[8][8];
@@ -501,7 +504,7 @@ void build_vlin_model(const ViennaDx& V, double s, VLinModel* L)
     for (int u = 0; u <= 30; u++) L->E_hairpin[u] = std::exp(V.hairpin[u]);
     L->E_hairpin[31] = L->E_hairpin[30];
     // generic loops and long bulges from the row-major (l1,l2) shape list
-    auto at = [&](int l1, int l2) { return l1 * 31 - l1 * (l1 - 1) / 2 + l2; };
+    const auto at = shape_index;
     int k = 0;
     for (int t = 0; t <= kMaxSingle; t++)
         for (int l1 = 0; l1 <= t; l1++, k++) {
@@ -518,6 +521,14 @@ void build_vdx_lin(const ViennaDx& V, double s, VDxLin* D)
     for (int k = 0; k < 40; k++) { D->E_d5[k] = std::exp(V.dangle5[k]); D->E_d3[k] = std::exp(V.dangle3[k]); }
     D->E_init = std::exp(V.duplex_init);
     D->s = s; D->lam = std::exp(-s);
+    D->sem20 = V.semantics == kViennaSem20;
+    if (!D->sem20) return;
+    for (int k = 0; k < 200; k++) { D->E_mm1n[k] = std::exp(V.mm1nI[k]); D->E_mm23[k] = std::exp(V.mm23I[k]); }
+    for (int k = 0; k < 8 * 36; k++) D->E_dxE[k] = std::exp(V.dxE[k]);
+    // the length-dependent part of a 1xn / 2x3 loop from the row-major (l1,l2) shape list; (l1,l2) and (l2,l1) score alike
+    const auto at = shape_index;
+    for (int tw = 4; tw <= kMaxSingle; tw++) D->W1N[tw] = std::exp(V.shape[at(1, tw - 1)].score) * std::pow(D->lam, tw + 2);
+    D->W23 = std::exp(V.shape[at(2, 3)].score) * std::pow(D->lam, 7);
 }
 
 }  // namespace rh
@@ -585,7 +596,7 @@ extern "C" int rh_debug_vienna_value(const char* defaults_file, int use_bl, cons
         case 14: if (!in(i, 8) || !in(j, 6) || !in(k, 6)) { rc = -1; break; } *out = V->dxE[i * 36 + j * 6 + k]; break;
         case 17: case 18: {
             if (!in(i, 31) || !in(j, 31) || i + j > 30) { rc = -1; break; }
-            const int idx = i * 31 - i * (i - 1) / 2 + j;
+            const int idx = rh::shape_index(i, j);
             *out = table == 17 ? V->shape[idx].score : (double)V->kind[idx];
             break;
         }

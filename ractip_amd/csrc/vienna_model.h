@@ -2,7 +2,8 @@
 //   kViennaSem18: ViennaRNA-1.8 LoopEnergy()/dangles, what the 1.8 branch of pf_duplex.c:209-433 calls (BL* default);
 //   kViennaSem20: ViennaRNA-2.x E_IntLoop / E_ExtLoop / E_MLstem / E_Hairpin (pf_duplex.c:128-206 is written against them):
 //                 mismatch1nI for 1xn loops, mismatch23I for 2x3 loops, mismatchExt / mismatchM instead of dangle sums where
-//                 both neighbours exist, tri/tetra/hexaloop energies that REPLACE the hairpin energy.  Log-space kernels only.
+//                 both neighbours exist, tri/tetra/hexaloop energies that REPLACE the hairpin energy.  Log-space kernels, except
+//                 pf_duplex on request (rh_set_duplex_mode: duplex_vlin.hip).
 //
 // Energy tables: /root/reference/src/boltzmann_param.c (BL* values, shipped as data in
 // ractip_amd/data/vienna_bl_star.params); energy function: the ViennaRNA-1.8 LoopEnergy() that the 1.8 branch of
@@ -127,6 +128,12 @@ struct VDxLin {
     double E_init;          // exp(DuplexInit)
     double s, lam;
     double pad_;
+    // ---- kViennaSem20 (dxvl_sweep4<true> / dxvl_logz_part<true>; unused under kViennaSem18)
+    double E_mm1n[8 * 25], E_mm23[8 * 25];   // exp(mismatch1nI / mismatch23I[t][a][b])
+    double E_dxE[8 * 36];   // exp(ViennaDx::dxE): the E_ExtLoop term of a duplex end, TerminalAU included
+    double W1N[32];         // 1x(tw-1) and (tw-1)x1 loops by total length tw >= 4: exp(length part) * lam^(tw+2)
+    double W23;             // the same for 2x3 and 3x2 loops (tw = 5)
+    int sem20, pad2_;
 };
 void build_vdx_lin(const ViennaDx& V, double s, VDxLin* out);
 

@@ -18,6 +18,9 @@
 //   RACTIP_AMD_VIENNA_DEFAULTS = ViennaRNA parameter file with the library's built-in tables (e.g. rna_turner2004.par)
 //   RACTIP_AMD_VIENNA_PARAMS   = the -P file (read_parameter_file, src/ractip.cpp:1567)
 //   RACTIP_AMD_NO_BL_PARAM=1   = --no-bl-param            RACTIP_AMD_VIENNA_SEMANTICS = 1 (1.8) | 2 (2.x); default by the files
+//   RACTIP_AMD_DUPLEX_MODE     = -1 (inherit, the default) | 0 (auto) | 1 (log space) | 2 (linear): rh_set_duplex_mode; under the 2.x
+//                                semantics 0 moves the sweeps from the log-space kernels to the scaled linear ones (log-space
+//                                fallback kept).  Anything but one of these four numbers aborts like a failed creation
 // RACTIP_AMD_DUPLEX_MODEL=contrafold selects the CONTRAfold duplex scores instead (what
 // RactIP::contraduplex computes, src/ractip.cpp:225-245).
 #include <cstdio>
@@ -52,6 +55,18 @@ double pf_duplex(const char* s1, const char* s2)
         if (!g_ctx) {  // the original aborts inside ViennaRNA's space() on failure; do the same, loudly
             std::fprintf(stderr, "pf_duplex (ractip_amd): %s\n", rh_last_error(nullptr));
             std::abort();
+        }
+        if (const char* dm = std::getenv("RACTIP_AMD_DUPLEX_MODE")) {
+            char* end = nullptr;
+            const long mode = std::strtol(dm, &end, 10);
+            if (end == dm || *end != '\0' || mode < RH_MODE_INHERIT || mode > RH_MODE_LINEAR) {
+                std::fprintf(stderr, "pf_duplex (ractip_amd): RACTIP_AMD_DUPLEX_MODE='%s' is not one of -1, 0, 1, 2\n", dm);
+                std::abort();
+            }
+            if (rh_set_duplex_mode(g_ctx, (int)mode) != RH_OK) {
+                std::fprintf(stderr, "pf_duplex (ractip_amd): %s\n", rh_last_error(g_ctx));
+                std::abort();
+            }
         }
         std::atexit(release_context);
     }

@@ -48,6 +48,7 @@ rh_ctx* ProbabilityEngine::vienna() const
                 vctxs_[k] = rh_create_vienna(devices_[k], v_defaults_.empty() ? nullptr : v_defaults_.c_str(), v_use_bl_ ? 1 : 0,
                                              v_param_.empty() ? nullptr : v_param_.c_str(), v_semantics_);
             if (!vctxs_[k]) throw std::logic_error(std::string("ractip_amd: ") + rh_last_error(nullptr));
+            rh_set_duplex_mode(vctxs_[k], duplex_mode_);
         }
         vctx_ = vctxs_[0];
     }
@@ -59,6 +60,14 @@ void ProbabilityEngine::set_vienna_parameters(const std::string& defaults_file, 
     v_defaults_ = defaults_file; v_use_bl_ = use_bl_param; v_param_ = param_file; v_semantics_ = semantics;
     for (rh_ctx*& c : vctxs_) { if (c) rh_destroy(c); c = nullptr; }
     vctx_ = nullptr;
+}
+
+void ProbabilityEngine::set_duplex_mode(int mode)
+{
+    if (mode < RH_MODE_INHERIT || mode > RH_MODE_LINEAR) throw std::logic_error("ractip_amd::set_duplex_mode: unknown mode");
+    duplex_mode_ = mode;
+    for (rh_ctx* c : ctxs_) rh_set_duplex_mode(c, mode);
+    for (rh_ctx* c : vctxs_) if (c) rh_set_duplex_mode(c, mode);
 }
 
 std::pair<int, int> ProbabilityEngine::shard_bounds(int num, int k, int parts)

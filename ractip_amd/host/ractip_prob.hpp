@@ -81,6 +81,10 @@ public:
     // (a v2.0 file selects the 2.x loop energies of the HAVE_VIENNA20 build), 1 = ViennaRNA-1.8, 2 = ViennaRNA-2.x (include/
     // ractip_hot.h, rh_create_vienna).  Takes effect for the Vienna-model members; existing Vienna contexts are rebuilt.
     void set_vienna_parameters(const std::string& defaults_file, bool use_bl_param, const std::string& param_file, int semantics = 0);
+    // arithmetic path of the pf_duplex sweeps alone (rh_set_duplex_mode: RH_MODE_INHERIT, AUTO, LOG, LINEAR), on every context of
+    // this engine, those created later included.  With the 2.x loop energies, RH_MODE_AUTO moves the --duplex branch
+    // (rnaduplex, solve_probabilities_default(..., duplex = true)) from the log-space kernels to the scaled linear ones
+    void set_duplex_mode(int mode);
 
     rh_ctx* raw() const { return ctx_; }
     int device_count() const { return (int)devices_.size(); }
@@ -104,6 +108,7 @@ private:
     std::string v_defaults_, v_param_;     // set_vienna_parameters
     bool v_use_bl_ = true;
     int v_semantics_ = 0;
+    int duplex_mode_ = -1;                 // RH_MODE_INHERIT
 };
 
 // offset[i] = i*(2(L+1)-i-1)/2, size L+1  (src/ractip.cpp:254-257; InferenceEngine.ipp:316)

@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("RACTIP_HOT_LIB") or os.path.join(PKG, "libractip_hot.
 
 RH_MODEL_CONTRAFOLD = 0
 RH_MODEL_VIENNA_BL = 1
+RH_MODE_INHERIT, RH_MODE_AUTO, RH_MODE_LOG, RH_MODE_LINEAR = -1, 0, 1, 2
 
 EXPORTS = [
     "rh_create", "rh_destroy", "rh_last_error", "rh_set_mode", "rh_last_path", "rh_bpp", "rh_unpaired", "rh_fold", "rh_duplex",
@@ -20,6 +21,7 @@ EXPORTS = [
     "rh_batch_timings", "rh_batch_device_views", "rh_batch_logz", "rh_batch_candidates_all", "rh_batch_layout",
     "rh_batch_results_all", "rh_set_max_w", "rh_get_max_w", "rh_set_overlap", "rh_batch_kernels", "rh_set_hybrid", "rh_last_hybrid_path", "rh_fold_constrained", "rh_cofold_constrained",
     "rh_host_alloc", "rh_host_free", "rh_batch_fallbacks", "rh_create_vienna", "rh_vienna_semantics", "rh_set_scale_memory", "rh_set_kernel_timing", "rh_kernel_times",
+    "rh_set_duplex_mode", "rh_get_duplex_mode",
     "rh_debug_vienna_cell", "rh_debug_vienna_value",   # loader inspection (host only; used by the CPU tests of the loader)
 ]
 
@@ -56,6 +58,10 @@ def load_library():
     L.rh_last_error.argtypes = [vp]
     L.rh_set_mode.argtypes = [vp, ci]
     L.rh_set_mode.restype = ci
+    L.rh_set_duplex_mode.argtypes = [vp, ci]
+    L.rh_set_duplex_mode.restype = ci
+    L.rh_get_duplex_mode.argtypes = [vp]
+    L.rh_get_duplex_mode.restype = ci
     L.rh_last_path.argtypes = [vp]
     L.rh_set_overlap.argtypes = [vp, ci]
     L.rh_set_scale_memory.argtypes = [vp, ci]
@@ -161,6 +167,14 @@ class Context:
     def set_mode(self, mode):
         """0 = auto (linear, log-space fallback), 1 = log-space, 2 = linear only."""
         self._check(self.L.rh_set_mode(self.h, mode))
+
+    def set_duplex_mode(self, mode):
+        """Path of the pf_duplex sweeps alone: RH_MODE_INHERIT (-1, default: as set_mode says), 0 = auto, 1 = log-space, 2 = linear.
+        Under the ViennaRNA-2.x semantics 0 / 2 run pf_duplex on the scaled linear kernels."""
+        self._check(self.L.rh_set_duplex_mode(self.h, mode))
+
+    def get_duplex_mode(self):
+        return self.L.rh_get_duplex_mode(self.h)
 
     def last_path(self):
         return self.L.rh_last_path(self.h)
