@@ -164,6 +164,20 @@ int rh_cofold_constrained(rh_ctx* ctx, const char* s1, int n1, const char* s2, i
 int rh_batch_upload(rh_ctx* ctx, int npairs,
                     const char* const* s1, const int* n1,
                     const char* const* s2, const int* n2);
+/* rh_batch_upload under structure constraints (RactIP's -c / --use-constraint, src/ractip.cpp:271-291, 330-350, 405-447), one
+ * per problem of the batch.  RH_MODEL_VIENNA_BL only (RH_ERR_UNSUPPORTED otherwise).
+ *   cons1[p], cons2[p]: constraints of the two single-molecule folds of pair p (bp and up), in the fold_constrained alphabet of
+ *     rh_bpp -- what RactIP::rnafold hands to pf_fold;
+ *   co_cons[p]: n1+n2 characters over s1+s2 as in rh_cofold_constrained, for the two-molecule ensemble that produces hp under
+ *     rh_set_hybrid(RH_HYBRID_COFOLD).  Under RH_HYBRID_DUPLEX it is checked and otherwise unused: the reference's --duplex branch
+ *     (src/ractip.cpp:390-398) takes no constraint either.
+ * Any of the three arrays, and any entry, may be NULL (no constraint); shorter strings are padded with '.'.  With no constraint at
+ * all this is rh_batch_upload.  An unbalanced string or a forced pair of non-complementary letters is rejected (RH_ERR_ARG, the
+ * message names the sequence 2p / 2p+1 or the pair p) before anything is staged: the previous batch stays in place.  The masks are
+ * built on the device; everything downstream (results, candidates, log Z, fallbacks) works as on any batch. */
+int rh_batch_upload_constrained(rh_ctx* ctx, int npairs,
+                                const char* const* s1, const int* n1, const char* const* s2, const int* n2,
+                                const char* const* cons1, const char* const* cons2, const char* const* co_cons);
 int rh_batch_compute(rh_ctx* ctx);
 int rh_batch_results(rh_ctx* ctx, int p,
                      double* bp1_tri, double* bp2_tri, double* up1, double* up2,
@@ -267,6 +281,11 @@ int rh_batch_device_views(rh_ctx* ctx, const double** bp, size_t* tri_stride,
 int rh_debug_vienna_cell(const char* param_file, int table, int i, int j, int k, int l, int m, int n, double* energy);
 int rh_debug_vienna_value(const char* defaults_file, int use_bl_param, const char* bl_path, const char* param_file, int semantics,
                           int table, int i, int j, int k, int l, double* out);
+
+/* The allowed-pair mask of the last upload as the kernels read it: which = 0, sequence k (2p = s1 of pair p), or which = 1, the
+ * concatenation s1+s2 of pair k.  *ld receives the row pitch; out (or NULL, to ask for ld first) receives ld*ld bytes, byte
+ * [a*ld + b] != 0 iff letters a < b (1-based) may pair.  Returns 0, 1 if that batch has no mask, or an error. */
+int rh_debug_batch_allow_mask(rh_ctx* ctx, int which, int k, unsigned char* out, int* ld);
 
 /* ---- source-compatible pf_duplex surface (src/pf_duplex.h:25-28) ----
  * double pf_duplex(const char*, const char*); extern double** pr_duplex; void free_pf_duplex();

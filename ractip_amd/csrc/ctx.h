@@ -292,6 +292,7 @@ struct Ctx {   // (the fields of rh_ctx, below)
     DevBuf d_gaps;
     DevBuf d_allow;   // structure-constraint masks [ns][ld*ld] bytes (Vienna-BL, optional)
     DevBuf d_coallow;   // the same for the s1+s2 batch
+    DevBuf d_cons;    // per-letter values of the constraint strings the masks are built from: P, enc [count][lds] ints, ch [count][lds] bytes
     DevBuf d_hplen;   // lam^d x hairpin length weight, d = 0..nmax (linear Vienna path)
     std::vector<double> h_hplen;
     // two-molecule (co_pf_fold) form of the hybridization matrix: one concatenated sequence s1+s2 per pair

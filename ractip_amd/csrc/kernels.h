@@ -75,6 +75,11 @@ template <int W, int BS, bool CUT, int MODE> __global__ void vlin_inside_diag(Mc
 template <int W, int BS, bool CUT, int MODE> __global__ void vlin_outside_diag(McBatch B, const VLinModel* __restrict__ L, int d, int pin, int* __restrict__ bad);
 __global__ void vlin_finish(McBatch B, const VLinModel* __restrict__ L, double* __restrict__ logz, int* __restrict__ bad);
 __global__ void mcv_extract_hp(McBatch B, double* __restrict__ hp, size_t hp_stride, int ldd, double* __restrict__ logz, double lin_s, int* __restrict__ bad);
+// allow_mask.hip: the structure-constraint masks [ns][ld][ld] from the per-letter values of constraint_prepass.h; grid (ns, tiles of
+// kAllowRows rows), kAllowThreads threads, 9 * lds bytes of dynamic LDS when in_lds
+constexpr int kAllowRows = 64, kAllowThreads = 256;
+__global__ void allow_mask_build(uint8_t* __restrict__ allow, const int* __restrict__ n_of, const uint8_t* __restrict__ g_ch,
+                                 const int* __restrict__ g_P, const int* __restrict__ g_enc, int ld, int lds, int in_lds);
 }  // namespace rh
 
 // defined by the host units (global namespace)

@@ -339,15 +339,43 @@ int rh_cofold_constrained(rh_ctx* c, const char* s1, int n1, const char* s2, int
 
 int rh_batch_upload(rh_ctx* c, int npairs, const char* const* s1, const int* n1, const char* const* s2, const int* n2)
 {
+    return rh_batch_upload_constrained(c, npairs, s1, n1, s2, n2, nullptr, nullptr, nullptr);
+}
+
+int rh_batch_upload_constrained(rh_ctx* c, int npairs, const char* const* s1, const int* n1, const char* const* s2, const int* n2,
+                                const char* const* cons1, const char* const* cons2, const char* const* co_cons)
+{
     if (!c) return RH_ERR_ARG;
     if (npairs < 1 || !s1 || !s2 || !n1 || !n2) return fail(c, RH_ERR_ARG, "bad batch");
-    std::vector<const char*> seqs(2 * (size_t)npairs);
+    std::vector<const char*> seqs(2 * (size_t)npairs), cons(2 * (size_t)npairs, nullptr);
     std::vector<int> lens(2 * (size_t)npairs);
+    bool any = false, any_co = false;   // an array whose entries are all NULL is no constraint: the batch of rh_batch_upload
     for (int p = 0; p < npairs; p++) {
         seqs[2 * p] = s1[p]; seqs[2 * p + 1] = s2[p];
         lens[2 * p] = n1[p]; lens[2 * p + 1] = n2[p];
+        if (cons1) cons[2 * p] = cons1[p];
+        if (cons2) cons[2 * p + 1] = cons2[p];
+        any = any || cons[2 * p] || cons[2 * p + 1];
+        any_co = any_co || (co_cons && co_cons[p]);
     }
-    return stage(c, 2 * npairs, seqs.data(), lens.data(), true, true);
+    if ((any || any_co) && c->model != RH_MODEL_VIENNA_BL)
+        return fail(c, RH_ERR_UNSUPPORTED, "structure constraints apply to the Vienna-BL model only (RactIP::contrafold takes none)");
+    return stage(c, 2 * npairs, seqs.data(), lens.data(), true, true, any ? cons.data() : nullptr, any_co ? co_cons : nullptr);
+}
+
+int rh_debug_batch_allow_mask(rh_ctx* c, int which, int k, unsigned char* out, int* ld)
+{
+    if (!c) return RH_ERR_ARG;
+    if (which != 0 && which != 1) return fail(c, RH_ERR_ARG, "rh_debug_batch_allow_mask: which = %d", which);
+    const bool co = which == 1;
+    if (c->ns == 0 || (co ? !c->has_dx : !c->has_mc)) return fail(c, RH_ERR_ARG, "no batch uploaded");
+    const bool co_staged = c->model == RH_MODEL_VIENNA_BL && c->hybrid == RH_HYBRID_COFOLD;   // (otherwise c->co is not of this batch)
+    if (k < 0 || k >= (co ? c->np : c->ns)) return fail(c, RH_ERR_ARG, "%s %d out of range", co ? "pair" : "sequence", k);
+    const McBatch* B = co ? (co_staged ? &c->co : nullptr) : &c->mc;
+    if (!B || !B->allow) return 1;
+    if (ld) *ld = B->ld;
+    if (out) HIP_TRY(c, hipMemcpy(out, B->allow + (size_t)k * B->ld * B->ld, (size_t)B->ld * B->ld, hipMemcpyDeviceToHost));
+    return RH_OK;
 }
 
 int rh_batch_compute(rh_ctx* c)

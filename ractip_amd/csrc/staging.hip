@@ -1,4 +1,4 @@
-// staging.hip -- sequence encoding, structure-constraint masks and the upload of a batch: sizes and allocates
+// staging.hip -- sequence encoding, the upload of a batch and of its structure-constraint masks (allow_mask.hip): sizes and allocates
 // every table the batch needs (buffers are kept and reused across batches of equal or smaller shape).
 #include <hip/hip_runtime.h>
 
@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 
+#include "constraint_prepass.h"
 #include "ctx.h"
 #include "kernels.h"
 
@@ -24,56 +25,39 @@ uint8_t nuc_code(char ch)
     }
 }
 
-uint8_t vienna_code(char ch)
-{  // ViennaRNA encode_char with energy_set 0: A,C,G,U -> 1..4 (T reads as U), anything else 0
-    switch (ch) {
-        case 'A': case 'a': return 1;
-        case 'C': case 'c': return 2;
-        case 'G': case 'g': return 3;
-        case 'U': case 'u': case 'T': case 't': return 4;
-        default: return 0;
-    }
-}
+// The per-letter values of `count` constraint strings (constraint_prepass.h), [count][lds] each, as allow_mask_build reads them
+struct ConsPass {
+    std::vector<uint8_t> ch;
+    std::vector<int> P, enc;
+    ConsPass(int count, int lds) : ch((size_t)count * lds, '.'), P((size_t)count * lds, 0), enc((size_t)count * lds, 0) {}
+};
 
-// Allowed-pair mask of pf_fold under fold_constrained (ViennaRNA 1.8 make_ptypes), M[a*ld + b], 1 <= a < b <= n:
-//   'x' the letter never pairs; '<' it pairs only with a later letter, '>' only with an earlier one; a matched '(' ')'
-//   is kept and every pair inconsistent with it (crossing it, or sharing a letter) is removed; '|' and '.' do not
-//   restrict the partition function.  Returns false for unbalanced brackets or a forced pair of non-complementary letters.
-bool build_allow_mask(const char* seq, int n, const char* cons, int ld, uint8_t* M, std::string* why)
+// The masks [count][ld][ld] of one batch, built on the device from the host pass: three small asynchronous copies and one launch on
+// s_mc, in front of the sweeps.  d_n: the lengths on the device.  The kernel writes every byte of the image.
+static int build_allow_masks(rh_ctx* c, const ConsPass& H, int count, int ld, int lds, const int* d_n, DevBuf& d_mask)
 {
-    for (int a = 0; a < ld; a++)
-        for (int b = 0; b < ld; b++) M[(size_t)a * ld + b] = (a >= 1 && a < b && b <= n) ? 1 : 0;
-    const size_t clen = std::strlen(cons);
-    std::vector<int> stack;
-    for (int j = 1; j <= n; j++) {
-        const char ch = (size_t)(j - 1) < clen ? cons[j - 1] : '.';
-        if (ch == 'x') {
-            for (int l = 1; l <= n; l++) { M[(size_t)l * ld + j] = 0; M[(size_t)j * ld + l] = 0; }
-        } else if (ch == '(' || ch == '<') {
-            if (ch == '(') stack.push_back(j);
-            for (int l = 1; l < j; l++) M[(size_t)l * ld + j] = 0;
-        } else if (ch == ')' || ch == '>') {
-            if (ch == ')') {
-                if (stack.empty()) { *why = "unbalanced ')' in the structure constraint"; return false; }
-                const int i = stack.back();
-                stack.pop_back();
-                const uint8_t keep = M[(size_t)i * ld + j];
-                for (int k = i; k <= j; k++) for (int l = j; l <= n; l++) M[(size_t)k * ld + l] = 0;
-                for (int k = 1; k <= i; k++) for (int l = i; l <= j; l++) M[(size_t)k * ld + l] = 0;
-                M[(size_t)i * ld + j] = keep;
-                const uint8_t x = vienna_code(seq[i - 1]), y = vienna_code(seq[j - 1]);
-                static const int T[5][5] = {{0, 0, 0, 0, 0}, {0, 0, 0, 0, 5}, {0, 0, 0, 1, 0}, {0, 0, 2, 0, 3}, {0, 6, 0, 4, 0}};
-                if (keep && !T[x][y]) { *why = "a forced pair of non-complementary letters (pair type 7) is not supported"; return false; }
-            }
-            for (int l = j + 1; l <= n; l++) M[(size_t)j * ld + l] = 0;
-        }
-    }
-    if (!stack.empty()) { *why = "unbalanced '(' in the structure constraint"; return false; }
-    return true;
+    int rc;
+    const size_t cells = (size_t)count * lds;
+    if ((rc = ensure(c, d_mask, (size_t)count * ld * ld, false))) return rc;
+    if ((rc = ensure(c, c->d_cons, cells * (2 * sizeof(int) + 1), false))) return rc;
+    int* d_P = c->d_cons.as<int>();
+    int* d_enc = d_P + cells;
+    uint8_t* d_ch = reinterpret_cast<uint8_t*>(d_enc + cells);
+    HIP_TRY(c, hipMemcpyAsync(d_P, H.P.data(), cells * sizeof(int), hipMemcpyHostToDevice, c->s_mc));
+    HIP_TRY(c, hipMemcpyAsync(d_enc, H.enc.data(), cells * sizeof(int), hipMemcpyHostToDevice, c->s_mc));
+    HIP_TRY(c, hipMemcpyAsync(d_ch, H.ch.data(), cells, hipMemcpyHostToDevice, c->s_mc));
+    const size_t lds_bytes = (size_t)lds * (2 * sizeof(int) + 1);
+    const int in_lds = lds_bytes <= 64 * 1024;   // longer sequences: the kernel reads the three arrays from global memory
+    hipLaunchKernelGGL(allow_mask_build, dim3(count, (ld + kAllowRows - 1) / kAllowRows), dim3(kAllowThreads), in_lds ? lds_bytes : 0, c->s_mc,
+                       d_mask.as<uint8_t>(), d_n, d_ch, d_P, d_enc, ld, lds, in_lds);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->s_mc));   // (the host arrays of the copies die with the caller's scope)
+    return RH_OK;
 }
 
-// Stage `ns` sequences; pairs are (2p, 2p+1) when with_dx.  Allocates what is needed.  cons: per-sequence structure
-// constraints (Vienna-BL, single-molecule batch only) or nullptr.
+// Stage `ns` sequences; pairs are (2p, 2p+1) when with_dx.  Allocates what is needed.  cons: per-sequence structure constraints of
+// the single-molecule folds, co_cons: per-pair constraints over s1+s2 of the two-molecule ensemble (Vienna-BL; either, or any entry,
+// may be nullptr).  Every constraint is checked before the context changes: a rejected upload leaves the previous batch in place.
 int stage(rh_ctx* c, int ns, const char* const* seqs, const int* lens, bool with_mc, bool with_dx, const char* const* cons, const char* const* co_cons)
 {
     HIP_TRY(c, hipSetDevice(c->device));
@@ -86,12 +70,26 @@ int stage(rh_ctx* c, int ns, const char* const* seqs, const int* lens, bool with
         if (with_dx) { if (k & 1) n2max = std::max(n2max, lens[k]); else n1max = std::max(n1max, lens[k]); }
     }
     if (with_dx && (ns & 1)) return fail(c, RH_ERR_ARG, "duplex batch needs an even number of sequences");
+    const int lds = (nmax + 3 + 15) & ~15;  // codes 0..n+2 readable
+    const int co_lds = (n1max + n2max + 3 + 15) & ~15;
+    const bool vienna = c->model == RH_MODEL_VIENNA_BL;
+    if (!with_mc) cons = nullptr;
+    if (!with_dx || !vienna) co_cons = nullptr;
+    ConsPass H(cons ? ns : 0, lds), CH(co_cons ? ns / 2 : 0, co_lds);
+    std::string why;
+    for (int k = 0; cons && k < ns; k++)
+        if (!constraint_prepass(seqs[k], lens[k], cons[k], &H.ch[(size_t)k * lds], &H.P[(size_t)k * lds], &H.enc[(size_t)k * lds], &why))
+            return fail(c, RH_ERR_ARG, "sequence %d: %s", k, why.c_str());
+    for (int p = 0; co_cons && p < ns / 2; p++) {   // over the concatenation s1+s2 (one string of n1+n2 characters per pair)
+        const std::string joint = std::string(seqs[2 * p], lens[2 * p]) + std::string(seqs[2 * p + 1], lens[2 * p + 1]);
+        if (!constraint_prepass(joint.c_str(), (int)joint.size(), co_cons[p], &CH.ch[(size_t)p * co_lds], &CH.P[(size_t)p * co_lds],
+                                &CH.enc[(size_t)p * co_lds], &why))
+            return fail(c, RH_ERR_ARG, "pair %d: %s", p, why.c_str());
+    }
     c->ns = ns; c->np = with_dx ? ns / 2 : 0;
     c->has_mc = with_mc; c->has_dx = with_dx; c->computed = false;
     c->n.assign(lens, lens + ns);
 
-    const int lds = (nmax + 3 + 15) & ~15;  // codes 0..n+2 readable
-    const bool vienna = c->model == RH_MODEL_VIENNA_BL;
     std::vector<uint8_t> codes((size_t)ns * lds, vienna ? 0 : 4);   // sentinel = the model's "no nucleotide" code
     for (int k = 0; k < ns; k++)
         for (int i = 0; i < lens[k]; i++) codes[(size_t)k * lds + 1 + i] = vienna ? vienna_code(seqs[k][i]) : nuc_code(seqs[k][i]);
@@ -166,13 +164,7 @@ int stage(rh_ctx* c, int ns, const char* const* seqs, const int* lens, bool with
         HIP_TRY(c, hipMemsetAsync(c->d_bp.p, 0, bp_bytes, c->s_mc));
         B.allow = nullptr;
         if (cons) {
-            std::vector<uint8_t> M((size_t)ns * B.ld * B.ld);
-            std::string why;
-            for (int k = 0; k < ns; k++)
-                if (!build_allow_mask(seqs[k], lens[k], cons[k] ? cons[k] : "", B.ld, M.data() + (size_t)k * B.ld * B.ld, &why))
-                    return fail(c, RH_ERR_ARG, "sequence %d: %s", k, why.c_str());
-            if ((rc = ensure(c, c->d_allow, M.size(), false))) return rc;
-            HIP_TRY(c, hipMemcpy(c->d_allow.p, M.data(), M.size(), hipMemcpyHostToDevice));
+            if ((rc = build_allow_masks(c, H, ns, B.ld, lds, c->d_n.as<const int>(), c->d_allow))) return rc;
             B.allow = c->d_allow.as<const uint8_t>();
         }
         if (c->tables_dirty) {
@@ -191,6 +183,7 @@ int stage(rh_ctx* c, int ns, const char* const* seqs, const int* lens, bool with
     }
     if (with_dx) {
         DxBatch& D = c->dx;
+        c->co.allow = nullptr;   // (under RH_HYBRID_DUPLEX nothing below rebuilds c->co: a joint mask of an earlier batch must not be seen)
         D.np = ns / 2; D.n1max = n1max; D.n2max = n2max; D.lds = lds;
         D.ldd = (n2max + 2 + 1) & ~1;
         D.tab_stride = (size_t)(n1max + 2) * D.ldd;
@@ -278,16 +271,8 @@ int stage(rh_ctx* c, int ns, const char* const* seqs, const int* lens, bool with
             const size_t fs = (size_t)C.ld * np;
             C.f5i = f; C.f5o = f + fs; C.xp = f + 2 * fs; C.xs = f + 3 * fs; C.xpo = f + 4 * fs; C.xso = f + 5 * fs;
             C.bp = c->d_cobp.as<double>(); C.up = nullptr;
-            if (co_cons) {   // constraints over the concatenation s1+s2 (one string of length n1+n2 per pair)
-                std::vector<uint8_t> M((size_t)np * C.ld * C.ld);
-                std::string why;
-                for (int p = 0; p < np; p++) {
-                    const std::string joint = std::string(seqs[2 * p], lens[2 * p]) + std::string(seqs[2 * p + 1], lens[2 * p + 1]);
-                    if (!build_allow_mask(joint.c_str(), (int)joint.size(), co_cons[p] ? co_cons[p] : "", C.ld, M.data() + (size_t)p * C.ld * C.ld, &why))
-                        return fail(c, RH_ERR_ARG, "pair %d: %s", p, why.c_str());
-                }
-                if ((rc = ensure(c, c->d_coallow, M.size(), false))) return rc;
-                HIP_TRY(c, hipMemcpy(c->d_coallow.p, M.data(), M.size(), hipMemcpyHostToDevice));
+            if (co_cons) {
+                if ((rc = build_allow_masks(c, CH, np, C.ld, co_lds, C.n, c->d_coallow))) return rc;
                 C.allow = c->d_coallow.as<const uint8_t>();
             }
         }

@@ -1,6 +1,8 @@
 // prob_cli.cpp -- drives the C++ adapters exactly as RactIP::solve does
 // (/root/reference/src/ractip.cpp:536-548) and prints the float matrices it would
 // hand to the ILP, one value per line, for tests/test_gpu_host_adapter.py.
+//   prob_cli constraint STR L | joint STR1 N1 STR2 N2      (the structure-line translations; no GPU needed)
+//   prob_cli solve_default_c MAX_W S1 STR1 S2 STR2 [...] | solve_default_duplex_c ...   (use_constraint_: structure lines per pair)
 //   [RACTIP_DEVICES=0,1,..] prob_cli contrafold SEQ | rnafold SEQ MAX_W | contraduplex S1 S2 TH | rnaduplex S1 S2 | cofold S1 S2 | pfduplex S1 S2 | solve S1 S2 [S1 S2 ...]
 #include <cstdio>
 #include <cstdlib>
@@ -42,6 +44,14 @@ int main(int argc, char** argv)
         if (mode == "bounds") {   // bounds NUM PARTS: the contiguous blocks of the in-process shard (no GPU needed)
             const int num = std::atoi(argv[2]), parts = argc > 3 ? std::atoi(argv[3]) : 1;
             for (int k = 0; k < parts; k++) { const auto b = ProbabilityEngine::shard_bounds(num, k, parts); std::printf("%d %d\n", b.first, b.second); }
+            return 0;
+        }
+        if (mode == "constraint" && argc == 4) {
+            std::printf("%s\n", fold_constraint(argv[2], (unsigned)std::atoi(argv[3])).c_str());
+            return 0;
+        }
+        if (mode == "joint" && argc == 6) {
+            std::printf("%s\n", joint_constraint(argv[2], (unsigned)std::atoi(argv[3]), argv[4], (unsigned)std::atoi(argv[5])).c_str());
             return 0;
         }
         if (mode == "pfduplex") {
@@ -92,11 +102,15 @@ int main(int argc, char** argv)
             dump_hp(hp);
         } else if (mode == "rnaduplex") {
             VVF hp; en.rnaduplex(argv[2], argv[3], hp); dump_hp(hp);
-        } else if (mode == "solve_default" || mode == "solve_default_duplex") {   // solve_default[_duplex] MAX_W S1 S2 [S1 S2 ...]
+        } else if (mode == "solve_default" || mode == "solve_default_duplex" || mode == "solve_default_c" || mode == "solve_default_duplex_c") {
+            // solve_default[_duplex] MAX_W S1 S2 [S1 S2 ...]; solve_default[_duplex]_c MAX_W S1 STR1 S2 STR2 [...]
             const unsigned mw = (unsigned)std::atoi(argv[2]);
-            std::vector<std::pair<std::string, std::string>> pairs;
-            for (int k = 3; k + 1 < argc; k += 2) pairs.emplace_back(argv[k], argv[k + 1]);
-            for (const PairProbabilities& r : en.solve_probabilities_default(pairs, mw, mode == "solve_default_duplex")) {
+            const bool cons = mode.back() == 'c', duplex = mode.find("duplex") != std::string::npos;
+            std::vector<std::pair<std::string, std::string>> pairs, structures;
+            if (cons) for (int k = 3; k + 3 < argc; k += 4) { pairs.emplace_back(argv[k], argv[k + 2]); structures.emplace_back(argv[k + 1], argv[k + 3]); }
+            else for (int k = 3; k + 1 < argc; k += 2) pairs.emplace_back(argv[k], argv[k + 1]);
+            for (const PairProbabilities& r : cons ? en.solve_probabilities_default(pairs, structures, mw, duplex)
+                                                   : en.solve_probabilities_default(pairs, mw, duplex)) {
                 std::printf("pair %.17g %.17g %.17g\n", r.logZ1, r.logZ2, r.logZd);
                 std::printf("bp %zu\n", r.bp1.size());
                 for (float v : r.bp1) std::printf("%.9g\n", v);

@@ -82,6 +82,31 @@ void ProbabilityEngine::raise(const char* where) const
     throw std::logic_error(std::string("ractip_amd::") + where + ": " + rh_last_error(ctx_));
 }
 
+std::string fold_constraint(const std::string& str, uint L)
+{
+    std::string c(L, '.');   // src/ractip.cpp:275-287
+    for (uint i = 0; i != str.size() && i != L; ++i) c[i] = (str[i] == '[' || str[i] == ']' || str[i] == 'e') ? 'x' : str[i];
+    return c;
+}
+
+std::string joint_constraint(const std::string& str1, uint n1, const std::string& str2, uint n2)
+{
+    std::string c(n1 + n2, '.');   // src/ractip.cpp:409-440
+    for (uint i = 0; i != str1.size() && i != n1; ++i)
+        switch (str1[i]) {
+            case '[': c[i] = '('; break;
+            case '(': case ')': case 'l': case 'x': c[i] = 'x'; break;
+            default: break;
+        }
+    for (uint i = 0; i != str2.size() && i != n2; ++i)
+        switch (str2[i]) {
+            case ']': c[n1 + i] = ')'; break;
+            case '(': case ')': case 'l': case 'x': c[n1 + i] = 'x'; break;
+            default: break;
+        }
+    return c;
+}
+
 namespace {
 // narrow to float exactly where the reference does (VF containers, src/ractip.cpp:82-83)
 void narrow_bp(const std::vector<double>& d, VF& bp)
@@ -134,8 +159,7 @@ void ProbabilityEngine::rnafold(const std::string& seq, VF& bp, VI& offset, VVF&
 void ProbabilityEngine::rnafold(const std::string& seq, const std::string& str, VF& bp, VI& offset, VVF& up, uint max_w) const
 {
     const uint L = seq.size();
-    std::string c(L, '.');   // src/ractip.cpp:275-287
-    for (uint i = 0; i != str.size() && i != L; ++i) c[i] = (str[i] == '[' || str[i] == ']' || str[i] == 'e') ? 'x' : str[i];
+    const std::string c = fold_constraint(str, L);
     std::vector<double> dbp((size_t)(L + 1) * (L + 2) / 2, 0.0), dup((size_t)L * max_w, 0.0);
     offset = make_offsets(L);
     rh_ctx* v = vienna();
@@ -173,19 +197,7 @@ void ProbabilityEngine::rnaduplex_cofold(const std::string& seq1, const std::str
     const uint n1 = seq1.size(), n2 = seq2.size();
     hp.assign(n1 + 1, VF(n2 + 1, 0.0f));
     if (n1 == 0 || n2 == 0) return;
-    std::string c(n1 + n2, '.');   // src/ractip.cpp:409-440
-    for (uint i = 0; i != str1.size() && i != n1; ++i)
-        switch (str1[i]) {
-            case '[': c[i] = '('; break;
-            case '(': case ')': case 'l': case 'x': c[i] = 'x'; break;
-            default: break;
-        }
-    for (uint i = 0; i != str2.size() && i != n2; ++i)
-        switch (str2[i]) {
-            case ']': c[n1 + i] = ')'; break;
-            case '(': case ')': case 'l': case 'x': c[n1 + i] = 'x'; break;
-            default: break;
-        }
+    const std::string c = joint_constraint(str1, n1, str2, n2);
     rh_ctx* v = vienna();
     std::vector<double> d((size_t)(n1 + 1) * (n2 + 1));
     if (rh_cofold_constrained(v, seq1.c_str(), (int)n1, seq2.c_str(), (int)n2, c.c_str(), d.data(), nullptr) != RH_OK)
@@ -244,14 +256,32 @@ std::vector<PairProbabilities> ProbabilityEngine::solve_probabilities_default(
     return out;
 }
 
+std::vector<PairProbabilities> ProbabilityEngine::solve_probabilities_default(
+    const std::vector<std::pair<std::string, std::string>>& pairs, const std::vector<std::pair<std::string, std::string>>& structures,
+    uint max_w, bool duplex) const
+{
+    if (structures.size() != pairs.size()) throw std::logic_error("ractip_amd::solve_probabilities_default: one (str1, str2) per pair");
+    vienna();
+    for (rh_ctx* v : vctxs_)
+        if (rh_set_max_w(v, (int)std::max(1u, max_w)) != RH_OK || rh_set_hybrid(v, duplex ? RH_HYBRID_DUPLEX : RH_HYBRID_COFOLD) != RH_OK)
+            throw std::logic_error(std::string("ractip_amd::solve_probabilities_default: ") + rh_last_error(v));
+    std::vector<PairProbabilities> out;
+    std::string error;
+    try { out = batch(vctx_, pairs, std::max(1u, max_w), !duplex, &structures); } catch (const std::logic_error& e) { error = e.what(); }
+    for (rh_ctx* v : vctxs_) rh_set_hybrid(v, RH_HYBRID_DUPLEX);
+    if (!error.empty()) throw std::logic_error(error);
+    return out;
+}
+
 // contiguous blocks of the pairs, one per listed device, each on its own context and host thread; results in iteration order
 std::vector<PairProbabilities> ProbabilityEngine::batch(rh_ctx* ctx, const std::vector<std::pair<std::string, std::string>>& pairs,
-                                                        uint max_w, bool threshold_hp) const
+                                                        uint max_w, bool threshold_hp,
+                                                        const std::vector<std::pair<std::string, std::string>>* structures) const
 {
     const int np = (int)pairs.size();
     const std::vector<rh_ctx*>& all = (ctx == ctx_) ? ctxs_ : vctxs_;
     const int parts = std::min<int>((int)all.size(), std::max(1, np));
-    if (parts <= 1) return batch_one(ctx, pairs, 0, np, max_w, threshold_hp);
+    if (parts <= 1) return batch_one(ctx, pairs, 0, np, max_w, threshold_hp, structures);
     std::vector<std::vector<PairProbabilities>> part(parts);
     std::vector<std::string> errors(parts);
     std::vector<std::thread> workers;
@@ -259,7 +289,7 @@ std::vector<PairProbabilities> ProbabilityEngine::batch(rh_ctx* ctx, const std::
         workers.emplace_back([&, k] {
             try {
                 const auto b = shard_bounds(np, k, parts);
-                part[k] = batch_one(all[k], pairs, b.first, b.second, max_w, threshold_hp);
+                part[k] = batch_one(all[k], pairs, b.first, b.second, max_w, threshold_hp, structures);
             } catch (const std::exception& e) { errors[k] = e.what(); }
         });
     for (std::thread& t : workers) t.join();
@@ -273,7 +303,8 @@ std::vector<PairProbabilities> ProbabilityEngine::batch(rh_ctx* ctx, const std::
 }
 
 std::vector<PairProbabilities> ProbabilityEngine::batch_one(rh_ctx* ctx, const std::vector<std::pair<std::string, std::string>>& all_pairs,
-                                                            int lo, int hi, uint max_w, bool threshold_hp) const
+                                                            int lo, int hi, uint max_w, bool threshold_hp,
+                                                            const std::vector<std::pair<std::string, std::string>>* structures) const
 {
     const std::vector<std::pair<std::string, std::string>> pairs(all_pairs.begin() + lo, all_pairs.begin() + hi);
     const int np = (int)pairs.size();
@@ -286,7 +317,18 @@ std::vector<PairProbabilities> ProbabilityEngine::batch_one(rh_ctx* ctx, const s
         na[p] = (int)pairs[p].first.size(); nb[p] = (int)pairs[p].second.size();
     }
     auto raise_ctx = [&](const char* where) { throw std::logic_error(std::string("ractip_amd::") + where + ": " + rh_last_error(ctx)); };
-    if (rh_batch_upload(ctx, np, a.data(), na.data(), b.data(), nb.data()) != RH_OK) raise_ctx("solve_probabilities");
+    if (structures) {   // this shard's structure lines, translated as the single-problem members translate them
+        std::vector<std::string> c1(np), c2(np), cj(np);
+        std::vector<const char*> p1(np), p2(np), pj(np);
+        for (int p = 0; p < np; ++p) {
+            const std::pair<std::string, std::string>& st = (*structures)[lo + p];
+            c1[p] = fold_constraint(st.first, na[p]); c2[p] = fold_constraint(st.second, nb[p]);
+            cj[p] = joint_constraint(st.first, na[p], st.second, nb[p]);
+            p1[p] = c1[p].c_str(); p2[p] = c2[p].c_str(); pj[p] = cj[p].c_str();
+        }
+        if (rh_batch_upload_constrained(ctx, np, a.data(), na.data(), b.data(), nb.data(), p1.data(), p2.data(), pj.data()) != RH_OK)
+            raise_ctx("solve_probabilities");
+    } else if (rh_batch_upload(ctx, np, a.data(), na.data(), b.data(), nb.data()) != RH_OK) raise_ctx("solve_probabilities");
     if (rh_batch_compute(ctx) != RH_OK) raise_ctx("solve_probabilities");
     // three device-to-host copies for the whole batch, then unpack the padded layout on the host
     size_t tri_stride = 0, hp_stride = 0;

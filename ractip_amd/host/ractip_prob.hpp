@@ -75,6 +75,14 @@ public:
     std::vector<PairProbabilities> solve_probabilities_default(const std::vector<std::pair<std::string, std::string>>& pairs,
                                                                uint max_w = 15, bool duplex = false) const;
 
+    // ... with use_constraint_: structures[p] = (str1, str2) are the FASTA structure lines of pair p, translated as rnafold(seq, str, ...)
+    // and rnaduplex_cofold(seq1, str1, seq2, str2, ...) translate them (fold_constraint / joint_constraint below) and handed to one
+    // constrained batch (rh_batch_upload_constrained); device shards split the structures with the pairs.  duplex = true: the folds
+    // are constrained, hp is not (the --duplex branch takes no constraint, :390-398)
+    std::vector<PairProbabilities> solve_probabilities_default(const std::vector<std::pair<std::string, std::string>>& pairs,
+                                                               const std::vector<std::pair<std::string, std::string>>& structures,
+                                                               uint max_w = 15, bool duplex = false) const;
+
     // the Vienna energy tables as RactIP::run installs them (:1563-1567): copy_boltzmann_parameters() unless use_bl_param_ is
     // off, then read_parameter_file(param_file_).  defaults_file stands for the tables built into the user's RNAlib (a ViennaRNA
     // parameter file; ViennaRNA is no part of the reference, so this library has none of its own); semantics: 0 = by the files
@@ -95,9 +103,10 @@ private:
     [[noreturn]] void raise(const char* where) const;
     rh_ctx* vienna() const;
     std::vector<PairProbabilities> batch(rh_ctx* ctx, const std::vector<std::pair<std::string, std::string>>& pairs, uint max_w,
-                                         bool threshold_hp) const;
+                                         bool threshold_hp, const std::vector<std::pair<std::string, std::string>>* structures = nullptr) const;
     std::vector<PairProbabilities> batch_one(rh_ctx* ctx, const std::vector<std::pair<std::string, std::string>>& pairs, int lo, int hi,
-                                             uint max_w, bool threshold_hp) const;
+                                             uint max_w, bool threshold_hp,
+                                             const std::vector<std::pair<std::string, std::string>>* structures = nullptr) const;
     rh_ctx* ctx_;                          // first device's CONTRAfold context
     mutable rh_ctx* vctx_ = nullptr;       // first device's Vienna-BL context (created on first use)
     std::vector<int> devices_;
@@ -110,6 +119,13 @@ private:
     int v_semantics_ = 0;
     int duplex_mode_ = -1;                 // RH_MODE_INHERIT
 };
+
+// The FASTA structure line of one sequence of L letters as RactIP::rnafold hands it to pf_fold (src/ractip.cpp:275-287): '[' ']' 'e'
+// become 'x', everything else is kept, missing positions are '.'
+std::string fold_constraint(const std::string& str, uint L);
+// The structure lines of a pair as the default branch of RactIP::rnaduplex hands them to co_pf_fold over s1+s2 (:409-440): '[' of s1
+// becomes '(' and ']' of s2 becomes ')', '(' ')' 'l' 'x' become 'x', everything else '.'
+std::string joint_constraint(const std::string& str1, uint n1, const std::string& str2, uint n2);
 
 // offset[i] = i*(2(L+1)-i-1)/2, size L+1  (src/ractip.cpp:254-257; InferenceEngine.ipp:316)
 VI make_offsets(uint L);

@@ -22,6 +22,7 @@ EXPORTS = [
     "rh_batch_results_all", "rh_set_max_w", "rh_get_max_w", "rh_set_overlap", "rh_batch_kernels", "rh_set_hybrid", "rh_last_hybrid_path", "rh_fold_constrained", "rh_cofold_constrained",
     "rh_host_alloc", "rh_host_free", "rh_batch_fallbacks", "rh_create_vienna", "rh_vienna_semantics", "rh_set_scale_memory", "rh_set_kernel_timing", "rh_kernel_times",
     "rh_set_duplex_mode", "rh_get_duplex_mode",
+    "rh_batch_upload_constrained", "rh_debug_batch_allow_mask",
     "rh_debug_vienna_cell", "rh_debug_vienna_value",   # loader inspection (host only; used by the CPU tests of the loader)
 ]
 
@@ -91,6 +92,10 @@ def load_library():
     L.rh_cofold_constrained.restype = ci
     L.rh_duplex.argtypes = [vp, cp, ci, cp, ci, vp, vp]
     L.rh_batch_upload.argtypes = [vp, ci, ctypes.POINTER(cp), ctypes.POINTER(ci), ctypes.POINTER(cp), ctypes.POINTER(ci)]
+    L.rh_batch_upload_constrained.argtypes = L.rh_batch_upload.argtypes + [ctypes.POINTER(cp)] * 3
+    L.rh_batch_upload_constrained.restype = ci
+    L.rh_debug_batch_allow_mask.argtypes = [vp, ci, ci, vp, vp]
+    L.rh_debug_batch_allow_mask.restype = ci
     L.rh_batch_compute.argtypes = [vp]
     L.rh_batch_results.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp]
     L.rh_batch_candidates.argtypes = [vp, ci, ci, ctypes.c_float, vp, ci]
@@ -234,14 +239,38 @@ class Context:
         return hp, z.value
 
     # ---- batched calls
-    def batch_upload(self, pairs):
+    def batch_upload(self, pairs, constraints=None, co_constraints=None):
+        """constraints: per pair (c1, c2), the fold_constrained strings of the two single-molecule folds (either may be None);
+        co_constraints: per pair a string over s1+s2 for the two-molecule ensemble, or None (rh_batch_upload_constrained)."""
         np_ = len(pairs)
         a = (ctypes.c_char_p * np_)(*[p[0].encode() for p in pairs])
         b = (ctypes.c_char_p * np_)(*[p[1].encode() for p in pairs])
         na = (ctypes.c_int * np_)(*[len(p[0]) for p in pairs])
         nb = (ctypes.c_int * np_)(*[len(p[1]) for p in pairs])
-        self._check(self.L.rh_batch_upload(self.h, np_, a, na, b, nb))
+        if constraints is None and co_constraints is None:
+            self._check(self.L.rh_batch_upload(self.h, np_, a, na, b, nb))
+        else:
+            def column(strings):
+                if strings is None:
+                    return None
+                if len(strings) != np_:
+                    raise RhError("%d constraints for %d pairs" % (len(strings), np_))
+                return (ctypes.c_char_p * np_)(*[None if x is None else x.encode() for x in strings])
+            pairs_c = None if constraints is None else [c if c is not None else (None, None) for c in constraints]
+            c1 = column(None if pairs_c is None else [c[0] for c in pairs_c])
+            c2 = column(None if pairs_c is None else [c[1] for c in pairs_c])
+            self._check(self.L.rh_batch_upload_constrained(self.h, np_, a, na, b, nb, c1, c2, column(co_constraints)))
         self._pairs = [(len(p[0]), len(p[1])) for p in pairs]
+
+    def debug_allow_mask(self, which, k):
+        """The allowed-pair mask of the last upload as the kernels read it (rh_debug_batch_allow_mask): which = 0, sequence k
+        (2p = s1 of pair p), which = 1 the concatenation of pair k.  An (ld, ld) uint8 array, or None if that batch has no mask."""
+        ld = ctypes.c_int()
+        if self._check(self.L.rh_debug_batch_allow_mask(self.h, which, k, None, ctypes.byref(ld))) == 1:
+            return None
+        out = np.empty((ld.value, ld.value), dtype=np.uint8)
+        self._check(self.L.rh_debug_batch_allow_mask(self.h, which, k, out.ctypes.data, ctypes.byref(ld)))
+        return out
 
     def batch_compute(self):
         self._check(self.L.rh_batch_compute(self.h))

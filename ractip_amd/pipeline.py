@@ -2,8 +2,10 @@
 integer programme (ractip_amd/ilp.py).  What `ractip s1.fa s2.fa` prints (/root/reference/src/ractip.cpp:1561-1610),
 without z-scores and energies.
 
-  python -m ractip_amd.pipeline [--contrafold] [--duplex] [--write-rip FILE] a.fa b.fa
+  python -m ractip_amd.pipeline [--contrafold] [--duplex] [--use-constraint] [--write-rip FILE] a.fa b.fa
 
+--use-constraint: the structure line that follows each sequence in its FASTA file constrains the folds and the two-molecule
+ensemble, as RactIP's -c does (src/ractip.cpp:271-291, 405-447); default path only.
 --write-rip FILE: also write bp1, bp2, hp as RIP tables (ractip_amd/rip.py) for a stock `ractip --rip FILE --min-w 0`.
 """
 import sys
@@ -28,16 +30,62 @@ def read_fasta(path):
     return name, "".join(seq)
 
 
-def probabilities(ctx, s1, s2):
-    ctx.batch_upload([(s1, s2)])
+STRUCTURE_CHARS = set("()[].?xle<>|")   # what a FASTA structure line is made of (src/fa.cpp:60-69, plus '<' '>' '|' of fold_constrained)
+
+
+def read_fasta_with_structure(path):
+    """(name, sequence, structure) of the first record: a line after the sequence that consists only of structure characters
+    (none of which is a nucleotide code) is the structure line, "" if there is none.  Sequence lines before it are joined as
+    read_fasta joins them."""
+    name, seq, structure = "", [], ""
+    for line in open(path):
+        line = line.strip()
+        if line.startswith(">"):
+            if seq:
+                break
+            name = line[1:]
+        elif line:
+            if seq and set(line) <= STRUCTURE_CHARS:
+                structure = line
+                break
+            seq.append(line)
+    return name, "".join(seq), structure
+
+
+def fold_constraint(structure, n):
+    """The structure line of one sequence as RactIP::rnafold hands it to pf_fold (src/ractip.cpp:275-287): '[' ']' 'e' become
+    'x', everything else is kept, missing positions are '.'."""
+    line = structure[:n]
+    return "".join("x" if ch in "[]e" else ch for ch in line) + "." * (n - len(line))
+
+
+def joint_constraint(str1, n1, str2, n2):
+    """The structure lines of a pair as the default branch of RactIP::rnaduplex hands them to co_pf_fold over s1+s2
+    (src/ractip.cpp:409-440): '[' of s1 becomes '(' and ']' of s2 becomes ')', '(' ')' 'l' 'x' become 'x', everything else '.'."""
+    def side(line, n, forced, to):
+        line = line[:n]
+        return "".join(to if ch == forced else "x" if ch in "()lx" else "." for ch in line) + "." * (n - len(line))
+    return side(str1, n1, "[", "(") + side(str2, n2, "]", ")")
+
+
+def probabilities(ctx, s1, s2, structures=None):
+    if structures is None:
+        ctx.batch_upload([(s1, s2)])
+    else:
+        str1, str2 = structures
+        ctx.batch_upload([(s1, s2)], constraints=[(fold_constraint(str1, len(s1)), fold_constraint(str2, len(s2)))],
+                         co_constraints=[joint_constraint(str1, len(s1), str2, len(s2))])
     ctx.batch_compute()
     return ctx.batch_results(0)
 
 
-def predict(s1, s2, model="vienna", duplex=False, device=0, options=None, ctx=None, rip_path=None):
+def predict(s1, s2, model="vienna", duplex=False, device=0, options=None, ctx=None, rip_path=None, structures=None):
     """model "vienna": RactIP's default path (rnafold + rnaduplex; duplex=True = --duplex, else co_pf_fold), parity
     unpinned; model "contrafold": the --contrafold path (bp from the CONTRAfold engine, width-1 up, accessibility off as
-    src/ractip.cpp:1511-1517 demands), hp from the CONTRAfold duplex engine."""
+    src/ractip.cpp:1511-1517 demands), hp from the CONTRAfold duplex engine.  structures = (str1, str2): the FASTA structure
+    lines, used as constraints (--use-constraint; model "vienna" only)."""
+    if structures is not None and model != "vienna":
+        raise ValueError("structure constraints apply to the default (Vienna-BL) path only")
     own = ctx is None
     if own:
         ctx = hot.Context(device=device, model=hot.RH_MODEL_VIENNA_BL if model == "vienna" else hot.RH_MODEL_CONTRAFOLD)
@@ -46,7 +94,7 @@ def predict(s1, s2, model="vienna", duplex=False, device=0, options=None, ctx=No
         if model == "vienna":
             ctx.set_max_w(max(1, opt.max_w))
             ctx.set_hybrid(not duplex)
-            r = probabilities(ctx, s1, s2)
+            r = probabilities(ctx, s1, s2, structures)
             if rip_path:
                 rip.write_rip(rip_path, s1, s2, r["bp1"], r["bp2"], r["hp"])
             return ilp.solve(s1, s2, r["bp1"], r["bp2"], r["hp"], r["up1"], r["up2"], opt)
@@ -122,8 +170,10 @@ def main(argv):
     files = [a for a in argv if not a.startswith("--")]
     if len(files) != 2:
         raise SystemExit(__doc__)
-    (n1, s1), (n2, s2) = read_fasta(files[0]), read_fasta(files[1])
-    r1, r2, _ = predict(s1, s2, model="contrafold" if "--contrafold" in flags else "vienna", duplex="--duplex" in flags, rip_path=rip_path)
+    (n1, s1, t1), (n2, s2, t2) = read_fasta_with_structure(files[0]), read_fasta_with_structure(files[1])
+    structures = (t1, t2) if "--use-constraint" in flags else None
+    r1, r2, _ = predict(s1, s2, model="contrafold" if "--contrafold" in flags else "vienna", duplex="--duplex" in flags, rip_path=rip_path,
+                        structures=structures)
     print(">%s\n%s\n%s\n>%s\n%s\n%s" % (n1, s1, r1, n2, s2, r2))   # src/ractip.cpp:1607-1610
 
 
