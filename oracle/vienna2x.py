@@ -366,10 +366,12 @@ def w_stem(T, which, t, si1, sj1):
 
 
 def w_hairpin(T, seq, S, i, j):
-    """exp_E_Hairpin: letters i..j (1-based), closed by (i, j)"""
+    """exp_E_Hairpin: letters i..j (1-based), closed by (i, j).  Above 30 letters the Boltzmann factor is
+    exphairpin[30] * exp(-lxc * log(u / 30) * 10 / kT): the extrapolation is not rounded to an integer energy (that is E_Hairpin,
+    the minimum-free-energy form; part_func.c of 1.8 does the same, see e_hairpin in oracle/vienna_oracle.c)"""
     u = j - i - 1
     t = PAIR[S[i], S[j]]
-    e = T["hairpin"][u] if u <= 30 else T["hairpin"][30] + int(T["lxc"] * math.log(u / 30.0))
+    e = T["hairpin"][u] if u <= 30 else T["hairpin"][30] + T["lxc"] * math.log(u / 30.0)
     sub = seq[i - 1:j].upper().replace("T", "U")
     if u == 3:
         if sub in T["Triloops"]:
@@ -382,14 +384,15 @@ def w_hairpin(T, seq, S, i, j):
     return -(e + T["mismatchH"][t, S[i + 1], S[j - 1]]) * 10.0 / KT
 
 
-def structures(n, S, min_hairpin=3):
-    """all secondary structures over letters 1..n as sorted tuples of (i, j), canonical pair types only"""
+def structures(n, S, min_hairpin=3, allow=None):
+    """all secondary structures over letters 1..n as sorted tuples of (i, j), canonical pair types only; allow: an (n+1) x (n+1)
+    allowed-pair mask (1-based, upper triangle) that every pair must pass, or None"""
     def rec(lo, hi):
         if hi - lo < min_hairpin + 1:
             return [()]
         out = list(rec(lo + 1, hi))                      # lo unpaired
         for k in range(lo + min_hairpin + 1, hi + 1):   # lo pairs with k
-            if PAIR[S[lo], S[k]]:
+            if PAIR[S[lo], S[k]] and (allow is None or allow[lo, k]):
                 for a in rec(lo + 1, k - 1):
                     for b in rec(k + 1, hi):
                         out.append(((lo, k),) + a + b)
@@ -397,7 +400,7 @@ def structures(n, S, min_hairpin=3):
     return rec(1, n)
 
 
-def brute_fold(T, seq, max_w=0):
+def brute_fold(T, seq, max_w=0, allow=None):
     """pf_fold by enumeration under the 2.x loop energies with dangles = 2: (log Z, bp dict[, up]) with
     up[i][w] = P(letters i+1 .. i+1+w unpaired), i and w from 0 (the layout of rh_fold), when max_w > 0"""
     S = encode(seq)
@@ -406,7 +409,7 @@ def brute_fold(T, seq, max_w=0):
     w = lambda E: -E * 10.0 / KT
     Z, bp = 0.0, {}
     up = np.zeros((n, max(max_w, 1)))
-    for st in structures(n, S):
+    for st in structures(n, S, allow=allow):
         partner = {}
         for (i, j) in st:
             partner[i] = j
@@ -460,7 +463,7 @@ def brute_fold(T, seq, max_w=0):
     return math.log(Z), {k: v / Z for k, v in bp.items()}
 
 
-def brute_cofold(T, seq1, seq2):
+def brute_cofold(T, seq1, seq2, allow=None):
     """co_pf_fold by enumeration over s1+s2 (cut after letter n1), 2.x energies, dangles = 2: (log Z, hp[(n1+1),(n2+1)]).
     The loop whose backbone holds the missing gap is exterior-like: every stem in it (the closing pair seen from inside
     included) scores as a stem of the exterior loop, a neighbour letter counts only if it sits on the same strand, and
@@ -474,7 +477,7 @@ def brute_cofold(T, seq1, seq2):
     nb3 = lambda q: S[q + 1] if (q + 1 <= n and q != cut) else -1          # letter after q, same strand
     Z = 0.0
     hp = np.zeros((n1 + 1, n2 + 1))
-    for st in structures(n, S):
+    for st in structures(n, S, allow=allow):
         partner = {i: j for (i, j) in st}
 
         def children(lo, hi):

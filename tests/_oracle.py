@@ -280,6 +280,62 @@ class ViennaOracle:
         return dict(logZ=z, pr=pr)
 
 
+class Vienna2xOracle:
+    """ViennaRNA-2.x folds with dangles = 2 in polynomial time (oracle/vienna2x_oracle.c) -- PARITY UNPINNED.  T: the table dict of
+    oracle/vienna2x.py (random_tables / read_par), handed over as flat arrays.  The allowed-pair mask is an argument of each call,
+    so constrained calls may run on several threads at once."""
+    INT_TABLES = ("stack", "mismatchH", "mismatchI", "mismatch1nI", "mismatch23I", "mismatchM", "mismatchExt", "dangle5", "dangle3",
+                  "int11", "int21", "int22", "hairpin", "bulge", "interior")
+    MISC = ("ninio", "max_ninio", "ML_base", "ML_closing", "ML_intern", "TerminalAU")
+
+    def __init__(self, T):
+        so = os.path.join(ORACLE_DIR, "libvienna2x_oracle.so")
+        src = os.path.join(ORACLE_DIR, "vienna2x_oracle.c")
+        if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
+            subprocess.check_call(["make", "-s", "-C", ORACLE_DIR, "oracle"])
+        L = ctypes.CDLL(so)
+        vp, cp, ci = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int
+        L.v2o_new.restype = vp
+        L.v2o_new.argtypes = [vp, ci, ctypes.c_double, cp, vp]
+        L.v2o_free.argtypes = [vp]
+        L.v2o_int_loop.restype = ci
+        L.v2o_int_loop.argtypes = [vp] + [ci] * 8
+        L.v2o_fold.restype = ctypes.c_double
+        L.v2o_fold.argtypes = [vp, cp, ci, ci, vp, ci, vp, vp, vp]
+        ints = np.concatenate([np.asarray(T[k]).ravel() for k in self.INT_TABLES] + [np.array([T[k] for k in self.MISC])]).astype(np.int32)
+        loops = [(k, e) for name in ("Triloops", "Tetraloops", "Hexaloops") for k, e in T[name].items()]
+        energies = np.array([e for _, e in loops] + [0], dtype=np.int32)
+        self.L = L
+        self.m = L.v2o_new(ints.ctypes.data, len(ints), float(T["lxc"]), " ".join(k for k, _ in loops).encode(), energies.ctypes.data)
+        assert self.m, "vienna2x_oracle.c does not take these tables"
+
+    def int_loop(self, n1, n2, t, t2, si1, sj1, sp1, sq1):
+        return self.L.v2o_int_loop(self.m, n1, n2, t, t2, si1, sj1, sp1, sq1)
+
+    def fold(self, seq, max_w=0, constraint=None, cut=0):
+        """logZ (inside), logZ_out (outside), post (triangular, reference layout), up[n][max_w] (one molecule only)"""
+        n = len(seq)
+        mask = constraint_mask(constraint, n) if constraint is not None else None
+        post = np.zeros(tri_size(n))
+        zo = ctypes.c_double()
+        up = np.zeros((n, max_w)) if max_w and not cut else None
+        z = self.L.v2o_fold(self.m, seq.encode(), n, cut, mask.ctypes.data if mask is not None else None, max_w if up is not None else 0,
+                            post.ctypes.data, up.ctypes.data if up is not None else None, ctypes.byref(zo))
+        return dict(logZ=z, logZ_out=zo.value, post=post, up=up)
+
+    def cofold(self, s1, s2, constraint=None):
+        """co_pf_fold semantics on s1+s2 (cut after s1; the constraint runs over the concatenation): logZ, the joint pair matrix and
+        the intermolecular block hp[i][j] = P(s1[i] pairs s2[j]), (n1+1) x (n2+1), 1-based"""
+        n1, n2 = len(s1), len(s2)
+        o = self.fold(s1 + s2, 0, constraint, cut=n1)
+        hp = np.zeros((n1 + 1, n2 + 1))
+        for i in range(1, n1 + 1):
+            off = tri_offset(n1 + n2, i)
+            hp[i, 1:] = o["post"][off + n1 + 1:off + n1 + n2 + 1]
+        o["hp"] = hp
+        return o
+
+
 ORACLE_WORKERS = 8   # threads of OraclePool: a fixed number, never sized by the machine's CPU count
 
 
@@ -295,6 +351,7 @@ class OraclePool:
         self.pool = ThreadPoolExecutor(max_workers=min(workers, ORACLE_WORKERS))
         self.cache = {}
         self.constrained_cache = {}
+        self.v2 = {}
         self.lock = threading.Lock()
 
     def _get(self, key, fn, *args):
@@ -318,6 +375,19 @@ class OraclePool:
 
     def pf_duplex(self, s1, s2):
         return self._get(("vo-dx", s1, s2), self.vo.pf_duplex, s1, s2)
+
+    def tables2x(self, name, T):
+        """Names a 2.x table set (a T dict of oracle/vienna2x.py) for fold2x / cofold2x."""
+        with self.lock:
+            if name not in self.v2:
+                self.v2[name] = Vienna2xOracle(T)
+        return self.v2[name]
+
+    def fold2x(self, tables, seq, max_w=15, constraint=None):
+        return self._get(("v2", tables, seq, max_w, constraint), self.v2[tables].fold, seq, max_w, constraint)
+
+    def cofold2x(self, tables, s1, s2, constraint=None):
+        return self._get(("v2-co", tables, s1, s2, constraint), self.v2[tables].cofold, s1, s2, constraint)
 
     def wait(self):
         """Returns when every call queued so far has ended."""
