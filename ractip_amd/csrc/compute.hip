@@ -1,5 +1,6 @@
 // compute.hip -- one batch from staged to computed: hipGraph capture / replay of the launch sequences, the two streams
-// and their events, and the decision which fallback a flagged problem takes.
+// and their events, and the decision which fallback a flagged problem takes: one schedule per product (CONTRAfold folds + duplex,
+// Vienna-BL folds + pf_duplex, Vienna-BL folds + two-molecule ensemble) under one driver (run_attempt), and compute() above it.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -66,7 +67,7 @@ McLinArgs mc_lin_args(const rh_ctx* c, int phase, const McBatch& B, const LinSet
         A.plan_sweep = plan_mc_lin(c, phase, A.nmax_sweep);
         A.plan_short = plan_mc_lin(c, phase, A.nmax_short);
     }
-    A.pin = B.ns % 8 == 0 ? 1 : 0;   // sequence -> XCD affinity only when the batch spreads evenly over the 8 XCDs (speed only)
+    A.pin = xcd_pin(B.ns);
     A.strip_xcd = c->strip_xcd;
     return A;
 }
@@ -76,7 +77,7 @@ static McVlinArgs mc_vlin_args(const rh_ctx* c, int phase, bool co)
 {
     McVlinArgs A;
     A.B = co ? c->co : c->mc; A.phase = phase; A.co = co;
-    A.pin = A.B.ns % 8 == 0 ? 1 : 0;
+    A.pin = xcd_pin(A.B.ns);
     A.plan = plan_mc_vlin(c, phase, co, A.B.nmax);
     A.d_vlin = c->d_vlin; A.h_vlin = c->h_vlin; A.hplen = c->h_hplen.data(); A.d_hplen = c->d_hplen.as<const double>();
     A.bad = co ? c->d_cobad.as<int>() : c->d_bad.as<int>();
@@ -95,15 +96,29 @@ static McVlinArgs mc_vlin_args(const rh_ctx* c, int phase, bool co)
     return A;
 }
 
-// The hybridization sweeps over the staged batch of pairs, either model
-DxLinArgs dx_lin_args(const rh_ctx* c)
+// The hybridization sweeps over the staged batch of pairs: what both models' arguments share ...
+static DxLinArgs dx_args(const rh_ctx* c)
 {
     DxLinArgs A;
     A.X = c->dxl; A.plan = c->plan[2]; A.lz_chunks = c->lz_chunks;
-    if (c->model == RH_MODEL_VIENNA_BL) { A.vdx_s = c->vdx_s; A.sem20 = c->vienna_sem == kViennaSem20; }
-    else { A.dm = c->d_dxlin; A.hm = &c->h_dxlin; }
     A.zpart = c->d_zpart.as<double>(); A.zbar = c->d_zbar.as<double>();
     A.logz = c->d_logz.as<double>(); A.bad = c->d_dxbad.as<int>();
+    return A;
+}
+
+// ... of launch_dx_lin (CONTRAfold model) ...
+DxLinArgs dx_lin_args(const rh_ctx* c)
+{
+    DxLinArgs A = dx_args(c);
+    A.dm = c->d_dxlin; A.hm = &c->h_dxlin;
+    return A;
+}
+
+// ... and of launch_dx_vlin (Vienna-BL pf_duplex)
+static DxLinArgs dx_vlin_args(const rh_ctx* c)
+{
+    DxLinArgs A = dx_args(c);
+    A.vdx_s = c->vdx_s; A.sem20 = c->vienna_sem == kViennaSem20;
     return A;
 }
 
@@ -118,124 +133,77 @@ int flagged(rh_ctx* c, const int* d_flags, int n, hipStream_t st, std::vector<in
     return RH_OK;
 }
 
-int compute_once(rh_ctx* c)
-{
-    HIP_TRY(c, hipSetDevice(c->device));
-    c->deferred = false;
-    c->went_log = false;
-    c->tev_n = 0;
-    c->n_launch[0] = c->n_launch[1] = c->n_launch[2] = 0;
-    c->n_far[0] = c->n_far[1] = c->n_far[2] = 0;
-    c->last_path = 0;
-    c->fallback_mc.clear(); c->fallback_dx.clear(); c->rescaled_mc.clear(); c->rescaled_dx.clear();
-    // the organisation of each sweep's linear first pass: decided here, on every compute (a replayed graph does not call its launcher);
-    // the arguments below carry the same plans to the launchers
-    const bool vienna = c->model == RH_MODEL_VIENNA_BL;
-    for (int phase = 0; phase < 2; phase++) c->plan[phase] = vienna ? plan_mc_vlin(c, phase, false, c->mc.nmax) : plan_mc_lin(c, phase, c->mc.nmax);
-    c->plan[2] = !vienna ? plan_dx_lin(c, c->dx_w) : c->hybrid == RH_HYBRID_COFOLD ? plan_mc_vlin(c, 0, true, c->co.nmax) : plan_dx_vlin(c->vienna_sem == kViennaSem20);
-    const int pin = (c->has_mc && c->mc.ns % 8 == 0) ? 1 : 0;   // (of the log-space sweeps; the linear ones: see their arguments)
-    // the path of the pf_duplex sweeps (RH_HYBRID_DUPLEX): rh_set_duplex_mode, or what rh_set_mode says
-    const int dx_mode = c->duplex_mode == RH_MODE_INHERIT ? c->mode : c->duplex_mode;
-    int rc;
-    std::vector<int> bad;
-    // the linear duplex kernels share d_dxtab with the log-space ones and read zero pad columns: after a log-space compute on this
-    // upload (another mode since, or a fallback) the image stage() left is gone
-    if (c->has_dx && c->dxtab_log && dx_mode != RH_MODE_LOG && !(c->model == RH_MODEL_VIENNA_BL && c->hybrid == RH_HYBRID_COFOLD)) {
-        HIP_TRY(c, hipMemsetAsync(c->d_dxtab.p, 0, c->dx_bytes, c->s_dx));
-        c->dxtab_log = false;
-    }
-    // duplex first on its own stream: it is independent of the McCaskill sweeps and overlaps them
-    HIP_TRY(c, hipEventRecord(c->ev[3], c->s_dx));
-    bool dx_lin_launched = false, co_lin_launched = false, co_seed_bad = false, out_from_ev5 = false;
-    // two-molecule sweeps in linear space next to the single-molecule folds of the same pairs (no structure constraints): the cells
-    // on one strand are copied from those folds (vlin_co_seed), so the sweeps over s1+s2 start when their inside tables are final
-    const bool co_seed = c->has_dx && c->has_mc && c->model == RH_MODEL_VIENNA_BL && c->hybrid == RH_HYBRID_COFOLD && c->mode != RH_MODE_LOG &&
-                         c->co_seed && !c->mc.allow && !c->co.allow && c->mc.ns == 2 * c->co.ns;
-    c->co.seeded = co_seed ? 1 : 0;
-    auto launch_co_lin = [&]() -> int {   // scaled linear sweeps over s1+s2; out-of-range values send the batch to the log-space kernels
-        return run_graphed(c, c->g_dx, c->s_dx, 2, launch_mc_vlin, mc_vlin_args(c, 0, true), mc_vlin_args(c, 1, true));   // (one graph of both)
-    };
-    if (c->has_dx && c->model == RH_MODEL_VIENNA_BL && c->hybrid == RH_HYBRID_COFOLD) {
-        HIP_TRY(c, hipMemsetAsync(c->d_cobp.p, 0, sizeof(double) * c->co.tri_stride * c->co.ns, c->s_dx));
-        bool co_log = c->mode == RH_MODE_LOG;
-        if (!co_log && !co_seed) {
-            if ((rc = launch_co_lin())) return rc;
-            c->last_dx_path = 1;
-            co_lin_launched = true;   // its overflow flags are read after the McCaskill stream has been fed (the two overlap)
-        }
-        if (co_log) {
-            if ((rc = launch_cofold(c))) return rc;
-            if (c->last_dx_path != 3) c->last_dx_path = 2;
-        }
-    } else if (c->has_dx && c->model == RH_MODEL_VIENNA_BL) {
-        if (dx_mode != RH_MODE_LOG) {   // scaled linear sweeps; pairs outside the double range send the batch to the log-space kernels
-            if ((rc = run_graphed(c, c->g_dx, c->s_dx, 2, launch_dx_vlin, dx_lin_args(c)))) return rc;
-            dx_lin_launched = true;
-        } else {
-            if ((rc = launch_dx_vlog(c))) return rc;
-            c->dxtab_log = true;
-            c->last_dx_path = 2;
-        }
-    } else if (c->has_dx) {
-        if (dx_mode != RH_MODE_LOG) {
-            if ((rc = run_graphed(c, c->g_dx, c->s_dx, 2, launch_dx_lin, dx_lin_args(c)))) return rc;
-            dx_lin_launched = true;
-        } else {
-            if ((rc = launch_dx_log(c, c->dx))) return rc;
-            c->dxtab_log = true;
-            c->last_dx_path = 2;
-        }
-    }
-    HIP_TRY(c, hipEventRecord(c->ev[4], c->s_dx));
-    if (!c->overlap) HIP_TRY(c, hipStreamSynchronize(c->s_dx));   // isolated phase timings: nothing else on the device
+// ---- One attempt at the staged batch: what compute() asks of a schedule, and what the schedule reports back.  Only the Vienna-BL
+// schedules defer (compute() has another exponent for the whole batch); the CONTRAfold schedule settles its flags itself.
+struct Attempt {
+    bool defer_log = false;           // in: a flagged problem ends the attempt instead of starting the log-space kernels
+    bool deferred = false;            // out: it ended that way ...
+    std::vector<int> flagged_seqs;    // ... with these sequences (folds) ...
+    std::vector<int> flagged_pairs;   // ... and pairs (folds, two-molecule sweeps or pf_duplex) flagged
+    bool went_log = false;            // out: the folds or the two-molecule sweeps ran on the log-space kernels
+    Ev outside_from = kEvMcInside;    // out: the event the outside phase starts at (kEvMcOutside: something ran between the sweeps)
+};
 
-    HIP_TRY(c, hipEventRecord(c->ev[0], c->s_mc));
-    bool need_log = c->has_mc && c->mode == RH_MODE_LOG && c->model != RH_MODEL_VIENNA_BL;
-    if (c->has_mc && c->model == RH_MODEL_VIENNA_BL) {
-        bool log_path = c->mode == RH_MODE_LOG;
-        if (!log_path) {   // scaled linear sweeps; a sequence that leaves the double range sends the batch to the log-space kernels
-            if ((rc = run_graphed(c, c->g_in, c->s_mc, 0, launch_mc_vlin, mc_vlin_args(c, 0, false)))) return rc;
-            HIP_TRY(c, hipEventRecord(c->ev[1], c->s_mc));
-            if (co_seed) {   // the inside tables of both molecules are final behind ev[1]
-                HIP_TRY(c, hipStreamWaitEvent(c->s_dx, c->ev[1], 0));
-                HIP_TRY(c, hipEventRecord(c->ev[3], c->s_dx));
-                if ((rc = launch_co_lin())) return rc;
-                HIP_TRY(c, hipEventRecord(c->ev[4], c->s_dx));
-                c->last_dx_path = 1;
-                co_lin_launched = true;
-                if (!c->overlap) HIP_TRY(c, hipStreamSynchronize(c->s_dx));   // isolated phase timings: nothing else on the device
-            }
-            HIP_TRY(c, hipEventRecord(c->ev[5], c->s_mc));   // start of the outside phase (= ev[1] unless the seeded sweeps ran in between)
-            out_from_ev5 = true;
-            if ((rc = run_graphed(c, c->g_out, c->s_mc, 1, launch_mc_vlin, mc_vlin_args(c, 1, false)))) return rc;
-            c->last_path = 1;
-            if (c->mode == RH_MODE_AUTO) {
-                if ((rc = flagged(c, c->d_bad.as<int>(), c->mc.ns, c->s_mc, &bad))) return rc;
-                log_path = !bad.empty();
-                if (log_path) { c->last_path = 3; c->tables_dirty = true; co_seed_bad = co_seed; }
-                if (log_path && c->defer_log) {   // another exponent first (compute): this attempt ends here
-                    for (int k : bad) { c->flagged_mc.push_back(k); if (c->has_dx) c->flagged_pairs.push_back(k / 2); }
-                    c->deferred = true;
-                    log_path = false;
-                }
-            }
-        }
-        if (log_path) {
-            c->went_log = true;
-            out_from_ev5 = false;
-            c->n_launch[0] = c->n_launch[1] = 0;
-            c->n_far[0] = c->n_far[1] = 0;
-            HIP_TRY(c, hipEventRecord(c->ev[0], c->s_mc));
-            HIP_TRY(c, hipMemsetAsync(c->d_bp.p, 0, sizeof(double) * c->mc.tri_stride * c->mc.ns, c->s_mc));
-            if ((rc = launch_mc_vienna(c, pin))) return rc;
-            if (c->last_path == 0) c->last_path = 2;
-        }
-    } else if (c->has_mc && c->mode != RH_MODE_LOG) {
+// ---- what the schedules share
+// The hybridization stream is fed: its end event, and -- isolated phase timings -- nothing else on the device while it runs
+static int close_dx_phase(rh_ctx* c)
+{
+    HIP_TRY(c, hipEventRecord(c->ev[kEvDxEnd], c->s_dx));
+    if (!c->overlap) HIP_TRY(c, hipStreamSynchronize(c->s_dx));
+    return RH_OK;
+}
+
+// Start the folds over in log space on the McCaskill stream: what the linear pass launched does not count, the phase times start
+// again, the bp rows are cleared, `launch` feeds the stream
+template <class Launch>
+static int restart_mc_log(rh_ctx* c, Launch launch)
+{
+    c->n_launch[0] = c->n_launch[1] = 0;
+    c->n_far[0] = c->n_far[1] = 0;
+    HIP_TRY(c, hipEventRecord(c->ev[kEvMcStart], c->s_mc));
+    HIP_TRY(c, hipMemsetAsync(c->d_bp.p, 0, sizeof(double) * c->mc.tri_stride * c->mc.ns, c->s_mc));
+    if (int rc = launch()) return rc;
+    if (c->last_path == 0) c->last_path = 2;
+    return RH_OK;
+}
+
+// The same for the hybridization source on its stream.  clear_cobp: the two-molecule sweeps accumulate into their bp rows; pf_duplex
+// and the duplex sweeps clear nothing
+template <class Launch>
+static int restart_dx_log(rh_ctx* c, bool clear_cobp, Launch launch)
+{
+    c->n_launch[2] = 0; c->n_far[2] = 0;
+    HIP_TRY(c, hipEventRecord(c->ev[kEvDxStart], c->s_dx));
+    if (clear_cobp) HIP_TRY(c, hipMemsetAsync(c->d_cobp.p, 0, sizeof(double) * c->co.tri_stride * c->co.ns, c->s_dx));
+    if (int rc = launch()) return rc;
+    HIP_TRY(c, hipEventRecord(c->ev[kEvDxEnd], c->s_dx));
+    c->last_dx_path = 3;
+    return RH_OK;
+}
+
+// ---- CONTRAfold model: duplex sweeps on s_dx, folds on s_mc; every flagged problem is settled here, alone where it can be
+static int schedule_contrafold(rh_ctx* c, int dx_mode)
+{
+    int rc;
+    // duplex first on its own stream: it is independent of the McCaskill sweeps and overlaps them
+    const bool dx_lin = c->has_dx && dx_mode != RH_MODE_LOG;
+    if (dx_lin) {
+        if ((rc = run_graphed(c, c->g_dx, c->s_dx, 2, launch_dx_lin, dx_lin_args(c)))) return rc;
+    } else if (c->has_dx) {
+        if ((rc = launch_dx_log(c, c->dx))) return rc;
+        c->dxtab_log = true;
+        c->last_dx_path = 2;
+    }
+    if ((rc = close_dx_phase(c))) return rc;
+
+    HIP_TRY(c, hipEventRecord(c->ev[kEvMcStart], c->s_mc));
+    bool need_log = c->has_mc && c->mode == RH_MODE_LOG;
+    if (c->has_mc && c->mode != RH_MODE_LOG) {
         // on the exponent most of the last batch needed (scale-exponent ladder), or the default one
-        const bool on_rung = c->mode == RH_MODE_AUTO && c->scale_ladder && c->lin_primary >= 0 && c->lin_r;
-        const LinSet* lin = on_rung ? &c->lin_r[c->lin_primary] : &c->lin0;
+        const int model = c->mode == RH_MODE_AUTO && c->scale_ladder && c->lin_primary >= 0 && c->lin_r ? c->lin_primary : -1;
+        const LinSet* lin = model < 0 ? &c->lin0 : &c->lin_r[model];
         if ((rc = run_graphed(c, c->g_in, c->s_mc, 0, launch_mc_lin, mc_lin_args(c, 0, c->mc, lin, true)))) return rc;
-        HIP_TRY(c, hipEventRecord(c->ev[1], c->s_mc));
+        HIP_TRY(c, hipEventRecord(c->ev[kEvMcInside], c->s_mc));
         if ((rc = run_graphed(c, c->g_out, c->s_mc, 1, launch_mc_lin, mc_lin_args(c, 1, c->mc, lin, true)))) return rc;
         c->last_path = 1;
         if (c->mode == RH_MODE_AUTO) {  // did every sequence stay inside the double range?
@@ -243,138 +211,262 @@ int compute_once(rh_ctx* c)
             if (!c->fallback_mc.empty()) {
                 c->last_path = 3;
                 c->tables_dirty = true;
-                if ((rc = retry_mc_lin_rungs(c, lin, &c->fallback_mc))) return rc;   // another exponent first; what is left goes to log space
+                int rescued_by[rh_ctx::kRungs + 1];
+                if ((rc = retry_mc_lin_rungs(c, model, &c->fallback_mc, rescued_by))) return rc;   // another exponent first; what is left goes to log space
                 for (int q = 0; q <= rh_ctx::kRungs; q++)   // more than half of the batch on one exponent: the next batch starts there
-                    if (c->scale_memory && c->mc.ns >= 8 && 2 * c->rescued_by[q] > c->mc.ns) c->lin_primary = q - 1;   // (a batch, not a single call)
+                    if (c->scale_memory && c->mc.ns >= 8 && 2 * rescued_by[q] > c->mc.ns) c->lin_primary = q - 1;   // (a batch, not a single call)
                 if (c->fallback_mc.empty()) { }
                 else if (2 * c->fallback_mc.size() > (size_t)c->mc.ns) need_log = true;   // most of the batch: redo it whole
                 else if ((rc = recompute_mc_subset_log(c, c->fallback_mc))) return rc;
             }
         }
     } else {
-        HIP_TRY(c, hipEventRecord(c->ev[1], c->s_mc));
+        HIP_TRY(c, hipEventRecord(c->ev[kEvMcInside], c->s_mc));
     }
-    if (need_log) {
-        c->n_launch[0] = c->n_launch[1] = 0;
-        c->n_far[0] = c->n_far[1] = 0;
-        HIP_TRY(c, hipEventRecord(c->ev[0], c->s_mc));
-        HIP_TRY(c, hipMemsetAsync(c->d_bp.p, 0, sizeof(double) * c->mc.tri_stride * c->mc.ns, c->s_mc));
-        if ((rc = launch_mc_log(c, pin, c->mc, c->d_mclogz.as<double>()))) return rc;
-        if (c->last_path == 0) c->last_path = 2;
-    }
-    HIP_TRY(c, hipEventRecord(c->ev[2], c->s_mc));
-    if (co_lin_launched && c->mode == RH_MODE_AUTO) {
-        if ((rc = flagged(c, c->d_cobad.as<int>(), c->co.ns, c->s_dx, &bad))) return rc;
-        const bool redo = co_seed_bad || !bad.empty();   // (a molecule left the double range on its own: what was copied from its fold is not usable)
-        if (redo && c->defer_log) {
-            c->tables_dirty = true; c->deferred = true;
-            c->flagged_pairs.insert(c->flagged_pairs.end(), bad.begin(), bad.end());
-        }
-        else if (redo) {   // some pair left the double range: recompute the two-molecule sweeps in log space
-            c->went_log = true;
-            c->tables_dirty = true;
-            c->n_launch[2] = 0; c->n_far[2] = 0;
-            HIP_TRY(c, hipEventRecord(c->ev[3], c->s_dx));
-            HIP_TRY(c, hipMemsetAsync(c->d_cobp.p, 0, sizeof(double) * c->co.tri_stride * c->co.ns, c->s_dx));
-            if ((rc = launch_cofold(c))) return rc;
-            HIP_TRY(c, hipEventRecord(c->ev[4], c->s_dx));
-            c->last_dx_path = 3;
-        }
-    }
-    if (dx_lin_launched) {
+    if (need_log && (rc = restart_mc_log(c, [&] { return launch_mc_log(c, xcd_pin(c->mc.ns), c->mc, c->d_mclogz.as<double>()); }))) return rc;
+    HIP_TRY(c, hipEventRecord(c->ev[kEvMcEnd], c->s_mc));
+
+    if (dx_lin) {
         c->last_dx_path = 1;
         if (dx_mode == RH_MODE_AUTO) {
             if ((rc = flagged(c, c->d_dxbad.as<int>(), c->dx.np, c->s_dx, &c->fallback_dx))) return rc;
-            const bool redo = !c->fallback_dx.empty();
-            if (redo && c->model != RH_MODEL_VIENNA_BL && 2 * c->fallback_dx.size() <= (size_t)c->dx.np) {
+            if (c->fallback_dx.empty()) { }
+            else if (2 * c->fallback_dx.size() <= (size_t)c->dx.np) {
                 // only the flagged pairs, as a compacted sub-batch with its own tables: another scale exponent on the linear kernels
                 // first (retry_dx_lin_rungs), the log-space kernels for what is left
                 if ((rc = retry_dx_lin_rungs(c, &c->fallback_dx))) return rc;
                 if (!c->fallback_dx.empty() && (rc = recompute_dx_subset_log(c, c->fallback_dx))) return rc;
-                HIP_TRY(c, hipEventRecord(c->ev[4], c->s_dx));
+                HIP_TRY(c, hipEventRecord(c->ev[kEvDxEnd], c->s_dx));
                 c->last_dx_path = 3;
-            } else if (redo && c->model == RH_MODEL_VIENNA_BL && c->defer_log) {   // (compute: the flagged pairs go to the helper context)
-                c->tables_dirty = true; c->deferred = true;
-                c->flagged_pairs.insert(c->flagged_pairs.end(), c->fallback_dx.begin(), c->fallback_dx.end());
-                c->fallback_dx.clear();
-            } else if (redo) {  // most pairs (or the Vienna-BL model): recompute the batch with the log-space kernels
-                c->n_launch[2] = 0;
-                HIP_TRY(c, hipEventRecord(c->ev[3], c->s_dx));
-                if ((rc = (c->model == RH_MODEL_VIENNA_BL ? launch_dx_vlog(c) : launch_dx_log(c, c->dx)))) return rc;
+            } else {   // most pairs: recompute the batch with the log-space kernels
+                if ((rc = restart_dx_log(c, false, [&] { return launch_dx_log(c, c->dx); }))) return rc;
                 c->dxtab_log = true;
-                HIP_TRY(c, hipEventRecord(c->ev[4], c->s_dx));
-                c->last_dx_path = 3;
             }
         }
     }
+    return RH_OK;
+}
+
+// ---- Vienna-BL model: the single-molecule folds of both schedules on s_mc, up to their end event.  between(): what the schedule
+// puts behind the inside sweep.  A flagged sequence sends the BATCH to the log-space kernels, or ends the attempt (defer_log).
+// *overflowed: a sequence was flagged
+template <class Between>
+static int vienna_folds(rh_ctx* c, Attempt* at, Between between, bool* overflowed)
+{
+    int rc;
+    *overflowed = false;
+    HIP_TRY(c, hipEventRecord(c->ev[kEvMcStart], c->s_mc));
+    if (!c->has_mc) {
+        HIP_TRY(c, hipEventRecord(c->ev[kEvMcInside], c->s_mc));
+        HIP_TRY(c, hipEventRecord(c->ev[kEvMcEnd], c->s_mc));
+        return RH_OK;
+    }
+    bool log_path = c->mode == RH_MODE_LOG;
+    if (!log_path) {   // scaled linear sweeps; a sequence that leaves the double range sends the batch to the log-space kernels
+        if ((rc = run_graphed(c, c->g_in, c->s_mc, 0, launch_mc_vlin, mc_vlin_args(c, 0, false)))) return rc;
+        HIP_TRY(c, hipEventRecord(c->ev[kEvMcInside], c->s_mc));
+        if ((rc = between())) return rc;
+        HIP_TRY(c, hipEventRecord(c->ev[kEvMcOutside], c->s_mc));   // (= kEvMcInside unless something ran in between)
+        at->outside_from = kEvMcOutside;
+        if ((rc = run_graphed(c, c->g_out, c->s_mc, 1, launch_mc_vlin, mc_vlin_args(c, 1, false)))) return rc;
+        c->last_path = 1;
+        if (c->mode == RH_MODE_AUTO) {
+            std::vector<int> bad;
+            if ((rc = flagged(c, c->d_bad.as<int>(), c->mc.ns, c->s_mc, &bad))) return rc;
+            log_path = *overflowed = !bad.empty();
+            if (log_path) { c->last_path = 3; c->tables_dirty = true; }
+            if (log_path && at->defer_log) {   // another exponent first (compute): this attempt ends here
+                for (int k : bad) { at->flagged_seqs.push_back(k); if (c->has_dx) at->flagged_pairs.push_back(k / 2); }
+                at->deferred = true;
+                log_path = false;
+            }
+        }
+    }
+    if (log_path) {
+        at->went_log = true;
+        at->outside_from = kEvMcInside;
+        if ((rc = restart_mc_log(c, [&] { return launch_mc_vienna(c, xcd_pin(c->mc.ns)); }))) return rc;
+    }
+    HIP_TRY(c, hipEventRecord(c->ev[kEvMcEnd], c->s_mc));
+    return RH_OK;
+}
+
+// ---- Vienna-BL model, hp from pf_duplex: its sweeps on s_dx, the folds on s_mc; a flagged pair sends the batch of pairs to the
+// log-space kernels, or ends the attempt (defer_log: the flagged pairs go to the helper context, or the batch to another exponent)
+static int schedule_vienna_duplex(rh_ctx* c, int dx_mode, Attempt* at)
+{
+    int rc;
+    const bool dx_lin = c->has_dx && dx_mode != RH_MODE_LOG;
+    if (dx_lin) {
+        if ((rc = run_graphed(c, c->g_dx, c->s_dx, 2, launch_dx_vlin, dx_vlin_args(c)))) return rc;
+    } else if (c->has_dx) {
+        if ((rc = launch_dx_vlog(c))) return rc;
+        c->dxtab_log = true;
+        c->last_dx_path = 2;
+    }
+    if ((rc = close_dx_phase(c))) return rc;
+
+    bool overflowed;
+    if ((rc = vienna_folds(c, at, [] { return (int)RH_OK; }, &overflowed))) return rc;
+
+    if (dx_lin) {
+        c->last_dx_path = 1;
+        if (dx_mode == RH_MODE_AUTO) {
+            if ((rc = flagged(c, c->d_dxbad.as<int>(), c->dx.np, c->s_dx, &c->fallback_dx))) return rc;
+            if (c->fallback_dx.empty()) { }
+            else if (at->defer_log) {
+                c->tables_dirty = true; at->deferred = true;
+                at->flagged_pairs.insert(at->flagged_pairs.end(), c->fallback_dx.begin(), c->fallback_dx.end());
+                c->fallback_dx.clear();
+            } else {
+                if ((rc = restart_dx_log(c, false, [&] { return launch_dx_vlog(c); }))) return rc;
+                c->dxtab_log = true;
+            }
+        }
+    }
+    return RH_OK;
+}
+
+// ---- Vienna-BL model, hp from the two-molecule ensemble: sweeps over s1+s2 on s_dx, the folds on s_mc.  Without structure
+// constraints the sweeps are seeded: their cells on one strand are copied from the folds of the same pairs (vlin_co_seed), so they
+// start behind the inside sweep of the folds instead of next to it.  A flagged pair -- or, seeded, a flagged sequence: what was
+// copied from its fold is not usable -- sends the batch of pairs to the log-space kernels, or ends the attempt (defer_log)
+static int schedule_vienna_cofold(rh_ctx* c, Attempt* at)
+{
+    int rc;
+    const bool seed = c->has_dx && c->has_mc && c->mode != RH_MODE_LOG && c->co_seed && !c->mc.allow && !c->co.allow && c->mc.ns == 2 * c->co.ns;
+    c->co.seeded = seed ? 1 : 0;
+    bool lin_launched = false;   // (its overflow flags are read after the McCaskill stream has been fed: the two overlap)
+    const auto launch_lin = [&]() -> int {   // scaled linear sweeps over s1+s2, one graph of both phases
+        if (int r = run_graphed(c, c->g_dx, c->s_dx, 2, launch_mc_vlin, mc_vlin_args(c, 0, true), mc_vlin_args(c, 1, true))) return r;
+        c->last_dx_path = 1;
+        lin_launched = true;
+        return RH_OK;
+    };
+    if (c->has_dx) {
+        HIP_TRY(c, hipMemsetAsync(c->d_cobp.p, 0, sizeof(double) * c->co.tri_stride * c->co.ns, c->s_dx));
+        if (c->mode == RH_MODE_LOG) {
+            if ((rc = launch_cofold(c))) return rc;
+            if (c->last_dx_path != 3) c->last_dx_path = 2;
+        } else if (!seed) {
+            if ((rc = launch_lin())) return rc;
+        }
+    }
+    if ((rc = close_dx_phase(c))) return rc;
+
+    bool overflowed;
+    const auto seeded_sweeps = [&]() -> int {   // the inside tables of both molecules are final behind kEvMcInside
+        if (!seed) return RH_OK;
+        HIP_TRY(c, hipStreamWaitEvent(c->s_dx, c->ev[kEvMcInside], 0));
+        HIP_TRY(c, hipEventRecord(c->ev[kEvDxStart], c->s_dx));
+        if (int r = launch_lin()) return r;
+        return close_dx_phase(c);
+    };
+    if ((rc = vienna_folds(c, at, seeded_sweeps, &overflowed))) return rc;
+
+    if (lin_launched && c->mode == RH_MODE_AUTO) {
+        std::vector<int> bad;
+        if ((rc = flagged(c, c->d_cobad.as<int>(), c->co.ns, c->s_dx, &bad))) return rc;
+        const bool redo = (seed && overflowed) || !bad.empty();
+        if (redo && at->defer_log) {
+            c->tables_dirty = true; at->deferred = true;
+            at->flagged_pairs.insert(at->flagged_pairs.end(), bad.begin(), bad.end());
+        } else if (redo) {
+            at->went_log = true;
+            c->tables_dirty = true;
+            if ((rc = restart_dx_log(c, true, [&] { return launch_cofold(c); }))) return rc;
+        }
+    }
+    return RH_OK;
+}
+
+// ---- the driver: what every product needs before and behind its schedule
+static int run_attempt(rh_ctx* c, Attempt* at)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->tev_n = 0;
+    c->n_launch[0] = c->n_launch[1] = c->n_launch[2] = 0;
+    c->n_far[0] = c->n_far[1] = c->n_far[2] = 0;
+    c->last_path = 0;
+    c->last_went_log = false;
+    c->fallback_mc.clear(); c->fallback_dx.clear(); c->rescaled_mc.clear(); c->rescaled_dx.clear();
+    const bool vienna = c->model == RH_MODEL_VIENNA_BL, cofold = vienna && c->hybrid == RH_HYBRID_COFOLD;
+    // the organisation of each sweep's linear first pass: decided here, on every compute (a replayed graph does not call its launcher);
+    // the arguments of the launchers carry the same plans to them
+    for (int phase = 0; phase < 2; phase++) c->plan[phase] = vienna ? plan_mc_vlin(c, phase, false, c->mc.nmax) : plan_mc_lin(c, phase, c->mc.nmax);
+    c->plan[2] = !vienna ? plan_dx_lin(c, c->dx_w) : cofold ? plan_mc_vlin(c, 0, true, c->co.nmax) : plan_dx_vlin(c->vienna_sem == kViennaSem20);
+    // the path of the duplex / pf_duplex sweeps: rh_set_duplex_mode, or what rh_set_mode says
+    const int dx_mode = c->duplex_mode == RH_MODE_INHERIT ? c->mode : c->duplex_mode;
+    // the linear duplex kernels share d_dxtab with the log-space ones and read zero pad columns: after a log-space compute on this
+    // upload (another mode since, or a fallback) the image stage() left is gone
+    if (c->has_dx && c->dxtab_log && dx_mode != RH_MODE_LOG && !cofold) {
+        HIP_TRY(c, hipMemsetAsync(c->d_dxtab.p, 0, c->dx_bytes, c->s_dx));
+        c->dxtab_log = false;
+    }
+    HIP_TRY(c, hipEventRecord(c->ev[kEvDxStart], c->s_dx));   // (the McCaskill stream's start event: where the schedule turns to it)
+
+    if (int rc = !vienna ? schedule_contrafold(c, dx_mode) : cofold ? schedule_vienna_cofold(c, at) : schedule_vienna_duplex(c, dx_mode, at)) return rc;
+
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(c->s_mc));
     HIP_TRY(c, hipStreamSynchronize(c->s_dx));
     float t01 = 0, t12 = 0, t34 = 0, t02 = 0;
-    HIP_TRY(c, hipEventElapsedTime(&t01, c->ev[0], c->ev[1]));
-    HIP_TRY(c, hipEventElapsedTime(&t12, c->ev[out_from_ev5 && !c->overlap ? 5 : 1], c->ev[2]));
-    HIP_TRY(c, hipEventElapsedTime(&t02, c->ev[0], c->ev[2]));
-    HIP_TRY(c, hipEventElapsedTime(&t34, c->ev[3], c->ev[4]));
+    HIP_TRY(c, hipEventElapsedTime(&t01, c->ev[kEvMcStart], c->ev[kEvMcInside]));
+    HIP_TRY(c, hipEventElapsedTime(&t12, c->ev[c->overlap ? kEvMcInside : at->outside_from], c->ev[kEvMcEnd]));
+    HIP_TRY(c, hipEventElapsedTime(&t02, c->ev[kEvMcStart], c->ev[kEvMcEnd]));
+    HIP_TRY(c, hipEventElapsedTime(&t34, c->ev[kEvDxStart], c->ev[kEvDxEnd]));
     c->ms[0] = t01; c->ms[1] = t12; c->ms[2] = t34; c->ms[3] = std::max(t02, t34);
+    c->last_went_log = at->went_log;
     c->computed = true;
     return RH_OK;
 }
 
 int compute(rh_ctx* c)
 {
-    c->defer_log = false;
-    c->flagged_mc.clear();
     const bool ladder = c->model == RH_MODEL_VIENNA_BL && c->mode == RH_MODE_AUTO && c->scale_ladder && c->has_mc && c->h_vienna &&
                         c->vienna_sem != kViennaSem20 && !std::getenv("RH_VLIN_S");
-    if (!ladder) return compute_once(c);
+    if (!ladder) { Attempt at; return run_attempt(c, &at); }
     HIP_TRY(c, hipSetDevice(c->device));
-    // the exponent the batch starts with, then the others: larger ones ascending, smaller ones descending
+    // the exponent the batch starts with, then the others
     std::vector<int> order = {c->vlin_primary};
-    {
-        std::vector<std::pair<double, int>> all = {{c->vlin_m[0].h->s, -1}};
-        for (int r = 0; r < rh_ctx::kVRungs; r++) all.push_back({kVRungS[r], r});
-        std::sort(all.begin(), all.end());
-        const double s0 = c->vlin_primary < 0 ? c->vlin_m[0].h->s : kVRungS[c->vlin_primary];
-        for (const auto& e : all) if (e.first > s0 + 1e-12) order.push_back(e.second);
-        for (auto it = all.rbegin(); it != all.rend(); ++it) if (it->first < s0 - 1e-12) order.push_back(it->second);
-    }
+    for (int model : exponent_order(c->vlin_primary, c->vlin_m[0].h->s, kVRungS, rh_ctx::kVRungs)) order.push_back(model);
     // (An attempt that failed leaves Inf / NaN in the tables of the flagged sequences; the next attempt runs over them without a clear.
     //  That is sound because the vlin kernels mask every operand by SELECT (`ok ? x : 0.0`), never by a multiplication with 0, and
     //  rewrite every interior cell they read before reading it -- the invariant `tests: test_vienna_bl_scale_exponent_ladder` and
     //  tools/fuzz_ladder.py exercise: chains of hairpins that overflow the first exponent, results equal to the log-space path's.)
     int rc = RH_OK;
     const bool per_pair = !c->is_helper && c->pair_helper && c->has_dx && c->np >= 4 && !c->mc.allow && !c->co.allow;
+    const auto sort_unique = [](std::vector<int>& v) { std::sort(v.begin(), v.end()); v.erase(std::unique(v.begin(), v.end()), v.end()); };
+    std::vector<int> flagged_seqs;   // by the deferred attempts so far
     for (size_t a = 0; a < order.size(); a++) {
         if ((rc = select_vlin(c, order[a]))) break;
-        c->defer_log = a + 1 < order.size();
-        c->flagged_pairs.clear();
-        if ((rc = compute_once(c))) break;
-        if (c->deferred && a == 0 && per_pair) {
-            std::sort(c->flagged_pairs.begin(), c->flagged_pairs.end());
-            c->flagged_pairs.erase(std::unique(c->flagged_pairs.begin(), c->flagged_pairs.end()), c->flagged_pairs.end());
+        Attempt at;
+        at.defer_log = a + 1 < order.size();
+        if ((rc = run_attempt(c, &at))) break;
+        flagged_seqs.insert(flagged_seqs.end(), at.flagged_seqs.begin(), at.flagged_seqs.end());
+        if (at.deferred && a == 0 && per_pair) {
+            sort_unique(at.flagged_pairs);
             // cost: the helper pays the launch latency of a few pairs (tens of ms per attempt at n = 500 - 1000, whatever the batch), a
             // second pass over the batch pays its whole device time again: the helper wins when the flagged pairs are a small share
             // (measured at n = 500: equal at 64 pairs and one flagged pair, 2 x at 256).  RH_PAIR_HELPER=2: whenever at most half are flagged
             const size_t share = c->pair_helper >= 2 ? 2 : 16;
-            if (!c->flagged_pairs.empty() && share * c->flagged_pairs.size() <= (size_t)c->np) {
-                rc = recompute_pairs_on_helper(c, c->flagged_pairs);
+            if (!at.flagged_pairs.empty() && share * at.flagged_pairs.size() <= (size_t)c->np) {
+                rc = recompute_pairs_on_helper(c, at.flagged_pairs);
                 break;
             }
         }
-        if (!c->deferred) {
+        if (!at.deferred) {
             if (a > 0) {   // held by another exponent
                 c->last_path = 3;
-                std::sort(c->flagged_mc.begin(), c->flagged_mc.end());
-                c->flagged_mc.erase(std::unique(c->flagged_mc.begin(), c->flagged_mc.end()), c->flagged_mc.end());
-                if (!c->went_log) {   // (the last attempt may still have ended in log space)
-                    c->rescaled_mc = c->flagged_mc;
+                sort_unique(flagged_seqs);
+                if (!at.went_log) {   // (the last attempt may still have ended in log space)
+                    c->rescaled_mc = flagged_seqs;
                     if (c->scale_memory && c->mc.ns >= 8) c->vlin_primary = order[a];   // a batch, not a single call: the next one starts here
                 }
             }
             break;
         }
     }
-    c->defer_log = false;
     const int back = select_vlin(c, c->vlin_primary);
     return rc ? rc : back;
 }

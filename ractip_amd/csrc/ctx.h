@@ -15,6 +15,7 @@
 #include "score_model.h"
 #include "lin_model.h"
 #include "vienna_model.h"
+#include "scale_order.h"
 
 struct rh_ctx;
 
@@ -148,12 +149,23 @@ struct DxLinArgs {   // launch_dx_lin (CONTRAfold model: dm, hm) and launch_dx_v
 };
 static_assert(std::is_trivially_copyable_v<McLinArgs> && std::is_trivially_copyable_v<McVlinArgs> && std::is_trivially_copyable_v<DxLinArgs>);
 
+// the events of one compute (Ctx::ev): three phases on the McCaskill stream, one on the hybridization stream
+enum Ev {
+    kEvMcStart,     // s_mc: before the inside sweep
+    kEvMcInside,    // s_mc: behind the inside sweep
+    kEvMcEnd,       // s_mc: behind the outside sweep and the accessibility
+    kEvDxStart,     // s_dx: before the hybridization sweeps
+    kEvDxEnd,       // s_dx: behind them
+    kEvMcOutside,   // s_mc: before the outside sweep, where something ran between the two sweeps (the seeded two-molecule sweeps)
+    kEvCount
+};
+
 struct Ctx {   // (the fields of rh_ctx, below)
     int device = 0;
     int model = 0;
     std::string err;
     hipStream_t s_mc = nullptr, s_dx = nullptr;
-    hipEvent_t ev[6] = {};  // mc: start, after inside, after outside ; dx: start, end ; all: end
+    hipEvent_t ev[kEvCount] = {};
     DevObj<ScoreModel> d_model;
     // other scale exponents of the linear McCaskill path, tried on the problems that leave the double range before the log-space
     // kernels are (retry_mc_lin_rungs): built on first use from the host copy of the score model
@@ -167,7 +179,6 @@ struct Ctx {   // (the fields of rh_ctx, below)
     // than half of the last batch (a stream of structured RNAs does not pay a failed first pass per batch)
     LinSet lin0;
     int lin_primary = -1;
-    int rescued_by[kRungs + 1] = {0, 0, 0, 0};  // sequences the last ladder moved to the default exponent [0] / rung k [k + 1]
     std::vector<int> rescaled_mc;              // sequences the last compute recomputed on the linear path with another exponent (rh_batch_fallbacks which = 2)
     DevObj<ViennaDx> d_vienna;     // RH_MODEL_VIENNA_BL only
     int vienna_sem = 0;            // kViennaSem18 / kViennaSem20 (0: CONTRAfold model)
@@ -179,19 +190,15 @@ struct Ctx {   // (the fields of rh_ctx, below)
     ViennaDx* h_vienna = nullptr;              // host copy of the energy tables the rung models are built from
     VLinSet vlin_m[kVRungs + 1];     // [0] = default, [k + 1] = rung k (owners)
     int vlin_cur = -1, vlin_primary = -1;      // model selected now / the one a batch starts with
-    bool defer_log = false, deferred = false;  // compute_once: a flagged problem ends the attempt instead of starting the log-space kernels
     // Vienna-BL, per-pair route of the ladder (round 3): when at most half of the pairs of a batch are flagged, only THOSE pairs are recomputed --
     // on a helper context of the same model (its own tables, its own whole-batch ladder and log-space fallback) -- and their results are
     // copied into this batch's result buffers; every other pair keeps the result of the first pass bit for bit
     rh_ctx* helper = nullptr;
     bool is_helper = false;
     int pair_helper = 1;           // RH_PAIR_HELPER=0: the whole batch is run again (round-2 behaviour); 2: helper whenever at most half of the pairs are flagged
-    std::vector<int> flagged_pairs;            // pairs the deferred attempt flagged (folds, two-molecule sweeps or pf_duplex)
     std::string p_param, p_defaults;           // creation arguments, for the helper
     bool p_has_param = false, p_has_defaults = false;
     int p_use_bl = 1, p_sem = 0;
-    bool went_log = false;                     // compute_once (Vienna-BL): the batch was recomputed by the log-space kernels
-    std::vector<int> flagged_mc;               // sequences the deferred attempts flagged
     DevObj<VLinModel> d_vdxl;      // the same tables at the duplex scale (duplex_vlin.hip)
     DevObj<VDxLin> d_vdx;
     double vdx_s = 0.27;           // log Z of pf_duplex per unit of a+b: 0.23 (random ACGU) .. 0.32 (70 % GC)
@@ -246,7 +253,9 @@ struct Ctx {   // (the fields of rh_ctx, below)
     int lin_w_in = 4;              // ... of the inside kernel (fewer, longer wavefronts: less per-wavefront scalar overhead)
     int lin_bs = 16;               // block size of the far/near split of the O(n^3) terms (0 = off)
     int last_path = 0;             // 1 = linear, 2 = log-space, 3 = linear then log-space fallback
-    SweepPlan plan[3];             // of the linear first pass over the batch as uploaded: inside, outside, hybridization (compute_once)
+    bool last_went_log = false;    // Vienna-BL: the last compute ended with the folds or the two-molecule sweeps on the log-space kernels
+                                   // (recompute_pairs_on_helper reads it from the helper context, to list its pairs under the right mechanism)
+    SweepPlan plan[3];             // of the linear first pass over the batch as uploaded: inside, outside, hybridization (run_attempt)
     int max_w = 1;                 // accessibility widths 1..max_w (src/ractip.cpp:370-375); the CONTRAfold path has width 1 only
 
     // current batch (host mirror)
@@ -359,6 +368,8 @@ const Row& row_of(const Row (&rows)[N], Pred&& is)
     assert(!"the plan names a kernel combination that has no row");
     return rows[0];
 }
+// sequence -> XCD affinity only when the batch spreads evenly over the 8 XCDs (speed only)
+inline int xcd_pin(int ns) { return ns % 8 == 0 ? 1 : 0; }
 // sequence-major launch order (sequence -> XCD affinity) or group-major
 inline dim3 seq_grid(int pin, int ns, int groups) { return pin ? dim3(ns, groups) : dim3(groups, ns); }
 // one pass of a McCaskill sweep on the scaled linear kernels: what the schedules and the block-product steps share
@@ -396,7 +407,7 @@ int launch_dx_lin(rh_ctx* c, const DxLinArgs& A);
 int launch_dx_vlin(rh_ctx* c, const DxLinArgs& A);
 int launch_dx_vlog(rh_ctx* c);
 // fallbacks.hip
-int retry_mc_lin_rungs(rh_ctx* c, const LinSet* first, std::vector<int>* rest);
+int retry_mc_lin_rungs(rh_ctx* c, int first_model, std::vector<int>* rest, int (&rescued_by)[Ctx::kRungs + 1]);
 int recompute_mc_subset_log(rh_ctx* c, const std::vector<int>& F);
 int retry_dx_lin_rungs(rh_ctx* c, std::vector<int>* rest);
 int recompute_dx_subset_log(rh_ctx* c, const std::vector<int>& F);

@@ -112,7 +112,7 @@ int recompute_mc_subset_log(rh_ctx* c, const std::vector<int>& F)
     HIP_TRY(c, hipStreamSynchronize(c->s_mc));   // (the uploads of `sub`)
     // (no table is cleared: the tables of the linear pass are dead, and the log-space kernels run over them as they are)
     double* sub_logz = c->d_subup.as<double>() + (size_t)c->mc.ld * c->max_w * nsub;
-    if ((rc = launch_mc_log(c, nsub % 8 == 0 ? 1 : 0, S, sub_logz))) return rc;
+    if ((rc = launch_mc_log(c, xcd_pin(nsub), S, sub_logz))) return rc;
     for (int k = 0; k < nsub; k++) {   // scatter to the flagged sequences' slots
         HIP_TRY(c, scatter_mc(c, k, F[k]));
         HIP_TRY(c, hipMemcpyAsync(c->d_mclogz.as<double>() + F[k], sub_logz + k, sizeof(double), hipMemcpyDeviceToDevice, c->s_mc));
@@ -145,35 +145,29 @@ int ensure_rungs(rh_ctx* c)
     return RH_OK;
 }
 
-// `first`: the model of the main pass; `rest`: the sequences it flagged, on return those that no rung could hold (for the log-space
-// kernels)
-int retry_mc_lin_rungs(rh_ctx* c, const LinSet* first, std::vector<int>* rest)
+// `first`: the model of the main pass (-1: the default exponent, k: rung k); `rest`: the sequences it flagged, on return those that
+// no rung could hold (for the log-space kernels); rescued_by: the sequences moved to the default exponent [0] / to rung k [k + 1]
+int retry_mc_lin_rungs(rh_ctx* c, int first_model, std::vector<int>* rest, int (&rescued_by)[rh_ctx::kRungs + 1])
 {
+    for (int& q : rescued_by) q = 0;
     if (!c->scale_ladder || rest->empty()) return RH_OK;
     int rc;
     if ((rc = ensure_rungs(c))) return rc;
     const McBatch& B = c->mc;
+    const LinSet* first = first_model < 0 ? &c->lin0 : &c->lin_r[first_model];
     // direction: log Z = log(Z~) + s n of the failed pass is +Inf / NaN / large after an overflow, -Inf or below s n after an underflow
     std::vector<double> lz(B.ns);
     HIP_TRY(c, hipMemcpyAsync(lz.data(), c->d_mclogz.p, sizeof(double) * B.ns, hipMemcpyDeviceToHost, c->s_mc));
     HIP_TRY(c, hipStreamSynchronize(c->s_mc));
     std::vector<int> over, under;
     for (int k : *rest) ((lz[k] == lz[k] && lz[k] < first->h.s * c->n[k]) ? under : over).push_back(k);
-    for (int& q : c->rescued_by) q = 0;
     // the exponents to try: larger ones in ascending order for the overflows, smaller ones in descending order for the underflows
     // (model -1 = the default exponent, when the main pass ran on a rung)
-    struct Try { int model; bool up; };
-    std::vector<Try> tries;
-    {
-        std::vector<std::pair<double, int>> all = {{c->lin0.h.s, -1}};
-        for (int r = 0; r < rh_ctx::kRungs; r++) all.push_back({kRungS[r], r});
-        std::sort(all.begin(), all.end());
-        for (const auto& e : all) if (e.first > first->h.s + 1e-12) tries.push_back({e.second, true});
-        for (auto it = all.rbegin(); it != all.rend(); ++it) if (it->first < first->h.s - 1e-12) tries.push_back({it->second, false});
-    }
-    for (const Try& t : tries) {
-        const int rung = t.model;
-        std::vector<int>& F = t.up ? over : under;
+    size_t n_larger = 0;
+    const std::vector<int> tries = exponent_order(first_model, c->lin0.h.s, kRungS, rh_ctx::kRungs, &n_larger);
+    for (size_t t = 0; t < tries.size(); t++) {
+        const int rung = tries[t];
+        std::vector<int>& F = t < n_larger ? over : under;
         if (F.empty()) continue;
         const SubBatch sub = gather(c, F, 1, B.lds);
         const int nsub = sub.nsub;
@@ -203,7 +197,7 @@ int retry_mc_lin_rungs(rh_ctx* c, const LinSet* first, std::vector<int>* rest)
             HIP_TRY(c, scatter_mc(c, k, F[k]));
             lz[F[k]] = slz[k];
             c->rescaled_mc.push_back(F[k]);
-            c->rescued_by[rung + 1]++;
+            rescued_by[rung + 1]++;
         }
         F.swap(still);
     }
@@ -353,14 +347,12 @@ int recompute_pairs_on_helper(rh_ctx* c, const std::vector<int>& P)
     c->last_path = 3;
     if (c->last_dx_path == 1 || c->last_dx_path == 0) c->last_dx_path = 3;
     c->rescaled_mc.clear(); c->fallback_mc.clear(); c->fallback_dx.clear();
-    const bool h_log = h->went_log || h->last_path == 2 || (h->last_path == 3 && h->rescaled_mc.empty() && !h->fallback_mc.empty());
+    const bool h_log = h->last_went_log || h->last_path == 2 || (h->last_path == 3 && h->rescaled_mc.empty() && !h->fallback_mc.empty());
     for (int k = 0; k < nsub; k++) {
         if (h_log) { c->fallback_mc.push_back(2 * P[k]); c->fallback_mc.push_back(2 * P[k] + 1); c->fallback_dx.push_back(P[k]); }
         else { c->rescaled_mc.push_back(2 * P[k]); c->rescaled_mc.push_back(2 * P[k] + 1); }
     }
-    c->deferred = false;
     c->tables_dirty = true;
-    c->computed = true;
     return RH_OK;
 }
 

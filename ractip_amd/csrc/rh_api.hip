@@ -243,7 +243,7 @@ static rh_ctx* create_ctx(int device, int model, const char* param_file, const c
         }
     }
     c->h_vienna = host_vienna;   // (kept: the rung models of the scale-exponent ladder are built from it)
-    for (int k = 0; ok && k < 6; k++) ok = hipEventCreate(&c->ev[k]) == hipSuccess;
+    for (int k = 0; ok && k < kEvCount; k++) ok = hipEventCreate(&c->ev[k]) == hipSuccess;
     if (!ok) {
         fail(nullptr, RH_ERR_HIP, "context setup failed: %s", hipGetErrorString(hipGetLastError()));
         rh_destroy(c);
@@ -506,7 +506,7 @@ int rh_batch_kernels(rh_ctx* c, const char* fine[3], const char* far[3], int n_f
 {
     if (!c) return RH_ERR_ARG;
     if (!c->computed) return fail(c, RH_ERR_ARG, "no computed batch");
-    // the plans of the linear first pass (compute_once) where it stood; the fixed names of the log-space kernels where it did not
+    // the plans of the linear first pass (run_attempt, compute.hip) where it stood; the fixed names of the log-space kernels where it did not
     const bool vienna = c->model == RH_MODEL_VIENNA_BL, lin = c->last_path == 1, dx_lin = c->last_dx_path == 1;
     const char* names[6] = {"", "", "", "", "", ""};
     if (c->has_mc) {
