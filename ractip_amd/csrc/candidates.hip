@@ -51,10 +51,12 @@ __global__ __launch_bounds__(256) void cand_count(const double* __restrict__ bas
     if (lane == 0) counts[row] = c;
 }
 __global__ __launch_bounds__(256) void cand_write(const double* __restrict__ base, int kind, int n, int n2, int ld, float th,
-                                                  int nrows, const int* __restrict__ offsets, rh_cand* __restrict__ out, int cap)
+                                                  int nrows, const int* __restrict__ counts, const int* __restrict__ offsets,
+                                                  rh_cand* __restrict__ out, int cap)
 {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= nrows) return;
+    if (counts[row] == 0) return;   // the count pass found nothing in this row: leave it unread
     const RowSpan r = cand_row(base, kind, n, n2, ld, row);
     if (!r.ok) return;
     int pos = offsets[row];
@@ -110,11 +112,12 @@ __global__ __launch_bounds__(256) void cand_count_all(const double* __restrict__
 }
 __global__ __launch_bounds__(256) void cand_write_all(const double* __restrict__ bp, const double* __restrict__ hp, const double* __restrict__ up,
                                                       const int* __restrict__ nn, size_t tri_stride, size_t hp_stride, int up_ld, int hp_ld,
-                                                      int which, int rmax, float th, const int* __restrict__ offsets,
-                                                      rh_cand* __restrict__ out, int cap)
+                                                      int which, int rmax, float th, const int* __restrict__ counts,
+                                                      const int* __restrict__ offsets, rh_cand* __restrict__ out, int cap)
 {
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63, p = blockIdx.y;
     if (r >= rmax) return;
+    if (counts[(size_t)p * rmax + r] == 0) return;   // the count pass found nothing in this row: leave it unread
     const RowSpan rs = cand_row_all(bp, hp, up, nn, tri_stride, hp_stride, up_ld, hp_ld, which, p, r);
     if (!rs.ok) return;
     int pos = offsets[(size_t)p * rmax + r];
@@ -176,7 +179,7 @@ int rh_batch_candidates(rh_ctx* c, int p, int which, float threshold, rh_cand* o
         if ((rc = ensure(c, c->d_cand, sizeof(rh_cand) * (size_t)take, false))) return rc;
         HIP_TRY(c, hipMemcpyAsync(d_offsets, offsets.data(), sizeof(int) * nrows, hipMemcpyHostToDevice, c->s_mc));
         hipLaunchKernelGGL(cand_write, dim3((nrows + 3) / 4), dim3(256), 0, c->s_mc, v.base, v.kind, v.n, v.n2, v.ld, threshold,
-                           nrows, d_offsets, c->d_cand.as<rh_cand>(), take);
+                           nrows, d_counts, d_offsets, c->d_cand.as<rh_cand>(), take);
         HIP_TRY(c, hipMemcpyAsync(out, c->d_cand.p, sizeof(rh_cand) * (size_t)take, hipMemcpyDeviceToHost, c->s_mc));
         HIP_TRY(c, hipStreamSynchronize(c->s_mc));
     }
@@ -213,7 +216,7 @@ int rh_batch_candidates_all(rh_ctx* c, int which, float threshold, rh_cand* out,
         if ((rc = ensure(c, c->d_cand, sizeof(rh_cand) * (size_t)take, false))) return rc;
         HIP_TRY(c, hipMemcpyAsync(d_offsets, offsets.data(), sizeof(int) * nrows, hipMemcpyHostToDevice, c->s_mc));
         hipLaunchKernelGGL(cand_write_all, grid, dim3(256), 0, c->s_mc, c->d_bp.as<const double>(), c->d_hp.as<const double>(), c->d_up.as<const double>(),
-                           c->d_n.as<const int>(), c->mc.tri_stride, c->dx.tab_stride, c->mc.ld * c->max_w, which >= 3 ? c->max_w : c->dx.ldd, which, rmax, threshold, d_offsets,
+                           c->d_n.as<const int>(), c->mc.tri_stride, c->dx.tab_stride, c->mc.ld * c->max_w, which >= 3 ? c->max_w : c->dx.ldd, which, rmax, threshold, d_counts, d_offsets,
                            c->d_cand.as<rh_cand>(), take);
         HIP_TRY(c, hipMemcpyAsync(out, c->d_cand.p, sizeof(rh_cand) * (size_t)take, hipMemcpyDeviceToHost, c->s_mc));
         HIP_TRY(c, hipStreamSynchronize(c->s_mc));

@@ -677,13 +677,87 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
 constexpr int kLzRows = 16;
 // A streaming reduction: the work of a chunk is the list of items (row, k), row = 0..kLzRows-1, k = 0..nk-1, item (row, k) being
 // column alo + 256 k + thread of the row; nk covers the longest row the batch shape allows, so the list is the same for every
-// workgroup and every thread adds its items in the order (sd, a + 256 k) whatever the pair.  Eight items at a time: all their loads
-// (letters and table value, from an address clamped into the row) are issued before anything is tested, and an item that is no cell or
-// no complementary pair is dropped by SELECT -- a load behind `if (!pairs) continue` is only issued once the letters have arrived.
-// The row factor is the same for the whole row: one pow() per row and workgroup, through LDS.
-__global__ __launch_bounds__(256) void dxl_logz_part(DxLinBatch B, const DxLinModel* __restrict__ L, double* __restrict__ zpart, int* __restrict__ cpart, int nchunk)
+// workgroup and every thread adds its items in the order (sd, a + 256 k) whatever the pair.  Eight items at a time: the table values
+// of the next eight (from an address clamped into the row) are in flight while these eight are added, and an item that is no cell or
+// no complementary pair is dropped by SELECT.  Only the table value of an item comes from global memory: the letters of the pair and
+// the 275 weights E_dl / E_dr / E_hc are staged in LDS at the head of the workgroup (one vector-memory instruction per item, not
+// eight -- the kernel was bound by address processing, not by HBM).  The staging loads and the first eight table values are issued
+// together, in front of the one barrier.  The row factor is the same for the whole row: one pow() per row and workgroup, through LDS.
+constexpr int kLzU = 8;
+constexpr int kLzWeights = 125 + 125 + 25;                 // E_dl, E_dr, E_hc as one LDS array
+constexpr int kLzWeightBytes = (kLzWeights * 8 + 15) & ~15;
+constexpr int kLzLdsMax = 64 * 1024 - 512;                 // dynamic LDS the launch may ask for (the static arrays take the rest)
+static_assert(kLzWeights > kLzThreads && kLzWeights <= 2 * kLzThreads, "every thread stages one weight, the first kLzWeights - kLzThreads a second");
+// bytes of dynamic LDS for a batch whose sequence rows are `lds` bytes (the kernel derives the same layout from B.lds); 0: the letters
+// of a pair do not fit (sequences of some 31 000 letters, whose duplex tables no device holds) and the launcher refuses the batch
+size_t dxl_logz_lds_bytes(int lds)
 {
-    constexpr int U = 8;
+    const size_t bytes = (size_t)kLzWeightBytes + 2 * (size_t)lds;
+    return bytes <= (size_t)kLzLdsMax ? bytes : 0;
+}
+struct LzItem { int i, j, sdc; bool live; };
+__device__ __forceinline__ LzItem lz_item(int sd0, int row, int k, int L1, int L2, int smax)
+{
+    const int sd = sd0 + row;
+    const int sdc = sd <= smax ? sd : smax;
+    const int alo = sdc - L2 > 1 ? sdc - L2 : 1, ahi = sdc - 1 < L1 ? sdc - 1 : L1;
+    const int a = alo + 256 * k + (int)threadIdx.x;
+    LzItem t;
+    t.live = sd <= smax && a <= ahi;
+    t.i = t.live ? a : alo;
+    t.j = L2 + 1 - (sdc - t.i);
+    t.sdc = sdc;
+    return t;
+}
+__device__ __forceinline__ void lz_load(const double* __restrict__ in, int lda, int sd0, int row, int k, int nk, int L1, int L2, int smax, double (&v)[kLzU])
+{
+#pragma unroll
+    for (int u = 0; u < kLzU; u++) {
+        const LzItem t = lz_item(sd0, row, k, L1, L2, smax);
+        v[u] = in[(size_t)t.sdc * lda + t.i];
+        if (++k == nk) { k = 0; row++; }
+    }
+}
+// s1 / s2 / E / srowf: LDS
+__device__ __forceinline__ void lz_sum(const uint8_t* __restrict__ s1, const uint8_t* __restrict__ s2, const double* __restrict__ E, const double* __restrict__ srowf,
+                                       const double* __restrict__ in, int lda, int sd0, int nk, int L1, int L2, int smax, double (&v)[kLzU],
+                                       double& acc, int& npair)
+{
+    constexpr int U = kLzU;
+    const int nitem = kLzRows * nk;                    // (a multiple of U)
+    int row = 0, k = 0;                                // item m = row * nk + k (wave-uniform)
+    for (int m0 = 0; m0 < nitem; m0 += U) {
+        double rowf[U], vn[U];
+        int x[U], y[U], xp[U], ym[U];
+        bool live[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const LzItem t = lz_item(sd0, row, k, L1, L2, smax);
+            live[u] = t.live;
+            x[u] = s1[t.i]; xp[u] = s1[t.i + 1]; y[u] = s2[t.j]; ym[u] = s2[t.j - 1];
+            rowf[u] = srowf[row];
+            if (++k == nk) { k = 0; row++; }
+        }
+        if (m0 + U < nitem) lz_load(in, lda, sd0, row, k, nk, L1, L2, smax, vn);
+        else {
+#pragma unroll
+            for (int u = 0; u < U; u++) vn[u] = 0.0;
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const bool on = live[u] && pairs(x[u], y[u]);
+            const double cl = rowf[u] * E[x[u] * 25 + y[u] * 5 + xp[u]] * E[125 + x[u] * 25 + y[u] * 5 + ym[u]] * E[250 + x[u] * 5 + y[u]];
+            const double next = fma(v[u], cl, acc);
+            acc = on ? next : acc;
+            npair += on ? 1 : 0;
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) v[u] = vn[u];
+    }
+}
+__global__ __launch_bounds__(kLzThreads) void dxl_logz_part(DxLinBatch B, const DxLinModel* __restrict__ L, double* __restrict__ zpart, int* __restrict__ cpart, int nchunk)
+{
+    extern __shared__ __align__(16) unsigned char lz_lds[];   // [kLzWeightBytes] weights, then [2][B.lds] letters (dxl_logz_lds_bytes)
     __shared__ double sm[4];
     __shared__ int sc[4];
     __shared__ double srowf[kLzRows];
@@ -697,44 +771,32 @@ __global__ __launch_bounds__(256) void dxl_logz_part(DxLinBatch B, const DxLinMo
         if (threadIdx.x == 0) { zpart[(size_t)pr * nchunk + chunk] = 0.0; cpart[(size_t)pr * nchunk + chunk] = 0; }
         return;
     }
+    double* const sE = reinterpret_cast<double*>(lz_lds);
+    uint8_t* const sl = lz_lds + kLzWeightBytes;
+    // staging loads first, then the first eight table values, then the stores to LDS: all of them in flight together
+    const auto weight = [&](int t) { return t < 125 ? L->E_dl[t] : t < 250 ? L->E_dr[t - 125] : L->E_hc[t - 250]; };
+    const double e0 = weight(threadIdx.x);
+    const double e1 = threadIdx.x < kLzWeights - kLzThreads ? weight(kLzThreads + threadIdx.x) : 0.0;
+    uint4 q = make_uint4(0, 0, 0, 0);
+    const int nq = 2 * B.lds / 16;   // (the two rows of a pair are adjacent and 16-byte aligned: lds is a multiple of 16)
+    if ((int)threadIdx.x < nq) q = reinterpret_cast<const uint4*>(s1)[threadIdx.x];
+    const int nmin = B.n1max < B.n2max ? B.n1max : B.n2max;
+    const int nk = (nmin + 255) / 256;                 // a row has at most min(L1, L2) cells
+    double v[kLzU];
+    lz_load(in, B.lda, sd0, 0, 0, nk, L1, L2, smax, v);
+    sE[threadIdx.x] = e0;
+    if (threadIdx.x < kLzWeights - kLzThreads) sE[kLzThreads + threadIdx.x] = e1;
+    if ((int)threadIdx.x < nq) reinterpret_cast<uint4*>(sl)[threadIdx.x] = q;
+    for (int t = kLzThreads + threadIdx.x; t < nq; t += kLzThreads) reinterpret_cast<uint4*>(sl)[t] = reinterpret_cast<const uint4*>(s1)[t];
     if (threadIdx.x < kLzRows) {
         // close~ = (lam*e^eu)^(L1+L2-sd) * lam^2 * dangles * helix_closing
         const int sd = sd0 + threadIdx.x;
         srowf[threadIdx.x] = pow(L->lam_eu, (double)(L1 + L2 - sd)) * L->lam_pow[2];
     }
     __syncthreads();
-    const int nmin = B.n1max < B.n2max ? B.n1max : B.n2max;
-    const int nk = (nmin + 255) / 256;                 // a row has at most min(L1, L2) cells
-    const int nitem = kLzRows * nk;                    // (a multiple of U)
     double acc = 0.0;
     int npair = 0;
-    int row = 0, k = 0;                                // item m = row * nk + k (wave-uniform)
-    for (int m0 = 0; m0 < nitem; m0 += U) {
-        double v[U], rowf[U];
-        int x[U], y[U], xp[U], ym[U];
-        bool live[U];
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const int sd = sd0 + row;
-            const int sdc = sd <= smax ? sd : smax;
-            const int alo = sdc - L2 > 1 ? sdc - L2 : 1, ahi = sdc - 1 < L1 ? sdc - 1 : L1;
-            const int a = alo + 256 * k + (int)threadIdx.x;
-            live[u] = sd <= smax && a <= ahi;
-            const int i = live[u] ? a : alo, j = L2 + 1 - (sdc - i);
-            x[u] = s1[i]; xp[u] = s1[i + 1]; y[u] = s2[j]; ym[u] = s2[j - 1];
-            v[u] = in[(size_t)sdc * B.lda + i];
-            rowf[u] = srowf[row];
-            if (++k == nk) { k = 0; row++; }
-        }
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const bool on = live[u] && pairs(x[u], y[u]);
-            const double cl = rowf[u] * L->E_dl[x[u] * 25 + y[u] * 5 + xp[u]] * L->E_dr[x[u] * 25 + y[u] * 5 + ym[u]] * L->E_hc[x[u] * 5 + y[u]];
-            const double next = fma(v[u], cl, acc);
-            acc = on ? next : acc;
-            npair += on ? 1 : 0;
-        }
-    }
+    lz_sum(sl, sl + B.lds, sE, srowf, in, B.lda, sd0, nk, L1, L2, smax, v, acc, npair);
     for (int o = 32; o > 0; o >>= 1) { acc += __shfl_xor(acc, o, 64); npair += __shfl_xor(npair, o, 64); }
     if ((threadIdx.x & 63) == 0) { sm[threadIdx.x >> 6] = acc; sc[threadIdx.x >> 6] = npair; }
     __syncthreads();

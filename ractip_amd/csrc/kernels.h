@@ -46,6 +46,8 @@ template <bool S20> __global__ void dxvl_logz_part(DxLinBatch B, const VLinModel
                                int* __restrict__ cpart, int nchunk);
 __global__ void dxvl_logz_final(DxLinBatch B, double s, const double* __restrict__ zpart, const int* __restrict__ cpart, int nchunk,
                                 double* __restrict__ zbar, double* __restrict__ logz, int* __restrict__ bad);
+constexpr int kLzThreads = 256;       // threads of a dxl_logz_part workgroup (its LDS staging is laid out for this count)
+size_t dxl_logz_lds_bytes(int lds);   // duplex_lin.hip: dynamic LDS of a dxl_logz_part launch (weights and the letters of a pair); 0 = does not fit
 __global__ void dxl_logz_part(DxLinBatch B, const DxLinModel* __restrict__ L, double* __restrict__ zpart, int* __restrict__ cpart, int nchunk);
 __global__ void dxl_logz_final(DxLinBatch B, const DxLinModel* __restrict__ L, const double* __restrict__ zpart, const int* __restrict__ cpart, int nchunk,
                                double* __restrict__ zbar, double* __restrict__ logz, int* __restrict__ bad);
@@ -87,10 +89,10 @@ __global__ void collect_logz(const double* __restrict__ mc_logz, rh::DxBatch D, 
 __global__ void log_finish(rh::McBatch B, double* __restrict__ logz);                                                       // launch_contrafold.hip
 // candidates.hip
 __global__ void cand_count(const double* __restrict__ base, int kind, int n, int n2, int ld, float th, int nrows, int* __restrict__ counts);
-__global__ void cand_write(const double* __restrict__ base, int kind, int n, int n2, int ld, float th, int nrows, const int* __restrict__ offsets,
-                           rh_cand* __restrict__ out, int cap);
+__global__ void cand_write(const double* __restrict__ base, int kind, int n, int n2, int ld, float th, int nrows, const int* __restrict__ counts,
+                           const int* __restrict__ offsets, rh_cand* __restrict__ out, int cap);
 __global__ void cand_count_all(const double* __restrict__ bp, const double* __restrict__ hp, const double* __restrict__ up, const int* __restrict__ nn,
                                size_t tri_stride, size_t hp_stride, int up_ld, int hp_ld, int which, int rmax, float th, int* __restrict__ counts);
 __global__ void cand_write_all(const double* __restrict__ bp, const double* __restrict__ hp, const double* __restrict__ up, const int* __restrict__ nn,
-                               size_t tri_stride, size_t hp_stride, int up_ld, int hp_ld, int which, int rmax, float th, const int* __restrict__ offsets,
-                               rh_cand* __restrict__ out, int cap);
+                               size_t tri_stride, size_t hp_stride, int up_ld, int hp_ld, int which, int rmax, float th, const int* __restrict__ counts,
+                               const int* __restrict__ offsets, rh_cand* __restrict__ out, int cap);

@@ -63,6 +63,8 @@ int launch_dx_lin(rh_ctx* c, const DxLinArgs& A)
     const int steps = smax / 2;
     const int groups = (X.n1max + 2 + 63) / 64;
     const double leu = A.hm->lam_eu, l2 = A.hm->lam_pow[2];
+    const size_t lz_lds = dxl_logz_lds_bytes(X.lds);
+    if (!lz_lds) return fail(c, RH_ERR_UNSUPPORTED, "duplex log Z: the letters of a pair do not fit in LDS");
     if (P.org == SweepPlan::kDxStrip8) {
         for (int t = 0; 8 * t < smax - 1; t++) {
             for (int k = 0; k < 8; k++) X.pw8[k] = std::pow(leu, 8.0 * t + k) * l2;
@@ -86,7 +88,7 @@ int launch_dx_lin(rh_ctx* c, const DxLinArgs& A)
         c->n_launch[2]++;
     }
     int* cpart = (int*)(A.zpart + (size_t)X.np * A.lz_chunks);
-    hipLaunchKernelGGL(dxl_logz_part, dim3(A.lz_chunks, X.np), dim3(256), 0, c->s_dx, X, dm, A.zpart, cpart, A.lz_chunks);
+    hipLaunchKernelGGL(dxl_logz_part, dim3(A.lz_chunks, X.np), dim3(kLzThreads), lz_lds, c->s_dx, X, dm, A.zpart, cpart, A.lz_chunks);
     hipLaunchKernelGGL(dxl_logz_final, dim3((X.np + 63) / 64), dim3(64), 0, c->s_dx, X, dm, (const double*)A.zpart, (const int*)cpart,
                        A.lz_chunks, A.zbar, A.logz, A.bad);
     hipLaunchKernelGGL(dxl_posterior, dim3((X.n1max + 31) / 32, (smax - 1 + 31) / 32, X.np), dim3(256), 0, c->s_dx, X, (const double*)A.zbar, A.bad);
