@@ -10,6 +10,8 @@ random ones) and the reference's outputs for them in double precision:
   duplex (DuplexEngine<double>): inside/outside logZ, posterior (n1+1)(n2+1),
     and for short pairs the inside/outside tables.
 Also the float-engine logZ (what RactIP itself instantiates, ractip.cpp:200-201).
+A second fixture, tests/golden/contrafold_planted_loops.npz (GOLDEN_ONLY=planted_loops writes it alone): log Z and the two
+stem posteriors of the 528 planted single-loop inputs of tests/_contrafold_cases.py (shape_set).
 """
 import ctypes, glob, os, random, sys
 import numpy as np
@@ -37,6 +39,31 @@ def golden_2000b(out):
     out["mc2000b/val"] = post[idx]
     print("mc2000b logZ=%.9f sum=%.9f nnz=%d" % (z, post.sum(), idx.size))
 
+
+def golden_planted_loops():
+    """tests/golden/contrafold_planted_loops.npz: InferenceEngine<double> on every interior loop (l1, l2), l1 + l2 <= 31, planted
+    between two GC stems (the generators: tests/_contrafold_cases.py)"""
+    sys.path.insert(0, os.path.join(here, "..", "tests"))
+    import _contrafold_cases as edges
+    shapes = edges.shape_set()
+    logz, outer, inner = [], [], []
+    for c in shapes:
+        n = len(c.seq)
+        post = np.zeros((n + 1) * (n + 2) // 2)
+        logz.append(lib.ref_inference(c.seq.encode(), 0, post.ctypes.data, None, None))
+        p = edges.stem_probs(post, c)
+        outer.append(p[0])
+        inner.append(p[1])
+    dst = os.path.join(here, "..", "tests", "golden", "contrafold_planted_loops.npz")
+    np.savez_compressed(dst, seq=np.array([c.seq.encode() for c in shapes]), loop=np.array([(c.l1, c.l2, c.h, c.lead) for c in shapes]),
+                        logZ=np.array(logz), outer=np.array(outer), inner=np.array(inner))
+    print("wrote", os.path.normpath(dst), os.path.getsize(dst), "bytes; stem posteriors within the budget >= %.4f / %.4f"
+          % (min(o for o, c in zip(outer, shapes) if c.l1 + c.l2 <= 30), min(i for i, c in zip(inner, shapes) if c.l1 + c.l2 <= 30)))
+
+
+if os.environ.get("GOLDEN_ONLY") == "planted_loops":
+    golden_planted_loops()
+    sys.exit(0)
 
 if os.environ.get("GOLDEN_ONLY") == "2000b":   # add this block to the existing fixture without regenerating the rest
     dst = os.path.join(here, "..", "tests", "golden", "contrafold_golden.npz")
@@ -211,3 +238,4 @@ out["dx_names"] = np.array(pnames)
 dst = os.path.join(here, "..", "tests", "golden", "contrafold_golden.npz")
 np.savez_compressed(dst, **out)
 print("wrote", os.path.normpath(dst), os.path.getsize(dst), "bytes")
+golden_planted_loops()
