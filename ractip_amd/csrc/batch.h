@@ -35,7 +35,25 @@ enum McTable {
     T_COUNT
 };
 
-constexpr int kViennaMcTables = 16;   // VmTable of mccaskill_vienna.hip (own enum, same square layout)
+// ---- scaled linear McCaskill path (mccaskill_lin.hip, mccaskill_strip.hip, mccaskill_far.hip): the same buffer, tables stored
+//      DIAGONAL-MAJOR (cell (i, i+d) at [d*ld + i])
+enum LinTable { L_FC = 0, L_FCX, L_FCA, L_FM1, L_FM, L_FCO, L_FCOX, L_FM2O, L_FMO, L_FM1O,
+                L_FM2F, L_FMOF, L_FM1OF,  // far-block partial sums (mccaskill_far.hip)
+                L_COUNT };
+static_assert((int)L_COUNT <= (int)T_COUNT, "linear tables reuse the log-space table buffer");
+
+// ---- Vienna-BL model, log space (mccaskill_vienna.hip): square ld x ld tables per sequence; *T = stored transposed ([j][i])
+enum VmTable { VM_FC = 0, VM_FCX, VM_FCA, VM_FCAT, VM_FM1, VM_FM1T, VM_FM, VM_FMT, VM_FMST,
+               VM_FCO, VM_FCOX, VM_FM2O, VM_FM2OT, VM_FMSOT, VM_FM1O, VM_FCOT,
+               VM_COUNT };   // tables per sequence of a Vienna-BL batch, log space or linear
+
+// ---- Vienna-BL model, scaled linear space (mccaskill_vlin.hip): diagonal-major, and the block products of mccaskill_far.hip run on
+//      these tables too, so the slots they address are LinTable's
+enum VLinTable { VL_FC = L_FC, VL_FCX = L_FCX, VL_FCA = L_FCA, VL_FM1 = L_FM1, VL_FM = L_FM, VL_FCO = L_FCO, VL_FCOX = L_FCOX, VL_FM2O = L_FM2O,
+                 VL_FMSO = L_FMO,   // the Vienna grammar keeps FMSo in that slot
+                 VL_FM1O = L_FM1O, VL_FM2F = L_FM2F, VL_FMOF = L_FMOF, VL_FM1OF = L_FM1OF,
+                 VL_FMS = L_COUNT, VL_FCB, VL_FCOB, VL_COUNT };
+static_assert((int)VL_COUNT <= (int)VM_COUNT, "linear tables reuse the log-space table buffer");
 
 struct McBatch {
     const uint8_t* seq;  // [NS][lds] nucleotide codes, seq[0] = seq[n+1] = 4
@@ -87,6 +105,8 @@ enum DxTable {
     D_OUTX,    // outside + terminal_mismatch[s2[j]][s1[i]][s2[j+1]][s1[i-1]] + base_pair[s1[i]][s2[j]]
     D_COUNT
 };
+// Vienna-BL model, log space (duplex_vienna.hip): the same layout, IN / OUT and two decorated copies of each
+enum DxvTable { V_IN = 0, V_INMM, V_INTAU, V_OUT, V_OUTMM, V_OUTTAU, V_COUNT };
 
 struct DxBatch {
     const uint8_t* seq;  // the McCaskill sequence buffer: pair p = sequences 2p (s1) and 2p+1 (s2)
@@ -100,7 +120,6 @@ struct DxBatch {
 };
 
 // ---- duplex, scaled linear path: anti-diagonal-major tables [sd*lda + kDxPad + a], a = i, sd = i + (L2+1-j)
-constexpr int kVdTables18 = 6, kVdTables20 = 10;   // tables per pair of the Vienna-BL linear duplex (DxvLinTable, duplex_vlin.hip): 1.8 / 2.x semantics
 constexpr int kDxPad = 32;   // zero columns on both sides of every row (>= 29: the longest window reach)
 // How far from its cells a row is ever read.  Row sd has cells at columns alo(sd) = max(1, sd-L2) .. ahi(sd) = min(L1, sd-1); both grow
 // with sd, by at most one per row.  A kept cell (sd, a), alo(sd) <= a <= ahi(sd), reads, with dir = -1 (inside) / +1 (outside):
@@ -129,6 +148,9 @@ inline int dxl_strip8_groups(int n1max, int n2max, int step)
 }
 
 enum DxLinTable { DL_IN = 0, DL_INX, DL_OUT, DL_OUTX, DL_COUNT };
+// Vienna-BL model (duplex_vlin.hip): VD_COUNT tables per pair under 1.8 semantics, VD_COUNT20 under 2.x; IN / OUT at DL_IN / DL_OUT: dxl_posterior reads them
+enum DxvLinTable { VD_IN = 0, VD_INX, VD_OUT, VD_OUTX, VD_INT, VD_OUTT, VD_IN1N, VD_OUT1N, VD_IN23, VD_OUT23, VD_COUNT20, VD_COUNT = VD_IN1N };
+static_assert((int)VD_IN == (int)DL_IN && (int)VD_OUT == (int)DL_OUT, "dxl_posterior serves both models");
 
 struct DxLinBatch {
     const uint8_t* seq;

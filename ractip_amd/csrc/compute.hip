@@ -90,7 +90,7 @@ static McVlinArgs mc_vlin_args(const rh_ctx* c, int phase, bool co)
     } else {
         A.logz = c->d_mclogz.as<double>(); A.gaps = c->d_gaps.as<double>(); A.max_w = c->max_w;
         // (vlin_acc_gaps_wide addresses a sequence's tables with 32-bit offsets; vlin_acc_final_t has up to fifteen widths)
-        A.acc_wide = c->acc_wide && (size_t)kViennaMcTables * A.B.tab_stride * sizeof(double) < ((size_t)1 << 32);
+        A.acc_wide = c->acc_wide && (size_t)VM_COUNT * A.B.tab_stride * sizeof(double) < ((size_t)1 << 32);
         A.acc_final_t = c->acc_final_t && c->max_w <= 15;
     }
     return A;

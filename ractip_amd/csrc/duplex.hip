@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #include "batch.h"
+#include "dev_util.h"
 #include "lse.h"
 #include "score_model.h"
 #include "kernels.h"
@@ -21,10 +22,6 @@
 namespace rh {
 
 namespace {
-
-constexpr uint32_t kPairMask = (1u << (0 * 5 + 3)) | (1u << (3 * 5 + 0)) | (1u << (1 * 5 + 2)) |
-                               (1u << (2 * 5 + 1)) | (1u << (2 * 5 + 3)) | (1u << (3 * 5 + 2));
-__device__ __forceinline__ bool complementary(int a, int b) { return (kPairMask >> (a * 5 + b)) & 1u; }
 
 __device__ __forceinline__ double tm4(const ScoreModel* M, int a, int b, int c, int d)
 {
@@ -102,7 +99,7 @@ __global__ __launch_bounds__(256) void dx_sweep_diag(DxBatch B, const ScoreModel
     const size_t ij = (size_t)i * ldd + j;
 
     const int a = s1[i], b = s2[j], a_m1 = s1[i - 1], a_p1 = s1[i + 1], b_m1 = s2[j - 1], b_p1 = s2[j + 1];
-    if (!complementary(a, b)) {
+    if (!pairs(a, b)) {
         if (lane == 0) {
             if (!outside) { tab[D_IN * ts + ij] = kNeg; tab[D_INX * ts + ij] = kNeg; }
             else          { tab[D_OUT * ts + ij] = kNeg; tab[D_OUTX * ts + ij] = kNeg; }
@@ -190,7 +187,7 @@ __global__ __launch_bounds__(1024) void dx_logz(DxBatch B, const ScoreModel* __r
     for (int c = threadIdx.x; c < total; c += blockDim.x) {
         const int i = c / L2 + 1, j = c % L2 + 1;
         const int a = s1[i], b = s2[j];
-        if (!complementary(a, b)) continue;
+        if (!pairs(a, b)) continue;
         lse_add(acc, in[(size_t)i * B.ldd + j] + close_score(M, i, j, L1, a, b, s1[i + 1], s2[j - 1]));
     }
     const double M1 = wave_max(acc.m);

@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 
 #include "batch.h"
+#include "dev_util.h"
 #include "lin_model.h"
 #include "kernels.h"
 
@@ -27,17 +28,12 @@
 namespace rh {
 
 namespace {
-constexpr uint32_t kPairMaskD = (1u << (0 * 5 + 3)) | (1u << (3 * 5 + 0)) | (1u << (1 * 5 + 2)) |
-                                (1u << (2 * 5 + 1)) | (1u << (2 * 5 + 3)) | (1u << (3 * 5 + 2));
-__device__ __forceinline__ bool pairs(int a, int b) { return (kPairMaskD >> (a * 5 + b)) & 1u; }
-// (T+1)-wide window sum over an LDS-resident segment, fully unrolled (no scalar loop control per tap)
-// volatile: keeps every tap a plain ds_read_b64 (2 LDS cycles per wavefront, 256 B/clk/CU); merged into
-// ds_read2_b64 by the compiler, two taps cost 8 cycles (128 B/clk/CU) on CDNA4
-typedef const volatile __attribute__((address_space(3))) double* lds_vptr;
+// (T+1)-wide window sum over an LDS-resident segment, fully unrolled (no scalar loop control per tap), every tap a
+// plain ds_read_b64 (lds_vp, dev_util.h)
 template <int T>
 __device__ __forceinline__ double win_sum(const double* seg)
 {
-    lds_vptr vs = (lds_vptr)seg;
+    lds_vp vs = (lds_vp)seg;
     double s0 = 0.0, s1 = 0.0;
 #pragma unroll
     for (int k = 0; k <= T; k += 2) {
@@ -72,7 +68,7 @@ __device__ __forceinline__ void win_pass(const double* seg0, const double* __res
             if (row >= 2 && row <= smax) {
                 const double* seg = seg0 + q * 96;
                 double s0 = 0.0, s1 = 0.0;
-                lds_vptr vs = (lds_vptr)seg;
+                lds_vp vs = (lds_vp)seg;
 #pragma unroll
                 for (int k = 0; k <= t; k += 2) {
                     s0 += vs[k];
@@ -317,7 +313,7 @@ __device__ __forceinline__ void win_pass4(const double* seg0, const double* __re
             if (t > 28) continue;
             const int row = outside ? sdA + 2 + t : sdA - 2 - t;
             if (row >= 2 && row <= smax) {
-                lds_vptr vs = (lds_vptr)(seg0 + q * 96);
+                lds_vp vs = (lds_vp)(seg0 + q * 96);
                 double s0 = 0.0, s1 = 0.0;
                 const int base = outside ? 0 : 3;
 #pragma unroll
@@ -460,7 +456,6 @@ __global__ __launch_bounds__(256) RH_WPE_DX void dxl_sweep4(DxLinBatch B, const 
 //   * a group with cells stores its 58 columns of all eight rows (a superset);
 //   * the grid holds only as many groups as the bands of one launch can touch: blockIdx.x counts from the first group of this
 //     pair's band (dxl_strip8_groups is the bound, a function of the batch shape and the step alone: the launches are captured).
-__device__ __forceinline__ void lds_barrier_dx() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 template <int WV>
 __device__ __forceinline__ void win_pass8(const double* seg0, const double* __restrict__ lam_pow, bool outside, int sdA, int smax, double acc[8])
@@ -473,7 +468,7 @@ __device__ __forceinline__ void win_pass8(const double* seg0, const double* __re
         if (r > 30) continue;
         const int row = outside ? sdA + r : sdA - r;
         if (row >= 2 && row <= smax) {
-            lds_vptr vs = (lds_vptr)(seg0 + q * 104);
+            lds_vp vs = (lds_vp)(seg0 + q * 104);
             const int len_max = r + 6 < 29 ? r + 6 : 29;      // longest window any of the 8 diagonals takes from this row
             double run = 0.0;
             // eight reads at a time: left alone the scheduler hoists the reads of the whole row above the (dependent) running sum,
@@ -625,12 +620,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
     for (int half = 0; half < 2; half++) {
 #pragma unroll
         for (int k = 0; k < 4; k++) part[(w * 4 + k) * 64 + lane] = acc[half * 4 + k];
-        lds_barrier_dx();
+        lds_barrier();
         if ((w >> 2) == half) {
 #pragma unroll
             for (int q = 0; q < 8; q++) g += part[(q * 4 + (w & 3)) * 64 + lane];
         }
-        lds_barrier_dx();
+        lds_barrier();
     }
     RH_DSTAMP(6);   // partial sums exchanged (two halves, four barriers)
     auto finish = [&](int k) {
@@ -655,7 +650,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
 #pragma unroll
     for (int sl = 0; sl < 4; sl++) {
         if ((w >> 1) == sl) finish(w);
-        lds_barrier_dx();
+        lds_barrier();
     }
     RH_DSTAMP(7);   // chain (four slots)
     // ---- the 2 x 8 rows go to HBM: row (table, k) by wavefront; all columns of the group, which covers what it owns of the rows' bands

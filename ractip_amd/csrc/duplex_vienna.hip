@@ -16,8 +16,6 @@
 
 namespace rh {
 
-enum DxvTable { V_IN = 0, V_INMM, V_INTAU, V_OUT, V_OUTMM, V_OUTTAU, V_COUNT };
-
 namespace {
 __device__ __forceinline__ bool diag_cell_v(int w, int s0, int L1, int L2, int* i, int* j)
 {

@@ -22,17 +22,13 @@
 #include <hip/hip_runtime.h>
 
 #include "batch.h"
+#include "dev_util.h"
 #include "vienna_model.h"
 #include "kernels.h"
 
 namespace rh {
 
-enum DxvLinTable { VD_IN = 0, VD_INX, VD_OUT, VD_OUTX, VD_INT, VD_OUTT, VD_IN1N, VD_OUT1N, VD_IN23, VD_OUT23, VD_COUNT20, VD_COUNT = VD_IN1N };   // IN / OUT at DL_IN / DL_OUT: dxl_posterior reads them
-
-static_assert(VD_COUNT == kVdTables18 && VD_COUNT20 == kVdTables20, "staging.hip sizes a pair's tables by these");
-
 namespace {
-typedef const volatile __attribute__((address_space(3))) double* lds_vp;
 
 __device__ __forceinline__ double small_wd(const VLinModel* L, int l1, int l2, int t1, int t2, int si1, int sj1, int sp1, int sq1)
 {   // as small_w of mccaskill_vlin.hip: t1 = pair closing the loop seen from outside, t2 = the other pair (its rtype is taken here)

@@ -29,7 +29,7 @@ int launch_mc_log(rh_ctx* c, int pin, const McBatch& B, double* logz_out)
         KLAUNCH(c, 0, mc_inside_diag, pin ? dim3(B.ns, (waves + 3) / 4) : dim3((waves + 3) / 4, B.ns), dim3(256), c->s_mc, B, c->d_model, d, pin);
         c->n_launch[0]++;
     }
-    HIP_TRY(c, hipEventRecord(c->ev[1], c->s_mc));
+    HIP_TRY(c, hipEventRecord(c->ev[kEvMcInside], c->s_mc));
     for (int d = B.nmax - 2; d >= 0; d--) {
         const int waves = (B.nmax - 1 - d) + 1;
         KLAUNCH(c, 2, mc_outside_diag, pin ? dim3(B.ns, (waves + 3) / 4) : dim3((waves + 3) / 4, B.ns), dim3(256), c->s_mc, B, c->d_model, d, pin);

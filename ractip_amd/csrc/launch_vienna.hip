@@ -23,7 +23,7 @@ int launch_mc_vienna(rh_ctx* c, int pin)
         KLAUNCH(c, 0, mcv_inside_diag, pin ? dim3(B.ns, (waves + 3) / 4) : dim3((waves + 3) / 4, B.ns), dim3(256), c->s_mc, B, c->d_vienna, d, pin);
         c->n_launch[0]++;
     }
-    HIP_TRY(c, hipEventRecord(c->ev[1], c->s_mc));
+    HIP_TRY(c, hipEventRecord(c->ev[kEvMcInside], c->s_mc));
     for (int d = B.nmax - 2; d >= 0; d--) {
         const int waves = (B.nmax - 1 - d) + 1;
         KLAUNCH(c, 2, mcv_outside_diag, pin ? dim3(B.ns, (waves + 3) / 4) : dim3((waves + 3) / 4, B.ns), dim3(256), c->s_mc, B, c->d_vienna, d, pin);
@@ -33,7 +33,7 @@ int launch_mc_vienna(rh_ctx* c, int pin)
     // accessibility P(i..i+w unpaired), w < max_w, from the finished tables
     const int tiles = (B.ld + 31) / 32;
     hipLaunchKernelGGL(mcv_acc_prep, dim3(tiles * tiles, B.ns, 3), dim3(256), 0, c->s_mc, B, c->d_vienna);
-    hipLaunchKernelGGL(mcv_acc_hscan, dim3((B.nmax + 1 + 255) / 256, B.ns), dim3(256), 0, c->s_mc, B, 1 /* VM_FCX */);
+    hipLaunchKernelGGL(mcv_acc_hscan, dim3((B.nmax + 1 + 255) / 256, B.ns), dim3(256), 0, c->s_mc, B, VM_FCX);
     hipLaunchKernelGGL(mcv_acc_gaps, dim3((B.nmax * 30 + 3) / 4, B.ns, 2), dim3(256), 0, c->s_mc, B, c->d_vienna, c->d_gaps.as<double>());
     hipLaunchKernelGGL(mcv_acc_final, dim3((B.nmax + 3) / 4, B.ns), dim3(256), 0, c->s_mc, B, c->d_vienna, c->d_gaps.as<const double>(), c->max_w);
     c->n_launch[1] += 4;
@@ -121,7 +121,7 @@ static void vlin_finish_acc(rh_ctx* c, const McVlinArgs& A, hipStream_t st)
     hipLaunchKernelGGL(vlin_finish, dim3((B.ns + 63) / 64), dim3(64), 0, st, B, d_vlin, A.logz, A.bad);
     const int tiles = (B.ld + 31) / 32;
     hipLaunchKernelGGL(vlin_acc_prep, dim3(tiles * tiles, B.ns), dim3(256), 0, st, B, d_vlin, A.d_hplen);
-    hipLaunchKernelGGL(mcv_acc_hscan, dim3((B.nmax + 1 + 255) / 256, B.ns), dim3(256), 0, st, B, 10 /* VL_FM2F */);
+    hipLaunchKernelGGL(mcv_acc_hscan, dim3((B.nmax + 1 + 255) / 256, B.ns), dim3(256), 0, st, B, VL_FM2F);
     hipLaunchKernelGGL(vlin_acc_hsum, dim3((B.nmax + 3) / 4, B.ns), dim3(256), 0, st, B, A.max_w);
     if (A.acc_wide) {
         // gap lengths 1, 2 (the tabulated shapes: six times the loads of a generic length): one thread per letter and length, the inner

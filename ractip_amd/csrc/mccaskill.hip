@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 
 #include "batch.h"
+#include "dev_util.h"
 #include "lse.h"
 #include "score_model.h"
 #include "kernels.h"
@@ -30,11 +31,6 @@
 namespace rh {
 
 namespace {
-
-// AU, CG, GU both ways (InferenceEngine.ipp:391-396); code 4 (unknown letter) never pairs
-constexpr uint32_t kPairMask = (1u << (0 * 5 + 3)) | (1u << (3 * 5 + 0)) | (1u << (1 * 5 + 2)) |
-                               (1u << (2 * 5 + 1)) | (1u << (2 * 5 + 3)) | (1u << (3 * 5 + 2));
-__device__ __forceinline__ bool complementary(int a, int b) { return (kPairMask >> (a * 5 + b)) & 1u; }
 
 __device__ __forceinline__ double tm4(const ScoreModel* M, int a, int b, int c, int d)
 {
@@ -66,8 +62,6 @@ __device__ __forceinline__ double single_nucs(const ScoreModel* M, int l1, int l
     return v;
 }
 
-__device__ __forceinline__ size_t tri_offset(int n, int i) { return (size_t)i * (size_t)(2 * (n + 1) - i - 1) / 2; }
-
 }  // namespace
 
 // ---------------------------------------------------------------------------------
@@ -79,19 +73,6 @@ __global__ void mc_init(McBatch B)
     const int n = B.n[sq];
     B.f5i[(size_t)sq * B.ld] = 0.0;
     B.f5o[(size_t)sq * B.ld + n] = 0.0;
-}
-
-// ---------------------------------------------------------------------------------
-// Work distribution shared by the two sweeps.  A launch covers every sequence of the
-// batch; `pin` selects the block->(sequence, wave slot) map:
-//   pin = 1: blockIdx.x = sequence (fastest varying).  Workgroups are dealt round-robin
-//            over the 8 XCDs by linear id, so with ns % 8 == 0 all blocks of a sequence
-//            share one XCD and its 4 MiB L2 sees only ns/8 sequences' rows (speed only).
-//   pin = 0: blockIdx.y = sequence: few, large sequences are spread over all XCDs.
-__device__ __forceinline__ void block_map(int pin, int* sq, int* slot)
-{
-    *sq = pin ? blockIdx.x : blockIdx.y;
-    *slot = pin ? blockIdx.y : blockIdx.x;
 }
 
 // ---------------------------------------------------------------------------------
@@ -129,7 +110,7 @@ __global__ __launch_bounds__(256) void mc_inside_diag(McBatch B, const ScoreMode
 
     const int i = wave + 1, j = i + d;
     const int s_im1 = s[i - 1], s_i = s[i], s_ip1 = s[i + 1], s_j = s[j], s_jp1 = s[j + 1], s_jp2 = s[j + 2];
-    const bool pairable = complementary(s_i, s_jp1);
+    const bool pairable = pairs(s_i, s_jp1);
     const bool inner = d >= 2;  // cells of span 0/1 have no FM2, FM1, FM and no enclosed pair
 
     // O(1) operands of FM1 / FM / the stacking term: issued before the streams so that they are in flight with them
@@ -238,7 +219,7 @@ __global__ __launch_bounds__(256) void mc_outside_diag(McBatch B, const ScoreMod
     const int i = wave + 1, j = i + d;
     const int s_im1 = s[i - 1], s_i = s[i], s_ip1 = s[i + 1], s_j = s[j], s_jp1 = s[j + 1], s_jp2 = s[j + 2];
     const bool guard_m = d >= 2;
-    const bool pairable = complementary(s_i, s_jp1);
+    const bool pairable = pairs(s_i, s_jp1);
 
     // O(1) operands, issued up front
     double op_fmo = kNeg, op_fm1o = kNeg, op_fm1o_up = kNeg, op_fco_up = kNeg, op_f5o = kNeg, op_f5i = kNeg;
@@ -324,7 +305,7 @@ __global__ __launch_bounds__(256) void mc_outside_diag(McBatch B, const ScoreMod
         const double e = fco + fc_in - Z;
         double p = e > kNeg / 2 ? exp(e) : 0.0;
         p = p > 1.0 ? 1.0 : p;
-        B.bp[(size_t)sq * B.tri_stride + tri_offset(n, i) + (j + 1)] = pairable ? p : 0.0;
+        B.bp[(size_t)sq * B.tri_stride + tri_off(n, i) + (j + 1)] = pairable ? p : 0.0;
     }
 }
 
@@ -350,14 +331,14 @@ __global__ __launch_bounds__(256) void mc_unpaired(McBatch B)
         double acc = 0.0;
         const int bmax = a0 + 64 < n ? a0 + 64 : n;   // rows b < a <= bmax
         for (int b = 1 + w; b < bmax; b += 4)
-            if (b < a && a <= n) acc += bp[tri_offset(n, b) + a];
+            if (b < a && a <= n) acc += bp[tri_off(n, b) + a];
         colsum[w][lane] = acc;
     }
     for (int q = w; q < 64; q += 4) {
         const int a = a0 + 1 + q;
         double acc = 0.0;
         if (a <= n)
-            for (int b2 = a + 1 + lane; b2 <= n; b2 += 64) acc += bp[tri_offset(n, a) + b2];
+            for (int b2 = a + 1 + lane; b2 <= n; b2 += 64) acc += bp[tri_off(n, a) + b2];
         acc = wave_sum(acc);
         if (lane == 0) rowsum[q] = acc;
     }

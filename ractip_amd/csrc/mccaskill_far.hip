@@ -18,7 +18,10 @@
 
 namespace rh {
 
-enum LinTableFar { LF_FM1 = 3, LF_FM = 4, LF_FM2O = 7, LF_FM2F = 10, LF_FMOF = 11, LF_FM1OF = 12 };
+// the products run on the tables of both linear models (mccaskill_lin.hip, mccaskill_vlin.hip) and address them by the L_ names
+static_assert((int)VL_FM1 == (int)L_FM1 && (int)VL_FM == (int)L_FM && (int)VL_FM2O == (int)L_FM2O && (int)VL_FM2F == (int)L_FM2F &&
+                  (int)VL_FMOF == (int)L_FMOF && (int)VL_FM1OF == (int)L_FM1OF,
+              "LinTable and VLinTable disagree on a slot of the block products: FM1, FM, FM2O, FM2F, FMOF, FM1OF");
 
 namespace {
 
@@ -96,8 +99,8 @@ __global__ __launch_bounds__(256) void lin_far_inside(McBatch B, int D)
     if (J * BS > n - 1) return;  // no interior column in this tile
     const int ld = B.ld;
     double* __restrict__ tab = B.tab + (size_t)sq * B.seq_stride;
-    const double* __restrict__ fm1 = tab + (size_t)LF_FM1 * B.tab_stride;
-    const double* __restrict__ fm = tab + (size_t)LF_FM * B.tab_stride;
+    const double* __restrict__ fm1 = tab + (size_t)L_FM1 * B.tab_stride;
+    const double* __restrict__ fm = tab + (size_t)L_FM * B.tab_stride;
     Acc<BS> acc;
     acc.zero();
     for (int K = I + 2; K <= J - 2; K++) {
@@ -107,7 +110,7 @@ __global__ __launch_bounds__(256) void lin_far_inside(McBatch B, int D)
         acc.mac(A, Bm);
         __syncthreads();
     }
-    acc.store(tab + (size_t)LF_FM2F * B.tab_stride, ld, n, I * BS, J * BS);
+    acc.store(tab + (size_t)L_FM2F * B.tab_stride, ld, n, I * BS, J * BS);
 }
 
 // outside: FMOF[tile]  = sum_{K<=I-2} FM1(K,I)^T x FM2o(K,J)
@@ -122,9 +125,9 @@ __global__ __launch_bounds__(256) void lin_far_outside(McBatch B, int D)
     if (J * BS > n - 1) return;
     const int ld = B.ld;
     double* __restrict__ tab = B.tab + (size_t)sq * B.seq_stride;
-    const double* __restrict__ fm1 = tab + (size_t)LF_FM1 * B.tab_stride;
-    const double* __restrict__ fm = tab + (size_t)LF_FM * B.tab_stride;
-    const double* __restrict__ fm2o = tab + (size_t)LF_FM2O * B.tab_stride;
+    const double* __restrict__ fm1 = tab + (size_t)L_FM1 * B.tab_stride;
+    const double* __restrict__ fm = tab + (size_t)L_FM * B.tab_stride;
+    const double* __restrict__ fm2o = tab + (size_t)L_FM2O * B.tab_stride;
     Acc<BS> acc;
     acc.zero();
     if (blockIdx.z == 0) {
@@ -135,7 +138,7 @@ __global__ __launch_bounds__(256) void lin_far_outside(McBatch B, int D)
             acc.mac(A, Bm);
             __syncthreads();
         }
-        acc.store(tab + (size_t)LF_FMOF * B.tab_stride, ld, n, I * BS, J * BS);
+        acc.store(tab + (size_t)L_FMOF * B.tab_stride, ld, n, I * BS, J * BS);
     } else {
         const int last = (n - 1) / BS;
         for (int K = J + 2; K <= last; K++) {
@@ -145,7 +148,7 @@ __global__ __launch_bounds__(256) void lin_far_outside(McBatch B, int D)
             acc.mac(A, Bm);
             __syncthreads();
         }
-        acc.store(tab + (size_t)LF_FM1OF * B.tab_stride, ld, n, I * BS, J * BS);
+        acc.store(tab + (size_t)L_FM1OF * B.tab_stride, ld, n, I * BS, J * BS);
     }
 }
 
@@ -207,15 +210,15 @@ __global__ __launch_bounds__(256) void lin_far_inside_mfma(McBatch B, int D)
     const int w = threadIdx.x >> 6;
     const int ld = B.ld;
     double* __restrict__ tab = B.tab + (size_t)sq * B.seq_stride;
-    const double* __restrict__ fm1 = tab + (size_t)LF_FM1 * B.tab_stride;
-    const double* __restrict__ fm = tab + (size_t)LF_FM * B.tab_stride;
+    const double* __restrict__ fm1 = tab + (size_t)L_FM1 * B.tab_stride;
+    const double* __restrict__ fm = tab + (size_t)L_FM * B.tab_stride;
     d4 acc = {0.0, 0.0, 0.0, 0.0};
     for (int K = I + 2 + w; K <= J - 2; K += 4) {
         load_chunk16_wave<false>(A[w], fm1, ld, n, I * 16, K * 16);
         load_chunk16_wave<false>(Bm[w], fm, ld, n, K * 16, J * 16);
         acc = mfma_chunk(A[w], Bm[w], acc);
     }
-    reduce_store(red, acc, tab + (size_t)LF_FM2F * B.tab_stride, ld, n, I * 16, J * 16);
+    reduce_store(red, acc, tab + (size_t)L_FM2F * B.tab_stride, ld, n, I * 16, J * 16);
 }
 
 __global__ __launch_bounds__(256) void lin_far_outside_mfma(McBatch B, int D)
@@ -228,9 +231,9 @@ __global__ __launch_bounds__(256) void lin_far_outside_mfma(McBatch B, int D)
     const int w = threadIdx.x >> 6;
     const int ld = B.ld;
     double* __restrict__ tab = B.tab + (size_t)sq * B.seq_stride;
-    const double* __restrict__ fm1 = tab + (size_t)LF_FM1 * B.tab_stride;
-    const double* __restrict__ fm = tab + (size_t)LF_FM * B.tab_stride;
-    const double* __restrict__ fm2o = tab + (size_t)LF_FM2O * B.tab_stride;
+    const double* __restrict__ fm1 = tab + (size_t)L_FM1 * B.tab_stride;
+    const double* __restrict__ fm = tab + (size_t)L_FM * B.tab_stride;
+    const double* __restrict__ fm2o = tab + (size_t)L_FM2O * B.tab_stride;
     d4 acc = {0.0, 0.0, 0.0, 0.0};
     if (blockIdx.z == 0) {
         for (int K = w; K <= I - 2; K += 4) {
@@ -238,7 +241,7 @@ __global__ __launch_bounds__(256) void lin_far_outside_mfma(McBatch B, int D)
             load_chunk16_wave<false>(Bm[w], fm2o, ld, n, K * 16, J * 16);  // Bm[kk][c] = FM2o[k0+kk, j0+c]
             acc = mfma_chunk(A[w], Bm[w], acc);
         }
-        reduce_store(red, acc, tab + (size_t)LF_FMOF * B.tab_stride, ld, n, I * 16, J * 16);
+        reduce_store(red, acc, tab + (size_t)L_FMOF * B.tab_stride, ld, n, I * 16, J * 16);
     } else {
         const int last = (n - 1) / 16;
         for (int K = J + 2 + w; K <= last; K += 4) {
@@ -246,7 +249,7 @@ __global__ __launch_bounds__(256) void lin_far_outside_mfma(McBatch B, int D)
             load_chunk16_wave<true>(Bm[w], fm, ld, n, J * 16, K * 16);     // Bm[kk][c] = FM  [j0+c, k0+kk]
             acc = mfma_chunk(A[w], Bm[w], acc);
         }
-        reduce_store(red, acc, tab + (size_t)LF_FM1OF * B.tab_stride, ld, n, I * 16, J * 16);
+        reduce_store(red, acc, tab + (size_t)L_FM1OF * B.tab_stride, ld, n, I * 16, J * 16);
     }
 }
 
@@ -275,7 +278,7 @@ __global__ __launch_bounds__(256) void lin_pack_tiles(McBatch B, int Dblk, int o
     const int n = B.n[sq];
     const int P = blockIdx.x, Q = P + Dblk;
     if (Q >= B.nb || Q * 16 > n - 1) return;   // no interior column: never read
-    const int slot = outside ? LF_FM2O : (blockIdx.z == 0 ? LF_FM1 : LF_FM);
+    const int slot = outside ? L_FM2O : (blockIdx.z == 0 ? L_FM1 : L_FM);
     const int copy = outside ? PK_FM2O_A : (blockIdx.z == 0 ? PK_FM1_A : PK_FM_A);
     const double* __restrict__ src = B.tab + (size_t)sq * B.seq_stride + (size_t)slot * B.tab_stride;
     {   // walk the chunk along its diagonals v-u = const (contiguous runs of the table)
@@ -356,7 +359,7 @@ __global__ __launch_bounds__(256) void lin_far_inside_pk(McBatch B, int D, int l
     const bool two = l2 > 0 && n >= l2 && J2 - I2 >= 4;   // K = 4(I2+2) .. 4(J2-1)-1 came from the macro tile (l2 = shortest two-level sequence, 0 = none)
     d4 acc = pk_loop(pk + PK_FM1_A * B.pk_stride, pk + PK_FM_B * B.pk_stride, I + 2, two ? 4 * (I2 + 2) - 1 : J - 2, ta, tb);
     if (two) acc = pk_loop(pk + PK_FM1_A * B.pk_stride, pk + PK_FM_B * B.pk_stride, 4 * (J2 - 1), J - 2, ta, tb, acc);
-    reduce_store(red, acc, B.tab + (size_t)sq * B.seq_stride + (size_t)LF_FM2F * B.tab_stride, B.ld, n, I * 16, J * 16, two);
+    reduce_store(red, acc, B.tab + (size_t)sq * B.seq_stride + (size_t)L_FM2F * B.tab_stride, B.ld, n, I * 16, J * 16, two);
 }
 
 __global__ __launch_bounds__(256) void lin_far_outside_pk(McBatch B, int D, int l2)
@@ -375,12 +378,12 @@ __global__ __launch_bounds__(256) void lin_far_outside_pk(McBatch B, int D, int 
         const bool two = l2 > 0 && n >= l2 && I2 >= 2;
         const d4 acc = pk_loop(pk + PK_FM1_B * B.pk_stride, pk + PK_FM2O_B * B.pk_stride, two ? 4 * (I2 - 1) : 0, I - 2,
                                [=](int K) { return pk_tile(nb, K, I); }, [=](int K) { return pk_tile(nb, K, J); });
-        reduce_store(red, acc, tab + (size_t)LF_FMOF * B.tab_stride, B.ld, n, I * 16, J * 16, two);
+        reduce_store(red, acc, tab + (size_t)L_FMOF * B.tab_stride, B.ld, n, I * 16, J * 16, two);
     } else {                 // FM1OF(I,J) = sum_{K>=J+2} FM2o(I,K) x FM(J,K)^T; K >= 4(J2+2) came from the macro tile
         const bool two = l2 > 0 && n >= l2 && 4 * (J2 + 2) <= last;
         const d4 acc = pk_loop(pk + PK_FM2O_A * B.pk_stride, pk + PK_FM_A * B.pk_stride, J + 2, two ? 4 * (J2 + 2) - 1 : last,
                                [=](int K) { return pk_tile(nb, I, K); }, [=](int K) { return pk_tile(nb, J, K); });
-        reduce_store(red, acc, tab + (size_t)LF_FM1OF * B.tab_stride, B.ld, n, I * 16, J * 16, two);
+        reduce_store(red, acc, tab + (size_t)L_FM1OF * B.tab_stride, B.ld, n, I * 16, J * 16, two);
     }
 }
 
@@ -440,7 +443,7 @@ __global__ __launch_bounds__(256) void lin_far2_inside(McBatch B, int D2, int l2
         for (int b = 0; b < 2; b++) A.c[a][b] = d4{0.0, 0.0, 0.0, 0.0};
     far2_loop(A, pk + PK_FM1_A * B.pk_stride, pk + PK_FM_B * B.pk_stride, 4 * (I2 + 2), 4 * (J2 - 1) - 1,
               [=](int a, int K) { return pk_tile(nb, Ia + a, K); }, [=](int K, int b) { return pk_tile(nb, K, Jb + b < nb ? Jb + b : nb - 1); });
-    store_quadrant(A, B.tab + (size_t)sq * B.seq_stride + (size_t)LF_FM2F * B.tab_stride, B.ld, n, I2, J2);
+    store_quadrant(A, B.tab + (size_t)sq * B.seq_stride + (size_t)L_FM2F * B.tab_stride, B.ld, n, I2, J2);
 }
 
 // outside: blockIdx.z = 0: FMOF(macro tile) = sum_{K <= 4(I2-1)-1} FM1(K,I)^T x FM2o(K,J);  1: FM1OF = sum_{K >= 4(J2+2)} FM2o(I,K) x FM(J,K)^T
@@ -466,12 +469,12 @@ __global__ __launch_bounds__(256) void lin_far2_outside(McBatch B, int D2, int l
         if (I2 < 2) return;   // nothing 64 or more to the left: the tile kernel writes these cells
         far2_loop(A, pk + PK_FM1_B * B.pk_stride, pk + PK_FM2O_B * B.pk_stride, 0, 4 * (I2 - 1) - 1,
                   [=](int a, int K) { return pk_tile(nb, K, Ia + a); }, [=](int K, int b) { return pk_tile(nb, K, cl(Jb + b)); });
-        store_quadrant(A, tab + (size_t)LF_FMOF * B.tab_stride, B.ld, n, I2, J2);
+        store_quadrant(A, tab + (size_t)L_FMOF * B.tab_stride, B.ld, n, I2, J2);
     } else {
         if (4 * (J2 + 2) > last) return;
         far2_loop(A, pk + PK_FM2O_A * B.pk_stride, pk + PK_FM_A * B.pk_stride, 4 * (J2 + 2), last,
                   [=](int a, int K) { return pk_tile(nb, Ia + a, K); }, [=](int K, int b) { return pk_tile(nb, cl(Jb + b), K); });
-        store_quadrant(A, tab + (size_t)LF_FM1OF * B.tab_stride, B.ld, n, I2, J2);
+        store_quadrant(A, tab + (size_t)L_FM1OF * B.tab_stride, B.ld, n, I2, J2);
     }
 }
 

@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include "batch.h"
+#include "dev_util.h"
 #include "lin_model.h"
 #include "kernels.h"
 
@@ -32,52 +33,7 @@ namespace rh {
 
 namespace {
 
-constexpr uint32_t kPairMaskL = (1u << (0 * 5 + 3)) | (1u << (3 * 5 + 0)) | (1u << (1 * 5 + 2)) |
-                                (1u << (2 * 5 + 1)) | (1u << (2 * 5 + 3)) | (1u << (3 * 5 + 2));
-__device__ __forceinline__ bool pairs(int a, int b) { return (kPairMaskL >> (a * 5 + b)) & 1u; }
-__device__ __forceinline__ size_t tri_off(int n, int i) { return (size_t)i * (size_t)(2 * (n + 1) - i - 1) / 2; }
-
-__device__ __forceinline__ double wsum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ void block_map(int pin, int* sq, int* slot)
-{
-    *sq = pin ? blockIdx.x : blockIdx.y;
-    *slot = pin ? blockIdx.y : blockIdx.x;
-}
-
-// (T+1)-tap filter over an LDS-resident row segment, fully unrolled: the weights are consecutive and
-// wave-uniform (wide scalar loads), every tap is one ds_read + one FMA and there is no loop control on the
-// scalar unit (a rolled loop costs ~5 SALU instructions per tap and the CU has ONE scalar ALU: measured
-// 2.4 SALU per VALU instruction before unrolling).
-template <int T>
-__device__ __forceinline__ double filt_fwd(const double* __restrict__ wt, const double* seg)
-{   // sum_l1 wt[l1] * seg[l1]
-    double s0 = 0.0, s1 = 0.0;
-#pragma unroll
-    for (int l1 = 0; l1 <= T; l1 += 2) {
-        s0 = fma(wt[l1], seg[l1], s0);
-        if (l1 + 1 <= T) s1 = fma(wt[l1 + 1], seg[l1 + 1], s1);
-    }
-    return s0 + s1;
-}
-template <int T>
-__device__ __forceinline__ double filt_rev(const double* __restrict__ wt, const double* seg)
-{   // sum_l1 wt[l1] * seg[T-l1]
-    double s0 = 0.0, s1 = 0.0;
-#pragma unroll
-    for (int l1 = 0; l1 <= T; l1 += 2) {
-        s0 = fma(wt[l1], seg[T - l1], s0);
-        if (l1 + 1 <= T) s1 = fma(wt[l1 + 1], seg[T - l1 - 1], s1);
-    }
-    return s0 + s1;
-}
-#define RH_T_CASES(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) \
-    X(17) X(18) X(19) X(20) X(21) X(22) X(23) X(24) X(25) X(26) X(27) X(28) X(29) X(30)
+#define RH_T_CASES(X) X(0) X(1) X(2) X(3) RH_T_CASES_4_30(X)
 __device__ __forceinline__ double filt_fwd_any(int t, const double* __restrict__ wt, const double* seg)
 {
     switch (t) {
@@ -98,11 +54,6 @@ __device__ __forceinline__ double filt_rev_any(int t, const double* __restrict__
 }
 
 }  // namespace
-
-enum LinTable { L_FC = 0, L_FCX, L_FCA, L_FM1, L_FM, L_FCO, L_FCOX, L_FM2O, L_FMO, L_FM1O,
-                L_FM2F, L_FMOF, L_FM1OF,  // far-block partial sums (mccaskill_far.hip)
-                L_COUNT };
-static_assert((int)L_COUNT <= (int)T_COUNT, "linear tables reuse the log-space table buffer");
 
 // F5i~[0] = 1, F5o~[n] = 1
 __global__ void lin_init(McBatch B, const LinModel* __restrict__ L, int* __restrict__ bad)

@@ -32,6 +32,7 @@
 #include <hip/hip_runtime.h>
 
 #include "batch.h"
+#include "dev_util.h"
 #include "lin_model.h"
 #include "kernels.h"
 
@@ -39,22 +40,9 @@ namespace rh {
 
 namespace {
 
-constexpr uint32_t kPairMaskS = (1u << (0 * 5 + 3)) | (1u << (3 * 5 + 0)) | (1u << (1 * 5 + 2)) |
-                                (1u << (2 * 5 + 1)) | (1u << (2 * 5 + 3)) | (1u << (3 * 5 + 2));
-__device__ __forceinline__ bool pairs_sm(int a, int b) { return (kPairMaskS >> (a * 5 + b)) & 1u; }
-__device__ __forceinline__ size_t tri_off_sm(int n, int i) { return (size_t)i * (size_t)(2 * (n + 1) - i - 1) / 2; }
-__device__ __forceinline__ double wsum_sm(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-// (volatile: keeps the reads as ds_read_b64 -- merged into ds_read2_b64 they run at half the LDS rate on CDNA4, and the filters are bound by it)
-typedef const volatile double __attribute__((address_space(3)))* lds_cp;
-// Barrier between the steps of a sweep: what the wavefronts exchange is in LDS.  __syncthreads() also waits for every global store in
-// flight (vmcnt(0)), and a store of a diagonal's FC / FCA / posterior row is acknowledged ~7000 cycles after it was issued -- that wait,
-// twice per diagonal, was two thirds of this kernel.  The stores are ordered once, by the fence between the sweeps.
-__device__ __forceinline__ void lds_barrier_sm() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+// lds_barrier() (dev_util.h) between the steps of a sweep: what the wavefronts exchange is in LDS.  __syncthreads() also waits for every global
+// store in flight (vmcnt(0)), and a store of a diagonal's FC / FCA / posterior row is acknowledged ~7000 cycles after it was issued -- that
+// wait, twice per diagonal, was two thirds of this kernel.  The stores are ordered once, by the fence between the sweeps.
 
 // The single-branch filters of one wavefront: rows t = q, q+WPG, ... <= tmax, row t = sum_{l=0..t} w(t, l) * seg_t[DIR * l], values in LDS,
 // weights wave-uniform from the zero-padded table wpad[t][32] (scalar loads, sixteen dwords per block).  With two wavefronts per SIMD a
@@ -72,7 +60,7 @@ __device__ __forceinline__ double filt_stream(const double* __restrict__ wpad, i
     bool more = true;
     double xa[8], wa[8], xb[8], wb[8];
     auto load = [&](double (&x)[8], double (&w)[8]) {   // the block (t, l)
-        const lds_cp seg = segof(t) + DIR * l;
+        const lds_vp seg = segof(t) + DIR * l;
         const double* __restrict__ wt = wpad + t * 32 + l;
 #pragma unroll
         for (int k = 0; k < 8; k++) { x[k] = seg[DIR * k]; w[k] = wt[k]; }
@@ -168,7 +156,6 @@ __global__ __launch_bounds__(512) void lin_small_fold(McBatch B, const LinModel*
     const size_t ts = B.tab_stride;
     const uint8_t* __restrict__ sg = B.seq + (size_t)sq * B.lds;
     double* __restrict__ tab = B.tab + (size_t)sq * B.seq_stride;
-    enum { S_FC = 0, S_FCA = 2 };   // table slots shared with mccaskill_lin.hip (L_FC, L_FCA)
     double* const FM = lds + P::OFF_A;
     double* const FM1 = lds + P::OFF_B;
     double* const FCX = lds + P::OFF_C;
@@ -241,17 +228,17 @@ __global__ __launch_bounds__(512) void lin_small_fold(McBatch B, const LinModel*
             acc2 = a0 + a1;
             // generic single-branch shapes: sum_t sum_l1 w(l1,t-l1) * FCX[d-2-t][i+1+l1]   (ipp:3597-3619)
             const int tmax = d - 2 < kMaxSingle ? d - 2 : kMaxSingle;
-            accc = filt_stream<1>(wpad, q, WPG, tmax, [&](int t) { return (lds_cp)(FCX + rowoff(d - 2 - t) + ic + 1); });
+            accc = filt_stream<1>(wpad, q, WPG, tmax, [&](int t) { return (lds_vp)(FCX + rowoff(d - 2 - t) + ic + 1); });
         }
         RH_SSTAMP(0);   // inside: term loops
         part[(w * 2 + 0) * 64 + lane] = acc2;
         part[(w * 2 + 1) * 64 + lane] = accc;
-        lds_barrier_sm();
+        lds_barrier();
         RH_SSTAMP(1);   // inside: barrier
         if (fin) {
             const int j = ic + d;
             const int s_im1 = s[ic - 1], s_i = s[ic], s_ip1 = s[ic + 1], s_j = s[j], s_jp1 = s[j + 1], s_jp2 = s[j + 2];
-            const bool pairable = valid && pairs_sm(s_i, s_jp1);
+            const bool pairable = valid && pairs(s_i, s_jp1);
             const int idx = cidx(s_i, s_ip1, s_jp1, s_j);       // (i,j)   as enclosing pair
             const int idd = cidx(s_jp1, s_jp2, s_i, s_im1);     // (j+1,i-1) as enclosed pair
             const double e_tjb = CT[P::CT_TJB + idx], e_tja = CT[P::CT_TJA + idx], e_tst = CT[P::CT_TST + idx], e_bp = CT[P::CT_BP + s_i * 5 + s_jp1];
@@ -295,12 +282,12 @@ __global__ __launch_bounds__(512) void lin_small_fold(McBatch B, const LinModel*
                 FC3[(d % 3) * P::RWS + i] = fc;
                 FCA3[(d % 3) * P::RWS + i] = fca;
                 RH_SSTAMP(11);   // epilogue: LDS stores
-                tab[S_FC * ts + (size_t)d * ld + i] = fc;
-                tab[S_FCA * ts + (size_t)d * ld + i] = fca;
+                tab[L_FC * ts + (size_t)d * ld + i] = fc;
+                tab[L_FCA * ts + (size_t)d * ld + i] = fca;
             }
         }
         RH_SSTAMP(2);   // inside: epilogue
-        lds_barrier_sm();
+        lds_barrier();
         RH_SSTAMP(3);   // inside: second barrier
     }
 
@@ -311,7 +298,7 @@ __global__ __launch_bounds__(512) void lin_small_fold(McBatch B, const LinModel*
         double* const FCA = FCX;
         for (int d = 0; d <= n - 2; d++) {
             const int ncell = n - 1 - d;
-            for (int c = 1 + (int)threadIdx.x; c <= ncell; c += 512) FCA[rowoff(d) + c] = tab[S_FCA * ts + (size_t)d * ld + c];
+            for (int c = 1 + (int)threadIdx.x; c <= ncell; c += 512) FCA[rowoff(d) + c] = tab[L_FCA * ts + (size_t)d * ld + c];
         }
         __syncthreads();
         if (w == 0) {
@@ -321,7 +308,7 @@ __global__ __launch_bounds__(512) void lin_small_fold(McBatch B, const LinModel*
                 double acc = 0.0;
                 { const int k = lane; if (k <= jj - 2) acc = v0 * FCA[rowoff(jj - 2 - k) + k + 1]; }
                 { const int k = lane + 64; if (k <= jj - 2) acc = fma(v1, FCA[rowoff(jj - 2 - k) + k + 1], acc); }
-                acc = wsum_sm(acc);
+                acc = wsum(acc);
                 const double val = prev * L->w_eu + acc * L->w_ep2;
                 if (jj == lane) v0 = val;
                 if (jj == lane + 64) v1 = val;
@@ -337,7 +324,7 @@ __global__ __launch_bounds__(512) void lin_small_fold(McBatch B, const LinModel*
                 double acc = 0.0;
                 { const int jj = lane; if (jj >= k + 2 && jj <= n) acc = v0 * FCA[rowoff(jj - 2 - k) + k + 1]; }
                 { const int jj = lane + 64; if (jj >= k + 2 && jj <= n) acc = fma(v1, FCA[rowoff(jj - 2 - k) + k + 1], acc); }
-                acc = wsum_sm(acc);
+                acc = wsum(acc);
                 const double val = next * L->w_eu + acc * L->w_ep2;
                 if (k == lane) v0 = val;
                 if (k == lane + 64) v1 = val;
@@ -373,7 +360,7 @@ __global__ __launch_bounds__(512) void lin_small_fold(McBatch B, const LinModel*
     // FC of the cell (posterior) is the one operand that comes from HBM: requested one step ahead by the finishing wavefronts
     auto fc_of = [&](int d, bool fin) {
         double v = 0.0;
-        if (fin && d >= 0) { const int ncell = n - 1 - d; v = tab[S_FC * ts + (size_t)d * ld + (i <= ncell ? i : ncell)]; }
+        if (fin && d >= 0) { const int ncell = n - 1 - d; v = tab[L_FC * ts + (size_t)d * ld + (i <= ncell ? i : ncell)]; }
         return v;
     };
     double fc_nx = fc_of(n - 2, q == 0 && grp == 0);
@@ -423,7 +410,7 @@ __global__ __launch_bounds__(512) void lin_small_fold(McBatch B, const LinModel*
             if (room >= 0) {
                 const int tmax = room < kMaxSingle ? room : kMaxSingle;
                 // (row t: sum_l1 w[l1] * FCoX[d+2+t][i-1-l1])
-                accc = filt_stream<-1>(wpad, q, WPG, tmax, [&](int t) { return (lds_cp)(RING + ((d + 2 + t) % P::NR) * P::RW + P::PADL + ic - 1); });
+                accc = filt_stream<-1>(wpad, q, WPG, tmax, [&](int t) { return (lds_vp)(RING + ((d + 2 + t) % P::NR) * P::RW + P::PADL + ic - 1); });
             }
         }
         asm volatile("" : "+v"(fc_nx));   // (pinned: left alone the optimizer reloads it where it is used, one step later)
@@ -431,11 +418,11 @@ __global__ __launch_bounds__(512) void lin_small_fold(McBatch B, const LinModel*
         part[(w * 3 + 0) * 64 + lane] = accm;
         part[(w * 3 + 1) * 64 + lane] = acc1;
         part[(w * 3 + 2) * 64 + lane] = accc;
-        lds_barrier_sm();
+        lds_barrier();
         RH_SSTAMP(6);   // outside: barrier
         if (fin) {
             const int s_im1 = s[ic - 1], s_i = s[ic], s_ip1 = s[ic + 1], s_j = s[j], s_jp1 = s[j + 1], s_jp2 = s[j + 2];
-            const bool pairable = valid && pairs_sm(s_i, s_jp1);
+            const bool pairable = valid && pairs(s_i, s_jp1);
             const int idx = cidx(s_i, s_ip1, s_jp1, s_j);
             const int idd = cidx(s_jp1, s_jp2, s_i, s_im1);
             const double e_tjb = CT[P::CT_TJB + idx], e_tja = CT[P::CT_TJA + idx], e_bp = CT[P::CT_BP + s_i * 5 + s_jp1];
@@ -477,11 +464,11 @@ __global__ __launch_bounds__(512) void lin_small_fold(McBatch B, const LinModel*
                 double p = fco * o_fc / Z;
                 if (!(p == p) || p > 1e300) { atomicOr(&bad[sq], 1); p = 0.0; }
                 p = p > 1.0 ? 1.0 : (p < 0.0 ? 0.0 : p);
-                B.bp[(size_t)sq * B.tri_stride + tri_off_sm(n, i) + (j + 1)] = p;
+                B.bp[(size_t)sq * B.tri_stride + tri_off(n, i) + (j + 1)] = p;
             }
         }
         RH_SSTAMP(7);   // outside: epilogue
-        lds_barrier_sm();
+        lds_barrier();
         RH_SSTAMP(8);   // outside: second barrier
     }
     RH_SSTAMP_END();

@@ -29,6 +29,7 @@
 #include <utility>
 
 #include "batch.h"
+#include "dev_util.h"
 #include "lin_model.h"
 #include "kernels.h"
 
@@ -36,26 +37,9 @@ namespace rh {
 
 namespace {
 
-constexpr uint32_t kPairMaskS = (1u << (0 * 5 + 3)) | (1u << (3 * 5 + 0)) | (1u << (1 * 5 + 2)) |
-                                (1u << (2 * 5 + 1)) | (1u << (2 * 5 + 3)) | (1u << (3 * 5 + 2));
-__device__ __forceinline__ bool pairs_s(int a, int b) { return (kPairMaskS >> (a * 5 + b)) & 1u; }
-__device__ __forceinline__ size_t tri_off_s(int n, int i) { return (size_t)i * (size_t)(2 * (n + 1) - i - 1) / 2; }
-
-__device__ __forceinline__ double wsum_s(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 template <int V> using IC = std::integral_constant<int, V>;
 template <class F, int... Is> __device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, Is...>) { (f(IC<Is>{}), ...); }
 template <int N, class F> __device__ __forceinline__ void static_for(F&& f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
-// workgroup barrier that orders LDS traffic only.  __syncthreads() also drains the wavefront's outstanding GLOBAL stores and
-// loads (s_waitcnt vmcnt(0)): inside the chain that would expose one HBM round trip per diagonal.
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-// volatile LDS pointer: keeps every read a plain ds_read_b64 (256 B/clk/CU); merged into ds_read2_b64 two reads cost 8 cycles on CDNA4
-typedef const volatile __attribute__((address_space(3))) double* lds_vp;
 
 }  // namespace
 
@@ -114,8 +98,6 @@ extern "C" int rh_debug_trace(unsigned long long* out)
 #define RH_TRACE(slot) do { } while (0)
 #define RH_TRACE_ID() do { } while (0)
 #endif
-
-enum StripTable { S_FC = 0, S_FCX, S_FCA, S_FM1, S_FM, S_FCO, S_FCOX, S_FM2O, S_FMO, S_FM1O, S_FM2F, S_FMOF, S_FM1OF };
 
 // ---------------------------------------------------------------------------------------------------------------
 // FACTORED single-branch filter (FILT = 1; host side: strip_weights in launch_contrafold.hip).  The weight of an interior loop (l1, l2), t = l1+l2,
@@ -266,7 +248,7 @@ __global__ __launch_bounds__(64 * W, (W >= 8 ? 4 : 2)) void lin_inside_strip(McB
 
     if (slot == ngroup) {
         // F5i[jj] = F5i[jj-1]*ext_unpaired + sum_{k<=jj-2} F5i[k]*FCA[k+1,jj-1]*ext_paired   (ipp:3692-3717)
-        const double* __restrict__ fca = tab + S_FCA * ts;
+        const double* __restrict__ fca = tab + L_FCA * ts;
 #pragma unroll 1
         for (int jj = f5_lo; jj <= d0 + 1; jj++) {
             if (jj < 1 || jj > n) continue;
@@ -275,7 +257,7 @@ __global__ __launch_bounds__(64 * W, (W >= 8 ? 4 : 2)) void lin_inside_strip(McB
             double acc = 0.0;
             if (threadIdx.x < 256)
                 for (int k = threadIdx.x; k <= jj - 2; k += 256) acc = fma(f5i[k], fca[(size_t)(jj - 2 - k) * ld + (k + 1)], acc);
-            acc = wsum_s(acc);
+            acc = wsum(acc);
             if (lane == 0) red[w] = acc;
             __syncthreads();
             if (threadIdx.x == 0) f5i[jj] = f5i[jj - 1] * L->w_eu + (red[0] + red[1] + red[2] + red[3]) * L->w_ep2;
@@ -298,9 +280,9 @@ __global__ __launch_bounds__(64 * W, (W >= 8 ? 4 : 2)) void lin_inside_strip(McB
     double* const LDm = lds;                        // fixed FM rows e = 1..
     double* const LA = lds + P::RD * CD;            // sliding FM rows
     double* const LE = LA + P::RA * CA;             // sliding FCX rows
-    const double* __restrict__ fm = tab + S_FM * ts;
-    const double* __restrict__ fm1 = tab + S_FM1 * ts;
-    const double* __restrict__ fcx = tab + S_FCX * ts;
+    const double* __restrict__ fm = tab + L_FM * ts;
+    const double* __restrict__ fm1 = tab + L_FM1 * ts;
+    const double* __restrict__ fcx = tab + L_FCX * ts;
 
     // sequence letters of this wavefront's chain steps k = w + W*sl: the FIRST loads issued (their table gathers follow as soon as the
     // staging loads are out, and vmcnt counts in order).  Unconditional loads at clamped positions, selected afterwards: a
@@ -430,7 +412,7 @@ __global__ __launch_bounds__(64 * W, (W >= 8 ? 4 : 2)) void lin_inside_strip(McB
             r_bp[sl] = L->E_bp[s_i * 5 + s_jp1[sl]];
             r_tjbd[sl] = L->TJB[idd]; r_tjad[sl] = L->TJA[idd];
             r_b01[sl] = L->E_b01[s_j[sl]]; r_b10[sl] = L->E_b10[s_ip1]; r_11[sl] = L->E_11[s_ip1 * 5 + s_j[sl]];
-            const double far = tab[S_FM2F * ts + (unsigned)(d * ld) + (unsigned)i];   // (rows < 64 hold nothing: selected away)
+            const double far = tab[L_FM2F * ts + (unsigned)(d * ld) + (unsigned)i];   // (rows < 64 hold nothing: selected away)
             p_far[sl] = (v & (d >= 64)) ? far : 0.0;
         }
         // the first of its steps may still need rows < d0 (unconditional loads, selected afterwards)
@@ -447,7 +429,7 @@ __global__ __launch_bounds__(64 * W, (W >= 8 ? 4 : 2)) void lin_inside_strip(McB
                 if (k0 < 3) {
                     x01 = fcx[(unsigned)((d - 3) * ld) + c1]; x10 = fcx[(unsigned)((d - 3) * ld) + c2];
                     if (k0 < 2) {
-                        fc = tab[S_FC * ts + (unsigned)((d - 2) * ld) + c1]; fca = tab[S_FCA * ts + (unsigned)((d - 2) * ld) + c1];
+                        fc = tab[L_FC * ts + (unsigned)((d - 2) * ld) + c1]; fca = tab[L_FCA * ts + (unsigned)((d - 2) * ld) + c1];
                         if (k0 < 1) { xm1 = fm1[(unsigned)((d - 1) * ld) + c1]; xm = fm[(unsigned)((d - 1) * ld) + (unsigned)i]; }
                     }
                 }
@@ -627,7 +609,7 @@ __global__ __launch_bounds__(64 * W, (W >= 8 ? 4 : 2)) void lin_inside_strip(McB
 #pragma unroll
     for (int sl = 0; sl < NSL; sl++) {
         const int d = d0 + w + W * sl;
-        const bool pr = i <= n - 1 - d && pairs_s(s_i, s_jp1[sl]);
+        const bool pr = i <= n - 1 - d && pairs(s_i, s_jp1[sl]);
         p_tjb[sl] = pr ? r_tjb[sl] : 0.0;
         p_ctja[sl] = pr ? r_tja[sl] * L->e_mpmb : 0.0;
         p_cst[sl] = pr ? r_tst[sl] * L->lam2 : 0.0;
@@ -752,7 +734,7 @@ __global__ __launch_bounds__(64 * W, (W >= 8 ? 4 : 2)) void lin_inside_strip(McB
 #pragma unroll 1
         for (int r = w; r < 5 * KD; r += W) {
             const int tb = r / KD, k = r - tb * KD, d = d0 + k;   // S row order: FM, FM1, FCX, FC, FCA
-            const int slot_of[5] = {S_FM, S_FM1, S_FCX, S_FC, S_FCA};
+            const int slot_of[5] = {L_FM, L_FM1, L_FCX, L_FC, L_FCA};
             if (i <= n - 1 - d) tab[slot_of[tb] * ts + (size_t)d * ld + i] = SFM[r * CS + lane];
         }
     }
@@ -769,12 +751,12 @@ __global__ __launch_bounds__(256) void lin_f5i_tail(McBatch B, const LinModel* _
     const int n = B.n[sq], ld = B.ld;
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     double* __restrict__ f5i = B.f5i + (size_t)sq * ld;
-    const double* __restrict__ fca = B.tab + (size_t)sq * B.seq_stride + S_FCA * B.tab_stride;
+    const double* __restrict__ fca = B.tab + (size_t)sq * B.seq_stride + L_FCA * B.tab_stride;
 #pragma unroll 1
     for (int jj = jlo < 1 ? 1 : jlo; jj <= n; jj++) {
         double acc = 0.0;
         for (int k = threadIdx.x; k <= jj - 2; k += 256) acc = fma(f5i[k], fca[(size_t)(jj - 2 - k) * ld + (k + 1)], acc);
-        acc = wsum_s(acc);
+        acc = wsum(acc);
         if (lane == 0) red[w] = acc;
         __syncthreads();
         if (threadIdx.x == 0) f5i[jj] = f5i[jj - 1] * L->w_eu + (red[0] + red[1] + red[2] + red[3]) * L->w_ep2;
@@ -822,7 +804,7 @@ __device__ __forceinline__ void f5o_range(const double* __restrict__ fca_tab, do
         double acc = 0.0;   // fixed partition (256 threads, 4 partial sums) whatever W is: see the inside strip
         if (threadIdx.x < 256)
             for (int jj = k + 2 + threadIdx.x; jj <= n; jj += 256) acc = fma(f5o[jj], fca[(size_t)(jj - 2 - k) * ld], acc);
-        acc = wsum_s(acc);
+        acc = wsum(acc);
         if (lane == 0) red[w] = acc;
         __syncthreads();
         if (threadIdx.x == 0) f5o[k] = f5o[k + 1] * L->w_eu + (red[0] + red[1] + red[2] + red[3]) * L->w_ep2;
@@ -836,7 +818,7 @@ __global__ __launch_bounds__(256) void lin_f5o_head(McBatch B, const LinModel* _
     __shared__ double red[4];
     const int sq = blockIdx.x;
     if (sq >= B.ns) return;
-    f5o_range<4>(B.tab + (size_t)sq * B.seq_stride + S_FCA * B.tab_stride, B.f5o + (size_t)sq * B.ld, L, B.n[sq], B.ld, khi, klo, red);
+    f5o_range<4>(B.tab + (size_t)sq * B.seq_stride + L_FCA * B.tab_stride, B.f5o + (size_t)sq * B.ld, L, B.n[sq], B.ld, khi, klo, red);
 }
 
 template <int KD, int W, int FILT>
@@ -876,7 +858,7 @@ __global__ __launch_bounds__(64 * W, (W >= 8 ? 4 : 2)) void lin_outside_strip(Mc
     const int ngroup = (ncell_max + GS - 1) / GS;
     if (slot > ngroup) return;
     if (slot == ngroup) {
-        f5o_range<W>(tab + S_FCA * ts, f5o, L, n, ld, f5_hi, f5_lo, red);
+        f5o_range<W>(tab + L_FCA * ts, f5o, L, n, ld, f5_hi, f5_lo, red);
         return;
     }
 
@@ -892,10 +874,10 @@ __global__ __launch_bounds__(64 * W, (W >= 8 ? 4 : 2)) void lin_outside_strip(Mc
     double* const LDm = lds;                               // fixed FM rows e = 1..
     double* const LA = lds + P::RD * CD;                   // zero rows + sliding FM2o rows
     double* const LE = LA + P::RA * CA;                    // sliding FCoX rows
-    const double* __restrict__ fm = tab + S_FM * ts;
-    const double* __restrict__ fm1 = tab + S_FM1 * ts;
-    const double* __restrict__ fm2o = tab + S_FM2O * ts;
-    const double* __restrict__ fcox = tab + S_FCOX * ts;
+    const double* __restrict__ fm = tab + L_FM * ts;
+    const double* __restrict__ fm1 = tab + L_FM1 * ts;
+    const double* __restrict__ fm2o = tab + L_FM2O * ts;
+    const double* __restrict__ fcox = tab + L_FCOX * ts;
 
     // sequence letters of this wavefront's chain steps k = w + W*sl: the first loads issued, unconditional at clamped positions
     // (see the inside strip for why nothing here is loaded under a branch)
@@ -1023,7 +1005,7 @@ __global__ __launch_bounds__(64 * W, (W >= 8 ? 4 : 2)) void lin_outside_strip(Mc
             r_tjbd[sl] = L->TJB[idd]; r_tjad[sl] = L->TJA[idd];
             r_b01[sl] = L->E_b01[s_jp2[sl]]; r_b10[sl] = L->E_b10[s_im1]; r_11[sl] = L->E_11[s_im1 * 5 + s_jp2[sl]];
             const unsigned at = (unsigned)(d * ld + ic);
-            const double fmof = tab[S_FMOF * ts + at], fm1of = tab[S_FM1OF * ts + at], fcv = tab[S_FC * ts + at];
+            const double fmof = tab[L_FMOF * ts + at], fm1of = tab[L_FM1OF * ts + at], fcv = tab[L_FC * ts + at];
             const double f5ov = f5o[j + 1 < 0 ? 0 : (j + 1 <= n ? j + 1 : n)];
             p_far_m[sl] = v ? fmof : 0.0;
             p_far_1[sl] = v ? fm1of : 0.0;
@@ -1178,8 +1160,8 @@ __global__ __launch_bounds__(64 * W, (W >= 8 ? 4 : 2)) void lin_outside_strip(Mc
             if (k0 < 3) {
                 l_x01 = fcox[a3 - 1]; l_x10 = fcox[a3 - 2];
                 if (k0 < 2) {
-                    l_fm1o_up = tab[S_FM1O * ts + a2 - 1]; l_fco_up = tab[S_FCO * ts + a2 - 1];          // ipp:3828
-                    if (k0 < 1) { l_fmo = tab[S_FMO * ts + a1]; l_fm1o = tab[S_FM1O * ts + a1 - 1]; }    // FMo[d+1][i], FM1o[d+1][i-1]   ipp:3806, 3833
+                    l_fm1o_up = tab[L_FM1O * ts + a2 - 1]; l_fco_up = tab[L_FCO * ts + a2 - 1];          // ipp:3828
+                    if (k0 < 1) { l_fmo = tab[L_FMO * ts + a1]; l_fm1o = tab[L_FM1O * ts + a1 - 1]; }    // FMo[d+1][i], FM1o[d+1][i-1]   ipp:3806, 3833
                 }
             }
         }
@@ -1232,7 +1214,7 @@ __global__ __launch_bounds__(64 * W, (W >= 8 ? 4 : 2)) void lin_outside_strip(Mc
 #pragma unroll
     for (int sl = 0; sl < NSL; sl++) {
         const int d = d0 - (w + W * sl);
-        const bool pr = i >= 1 && d >= 0 && i <= n - 1 - d && pairs_s(s_i, s_jp1[sl]);
+        const bool pr = i >= 1 && d >= 0 && i <= n - 1 - d && pairs(s_i, s_jp1[sl]);
         p_cbd[sl] = pr ? r_bp[sl] * r_tjbd[sl] : 0.0;      // e_bp * e_tjbd
         p_cad[sl] = pr ? r_bp[sl] * r_tjad[sl] : 0.0;      // e_bp * e_tjad
         p_cst[sl] = pr ? r_tst[sl] * L->lam2 : 0.0;
@@ -1376,7 +1358,7 @@ __global__ __launch_bounds__(64 * W, (W >= 8 ? 4 : 2)) void lin_outside_strip(Mc
 #pragma unroll 1
         for (int r = w; r < 5 * KD; r += W) {
             const int tb = r / KD, k = r - tb * KD, d = d0 - k;   // S row order: FM2o, FMo, FM1o, FCo, FCoX
-            const int slot_of[5] = {S_FM2O, S_FMO, S_FM1O, S_FCO, S_FCOX};
+            const int slot_of[5] = {L_FM2O, L_FMO, L_FM1O, L_FCO, L_FCOX};
             if (d >= 0 && i <= n - 1 - d) tab[slot_of[tb] * ts + (size_t)d * ld + i] = SFM2O[r * CS + PADL + lane];
         }
     }
@@ -1384,7 +1366,7 @@ __global__ __launch_bounds__(64 * W, (W >= 8 ? 4 : 2)) void lin_outside_strip(Mc
     for (int t = threadIdx.x; t < 64 * KD; t += 64 * W) {
         const int c = t / KD, k = t - c * KD, ii = i0 + c, d = d0 - k;
         if (c >= KD - 1 && ii >= 1 && d >= 0 && ii <= n - 1 - d)
-            B.bp[(size_t)sq * B.tri_stride + tri_off_s(n, ii) + (ii + d + 1)] = PART[(k * 3) * 64 + c];
+            B.bp[(size_t)sq * B.tri_stride + tri_off(n, ii) + (ii + d + 1)] = PART[(k * 3) * 64 + c];
     }
     RH_STAMPO(8);
 }

@@ -26,29 +26,20 @@
 #include <hip/hip_runtime.h>
 
 #include "batch.h"
+#include "dev_util.h"
 #include "lse.h"
 #include "vienna_model.h"
 #include "kernels.h"
 
 namespace rh {
 
-// square ld x ld tables per sequence; *T = stored transposed ([j][i])
-enum VmTable { VM_FC = 0, VM_FCX, VM_FCA, VM_FCAT, VM_FM1, VM_FM1T, VM_FM, VM_FMT, VM_FMST,
-               VM_FCO, VM_FCOX, VM_FM2O, VM_FM2OT, VM_FMSOT, VM_FM1O, VM_FCOT, VM_COUNT };
 // scratch slots of the accessibility pass (their sweep contents are dead by then)
 constexpr int VM_S_FCT = VM_FCAT;    // FC transposed
 constexpr int VM_S_FCOT = VM_FCOT;   // FCo transposed (written by the outside cells themselves)
 constexpr int VM_S_HP = VM_FCX;      // hairpin probabilities [p][q] -> exclusive prefix sums over p
-static_assert((int)VM_COUNT == kViennaMcTables, "batch.h and mccaskill_vienna.hip disagree on the table count");
 
 namespace {
 
-__device__ __forceinline__ void block_map_v(int pin, int* sq, int* slot)
-{
-    *sq = pin ? blockIdx.x : blockIdx.y;
-    *slot = pin ? blockIdx.y : blockIdx.x;
-}
-__device__ __forceinline__ size_t tri_offset_v(int n, int i) { return (size_t)i * (size_t)(2 * (n + 1) - i - 1) / 2; }
 // letters g and g+1 are neighbours on one strand
 __device__ __forceinline__ bool gap_ok(int cut, int g) { return g != cut; }   // cut = 0 never equals a gap index >= 1
 // the missing gap lies among gaps lo..hi
@@ -113,7 +104,7 @@ __global__ void mcv_init(McBatch B)
 __global__ __launch_bounds__(256) void mcv_inside_diag(McBatch B, const ViennaDx* __restrict__ V, int d, int pin)
 {
     int sq, slot;
-    block_map_v(pin, &sq, &slot);
+    block_map(pin, &sq, &slot);
     if (sq >= B.ns) return;
     const int n = B.n[sq];
     const int wave = slot * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -260,7 +251,7 @@ __global__ __launch_bounds__(256) void mcv_inside_diag(McBatch B, const ViennaDx
 __global__ __launch_bounds__(256) void mcv_outside_diag(McBatch B, const ViennaDx* __restrict__ V, int d, int pin)
 {
     int sq, slot;
-    block_map_v(pin, &sq, &slot);
+    block_map(pin, &sq, &slot);
     if (sq >= B.ns) return;
     const int n = B.n[sq];
     const int wave = slot * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -419,7 +410,7 @@ __global__ __launch_bounds__(256) void mcv_outside_diag(McBatch B, const ViennaD
         const double e = fco + fc_in - Z;
         double p = e > kNeg / 2 ? exp(e) : 0.0;
         p = p > 1.0 ? 1.0 : p;
-        B.bp[(size_t)sq * B.tri_stride + tri_offset_v(n, i) + (j + 1)] = (pairable && d >= kMinHairpin) ? p : 0.0;
+        B.bp[(size_t)sq * B.tri_stride + tri_off(n, i) + (j + 1)] = (pairable && d >= kMinHairpin) ? p : 0.0;
     }
 }
 
@@ -629,7 +620,7 @@ __global__ __launch_bounds__(256) void mcv_extract_hp(McBatch B, double* __restr
     }
     if (c >= n1 * n2) return;
     const int i = c / n2 + 1, j = c % n2 + 1;
-    hp[(size_t)p * hp_stride + (size_t)i * ldd + j] = B.bp[(size_t)p * B.tri_stride + tri_offset_v(n, i) + n1 + j];
+    hp[(size_t)p * hp_stride + (size_t)i * ldd + j] = B.bp[(size_t)p * B.tri_stride + tri_off(n, i) + n1 + j];
 }
 
 // logZ = F5i[n]

@@ -15,21 +15,13 @@
 #include <hip/hip_runtime.h>
 
 #include "batch.h"
+#include "dev_util.h"
 #include "vienna_model.h"
 #include "kernels.h"
 
 namespace rh {
 
 namespace {
-
-__device__ __forceinline__ size_t tri_off_vl(int n, int i) { return (size_t)i * (size_t)(2 * (n + 1) - i - 1) / 2; }
-
-__device__ __forceinline__ double wsum_vl(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // pin bits 0..6: sequence on blockIdx.x (1) or blockIdx.y (0); bit 7: windowed grid of the two-molecule sweeps, first cell group in
 // bits 8.. (see window_slot_vl)
@@ -74,29 +66,7 @@ __device__ __forceinline__ bool window_slot_vl(int pin, int ngroup, int* slot)
     return *slot < ngroup;
 }
 
-template <int T>
-__device__ __forceinline__ double vfilt_fwd(const double* __restrict__ wt, const double* seg)
-{
-    double s0 = 0.0, s1 = 0.0;
-#pragma unroll
-    for (int l1 = 0; l1 <= T; l1 += 2) {
-        s0 = fma(wt[l1], seg[l1], s0);
-        if (l1 + 1 <= T) s1 = fma(wt[l1 + 1], seg[l1 + 1], s1);
-    }
-    return s0 + s1;
-}
-template <int T>
-__device__ __forceinline__ double vfilt_rev(const double* __restrict__ wt, const double* seg)
-{
-    double s0 = 0.0, s1 = 0.0;
-#pragma unroll
-    for (int l1 = 0; l1 <= T; l1 += 2) {
-        s0 = fma(wt[l1], seg[T - l1], s0);
-        if (l1 + 1 <= T) s1 = fma(wt[l1 + 1], seg[T - l1 - 1], s1);
-    }
-    return s0 + s1;
-}
-// the same filters with a per-lane limit on each gap (two-molecule form: a loop side may not cross the missing gap).
+// the unrolled filters filt_fwd<T> / filt_rev<T> (dev_util.h) with a per-lane limit on each gap (two-molecule form: a loop side may not cross the missing gap).
 // Only the few 64-cell groups next to the gap take this path: a rolled loop, taps outside [lo, hi] are skipped per lane.
 __device__ __forceinline__ double vfilt_fwd_m(int t, const double* __restrict__ wt, const double* seg, int l1max, int l2max)
 {
@@ -133,8 +103,7 @@ __device__ __forceinline__ void vfilt_pair_any(int r, const double* __restrict__
 {
     switch (r) {
 #define X(T) case T: vfilt_pair<T>(wA, wB, seg, sa, sb); return;
-        X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(17) X(18) X(19) X(20) X(21) X(22) X(23) X(24)
-        X(25) X(26) X(27) X(28) X(29) X(30) X(31)
+        RH_T_CASES_4_30(X) X(31)
 #undef X
     }
     sa = 0.0; sb = 0.0;
@@ -174,8 +143,7 @@ __device__ __forceinline__ void vfilt_pair_rev_any(int r, const double* __restri
 {
     switch (r) {
 #define X(T) case T: vfilt_pair_rev<T>(wA, wB, seg, sa, sb); return;
-        X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(17) X(18) X(19) X(20) X(21) X(22) X(23) X(24)
-        X(25) X(26) X(27) X(28) X(29) X(30) X(31)
+        RH_T_CASES_4_30(X) X(31)
 #undef X
     }
     sa = 0.0; sb = 0.0;
@@ -197,13 +165,11 @@ __device__ __forceinline__ void vfilt_pair_rev_m(int r, const double* __restrict
     sa = a; sb = b;
 }
 // generic loops need l1, l2 >= 1 and t >= 4 (1x1, 1x2, 2x1 are tabulated; 2x2 has weight 0 in shape_w)
-#define RH_VT_CASES(X) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) \
-    X(17) X(18) X(19) X(20) X(21) X(22) X(23) X(24) X(25) X(26) X(27) X(28) X(29) X(30)
 __device__ __forceinline__ double vfilt_fwd_any(int t, const double* __restrict__ wt, const double* seg)
 {
     switch (t) {
-#define X(T) case T: return vfilt_fwd<T>(wt, seg);
-        RH_VT_CASES(X)
+#define X(T) case T: return filt_fwd<T>(wt, seg);
+        RH_T_CASES_4_30(X)
 #undef X
     }
     return 0.0;
@@ -211,8 +177,8 @@ __device__ __forceinline__ double vfilt_fwd_any(int t, const double* __restrict_
 __device__ __forceinline__ double vfilt_rev_any(int t, const double* __restrict__ wt, const double* seg)
 {
     switch (t) {
-#define X(T) case T: return vfilt_rev<T>(wt, seg);
-        RH_VT_CASES(X)
+#define X(T) case T: return filt_rev<T>(wt, seg);
+        RH_T_CASES_4_30(X)
 #undef X
     }
     return 0.0;
@@ -270,10 +236,6 @@ extern "C" int rh_debug_vstamps(unsigned long long* out, int reset)
 #define RH_VLA_WPE 4   // wavefronts/SIMD the look-ahead (MODE 1) kernel is compiled for
 #endif
 #define GAPOK(g) (!CUT || gap_ok_vl(cut, (g)))
-// table slots: 3, 4, 7, 10, 11, 12 are the ones mccaskill_far.hip addresses (LinTableFar)
-enum VLinTable { VL_FC = 0, VL_FCX, VL_FCA, VL_FM1, VL_FM, VL_FCO, VL_FCOX, VL_FM2O, VL_FMSO, VL_FM1O,
-                 VL_FM2F, VL_FMOF, VL_FM1OF, VL_FMS, VL_FCB, VL_FCOB, VL_COUNT };
-static_assert((int)VL_COUNT <= kViennaMcTables, "linear tables reuse the log-space table buffer");
 
 __global__ void vlin_init(McBatch B, int* __restrict__ bad)
 {
@@ -359,7 +321,7 @@ __global__ __launch_bounds__(MODE == 2 ? 64 : 64 * W) __attribute__((amdgpu_wave
         double acc = 0.0;
         if (is_xp) acc = dot4_vl(cut, b - 2, threadIdx.x, 64 * WR, acc, [&](int k) { return xv[k]; }, [&](int k) { return fca[(b - k - 2) * ld + (k + 1)]; });
         else acc = dot4_vl(a + 4, cut, threadIdx.x, 64 * WR, acc, [&](int l) { return fca[(l - 1 - a) * ld + a]; }, [&](int l) { return xv[l + 1]; });
-        acc = wsum_vl(acc);
+        acc = wsum(acc);
         if (lane == 0) part[0][w][0] = acc;
         __syncthreads();
         if (threadIdx.x == 0) {
@@ -377,7 +339,7 @@ __global__ __launch_bounds__(MODE == 2 ? 64 : 64 * W) __attribute__((amdgpu_wave
         const double* __restrict__ fca = tab + VL_FCA * ts;
         double acc = 0.0;
         acc = dot4_vl(0, jj - 2, threadIdx.x, 64 * WR, acc, [&](int k) { return f5i[k]; }, [&](int k) { return fca[(jj - 2 - k) * ld + (k + 1)]; });
-        acc = wsum_vl(acc);
+        acc = wsum(acc);
         if (lane == 0) part[0][w][0] = acc;
         __syncthreads();
         if (threadIdx.x == 0) {
@@ -850,7 +812,7 @@ __global__ __launch_bounds__(MODE == 2 ? 64 : 64 * W) __attribute__((amdgpu_wave
             }
             acc2 = dot4_vl(1, a - 2, threadIdx.x, 64 * WR, acc2, [&](int aa) { return xso[aa]; }, [&](int aa) { return fca[(a - 2 - aa) * ld + aa]; });
         }
-        acc = wsum_vl(acc); acc2 = wsum_vl(acc2);
+        acc = wsum(acc); acc2 = wsum(acc2);
         if (lane == 0) { part[0][w][0] = acc; part[1][w][0] = acc2; }
         __syncthreads();
         if (threadIdx.x == 0) {
@@ -868,7 +830,7 @@ __global__ __launch_bounds__(MODE == 2 ? 64 : 64 * W) __attribute__((amdgpu_wave
         const double* __restrict__ fca = tab + VL_FCA * ts + (k + 1);
         double acc = 0.0;
         acc = dot4_vl(k + 2, n, threadIdx.x, 64 * WR, acc, [&](int jj) { return f5o[jj]; }, [&](int jj) { return fca[(jj - 2 - k) * ld]; });
-        acc = wsum_vl(acc);
+        acc = wsum(acc);
         if (lane == 0) part[0][w][0] = acc;
         __syncthreads();
         if (threadIdx.x == 0) {
@@ -1254,7 +1216,7 @@ __global__ __launch_bounds__(MODE == 2 ? 64 : 64 * W) __attribute__((amdgpu_wave
     const bool wanted = !(CUT && cut > 0) || (i <= cut && j + 1 > cut);
     if (!(p == p) || p > 1e300) { if (wanted) atomicOr(&bad[sq], 1); p = 0.0; }
     p = p > 1.0 ? 1.0 : (p < 0.0 ? 0.0 : p);
-    B.bp[(size_t)sq * B.tri_stride + tri_off_vl(n, i) + (j + 1)] = wanted ? p : 0.0;
+    B.bp[(size_t)sq * B.tri_stride + tri_off(n, i) + (j + 1)] = wanted ? p : 0.0;
 }
 
 // logZ = log F5i~[n] + s*n; flags a sequence whose scaled values left the double range
@@ -1630,7 +1592,7 @@ __global__ __launch_bounds__(256) void vlin_acc_hsum(McBatch B, int max_w)
     // tail beyond the widest region, then one more column per narrower width
     double tail = 0.0;
     for (int q = a + max_w + lane; q <= n; q += 64) tail += C[q];
-    tail = wsum_vl(tail);
+    tail = wsum(tail);
     if (lane == 0) {
         double run = tail;
         for (int w = max_w - 1; w >= 0; w--) {

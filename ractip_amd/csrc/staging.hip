@@ -134,7 +134,7 @@ int stage(rh_ctx* c, int ns, const char* const* seqs, const int* lens, bool with
         B.ns = ns; B.nmax = nmax; B.lds = lds;
         B.ld = (nmax + 2 + 1) & ~1;
         B.tab_stride = (size_t)B.ld * B.ld;
-        B.seq_stride = B.tab_stride * (vienna ? (int)kViennaMcTables : (int)T_COUNT);
+        B.seq_stride = B.tab_stride * (vienna ? (int)VM_COUNT : (int)T_COUNT);
         B.tri_stride = (tri_size(nmax) + 1) & ~(size_t)1;
         if ((rc = ensure(c, c->d_mctab, sizeof(double) * B.seq_stride * ns, false))) return rc;
         B.nb = (nmax - 1) / 16 + 1;
@@ -187,7 +187,7 @@ int stage(rh_ctx* c, int ns, const char* const* seqs, const int* lens, bool with
         D.np = ns / 2; D.n1max = n1max; D.n2max = n2max; D.lds = lds;
         D.ldd = (n2max + 2 + 1) & ~1;
         D.tab_stride = (size_t)(n1max + 2) * D.ldd;
-        D.pair_stride = D.tab_stride * 6;   // 4 tables (CONTRAfold model) or 6 (Vienna model: IN/OUT + two decorated copies each)
+        D.pair_stride = D.tab_stride * std::max((int)D_COUNT, (int)V_COUNT);   // 4 tables (CONTRAfold model) or 6 (Vienna model: IN/OUT + two decorated copies each)
         // the linear path keeps anti-diagonal-major tables in the same buffer (sequential use)
         DxLinBatch& X = c->dxl;
         X.np = D.np; X.n1max = n1max; X.n2max = n2max; X.lds = lds; X.ldd = D.ldd;
@@ -197,7 +197,7 @@ int stage(rh_ctx* c, int ns, const char* const* seqs, const int* lens, bool with
         // Vienna-BL: raw + two decorated copies per direction; 2.x semantics: two more copies each (mismatch1nI, mismatch23I) -- sized
         // by the context, not by rh_set_duplex_mode, which may change between upload and compute: a 2.x context that stays on the
         // log-space kernels pays for it with a larger buffer and clear (10 linear tables against the 6 log-space ones, whichever is larger)
-        X.pair_stride = X.tab_stride * (!vienna ? (int)DL_COUNT : c->vienna_sem == kViennaSem20 ? kVdTables20 : kVdTables18);
+        X.pair_stride = X.tab_stride * (!vienna ? (int)DL_COUNT : c->vienna_sem == kViennaSem20 ? (int)VD_COUNT20 : (int)VD_COUNT);
         const size_t dx_bytes = sizeof(double) * std::max(D.pair_stride, X.pair_stride) * D.np;
         void* before = c->d_dxtab.p;
         if ((rc = ensure(c, c->d_dxtab, dx_bytes, false))) return rc;
@@ -232,7 +232,7 @@ int stage(rh_ctx* c, int ns, const char* const* seqs, const int* lens, bool with
             C.lds = (cmax + 3 + 15) & ~15;
             C.ld = (cmax + 2 + 1) & ~1;
             C.tab_stride = (size_t)C.ld * C.ld;
-            C.seq_stride = C.tab_stride * kViennaMcTables;
+            C.seq_stride = C.tab_stride * (int)VM_COUNT;
             C.tri_stride = (tri_size(cmax) + 1) & ~(size_t)1;
             std::vector<uint8_t> cc((size_t)np * C.lds, 0);
             std::vector<int> nn(2 * (size_t)np);
