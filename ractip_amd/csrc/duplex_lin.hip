@@ -443,32 +443,40 @@ __global__ __launch_bounds__(256) RH_WPE_DX void dxl_sweep4(DxLinBatch B, const 
 //   * X_k also reads the strip's own rows k' <= k-2 (kept in LDS, raw and decorated): four time slots, two diagonals each
 //     (wavefronts 2s, 2s+1), an LDS-only barrier in between;
 //   * X_k reaches k-1-k' columns into row k': the valid lanes shrink by up to 6 from the `dir` side, groups advance by 58 columns
-//     and the overlap is recomputed.
+//     and the overlap is recomputed;
+//   * the shapes with t <= 2 of X_0..X_3 that end on rows of earlier launches take the decorated rows 3 and 4 before the cell from the
+//     staged rows r = 1..4 (opr, behind the window-pass barrier); only the stacked-pair operand of X_0 / X_1 (raw table, row 2 before
+//     it) is a global load of its own.  A cell's weights come from the fused, pair-indexed tables (DxLinModel::F, lin_model.h): every
+//     thread requests its share of the direction's 1050 doubles at the head of the kernel, whatever the letters are, and finish()
+//     takes them from LDS by letter index -- the kernel has no global load that waits for another one.
 // What a launch leaves behind (the band invariant).  Row sd has cells at columns alo(sd) = max(1, sd-L2) .. ahi(sd) = min(L1, sd-1).
 // After the launch each of its rows is correct -- the cell's value, 0 where there is no cell -- on [alo-kDxBand, ahi+kDxBand] clipped
 // to the columns 0..n1max+1 of the row, and UNSPECIFIED beyond (whatever an earlier batch of the same table layout left there,
 // Inf / NaN included).  That is all anyone reads, see the proof at kDxBand (batch.h): a kept cell reads a row only within 30 columns
 // of that row's cells, and dxl_logz_part / dxl_posterior read cells only.  A lane outside [alo, ahi] of its diagonal may load and sum
-// such stale values, but none of them reaches a stored value: `pairable` (dx_cell_weights) is false for it, so its operands are
-// selected to 0 and finish() stores 0 for it, and windows, partial sums and the strip's own rows are per lane -- a kept lane takes
-// from srow only lanes that are themselves kept cells or zeros.  Hence no clear of these tables after an overflowed batch either.
+// such stale values, but none of them reaches a stored value: `pairable` is false for it, so its operands are selected to 0 and
+// finish() stores 0 for it, and windows, partial sums and the strip's own rows are per lane -- a kept lane takes from srow only lanes
+// that are themselves kept cells or zeros.  The operands taken from the staged rows (opr) are the table values at columns
+// a + dir*(1..3) of rows 3 and 4 before the cell, exactly what the global loads of dx_cell_loads fetch: within 3 columns of a kept
+// cell, inside the band of those rows and inside the padded row (kDxPad >= 3), where the staging keeps the table value; a lane that
+// is no cell reads whatever the segment holds there and selects 0.  Hence no clear of these tables after an overflowed batch either.
 //   * a group with cells on none of the eight diagonals stores zeros where its columns meet the band of a row, and nothing else;
 //   * a group with cells stores its 58 columns of all eight rows (a superset);
 //   * the grid holds only as many groups as the bands of one launch can touch: blockIdx.x counts from the first group of this
 //     pair's band (dxl_strip8_groups is the bound, a function of the batch shape and the step alone: the launches are captured).
 
 template <int WV>
-__device__ __forceinline__ void win_pass8(const double* seg0, const double* __restrict__ lam_pow, bool outside, int sdA, int smax, double acc[8])
+__device__ __forceinline__ void win_pass8(const double* seg0, const double* segq0, const double* __restrict__ lam_pow, bool outside, int sdA, int smax, double acc[8])
 {
-    // rows r = 1 + WV + 8q of wavefront WV; seg0[q*104 + c]: inside column a-36+c (window element l = 1.. at index 36-l), outside
-    // column a+1+c (element l at index l-1)
+    // rows r = 1 + WV + 8q of wavefront WV; seg0[q*104 + c] (q = 0: segq0[c]): inside column a-36+c (window element l = 1.. at index
+    // 36-l), outside column a+1+c (element l at index l-1)
 #pragma unroll
     for (int q = 0; q < 4; q++) {
         const int r = 1 + WV + 8 * q;            // compile-time after unrolling
         if (r > 30) continue;
         const int row = outside ? sdA + r : sdA - r;
         if (row >= 2 && row <= smax) {
-            lds_vp vs = (lds_vp)(seg0 + q * 104);
+            lds_vp vs = (lds_vp)(q == 0 ? segq0 : seg0 + q * 104);
             const int len_max = r + 6 < 29 ? r + 6 : 29;      // longest window any of the 8 diagonals takes from this row
             double run = 0.0;
             // eight reads at a time: left alone the scheduler hoists the reads of the whole row above the (dependent) running sum,
@@ -513,8 +521,14 @@ extern "C" int rh_debug_dstamps(unsigned long long* out, int reset)
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6, 8))) void dxl_strip8(DxLinBatch B, const DxLinModel* __restrict__ L, int step)
 {
     constexpr int KD = 8, GS = 58, PAD = 8, CS = 80;
-    __shared__ double seg[8][4][104];        // staged rows; afterwards: partial sums [8 wavefronts][8 diagonals][64]
+    __shared__ double seg[8][4][104];        // staged rows r = 5..30; afterwards: partial sums [8 wavefronts][4 diagonals][64], fused weights [kDxFused]
+    __shared__ double opr[4][104];           // staged rows r = 1..4 (wavefronts 0..3, q = 0): also the 0x1 / 1x0 / t = 2 operands of X_0..X_3
     __shared__ double srow[2][KD][CS];        // the strip's own rows: raw, decorated; lane l at index l+PAD
+    static_assert(kDxPairMask == kPairMask, "the fused tables number the pair types by the bits of the pair mask");
+    static_assert(8 * 4 * 64 + kDxFused <= 8 * 4 * 104, "partial sums and fused weights share the dead staging area");
+    static_assert(kDxFused > 1024 && kDxFused <= 1536, "every thread requests two fused weights, the first kDxFused - 1024 a third");
+    static_assert(sizeof(seg) + sizeof(srow) + sizeof(opr) <= 40960, "four workgroups per CU");
+    static_assert(kDxPad >= 3, "the operands of a cell lie within 3 columns of it");
     const int pr = blockIdx.y;
     const int L1 = B.n[2 * pr], L2 = B.n[2 * pr + 1];
     const bool outside = blockIdx.z != 0;
@@ -577,11 +591,27 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
         vl[q] = dect[(unsigned)(rowc * lda + cls)];     // (32-bit offsets from a uniform base: one address register per load;
         vh[q] = dect[(unsigned)(rowc * lda + chs)];     //  rowc >= 2 and cls >= -kDxPad: never negative)
     }
-    // ---- operands of X_w that come from rows of earlier launches (rows 2, 3, 4 before it while those lie outside the strip)
+    // ---- what finish() needs besides: the fused weights of this direction (lin_model.h), 1050 doubles, two or three per thread whatever
+    // the letters are (coalesced; they go to LDS behind the window pass and are taken from there by letter index: no dependent round
+    // trip through global memory), the six letters of the cell, and -- last, the only load under a condition, wavefronts 0 and 1 --
+    // the stacked-pair operand of X_0 / X_1 from the raw table (row 2 before it; the decorated rows 3 and 4 before X_w are staged rows)
+    const double* __restrict__ F = L->F[outside ? 1 : 0];
+    double fw0 = F[threadIdx.x], fw1 = F[512 + threadIdx.x];
+    double fw2 = F[threadIdx.x < kDxFused - 1024 ? 1024 + threadIdx.x : kDxFused - 1];
     const int sdw = sdA + w * fwd;
     const bool mine = sdw >= 2 && sdw <= smax;
-    bool pairable = false;
-    const DxCellRaw craw = dx_cell_loads(lda, rawt, dect, s1, s2, outside, sdw, a, L1, L2, smax, (w < 2 ? 1 : 0) | (w < 3 ? 2 : 0) | (w < 4 ? 4 : 0));
+    const int b = sdw - a;
+    const bool incell = mine && a >= 1 && a <= L1 && b >= 1 && b <= L2;
+    const int ci = incell ? a : 1, cj = incell ? L2 + 1 - b : 1;
+    const int x = s1[ci], xm = s1[ci - 1], xp = s1[ci + 1], y = s2[cj], ym = s2[cj - 1], yp = s2[cj + 1];
+    double v_st = 0.0;
+    bool ok2 = false;
+    if (w < 2) {
+        const int r2 = sdw + 2 * dir;
+        ok2 = r2 >= 2 && r2 <= smax;
+        const int ac = a < 0 ? 0 : (a > L1 + 1 ? L1 + 1 : a);   // a cell has 1 <= a <= L1; anything else only needs an address inside the row
+        v_st = rawt[(unsigned)((ok2 ? r2 : 2) * lda + ac + dir)];
+    }
     __builtin_amdgcn_sched_barrier(0);
     RH_DSTAMP(0);   // loads issued
 #pragma unroll
@@ -592,28 +622,53 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
         const int r = 1 + w + 8 * q;
         const int row = outside ? sdA + r : sdA - r;
         const bool rv = r <= 30 && row >= 2 && row <= smax;               // wave-uniform; rows that do not exist are never read
-        seg[w][q][lane] = rv && okl ? vl[q] : 0.0;
-        if (lane < 40) seg[w][q][64 + lane] = rv && okh ? vh[q] : 0.0;
+        double* const dst = (q == 0 && w < 4) ? &opr[w][0] : &seg[w][q][0];
+        dst[lane] = rv && okl ? vl[q] : 0.0;
+        if (lane < 40) dst[64 + lane] = rv && okh ? vh[q] : 0.0;
     }
     __builtin_amdgcn_sched_barrier(0);
     RH_DSTAMP(2);   // staged
-    DxCellOps o = dx_cell_weights(L, craw, outside, &pairable);
-    RH_DSTAMP(3);   // cell operands arrived, weights computed
+    asm volatile("" : "+v"(fw0)); asm volatile("" : "+v"(fw1)); asm volatile("" : "+v"(fw2));
+    // is it a pair, and where its weights are: eo the entry of its own weights, ed of the weight it is decorated with
+    const bool pairable = incell && pairs(x, y);
+    const int pt = pairable ? dx_pair_type(x, y) : 0;
+    const int eo = ((pt * 5 + (outside ? xp : xm)) * 5 + (outside ? ym : yp)) * kDxFusedK;
+    const int ed = ((pt * 5 + (outside ? xm : xp)) * 5 + (outside ? yp : ym)) * kDxFusedK;
+    RH_DSTAMP(3);   // letters and weights arrived, entries computed
     for (int k = threadIdx.x; k < 2 * KD * CS; k += 512) (&srow[0][0][0])[k] = 0.0;
     double acc[KD];
 #pragma unroll
     for (int k = 0; k < KD; k++) acc[k] = 0.0;
     switch (w) {   // (each wavefront reads only the rows it staged itself: no barrier needed before the pass)
-#define X(V) case V: win_pass8<V>(&seg[w][0][lane], L->lam_pow, outside, sdA, smax, acc); break;
+#define X(V) case V: win_pass8<V>(&seg[w][0][lane], V < 4 ? &opr[V < 4 ? V : 0][lane] : &seg[w][0][lane], L->lam_pow, outside, sdA, smax, acc); break;
         X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7)
 #undef X
     }
     RH_DSTAMP(4);   // window pass
     __syncthreads();
     RH_DSTAMP(5);   // barrier
+    // ---- operands of X_w, w < 4, from rows of earlier launches: the decorated rows 3 and 4 before it are the staged rows r = 3 - w and
+    // r = 4 - w (opr[r - 1], staged by wavefront r - 1: behind the barrier), columns a + dir*(1..3); zero where the row does not exist
+    DxCellOps o;
+    o.o_st = pairable && ok2 ? v_st : 0.0;
+    o.o_01 = o.o_10 = o.o_02 = o.o_11 = o.o_20 = 0.0;
+    if (w < 4) {
+        const int r3 = sdw + 3 * dir, r4 = sdw + 4 * dir;
+        const bool ok3 = w < 3 && r3 >= 2 && r3 <= smax, ok4 = r4 >= 2 && r4 <= smax;
+        const double* const p3 = &opr[w < 3 ? 2 - w : 0][outside ? lane : lane + 33];   // inside: column a-3+c, outside: column a+1+c
+        const double* const p4 = &opr[3 - w][outside ? lane : lane + 33];
+        const double v_01 = p3[outside ? 0 : 2], v_10 = p3[1];
+        const double v_02 = p4[outside ? 0 : 2], v_11 = p4[1], v_20 = p4[outside ? 2 : 0];
+        o.o_01 = pairable && ok3 ? v_01 : 0.0; o.o_10 = pairable && ok3 ? v_10 : 0.0;
+        o.o_02 = pairable && ok4 ? v_02 : 0.0; o.o_11 = pairable && ok4 ? v_11 : 0.0; o.o_20 = pairable && ok4 ? v_20 : 0.0;
+    }
     // partial sums meet over the dead staging area, [8 wavefronts][4 diagonals][64] at a time: diagonals 0..3 (read by their owners,
-    // wavefronts 0..3), then diagonals 4..7
+    // wavefronts 0..3), then diagonals 4..7; the fused weights go behind them (published by the barriers of the exchange)
     double* const part = &seg[0][0][0];
+    double* const wt = part + 8 * 4 * 64;
+    wt[threadIdx.x] = fw0;
+    wt[512 + threadIdx.x] = fw1;
+    if (threadIdx.x < kDxFused - 1024) wt[1024 + threadIdx.x] = fw2;
     // ---- chain: slot s finishes X_2s and X_2s+1 (wavefronts 2s, 2s+1)
     double g = 0.0;
 #pragma unroll
@@ -626,6 +681,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
             for (int q = 0; q < 8; q++) g += part[(q * 4 + (w & 3)) * 64 + lane];
         }
         lds_barrier();
+    }
+    {   // the cell's weights by letter index
+        const double f_dec = wt[ed], f_own = wt[eo + 1];
+        o.e_up = outside ? f_own : f_dec;
+        o.e_dn = outside ? f_dec : f_own;
+        o.e_ends = wt[eo + 2]; o.e_st = wt[eo + 3]; o.e_b01 = wt[eo + 4]; o.e_b10 = wt[eo + 5]; o.e_11 = wt[eo + 6];
     }
     RH_DSTAMP(6);   // partial sums exchanged (two halves, four barriers)
     auto finish = [&](int k) {

@@ -45,6 +45,20 @@ struct LinModel {
 
 void build_lin_model(const ScoreModel& m, double s, LinModel* out);
 
+// The fused weights of a duplex cell (dxl_strip8).  A cell's weights are used only if its letters (x, y) pair; the six pairing
+// combinations are numbered in the order of their bit x*5+y in the pair mask (AU 0, CG 1, GC 2, GU 3, UA 4, UG 5), and every weight
+// is a product of table entries indexed by that pair type and two neighbour letters n1 (strand 1), n2 (strand 2), each 0..4 (4: an
+// unknown letter or the sentinel at positions 0 and L+1 of a row).  Entry e = (type*5 + n1)*5 + n2 holds kDxFusedK doubles:
+//   [0]    the weight the value is decorated with (vx = v * ...): inside e_up with (n1, n2) = (xp, ym), outside e_dn with (xm, yp)
+//   [1..6] e_own, e_ends, e_st, e_b01, e_b10, e_11 of the cell itself: inside (n1, n2) = (xm, yp) and e_own = e_dn,
+//          outside (xp, ym) and e_own = e_up
+// each product evaluated left to right exactly as dx_cell_weights (duplex_lin.hip) writes it: the same bits.
+constexpr uint32_t kDxPairMask = (1u << (0 * 5 + 3)) | (1u << (3 * 5 + 0)) | (1u << (1 * 5 + 2)) |
+                                 (1u << (2 * 5 + 1)) | (1u << (2 * 5 + 3)) | (1u << (3 * 5 + 2));
+constexpr int kDxFusedEntries = 6 * 5 * 5, kDxFusedK = 7, kDxFused = kDxFusedEntries * kDxFusedK;
+// rank of (x, y) among the pairing combinations (meaningful only where they pair); host and device
+constexpr int dx_pair_type(int x, int y) { return __builtin_popcount(kDxPairMask & ((1u << (x * 5 + y)) - 1u)); }
+
 // duplex scores in scaled linear space (duplex_lin.hip); lam = exp(-s) per unit of a+b
 struct DxLinModel {
     double E_tm[625], E_hs[625];
@@ -54,6 +68,7 @@ struct DxLinModel {
     double lam_pow[32];   // lam^k
     double lam_eu;        // lam * exp(external_unpaired)
     double s;
+    double F[2][kDxFused];   // fused weights, [inside, outside][entry * kDxFusedK + k]
 };
 void build_dx_lin_model(const ScoreModel& m, double s, DxLinModel* out);
 

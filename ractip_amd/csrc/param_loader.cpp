@@ -196,6 +196,31 @@ void build_dx_lin_model(const ScoreModel& m, double s, DxLinModel* D)
     }
     for (int k = 0; k < 125; k++) { D->E_dl[k] = std::exp(m.dangle_left[k]); D->E_dr[k] = std::exp(m.dangle_right[k]); }
     for (int k = 0; k < 5; k++) { D->E_b01[k] = std::exp(m.bulge_0x1[k]); D->E_b10[k] = std::exp(m.bulge_1x0[k]); }
+    // fused weights (lin_model.h): per pairing (x, y) and neighbour letters, the products of dx_cell_weights in its order of evaluation
+    for (int x = 0; x < 5; x++) for (int y = 0; y < 5; y++) {
+        if (!((kDxPairMask >> (x * 5 + y)) & 1u)) continue;
+        for (int n1 = 0; n1 < 5; n1++) for (int n2 = 0; n2 < 5; n2++) {
+            const int e = ((dx_pair_type(x, y) * 5 + n1) * 5 + n2) * kDxFusedK;
+            double* fi = &D->F[0][e];
+            double* fo = &D->F[1][e];
+            {   // inside: decorated with e_up of (xp, ym) = (n1, n2); own weights with (xm, yp) = (n1, n2)
+                const int xp = n1, ym = n2, xm = n1, yp = n2;
+                fi[0] = D->E_tm[((x * 5 + y) * 5 + xp) * 5 + ym];
+                fi[1] = D->E_tm[((y * 5 + x) * 5 + yp) * 5 + xm] * D->E_bp[x * 5 + y];
+                fi[2] = D->E_dr[y * 25 + x * 5 + xm] * D->E_dl[y * 25 + x * 5 + yp] * D->E_bp[y * 5 + x] * D->E_hc[y * 5 + x];
+                fi[3] = D->E_bp[x * 5 + y] * D->E_hs[((xm * 5 + yp) * 5 + x) * 5 + y];
+                fi[4] = D->E_b01[yp]; fi[5] = D->E_b10[xm]; fi[6] = D->E_11[xm * 5 + yp];
+            }
+            {   // outside: decorated with e_dn of (xm, yp) = (n1, n2); own weights with (xp, ym) = (n1, n2)
+                const int xm = n1, yp = n2, xp = n1, ym = n2;
+                fo[0] = D->E_tm[((y * 5 + x) * 5 + yp) * 5 + xm] * D->E_bp[x * 5 + y];
+                fo[1] = D->E_tm[((x * 5 + y) * 5 + xp) * 5 + ym];
+                fo[2] = D->E_dl[x * 25 + y * 5 + xp] * D->E_dr[x * 25 + y * 5 + ym] * D->E_hc[x * 5 + y];
+                fo[3] = D->E_bp[xp * 5 + ym] * D->E_hs[((x * 5 + y) * 5 + xp) * 5 + ym];
+                fo[4] = D->E_b01[ym]; fo[5] = D->E_b10[xp]; fo[6] = D->E_11[xp * 5 + ym];
+            }
+        }
+    }
 }
 
 }  // namespace rh
