@@ -178,6 +178,32 @@ int rh_batch_upload(rh_ctx* ctx, int npairs,
 int rh_batch_upload_constrained(rh_ctx* ctx, int npairs,
                                 const char* const* s1, const int* n1, const char* const* s2, const int* n2,
                                 const char* const* cons1, const char* const* cons2, const char* const* co_cons);
+/* ---- indexed batches: fold each distinct sequence once, pair by index ----
+ * nseq distinct sequences, npairs pairs of them: pair p = (seqs[first[p]], seqs[second[p]]).
+ * Every sequence is folded once (bp, up, log Z); every pair gets its hp.  A sequence may be used by any number of pairs, in
+ * either role, or by none (it is folded all the same).  A 32 x 32 cross product is 1024 pairs over 64 folds, and its McCaskill
+ * tables are those of 64 sequences; under RH_HYBRID_COFOLD the N + M folds seed the N x M two-molecule sweeps.
+ * Both models; under RH_MODEL_VIENNA_BL both rh_set_hybrid sources.  Structure constraints on an indexed batch are not supported
+ * (there is no _constrained form).
+ * An index outside [0, nseq), npairs < 1, nseq < 1, a NULL sequence or a length < 1 is RH_ERR_ARG.  All arguments are checked before
+ * anything is staged: a rejected upload leaves the previous batch in place, as rh_batch_upload_constrained does.
+ * rh_batch_upload IS the indexed upload with the identity index (nseq = 2*npairs, first[p] = 2p, second[p] = 2p+1), bit for bit:
+ * both stage the distinct sequences once and build the pair-major image the duplex kernels read on the device, and a sequence's
+ * result bits depend on its own letters only, so pair p of an indexed batch has the bits it has in the expanded batch.
+ *
+ * The batched entry points on an indexed batch:
+ *   per pair, through the index: rh_batch_results(p, ...), rh_batch_candidates(p, which, ...), rh_batch_logz (out[3p..3p+2]) and
+ *     rh_batch_candidates_all (which = 0..4: npairs+1 offsets, the lists of the expanded batch -- a sequence's list is repeated
+ *     for every pair that uses it; rh_batch_candidates_seq_all is the form that does not replicate);
+ *   per distinct sequence: rh_batch_layout, rh_batch_results_all and rh_batch_device_views describe bp [nseq][tri_stride],
+ *     up [nseq][up_ld] and hp [npairs][hp_stride]; rh_batch_fallbacks which = 0 / 2 lists distinct-sequence indices, each once,
+ *     which = 1 / 3 pair indices.  A sequence that leaves the double range flags every pair that references it.
+ *   rh_debug_batch_allow_mask returns 1 (an indexed batch has no mask). */
+int rh_batch_upload_indexed(rh_ctx* ctx, int nseq, const char* const* seqs, const int* lens,
+                            int npairs, const int* first, const int* second);
+/* The index of the last upload (any pointer may be NULL; first / second hold npairs entries); for a plain rh_batch_upload:
+ * nseq = 2*npairs, first[p] = 2p, second[p] = 2p+1. */
+int rh_batch_index(rh_ctx* ctx, int* nseq, int* npairs, int* first, int* second);
 int rh_batch_compute(rh_ctx* ctx);
 int rh_batch_results(rh_ctx* ctx, int p,
                      double* bp1_tri, double* bp2_tri, double* up1, double* up2,
@@ -199,10 +225,15 @@ int rh_batch_candidates(rh_ctx* ctx, int p, int which, float threshold, rh_cand*
  * for each of 1000 pairs): out holds the concatenated lists, pair p owns out[first[p] .. first[p+1]) (first has
  * npairs+1 entries).  Returns the total number found (>= 0; only min(total, cap) entries are written) or an error. */
 int rh_batch_candidates_all(rh_ctx* ctx, int which, float threshold, rh_cand* out, int cap, int* first);
+/* Thresholded bp (what = 0) or up (what = 1) lists per DISTINCT sequence of the last upload: `first_out` has nseq+1 entries, sequence k
+ * owns out[first_out[k] .. first_out[k+1]).  Records are those of rh_batch_candidates_all, which = 0 / 3.  On a plain
+ * rh_batch_upload the sequences are 2p = s1, 2p+1 = s2 of pair p. */
+int rh_batch_candidates_seq_all(rh_ctx* ctx, int what, float threshold, rh_cand* out, int cap, int* first_out);
 
 /* Dense results of the whole batch in three copies, in the padded device layout described by rh_batch_layout:
- *   bp [2*npairs][tri_stride]  (sequence 2p = s1 of pair p; each table in the reference's triangular layout for ITS n)
- *   up [2*npairs][up_ld]       (n*max_w entries used, row-major position x width)
+ *   bp [nseq][tri_stride]      (rh_batch_upload: nseq = 2*npairs, sequence 2p = s1 of pair p; rh_batch_upload_indexed: the distinct
+ *                               sequences; each table in the reference's triangular layout for ITS n)
+ *   up [nseq][up_ld]           (n*max_w entries used, row-major position x width)
  *   hp [npairs][hp_stride] with row pitch hp_ld       logz [3*npairs]
  * Any pointer may be NULL. */
 int rh_batch_layout(rh_ctx* ctx, size_t* tri_stride, int* up_ld, size_t* hp_stride, int* hp_ld);
@@ -263,7 +294,7 @@ int rh_batch_fallbacks(rh_ctx* ctx, int which, int* out, int cap);
 int rh_set_scale_memory(rh_ctx* ctx, int on);
 
 /* Device pointers of the last batch (for callers that keep results on the GPU):
- * bp tables [2*npairs][tri_stride] (sequence 2p = s1 of pair p, 2p+1 = s2),
+ * bp tables [nseq][tri_stride] (rh_batch_upload: sequence 2p = s1 of pair p, 2p+1 = s2; indexed: the distinct sequences),
  * hp tables [npairs][hp_stride]. */
 int rh_batch_device_views(rh_ctx* ctx, const double** bp, size_t* tri_stride,
                           const double** hp, size_t* hp_stride, int* hp_ld);

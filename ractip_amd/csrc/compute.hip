@@ -83,7 +83,7 @@ static McVlinArgs mc_vlin_args(const rh_ctx* c, int phase, bool co)
     A.bad = co ? c->d_cobad.as<int>() : c->d_bad.as<int>();
     if (co) {
         const DxBatch& D = c->dx;
-        if (A.B.seeded) A.from = c->mc;
+        if (A.B.seeded) { A.from = c->mc; A.pair_seq = c->d_pidx.as<const int>(); }
         A.hp = D.hp; A.hp_logz = D.logz; A.hp_stride = D.tab_stride; A.hp_ldd = D.ldd; A.n1max = D.n1max; A.n2max = D.n2max;
         A.cut_min = c->co_cut_min; A.cut_max = c->co_cut_max;
         A.window = c->co_window && c->co_cut_min >= 1 && (phase == 1 || A.B.seeded);   // (an unseeded inside sweep computes every group)
@@ -276,7 +276,7 @@ static int vienna_folds(rh_ctx* c, Attempt* at, Between between, bool* overflowe
             log_path = *overflowed = !bad.empty();
             if (log_path) { c->last_path = 3; c->tables_dirty = true; }
             if (log_path && at->defer_log) {   // another exponent first (compute): this attempt ends here
-                for (int k : bad) { at->flagged_seqs.push_back(k); if (c->has_dx) at->flagged_pairs.push_back(k / 2); }
+                for (int k : bad) { at->flagged_seqs.push_back(k); if (c->has_dx) pairs_of_seq(c, k, &at->flagged_pairs); }
                 at->deferred = true;
                 log_path = false;
             }
@@ -329,12 +329,14 @@ static int schedule_vienna_duplex(rh_ctx* c, int dx_mode, Attempt* at)
 
 // ---- Vienna-BL model, hp from the two-molecule ensemble: sweeps over s1+s2 on s_dx, the folds on s_mc.  Without structure
 // constraints the sweeps are seeded: their cells on one strand are copied from the folds of the same pairs (vlin_co_seed), so they
-// start behind the inside sweep of the folds instead of next to it.  A flagged pair -- or, seeded, a flagged sequence: what was
+// start behind the inside sweep of the folds instead of next to it; through the index of the upload, N + M folds seed N x M sweeps.  A flagged pair -- or, seeded, a flagged sequence: what was
 // copied from its fold is not usable -- sends the batch of pairs to the log-space kernels, or ends the attempt (defer_log)
 static int schedule_vienna_cofold(rh_ctx* c, Attempt* at)
 {
     int rc;
-    const bool seed = c->has_dx && c->has_mc && c->mode != RH_MODE_LOG && c->co_seed && !c->mc.allow && !c->co.allow && c->mc.ns == 2 * c->co.ns;
+    // (both sequences of every pair are in c->mc: stage() has checked the index of an upload that has folds and pairs against it)
+    const bool seed = c->has_dx && c->has_mc && c->mode != RH_MODE_LOG && c->co_seed && !c->mc.allow && !c->co.allow &&
+                      c->pair_seq.size() == 2 * (size_t)c->co.ns && c->mc.ns == c->ns;
     c->co.seeded = seed ? 1 : 0;
     bool lin_launched = false;   // (its overflow flags are read after the McCaskill stream has been fed: the two overlap)
     const auto launch_lin = [&]() -> int {   // scaled linear sweeps over s1+s2, one graph of both phases
@@ -435,7 +437,9 @@ int compute(rh_ctx* c)
     //  rewrite every interior cell they read before reading it -- the invariant `tests: test_vienna_bl_scale_exponent_ladder` and
     //  tools/fuzz_ladder.py exercise: chains of hairpins that overflow the first exponent, results equal to the log-space path's.)
     int rc = RH_OK;
-    const bool per_pair = !c->is_helper && c->pair_helper && c->has_dx && c->np >= 4 && !c->mc.allow && !c->co.allow;
+    // (the helper recomputes whole pairs and copies their folds back into the pairs' own rows: an indexed batch, whose fold rows are
+    //  shared between pairs, runs the whole batch again instead)
+    const bool per_pair = !c->is_helper && c->pair_helper && c->has_dx && c->np >= 4 && !c->mc.allow && !c->co.allow && !c->indexed;
     const auto sort_unique = [](std::vector<int>& v) { std::sort(v.begin(), v.end()); v.erase(std::unique(v.begin(), v.end()), v.end()); };
     std::vector<int> flagged_seqs;   // by the deferred attempts so far
     for (size_t a = 0; a < order.size(); a++) {

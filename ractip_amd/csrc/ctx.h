@@ -114,7 +114,8 @@ struct McLinArgs {   // launch_mc_lin: one phase (0 inside, 1 outside) of the CO
 
 struct McVlinArgs {   // launch_mc_vlin: one phase of the Vienna-BL sweeps over the single-molecule batch or (co) the s1+s2 batch
     McBatch B;
-    McBatch from;              // seeded two-molecule sweeps: the single-molecule batch whose inside tables they copy
+    McBatch from;              // seeded two-molecule sweeps: the single-molecule batch whose inside tables they copy ...
+    const int* pair_seq;       // ... and the index of the upload (device, [2 np]): pair p copies from sequences pair_seq[2p], pair_seq[2p+1]
     SweepPlan plan;
     const VLinModel* d_vlin;   // the model at the scale exponent of this pass, device and host (select_vlin) ...
     const VLinModel* h_vlin;
@@ -260,6 +261,11 @@ struct Ctx {   // (the fields of rh_ctx, below)
 
     // current batch (host mirror)
     int np = 0, ns = 0;
+    // the index of the upload: pair p = sequences pair_seq[2p] (s1) and pair_seq[2p+1] (s2) of the fold batch.  rh_batch_upload
+    // stages the identity (2p, 2p+1); rh_batch_upload_indexed any pairs of the ns distinct sequences.  Read through seq_of().
+    std::vector<int> pair_seq;
+    std::vector<int> pair_seq_dev; // what d_pidx holds (a stream of uploads with one index, the identity of plain batches, copies it once)
+    bool indexed = false;          // the batch came from rh_batch_upload_indexed
     bool has_mc = false, has_dx = false, computed = false;
     std::vector<int> n;  // [ns]
     McBatch mc = {};
@@ -267,6 +273,9 @@ struct Ctx {   // (the fields of rh_ctx, below)
     // owned device buffers
     DevBuf d_seq;
     DevBuf d_n;
+    DevBuf d_pseq;    // pair-major image of the codes [2 np][lds] the duplex kernels read (pair_gather) ...
+    DevBuf d_pn;      // ... its lengths [2 np] ...
+    DevBuf d_pidx;    // ... and pair_seq on the device
     DevBuf d_mctab;
     DevBuf d_corowp;
     DevBuf d_rowp;    // look-ahead partial sums of the next inside diagonal
@@ -357,7 +366,15 @@ int fail(rh_ctx* c, int code, const char* fmt, ...);
 int ensure(rh_ctx* c, DevBuf& buf, size_t bytes, bool zero);
 // staging.hip
 int stage(rh_ctx* c, int ns, const char* const* seqs, const int* lens, bool with_mc, bool with_dx, const char* const* cons = nullptr,
-          const char* const* co_cons = nullptr);
+          const char* const* co_cons = nullptr, int npairs = 0, const int* first = nullptr, const int* second = nullptr);
+// sequence of the fold batch that is strand `side` (0: s1, 1: s2) of pair p: the one place that knows how pairs map to sequences
+inline int seq_of(const Ctx* c, int p, int side) { return c->pair_seq[2 * (size_t)p + side]; }
+// the pairs that use sequence k, appended to *pairs (a flagged sequence flags every pair that references it)
+inline void pairs_of_seq(const Ctx* c, int k, std::vector<int>* pairs)
+{
+    for (int p = 0; p < c->np; p++)
+        if (seq_of(c, p, 0) == k || seq_of(c, p, 1) == k) pairs->push_back(p);
+}
 // a kernel on one line with the name reported for it
 template <class K> struct Named { K kern; const char* name; };
 #define NAMED(...) {__VA_ARGS__, #__VA_ARGS__}

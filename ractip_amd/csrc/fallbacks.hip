@@ -21,7 +21,7 @@ namespace rh::host {
 // upload them to the d_sub* buffers, run, and copy the result rows back to the flagged slots.  What differs stays in each path:
 // which tables are cleared, whether the sub-batch has tables of its own, the stream, and what an error has to undo.
 struct SubBatch {
-    int nsub = 0;                  // problems: sequences (per = 1) or pairs (per = 2: sequences 2p, 2p+1 of the batch)
+    int nsub = 0;                  // problems: sequences (per = 1) or pairs (per = 2: both sequences of pair p, through seq_of)
     std::vector<uint8_t> codes;    // [per * nsub][lds]
     std::vector<int> lens;         // [per * nsub]
     int nmax[2] = {0, 0};          // longest sequence (pairs: longest first / second strand)
@@ -35,7 +35,7 @@ SubBatch gather(const rh_ctx* c, const std::vector<int>& F, int per, int lds)
     s.lens.resize((size_t)per * s.nsub);
     for (int k = 0; k < s.nsub; k++)
         for (int h = 0; h < per; h++) {
-            const size_t to = (size_t)per * k + h, from = (size_t)per * F[k] + h;
+            const size_t to = (size_t)per * k + h, from = per == 2 ? (size_t)seq_of(c, F[k], h) : (size_t)F[k];
             std::memcpy(s.codes.data() + to * lds, c->h_codes.data() + from * lds, lds);
             s.lens[to] = c->n[from];
             s.nmax[h] = std::max(s.nmax[h], s.lens[to]);
@@ -295,7 +295,8 @@ int retry_dx_lin_rungs(rh_ctx* c, std::vector<int>* rest)
 }
 
 // The flagged pairs P of a Vienna-BL batch, recomputed on the helper context and copied into this batch's result buffers (bp, up, hp and
-// the three log partition functions of each pair); the layouts differ only in their strides.
+// the three log partition functions of each pair); the layouts differ only in their strides.  Plain uploads only (compute()): every
+// pair owns its two fold rows there.
 int recompute_pairs_on_helper(rh_ctx* c, const std::vector<int>& P)
 {
     if (!c->helper) {
@@ -314,7 +315,7 @@ int recompute_pairs_on_helper(rh_ctx* c, const std::vector<int>& P)
     std::vector<int> lens(2 * (size_t)nsub);
     for (int k = 0; k < nsub; k++)
         for (int hh = 0; hh < 2; hh++) {
-            const int sq = 2 * P[k] + hh, n = c->n[sq];
+            const int sq = seq_of(c, P[k], hh), n = c->n[sq];
             std::string& t = text[2 * k + hh];
             t.resize(n);
             for (int i = 0; i < n; i++) t[i] = "NACGU"[c->h_codes[(size_t)sq * lds + 1 + i] <= 4 ? c->h_codes[(size_t)sq * lds + 1 + i] : 0];   // vienna_code^-1
@@ -329,14 +330,14 @@ int recompute_pairs_on_helper(rh_ctx* c, const std::vector<int>& P)
     const size_t up_c = (size_t)c->mc.ld * c->max_w, up_h = (size_t)h->mc.ld * h->max_w;
     for (int k = 0; k < nsub; k++) {
         for (int hh = 0; hh < 2; hh++) {
-            const int sq = 2 * P[k] + hh, sh = 2 * k + hh, n = c->n[sq];
+            const int sq = seq_of(c, P[k], hh), sh = 2 * k + hh, n = c->n[sq];
             HIP_TRY(c, hipMemcpyAsync(c->d_bp.as<double>() + (size_t)sq * c->mc.tri_stride, h->d_bp.as<const double>() + (size_t)sh * h->mc.tri_stride,
                                       sizeof(double) * tri_size(n), hipMemcpyDeviceToDevice, c->s_mc));
             HIP_TRY(c, hipMemcpyAsync(c->d_up.as<double>() + (size_t)sq * up_c, h->d_up.as<const double>() + (size_t)sh * up_h, sizeof(double) * (size_t)n * c->max_w,
                                       hipMemcpyDeviceToDevice, c->s_mc));
             HIP_TRY(c, hipMemcpyAsync(c->d_mclogz.as<double>() + sq, h->d_mclogz.as<const double>() + sh, sizeof(double), hipMemcpyDeviceToDevice, c->s_mc));
         }
-        const int n1 = c->n[2 * P[k]], n2 = c->n[2 * P[k] + 1];
+        const int n1 = c->n[seq_of(c, P[k], 0)], n2 = c->n[seq_of(c, P[k], 1)];
         HIP_TRY(c, hipMemcpy2DAsync(c->d_hp.as<double>() + (size_t)P[k] * c->dx.tab_stride, sizeof(double) * c->dx.ldd,
                                     h->d_hp.as<const double>() + (size_t)k * h->dx.tab_stride, sizeof(double) * h->dx.ldd,
                                     sizeof(double) * (n2 + 1), (size_t)n1 + 1, hipMemcpyDeviceToDevice, c->s_mc));
@@ -349,8 +350,9 @@ int recompute_pairs_on_helper(rh_ctx* c, const std::vector<int>& P)
     c->rescaled_mc.clear(); c->fallback_mc.clear(); c->fallback_dx.clear();
     const bool h_log = h->last_went_log || h->last_path == 2 || (h->last_path == 3 && h->rescaled_mc.empty() && !h->fallback_mc.empty());
     for (int k = 0; k < nsub; k++) {
-        if (h_log) { c->fallback_mc.push_back(2 * P[k]); c->fallback_mc.push_back(2 * P[k] + 1); c->fallback_dx.push_back(P[k]); }
-        else { c->rescaled_mc.push_back(2 * P[k]); c->rescaled_mc.push_back(2 * P[k] + 1); }
+        const int sq1 = seq_of(c, P[k], 0), sq2 = seq_of(c, P[k], 1);
+        if (h_log) { c->fallback_mc.push_back(sq1); c->fallback_mc.push_back(sq2); c->fallback_dx.push_back(P[k]); }
+        else { c->rescaled_mc.push_back(sq1); c->rescaled_mc.push_back(sq2); }
     }
     c->tables_dirty = true;
     return RH_OK;

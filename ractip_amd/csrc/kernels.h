@@ -72,7 +72,6 @@ __global__ void mcv_acc_gaps(McBatch B, const ViennaDx* __restrict__ V, double* 
 __global__ void mcv_acc_final(McBatch B, const ViennaDx* __restrict__ V, const double* __restrict__ gaps, int max_w);
 __global__ void mcv_finish(McBatch B, double* __restrict__ logz);
 __global__ void vlin_init(McBatch B, int* __restrict__ bad);
-__global__ void vlin_co_seed(McBatch B, McBatch S);
 template <int W, int BS, bool CUT, int MODE> __global__ void vlin_inside_diag(McBatch B, const VLinModel* __restrict__ L, int d, double hp_d, int pin);
 template <int W, int BS, bool CUT, int MODE> __global__ void vlin_outside_diag(McBatch B, const VLinModel* __restrict__ L, int d, int pin, int* __restrict__ bad);
 __global__ void vlin_finish(McBatch B, const VLinModel* __restrict__ L, double* __restrict__ logz, int* __restrict__ bad);
@@ -82,17 +81,32 @@ __global__ void mcv_extract_hp(McBatch B, double* __restrict__ hp, size_t hp_str
 constexpr int kAllowRows = 64, kAllowThreads = 256;
 __global__ void allow_mask_build(uint8_t* __restrict__ allow, const int* __restrict__ n_of, const uint8_t* __restrict__ g_ch,
                                  const int* __restrict__ g_P, const int* __restrict__ g_enc, int ld, int lds, int in_lds);
+// pair_index.hip: the pair-major image of an upload, built from the distinct sequences and the index (pair p = sequences
+// idx[2p], idx[2p+1]); grid (np, 2), kPairGatherThreads threads
+struct PairImage {
+    const uint8_t* seq;   // [ns][lds] codes of the distinct sequences (both sentinels included)
+    const int* n;         // [ns]
+    const int* idx;       // [2 np]
+    uint8_t* pseq;        // [2 np][lds]: row 2p + side = the codes of idx[2p + side]
+    int* pn;              // [2 np]
+    uint8_t* coseq;       // two-molecule ensemble (or nullptr): [np][co_lds], s1 at 1..n1, s2 at n1+1..n1+n2, code 0 elsewhere
+    int* con;             // [2][np]: joint lengths, cuts
+    int np, lds, co_lds;
+};
+constexpr int kPairGatherThreads = 256;
+__global__ void pair_gather(PairImage G);
+__global__ void vlin_co_seed(McBatch B, McBatch S, const int* __restrict__ idx);
 }  // namespace rh
 
 // defined by the host units (global namespace)
-__global__ void collect_logz(const double* __restrict__ mc_logz, rh::DxBatch D, double* __restrict__ out);                 // rh_api.hip
+__global__ void collect_logz(const double* __restrict__ mc_logz, const int* __restrict__ idx, rh::DxBatch D, double* __restrict__ out);              // rh_api.hip
 __global__ void log_finish(rh::McBatch B, double* __restrict__ logz);                                                       // launch_contrafold.hip
 // candidates.hip
 __global__ void cand_count(const double* __restrict__ base, int kind, int n, int n2, int ld, float th, int nrows, int* __restrict__ counts);
 __global__ void cand_write(const double* __restrict__ base, int kind, int n, int n2, int ld, float th, int nrows, const int* __restrict__ counts,
                            const int* __restrict__ offsets, rh_cand* __restrict__ out, int cap);
 __global__ void cand_count_all(const double* __restrict__ bp, const double* __restrict__ hp, const double* __restrict__ up, const int* __restrict__ nn,
-                               size_t tri_stride, size_t hp_stride, int up_ld, int hp_ld, int which, int rmax, float th, int* __restrict__ counts);
+                               const int* __restrict__ idx, int per, size_t tri_stride, size_t hp_stride, int up_ld, int hp_ld, int which, int rmax, float th, int* __restrict__ counts);
 __global__ void cand_write_all(const double* __restrict__ bp, const double* __restrict__ hp, const double* __restrict__ up, const int* __restrict__ nn,
-                               size_t tri_stride, size_t hp_stride, int up_ld, int hp_ld, int which, int rmax, float th, const int* __restrict__ counts,
+                               const int* __restrict__ idx, int per, size_t tri_stride, size_t hp_stride, int up_ld, int hp_ld, int which, int rmax, float th, const int* __restrict__ counts,
                                const int* __restrict__ offsets, rh_cand* __restrict__ out, int cap);

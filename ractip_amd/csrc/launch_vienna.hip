@@ -102,7 +102,7 @@ static void vlin_inside(const SweepPass& S, const McVlinArgs& A)
     const VlinKernels& K = vlin_kernels(S.P.BS, A.co);
     const bool ahead = S.P.org == SweepPlan::kLookahead;
     hipLaunchKernelGGL(vlin_init, dim3((B.ns + 63) / 64), dim3(64), 0, S.st, B, A.bad);
-    if (A.co && B.seeded) hipLaunchKernelGGL(vlin_co_seed, dim3(A.from.nmax, B.ns), dim3(256), 0, S.st, B, A.from);
+    if (A.co && B.seeded) hipLaunchKernelGGL(vlin_co_seed, dim3(A.from.nmax, B.ns), dim3(256), 0, S.st, B, A.from, A.pair_seq);
     for (int d = 0; d <= B.nmax - 1; d++) {
         const int mode = !ahead ? 0 : (d & 1) ? 2 : 1;
         const int cells = (std::max(B.nmax - 1 - d, 0) + 63) / 64;

@@ -22,13 +22,13 @@
 using namespace rh;
 using namespace rh::host;
 
-// out[3p..3p+2] = F5i[n] of sequences 2p, 2p+1 and the duplex logZ of pair p
-__global__ void collect_logz(const double* __restrict__ mc_logz, DxBatch D, double* __restrict__ out)
+// out[3p..3p+2] = F5i[n] of pair p's sequences idx[2p], idx[2p+1] and the duplex logZ of pair p
+__global__ void collect_logz(const double* __restrict__ mc_logz, const int* __restrict__ idx, DxBatch D, double* __restrict__ out)
 {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= D.np) return;
-    out[3 * p + 0] = mc_logz[2 * p];
-    out[3 * p + 1] = mc_logz[2 * p + 1];
+    out[3 * p + 0] = mc_logz[idx[2 * p]];
+    out[3 * p + 1] = mc_logz[idx[2 * p + 1]];
     out[3 * p + 2] = D.logz[p];
 }
 
@@ -99,7 +99,7 @@ int fetch_logz(rh_ctx* c, int sq, double* out)
 }
 int fetch_hp(rh_ctx* c, int p, double* out, double* logz)
 {
-    const int n1 = c->n[2 * p], n2 = c->n[2 * p + 1];
+    const int n1 = c->n[seq_of(c, p, 0)], n2 = c->n[seq_of(c, p, 1)];
     if (out)
         HIP_TRY(c, hipMemcpy2D(out, sizeof(double) * (n2 + 1), c->d_hp.as<const double>() + (size_t)p * c->dx.tab_stride,
                                sizeof(double) * c->dx.ldd, sizeof(double) * (n2 + 1), n1 + 1, hipMemcpyDeviceToHost));
@@ -363,6 +363,26 @@ int rh_batch_upload_constrained(rh_ctx* c, int npairs, const char* const* s1, co
     return stage(c, 2 * npairs, seqs.data(), lens.data(), true, true, any ? cons.data() : nullptr, any_co ? co_cons : nullptr);
 }
 
+int rh_batch_upload_indexed(rh_ctx* c, int nseq, const char* const* seqs, const int* lens, int npairs, const int* first, const int* second)
+{
+    if (!c) return RH_ERR_ARG;
+    if (nseq < 1 || npairs < 1 || !seqs || !lens || !first || !second) return fail(c, RH_ERR_ARG, "bad indexed batch");
+    return stage(c, nseq, seqs, lens, true, true, nullptr, nullptr, npairs, first, second);   // (checks every index before it changes the context)
+}
+
+int rh_batch_index(rh_ctx* c, int* nseq, int* npairs, int* first, int* second)
+{
+    if (!c) return RH_ERR_ARG;
+    if (c->ns == 0 || !c->has_mc || !c->has_dx) return fail(c, RH_ERR_ARG, "no pair batch");
+    if (nseq) *nseq = c->ns;
+    if (npairs) *npairs = c->np;
+    for (int p = 0; p < c->np; p++) {
+        if (first) first[p] = seq_of(c, p, 0);
+        if (second) second[p] = seq_of(c, p, 1);
+    }
+    return RH_OK;
+}
+
 int rh_debug_batch_allow_mask(rh_ctx* c, int which, int k, unsigned char* out, int* ld)
 {
     if (!c) return RH_ERR_ARG;
@@ -391,14 +411,15 @@ int rh_batch_results(rh_ctx* c, int p, double* bp1, double* bp2, double* up1, do
     if (!c->computed || !c->has_mc || !c->has_dx) return fail(c, RH_ERR_ARG, "no computed pair batch");
     if (p < 0 || p >= c->np) return fail(c, RH_ERR_ARG, "pair %d out of range", p);
     int rc;
-    if (bp1 && (rc = fetch_bp(c, 2 * p, bp1))) return rc;
-    if (bp2 && (rc = fetch_bp(c, 2 * p + 1, bp2))) return rc;
-    if (up1 && (rc = fetch_up(c, 2 * p, up1))) return rc;
-    if (up2 && (rc = fetch_up(c, 2 * p + 1, up2))) return rc;
+    const int sq1 = seq_of(c, p, 0), sq2 = seq_of(c, p, 1);
+    if (bp1 && (rc = fetch_bp(c, sq1, bp1))) return rc;
+    if (bp2 && (rc = fetch_bp(c, sq2, bp2))) return rc;
+    if (up1 && (rc = fetch_up(c, sq1, up1))) return rc;
+    if (up2 && (rc = fetch_up(c, sq2, up2))) return rc;
     if ((hp || logZ3) && (rc = fetch_hp(c, p, hp, logZ3 ? logZ3 + 2 : nullptr))) return rc;
     if (logZ3) {
-        if ((rc = fetch_logz(c, 2 * p, logZ3))) return rc;
-        if ((rc = fetch_logz(c, 2 * p + 1, logZ3 + 1))) return rc;
+        if ((rc = fetch_logz(c, sq1, logZ3))) return rc;
+        if ((rc = fetch_logz(c, sq2, logZ3 + 1))) return rc;
     }
     return RH_OK;
 }
@@ -409,7 +430,7 @@ int rh_batch_logz(rh_ctx* c, double* out)
     if (!c->computed || !c->has_mc || !c->has_dx || !out) return fail(c, RH_ERR_ARG, "no computed pair batch");
     int rc;
     if ((rc = ensure(c, c->d_scal, sizeof(double) * 3 * c->np, false))) return rc;
-    hipLaunchKernelGGL(collect_logz, dim3((c->np + 63) / 64), dim3(64), 0, c->s_mc, c->d_mclogz.as<const double>(), c->dx, c->d_scal.as<double>());
+    hipLaunchKernelGGL(collect_logz, dim3((c->np + 63) / 64), dim3(64), 0, c->s_mc, c->d_mclogz.as<const double>(), c->d_pidx.as<const int>(), c->dx, c->d_scal.as<double>());
     HIP_TRY(c, hipMemcpyAsync(out, c->d_scal.p, sizeof(double) * 3 * c->np, hipMemcpyDeviceToHost, c->s_mc));
     HIP_TRY(c, hipStreamSynchronize(c->s_mc));
     return RH_OK;

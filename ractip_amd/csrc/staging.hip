@@ -55,10 +55,12 @@ static int build_allow_masks(rh_ctx* c, const ConsPass& H, int count, int ld, in
     return RH_OK;
 }
 
-// Stage `ns` sequences; pairs are (2p, 2p+1) when with_dx.  Allocates what is needed.  cons: per-sequence structure constraints of
+// Stage `ns` sequences; with_dx: pair p is (first[p], second[p]) of them, npairs pairs -- or, first == nullptr, the ns / 2 pairs
+// (2p, 2p+1).  Allocates what is needed.  cons: per-sequence structure constraints of
 // the single-molecule folds, co_cons: per-pair constraints over s1+s2 of the two-molecule ensemble (Vienna-BL; either, or any entry,
 // may be nullptr).  Every constraint is checked before the context changes: a rejected upload leaves the previous batch in place.
-int stage(rh_ctx* c, int ns, const char* const* seqs, const int* lens, bool with_mc, bool with_dx, const char* const* cons, const char* const* co_cons)
+int stage(rh_ctx* c, int ns, const char* const* seqs, const int* lens, bool with_mc, bool with_dx, const char* const* cons, const char* const* co_cons,
+          int npairs, const int* first, const int* second)
 {
     HIP_TRY(c, hipSetDevice(c->device));
     if (ns <= 0) return fail(c, RH_ERR_ARG, "empty batch");
@@ -67,26 +69,40 @@ int stage(rh_ctx* c, int ns, const char* const* seqs, const int* lens, bool with
         if (lens[k] < 1) return fail(c, RH_ERR_ARG, "sequence %d has length %d (must be >= 1)", k, lens[k]);
         if (!seqs[k]) return fail(c, RH_ERR_ARG, "sequence %d is NULL", k);
         nmax = std::max(nmax, lens[k]);
-        if (with_dx) { if (k & 1) n2max = std::max(n2max, lens[k]); else n1max = std::max(n1max, lens[k]); }
     }
-    if (with_dx && (ns & 1)) return fail(c, RH_ERR_ARG, "duplex batch needs an even number of sequences");
+    const bool indexed = with_dx && first && second;
+    if (with_dx && !indexed && (ns & 1)) return fail(c, RH_ERR_ARG, "duplex batch needs an even number of sequences");
+    if (!indexed) npairs = with_dx ? ns / 2 : 0;
+    if (indexed && npairs < 1) return fail(c, RH_ERR_ARG, "indexed batch of %d pairs (must be >= 1)", npairs);
+    std::vector<int> pair_seq(2 * (size_t)npairs);
+    int cut_min = 0, cut_max = 0;
+    for (int p = 0; p < npairs; p++) {   // lengths over the pairs, through the index
+        const int a = indexed ? first[p] : 2 * p, b = indexed ? second[p] : 2 * p + 1;
+        if (a < 0 || a >= ns || b < 0 || b >= ns) return fail(c, RH_ERR_ARG, "pair %d = (%d, %d): index outside [0, %d)", p, a, b, ns);
+        pair_seq[2 * (size_t)p] = a; pair_seq[2 * (size_t)p + 1] = b;
+        n1max = std::max(n1max, lens[a]); n2max = std::max(n2max, lens[b]);
+        cut_min = p == 0 ? lens[a] : std::min(cut_min, lens[a]);
+        cut_max = p == 0 ? lens[a] : std::max(cut_max, lens[a]);
+    }
     const int lds = (nmax + 3 + 15) & ~15;  // codes 0..n+2 readable
     const int co_lds = (n1max + n2max + 3 + 15) & ~15;
     const bool vienna = c->model == RH_MODEL_VIENNA_BL;
-    if (!with_mc) cons = nullptr;
+    if (!with_mc || indexed) cons = nullptr;
+    if (indexed) co_cons = nullptr;
     if (!with_dx || !vienna) co_cons = nullptr;
-    ConsPass H(cons ? ns : 0, lds), CH(co_cons ? ns / 2 : 0, co_lds);
+    ConsPass H(cons ? ns : 0, lds), CH(co_cons ? npairs : 0, co_lds);
     std::string why;
     for (int k = 0; cons && k < ns; k++)
         if (!constraint_prepass(seqs[k], lens[k], cons[k], &H.ch[(size_t)k * lds], &H.P[(size_t)k * lds], &H.enc[(size_t)k * lds], &why))
             return fail(c, RH_ERR_ARG, "sequence %d: %s", k, why.c_str());
-    for (int p = 0; co_cons && p < ns / 2; p++) {   // over the concatenation s1+s2 (one string of n1+n2 characters per pair)
+    for (int p = 0; co_cons && p < npairs; p++) {   // over the concatenation s1+s2 (one string of n1+n2 characters per pair)
         const std::string joint = std::string(seqs[2 * p], lens[2 * p]) + std::string(seqs[2 * p + 1], lens[2 * p + 1]);
         if (!constraint_prepass(joint.c_str(), (int)joint.size(), co_cons[p], &CH.ch[(size_t)p * co_lds], &CH.P[(size_t)p * co_lds],
                                 &CH.enc[(size_t)p * co_lds], &why))
             return fail(c, RH_ERR_ARG, "pair %d: %s", p, why.c_str());
     }
-    c->ns = ns; c->np = with_dx ? ns / 2 : 0;
+    c->ns = ns; c->np = npairs;
+    c->pair_seq.swap(pair_seq); c->indexed = indexed;
     c->has_mc = with_mc; c->has_dx = with_dx; c->computed = false;
     c->n.assign(lens, lens + ns);
 
@@ -99,6 +115,12 @@ int stage(rh_ctx* c, int ns, const char* const* seqs, const int* lens, bool with
     c->h_codes = codes;
     HIP_TRY(c, hipMemcpyAsync(c->d_seq.p, codes.data(), codes.size(), hipMemcpyHostToDevice, c->s_mc));
     HIP_TRY(c, hipMemcpyAsync(c->d_n.p, lens, sizeof(int) * ns, hipMemcpyHostToDevice, c->s_mc));
+    if (with_dx && c->pair_seq_dev != c->pair_seq) {
+        c->pair_seq_dev.clear();
+        if ((rc = ensure(c, c->d_pidx, sizeof(int) * 2 * npairs, false))) return rc;
+        HIP_TRY(c, hipMemcpyAsync(c->d_pidx.p, c->pair_seq.data(), sizeof(int) * 2 * npairs, hipMemcpyHostToDevice, c->s_mc));
+        c->pair_seq_dev = c->pair_seq;
+    }
     c->small_list.clear();
     c->nmax_sweep = nmax;
     c->n_short = 0; c->nmax_short = 0;
@@ -184,7 +206,7 @@ int stage(rh_ctx* c, int ns, const char* const* seqs, const int* lens, bool with
     if (with_dx) {
         DxBatch& D = c->dx;
         c->co.allow = nullptr;   // (under RH_HYBRID_DUPLEX nothing below rebuilds c->co: a joint mask of an earlier batch must not be seen)
-        D.np = ns / 2; D.n1max = n1max; D.n2max = n2max; D.lds = lds;
+        D.np = npairs; D.n1max = n1max; D.n2max = n2max; D.lds = lds;
         D.ldd = (n2max + 2 + 1) & ~1;
         D.tab_stride = (size_t)(n1max + 2) * D.ldd;
         D.pair_stride = D.tab_stride * std::max((int)D_COUNT, (int)V_COUNT);   // 4 tables (CONTRAfold model) or 6 (Vienna model: IN/OUT + two decorated copies each)
@@ -216,17 +238,20 @@ int stage(rh_ctx* c, int ns, const char* const* seqs, const int* lens, bool with
         if ((rc = ensure(c, c->d_logz, sizeof(double) * D.np, false))) return rc;
         const size_t hp_bytes = sizeof(double) * D.tab_stride * D.np;
         if ((rc = ensure(c, c->d_hp, hp_bytes, false))) return rc;
-        D.seq = c->d_seq.as<const uint8_t>(); D.n = c->d_n.as<const int>();
+        // the pair-major image the duplex kernels read, and (below) the joint image of the two-molecule ensemble: built on the device
+        // from the distinct sequences, which are on it once (the copies on s_mc above are complete)
+        PairImage G{};
+        bool gathered = false;
+        if ((rc = ensure(c, c->d_pseq, 2 * (size_t)npairs * lds, false))) return rc;
+        if ((rc = ensure(c, c->d_pn, sizeof(int) * 2 * npairs, false))) return rc;
+        G.seq = c->d_seq.as<const uint8_t>(); G.n = c->d_n.as<const int>(); G.idx = c->d_pidx.as<const int>();
+        G.pseq = c->d_pseq.as<uint8_t>(); G.pn = c->d_pn.as<int>(); G.np = npairs; G.lds = lds;
+        D.seq = c->d_pseq.as<const uint8_t>(); D.n = c->d_pn.as<const int>();
         D.tab = c->d_dxtab.as<double>(); D.hp = c->d_hp.as<double>(); D.logz = c->d_logz.as<double>();
-        // row 0, column 0 and what lies beyond L1 / L2 stay zero.  CONTRAfold model: every path stores all of 1..L1 x 1..L2 (see
-        // dx_hp_clear_rest), so only the rest is zeroed.  Vienna-BL keeps the whole clear: its hp also comes from the two-molecule
-        // ensemble (cofold) and from the helper context, which copy or store parts of the matrix only.
-        if (vienna) HIP_TRY(c, hipMemsetAsync(c->d_hp.p, 0, hp_bytes, c->s_dx));
-        else hipLaunchKernelGGL(dx_hp_clear_rest, dim3(16, D.np), dim3(256), 0, c->s_dx, D);
         if (vienna && c->hybrid == RH_HYBRID_COFOLD) {
             // concatenated sequences s1+s2, cut after s1
             McBatch& C = c->co;
-            const int np = ns / 2, cmax = n1max + n2max;
+            const int np = npairs, cmax = n1max + n2max;
             C = McBatch{};
             C.ns = np; C.nmax = cmax;
             C.lds = (cmax + 3 + 15) & ~15;
@@ -234,18 +259,10 @@ int stage(rh_ctx* c, int ns, const char* const* seqs, const int* lens, bool with
             C.tab_stride = (size_t)C.ld * C.ld;
             C.seq_stride = C.tab_stride * (int)VM_COUNT;
             C.tri_stride = (tri_size(cmax) + 1) & ~(size_t)1;
-            std::vector<uint8_t> cc((size_t)np * C.lds, 0);
-            std::vector<int> nn(2 * (size_t)np);
-            for (int p = 0; p < np; p++) {
-                const int a = lens[2 * p], b = lens[2 * p + 1];
-                for (int i = 0; i < a; i++) cc[(size_t)p * C.lds + 1 + i] = vienna_code(seqs[2 * p][i]);
-                for (int i = 0; i < b; i++) cc[(size_t)p * C.lds + 1 + a + i] = vienna_code(seqs[2 * p + 1][i]);
-                nn[p] = a + b; nn[np + p] = a;
-                c->co_cut_min = p == 0 ? a : std::min(c->co_cut_min, a);
-                c->co_cut_max = p == 0 ? a : std::max(c->co_cut_max, a);
-            }
-            if ((rc = ensure(c, c->d_coseq, cc.size(), false))) return rc;
-            if ((rc = ensure(c, c->d_con, sizeof(int) * nn.size(), false))) return rc;
+            c->co_cut_min = cut_min; c->co_cut_max = cut_max;
+            if ((rc = ensure(c, c->d_coseq, (size_t)np * C.lds, false))) return rc;
+            if ((rc = ensure(c, c->d_con, sizeof(int) * 2 * np, false))) return rc;
+            G.coseq = c->d_coseq.as<uint8_t>(); G.con = c->d_con.as<int>(); G.co_lds = C.lds;   // concatenated codes, lengths and cuts: pair_gather
             if ((rc = ensure(c, c->d_cotab, sizeof(double) * C.seq_stride * np, false))) return rc;
             C.nb = (cmax - 1) / 16 + 1;
             C.pk_stride = (size_t)C.nb * (C.nb + 1) / 2 * 256;
@@ -262,9 +279,6 @@ int stage(rh_ctx* c, int ns, const char* const* seqs, const int* lens, bool with
                 for (int d = 0; d < C.ld; d++)
                     c->h_hplen[d] = (d <= 30 ? H.E_hairpin[d] : std::exp(H.hairpin30 - H.lxc * std::log(d / 30.0))) * std::exp(-H.s * d);
             }
-            HIP_TRY(c, hipMemcpyAsync(c->d_coseq.p, cc.data(), cc.size(), hipMemcpyHostToDevice, c->s_dx));
-            HIP_TRY(c, hipMemcpyAsync(c->d_con.p, nn.data(), sizeof(int) * nn.size(), hipMemcpyHostToDevice, c->s_dx));
-            HIP_TRY(c, hipStreamSynchronize(c->s_dx));
             C.seq = c->d_coseq.as<const uint8_t>(); C.n = c->d_con.as<const int>(); C.cut = c->d_con.as<const int>() + np;
             C.tab = c->d_cotab.as<double>();
             double* f = c->d_cof5.as<double>();
@@ -272,10 +286,21 @@ int stage(rh_ctx* c, int ns, const char* const* seqs, const int* lens, bool with
             C.f5i = f; C.f5o = f + fs; C.xp = f + 2 * fs; C.xs = f + 3 * fs; C.xpo = f + 4 * fs; C.xso = f + 5 * fs;
             C.bp = c->d_cobp.as<double>(); C.up = nullptr;
             if (co_cons) {
+                hipLaunchKernelGGL(pair_gather, dim3(npairs, 2), dim3(kPairGatherThreads), 0, c->s_dx, G);   // (the mask kernel on s_mc reads the joint lengths)
+                HIP_TRY(c, hipStreamSynchronize(c->s_dx));
+                gathered = true;
                 if ((rc = build_allow_masks(c, CH, np, C.ld, co_lds, C.n, c->d_coallow))) return rc;
                 C.allow = c->d_coallow.as<const uint8_t>();
             }
         }
+        if (!gathered) hipLaunchKernelGGL(pair_gather, dim3(npairs, 2), dim3(kPairGatherThreads), 0, c->s_dx, G);
+        HIP_TRY(c, hipGetLastError());
+        // row 0, column 0 and what lies beyond L1 / L2 stay zero.  CONTRAfold model: every path stores all of 1..L1 x 1..L2 (see
+        // dx_hp_clear_rest), so only the rest is zeroed -- behind pair_gather, which writes the pair-major lengths that kernel reads.
+        // Vienna-BL keeps the whole clear: its hp also comes from the two-molecule ensemble (cofold) and from the helper context, which
+        // copy or store parts of the matrix only.
+        if (vienna) HIP_TRY(c, hipMemsetAsync(c->d_hp.p, 0, hp_bytes, c->s_dx));
+        else hipLaunchKernelGGL(dx_hp_clear_rest, dim3(16, D.np), dim3(256), 0, c->s_dx, D);
         X.seq = D.seq; X.n = D.n; X.tab = D.tab; X.hp = D.hp; X.hp_stride = D.tab_stride;
     }
     return RH_OK;

@@ -3,6 +3,8 @@
 // hand to the ILP, one value per line, for tests/test_gpu_host_adapter.py.
 //   prob_cli constraint STR L | joint STR1 N1 STR2 N2      (the structure-line translations; no GPU needed)
 //   prob_cli solve_default_c MAX_W S1 STR1 S2 STR2 [...] | solve_default_duplex_c ...   (use_constraint_: structure lines per pair)
+//   prob_cli solve_indexed S1 S2 [...] | solve_default_indexed MAX_W S1 S2 [...] | solve_default_duplex_indexed ...   (the same pairs through
+//     the indexed members: identical strings once, pairs by index; prints what solve / solve_default[_duplex] print)
 //   [RACTIP_DEVICES=0,1,..] prob_cli contrafold SEQ | rnafold SEQ MAX_W | contraduplex S1 S2 TH | rnaduplex S1 S2 | cofold S1 S2 | pfduplex S1 S2 | solve S1 S2 [S1 S2 ...]
 #include <cstdio>
 #include <cstdlib>
@@ -19,6 +21,17 @@ void free_pf_duplex();
 }
 
 using namespace ractip_amd;
+
+// identical strings once, in the order of their first appearance; pair p = (seqs[index[p].first], seqs[index[p].second])
+static void index_pairs(const std::vector<std::pair<std::string, std::string>>& pairs, std::vector<std::string>* seqs, std::vector<std::pair<int, int>>* index)
+{
+    const auto slot = [&](const std::string& s) {
+        for (size_t k = 0; k < seqs->size(); k++) if ((*seqs)[k] == s) return (int)k;
+        seqs->push_back(s);
+        return (int)seqs->size() - 1;
+    };
+    for (const auto& pr : pairs) { const int a = slot(pr.first); index->emplace_back(a, slot(pr.second)); }
+}
 
 static void dump_bp(const VF& bp, const VI& off, const VVF& up)
 {
@@ -102,15 +115,20 @@ int main(int argc, char** argv)
             dump_hp(hp);
         } else if (mode == "rnaduplex") {
             VVF hp; en.rnaduplex(argv[2], argv[3], hp); dump_hp(hp);
-        } else if (mode == "solve_default" || mode == "solve_default_duplex" || mode == "solve_default_c" || mode == "solve_default_duplex_c") {
+        } else if (mode == "solve_default" || mode == "solve_default_duplex" || mode == "solve_default_c" || mode == "solve_default_duplex_c" ||
+                   mode == "solve_default_indexed" || mode == "solve_default_duplex_indexed") {
             // solve_default[_duplex] MAX_W S1 S2 [S1 S2 ...]; solve_default[_duplex]_c MAX_W S1 STR1 S2 STR2 [...]
             const unsigned mw = (unsigned)std::atoi(argv[2]);
-            const bool cons = mode.back() == 'c', duplex = mode.find("duplex") != std::string::npos;
+            const bool cons = mode.back() == 'c', duplex = mode.find("duplex") != std::string::npos, indexed = mode.back() == 'd';
+            std::vector<std::string> seqs;
+            std::vector<std::pair<int, int>> index;
             std::vector<std::pair<std::string, std::string>> pairs, structures;
             if (cons) for (int k = 3; k + 3 < argc; k += 4) { pairs.emplace_back(argv[k], argv[k + 2]); structures.emplace_back(argv[k + 1], argv[k + 3]); }
             else for (int k = 3; k + 1 < argc; k += 2) pairs.emplace_back(argv[k], argv[k + 1]);
-            for (const PairProbabilities& r : cons ? en.solve_probabilities_default(pairs, structures, mw, duplex)
-                                                   : en.solve_probabilities_default(pairs, mw, duplex)) {
+            if (indexed) index_pairs(pairs, &seqs, &index);
+            for (const PairProbabilities& r : indexed ? en.solve_probabilities_default_indexed(seqs, index, mw, duplex)
+                                              : cons  ? en.solve_probabilities_default(pairs, structures, mw, duplex)
+                                                      : en.solve_probabilities_default(pairs, mw, duplex)) {
                 std::printf("pair %.17g %.17g %.17g\n", r.logZ1, r.logZ2, r.logZd);
                 std::printf("bp %zu\n", r.bp1.size());
                 for (float v : r.bp1) std::printf("%.9g\n", v);
@@ -118,10 +136,13 @@ int main(int argc, char** argv)
                 for (const VF& row : r.up2) for (float v : row) std::printf("%.9g\n", v);
                 dump_hp(r.hp);
             }
-        } else if (mode == "solve") {
+        } else if (mode == "solve" || mode == "solve_indexed") {
             std::vector<std::pair<std::string, std::string>> pairs;
+            std::vector<std::string> seqs;
+            std::vector<std::pair<int, int>> index;
             for (int k = 2; k + 1 < argc; k += 2) pairs.emplace_back(argv[k], argv[k + 1]);
-            for (const PairProbabilities& r : en.solve_probabilities(pairs)) {
+            if (mode == "solve_indexed") index_pairs(pairs, &seqs, &index);
+            for (const PairProbabilities& r : mode == "solve_indexed" ? en.solve_probabilities_indexed(seqs, index) : en.solve_probabilities(pairs)) {
                 std::printf("pair %.17g %.17g %.17g\n", r.logZ1, r.logZ2, r.logZd);
                 dump_bp(r.bp1, r.offset1, r.up1);
                 dump_bp(r.bp2, r.offset2, r.up2);

@@ -273,6 +273,77 @@ std::vector<PairProbabilities> ProbabilityEngine::solve_probabilities_default(
     return out;
 }
 
+std::vector<PairProbabilities> ProbabilityEngine::solve_probabilities_indexed(const std::vector<std::string>& seqs,
+                                                                              const std::vector<std::pair<int, int>>& index_pairs) const
+{
+    return batch_indexed(ctx_, seqs, index_pairs, 1, false);
+}
+
+std::vector<PairProbabilities> ProbabilityEngine::solve_probabilities_default_indexed(const std::vector<std::string>& seqs,
+                                                                                      const std::vector<std::pair<int, int>>& index_pairs,
+                                                                                      uint max_w, bool duplex) const
+{
+    vienna();
+    for (rh_ctx* v : vctxs_)
+        if (rh_set_max_w(v, (int)std::max(1u, max_w)) != RH_OK || rh_set_hybrid(v, duplex ? RH_HYBRID_DUPLEX : RH_HYBRID_COFOLD) != RH_OK)
+            throw std::logic_error(std::string("ractip_amd::solve_probabilities_default_indexed: ") + rh_last_error(v));
+    std::vector<PairProbabilities> out;
+    std::string error;
+    try { out = batch_indexed(vctx_, seqs, index_pairs, std::max(1u, max_w), !duplex); } catch (const std::logic_error& e) { error = e.what(); }
+    for (rh_ctx* v : vctxs_) rh_set_hybrid(v, RH_HYBRID_DUPLEX);
+    if (!error.empty()) throw std::logic_error(error);
+    return out;
+}
+
+// The indexed counterpart of batch(): the same contiguous blocks of the pairs, one per listed device; each shard uploads only the
+// sequences its block references, re-indexed in the order of their first appearance in the block
+std::vector<PairProbabilities> ProbabilityEngine::batch_indexed(rh_ctx* ctx, const std::vector<std::string>& seqs,
+                                                                const std::vector<std::pair<int, int>>& index_pairs, uint max_w,
+                                                                bool threshold_hp) const
+{
+    const int np = (int)index_pairs.size(), ns = (int)seqs.size();
+    for (const std::pair<int, int>& ip : index_pairs)
+        if (ip.first < 0 || ip.first >= ns || ip.second < 0 || ip.second >= ns)
+            throw std::logic_error("ractip_amd::solve_probabilities_indexed: index outside the sequences");
+    if (np == 0) return {};
+    const std::vector<rh_ctx*>& all = (ctx == ctx_) ? ctxs_ : vctxs_;
+    const int parts = std::min<int>((int)all.size(), np);
+    const auto one = [&](rh_ctx* c, int lo, int hi) {
+        std::vector<int> slot(ns, -1), first(hi - lo), second(hi - lo), lens, na(hi - lo), nb(hi - lo);
+        std::vector<const char*> ptr;
+        const auto use = [&](int k) {
+            if (slot[k] < 0) { slot[k] = (int)ptr.size(); ptr.push_back(seqs[k].c_str()); lens.push_back((int)seqs[k].size()); }
+            return slot[k];
+        };
+        for (int p = lo; p < hi; ++p) {
+            first[p - lo] = use(index_pairs[p].first); second[p - lo] = use(index_pairs[p].second);
+            na[p - lo] = (int)seqs[index_pairs[p].first].size(); nb[p - lo] = (int)seqs[index_pairs[p].second].size();
+        }
+        if (rh_batch_upload_indexed(c, (int)ptr.size(), ptr.data(), lens.data(), hi - lo, first.data(), second.data()) != RH_OK)
+            throw std::logic_error(std::string("ractip_amd::solve_probabilities_indexed: ") + rh_last_error(c));
+        return compute_and_unpack(c, (int)ptr.size(), first, second, na, nb, max_w, threshold_hp);
+    };
+    if (parts <= 1) return one(ctx, 0, np);
+    std::vector<std::vector<PairProbabilities>> part(parts);
+    std::vector<std::string> errors(parts);
+    std::vector<std::thread> workers;
+    for (int k = 0; k < parts; ++k)
+        workers.emplace_back([&, k] {
+            try {
+                const auto b = shard_bounds(np, k, parts);
+                part[k] = one(all[k], b.first, b.second);
+            } catch (const std::exception& e) { errors[k] = e.what(); }
+        });
+    for (std::thread& t : workers) t.join();
+    std::vector<PairProbabilities> out;
+    out.reserve(np);
+    for (int k = 0; k < parts; ++k) {
+        if (!errors[k].empty()) throw std::logic_error(errors[k]);
+        for (PairProbabilities& r : part[k]) out.push_back(std::move(r));
+    }
+    return out;
+}
+
 // contiguous blocks of the pairs, one per listed device, each on its own context and host thread; results in iteration order
 std::vector<PairProbabilities> ProbabilityEngine::batch(rh_ctx* ctx, const std::vector<std::pair<std::string, std::string>>& pairs,
                                                         uint max_w, bool threshold_hp,
@@ -308,8 +379,7 @@ std::vector<PairProbabilities> ProbabilityEngine::batch_one(rh_ctx* ctx, const s
 {
     const std::vector<std::pair<std::string, std::string>> pairs(all_pairs.begin() + lo, all_pairs.begin() + hi);
     const int np = (int)pairs.size();
-    std::vector<PairProbabilities> out(np);
-    if (np == 0) return out;
+    if (np == 0) return {};
     std::vector<const char*> a(np), b(np);
     std::vector<int> na(np), nb(np);
     for (int p = 0; p < np; ++p) {
@@ -329,27 +399,40 @@ std::vector<PairProbabilities> ProbabilityEngine::batch_one(rh_ctx* ctx, const s
         if (rh_batch_upload_constrained(ctx, np, a.data(), na.data(), b.data(), nb.data(), p1.data(), p2.data(), pj.data()) != RH_OK)
             raise_ctx("solve_probabilities");
     } else if (rh_batch_upload(ctx, np, a.data(), na.data(), b.data(), nb.data()) != RH_OK) raise_ctx("solve_probabilities");
+    std::vector<int> first(np), second(np);
+    for (int p = 0; p < np; ++p) { first[p] = 2 * p; second[p] = 2 * p + 1; }
+    return compute_and_unpack(ctx, 2 * np, first, second, na, nb, max_w, threshold_hp);
+}
+
+// the staged batch computed and unpacked: pair p = sequences first[p], second[p] of the nseq fold rows, of n1[p] and n2[p] letters
+std::vector<PairProbabilities> ProbabilityEngine::compute_and_unpack(rh_ctx* ctx, int nseq, const std::vector<int>& first, const std::vector<int>& second,
+                                                                     const std::vector<int>& na, const std::vector<int>& nb, uint max_w,
+                                                                     bool threshold_hp) const
+{
+    const int np = (int)first.size();
+    std::vector<PairProbabilities> out(np);
+    auto raise_ctx = [&](const char* where) { throw std::logic_error(std::string("ractip_amd::") + where + ": " + rh_last_error(ctx)); };
     if (rh_batch_compute(ctx) != RH_OK) raise_ctx("solve_probabilities");
     // three device-to-host copies for the whole batch, then unpack the padded layout on the host
     size_t tri_stride = 0, hp_stride = 0;
     int up_ld = 0, hp_ld = 0;
     if (rh_batch_layout(ctx, &tri_stride, &up_ld, &hp_stride, &hp_ld) != RH_OK) raise_ctx("solve_probabilities");
-    std::vector<double> bp((size_t)2 * np * tri_stride), up((size_t)2 * np * up_ld), hp((size_t)np * hp_stride), z((size_t)3 * np);
+    std::vector<double> bp((size_t)nseq * tri_stride), up((size_t)nseq * up_ld), hp((size_t)np * hp_stride), z((size_t)3 * np);
     if (rh_batch_results_all(ctx, bp.data(), up.data(), hp.data(), z.data()) != RH_OK) raise_ctx("solve_probabilities");
     for (int p = 0; p < np; ++p) {
         const uint n1 = na[p], n2 = nb[p];
         PairProbabilities& r = out[p];
-        const double* b1 = bp.data() + (size_t)(2 * p) * tri_stride;
-        const double* b2 = bp.data() + (size_t)(2 * p + 1) * tri_stride;
+        const double* b1 = bp.data() + (size_t)first[p] * tri_stride;
+        const double* b2 = bp.data() + (size_t)second[p] * tri_stride;
         r.bp1.resize((size_t)(n1 + 1) * (n1 + 2) / 2);
         r.bp2.resize((size_t)(n2 + 1) * (n2 + 2) / 2);
         std::transform(b1, b1 + r.bp1.size(), r.bp1.begin(), [](double v) { return (float)v; });
         std::transform(b2, b2 + r.bp2.size(), r.bp2.begin(), [](double v) { return (float)v; });
         r.up1.assign(n1, VF(max_w)); r.up2.assign(n2, VF(max_w));
         for (uint i = 0; i < n1; ++i)
-            for (uint w = 0; w < max_w; ++w) r.up1[i][w] = (float)up[(size_t)(2 * p) * up_ld + (size_t)i * max_w + w];
+            for (uint w = 0; w < max_w; ++w) r.up1[i][w] = (float)up[(size_t)first[p] * up_ld + (size_t)i * max_w + w];
         for (uint i = 0; i < n2; ++i)
-            for (uint w = 0; w < max_w; ++w) r.up2[i][w] = (float)up[(size_t)(2 * p + 1) * up_ld + (size_t)i * max_w + w];
+            for (uint w = 0; w < max_w; ++w) r.up2[i][w] = (float)up[(size_t)second[p] * up_ld + (size_t)i * max_w + w];
         r.offset1 = make_offsets(n1); r.offset2 = make_offsets(n2);
         r.hp.assign(n1 + 1, VF(n2 + 1));
         const double* h = hp.data() + (size_t)p * hp_stride;

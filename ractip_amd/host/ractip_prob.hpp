@@ -83,6 +83,17 @@ public:
                                                                const std::vector<std::pair<std::string, std::string>>& structures,
                                                                uint max_w = 15, bool duplex = false) const;
 
+    // Indexed batches (rh_batch_upload_indexed): every string of `seqs` is folded once, pair p = (seqs[i], seqs[j]) for (i, j) =
+    // index_pairs[p] -- a screen of queries against targets, or a z-score loop that shuffles one molecule only.  The same
+    // PairProbabilities per pair as the members above return for the expanded pairs.  Device shards split the pairs into the usual
+    // contiguous blocks; each shard uploads only the sequences its block references.  (The members above do not dedupe: they fold
+    // what they are given.)
+    std::vector<PairProbabilities> solve_probabilities_indexed(const std::vector<std::string>& seqs,
+                                                               const std::vector<std::pair<int, int>>& index_pairs) const;
+    std::vector<PairProbabilities> solve_probabilities_default_indexed(const std::vector<std::string>& seqs,
+                                                                       const std::vector<std::pair<int, int>>& index_pairs,
+                                                                       uint max_w = 15, bool duplex = false) const;
+
     // the Vienna energy tables as RactIP::run installs them (:1563-1567): copy_boltzmann_parameters() unless use_bl_param_ is
     // off, then read_parameter_file(param_file_).  defaults_file stands for the tables built into the user's RNAlib (a ViennaRNA
     // parameter file; ViennaRNA is no part of the reference, so this library has none of its own); semantics: 0 = by the files
@@ -107,6 +118,10 @@ private:
     std::vector<PairProbabilities> batch_one(rh_ctx* ctx, const std::vector<std::pair<std::string, std::string>>& pairs, int lo, int hi,
                                              uint max_w, bool threshold_hp,
                                              const std::vector<std::pair<std::string, std::string>>* structures = nullptr) const;
+    std::vector<PairProbabilities> batch_indexed(rh_ctx* ctx, const std::vector<std::string>& seqs, const std::vector<std::pair<int, int>>& index_pairs,
+                                                 uint max_w, bool threshold_hp) const;
+    std::vector<PairProbabilities> compute_and_unpack(rh_ctx* ctx, int nseq, const std::vector<int>& first, const std::vector<int>& second,
+                                                      const std::vector<int>& n1, const std::vector<int>& n2, uint max_w, bool threshold_hp) const;
     rh_ctx* ctx_;                          // first device's CONTRAfold context
     mutable rh_ctx* vctx_ = nullptr;       // first device's Vienna-BL context (created on first use)
     std::vector<int> devices_;

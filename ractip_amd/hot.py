@@ -23,6 +23,7 @@ EXPORTS = [
     "rh_host_alloc", "rh_host_free", "rh_batch_fallbacks", "rh_create_vienna", "rh_vienna_semantics", "rh_set_scale_memory", "rh_set_kernel_timing", "rh_kernel_times",
     "rh_set_duplex_mode", "rh_get_duplex_mode",
     "rh_batch_upload_constrained", "rh_debug_batch_allow_mask",
+    "rh_batch_upload_indexed", "rh_batch_index", "rh_batch_candidates_seq_all",
     "rh_debug_vienna_cell", "rh_debug_vienna_value",   # loader inspection (host only; used by the CPU tests of the loader)
 ]
 
@@ -94,6 +95,12 @@ def load_library():
     L.rh_batch_upload.argtypes = [vp, ci, ctypes.POINTER(cp), ctypes.POINTER(ci), ctypes.POINTER(cp), ctypes.POINTER(ci)]
     L.rh_batch_upload_constrained.argtypes = L.rh_batch_upload.argtypes + [ctypes.POINTER(cp)] * 3
     L.rh_batch_upload_constrained.restype = ci
+    L.rh_batch_upload_indexed.argtypes = [vp, ci, ctypes.POINTER(cp), ctypes.POINTER(ci), ci, ctypes.POINTER(ci), ctypes.POINTER(ci)]
+    L.rh_batch_upload_indexed.restype = ci
+    L.rh_batch_index.argtypes = [vp, vp, vp, vp, vp]
+    L.rh_batch_index.restype = ci
+    L.rh_batch_candidates_seq_all.argtypes = [vp, ci, ctypes.c_float, vp, ci, vp]
+    L.rh_batch_candidates_seq_all.restype = ci
     L.rh_debug_batch_allow_mask.argtypes = [vp, ci, ci, vp, vp]
     L.rh_debug_batch_allow_mask.restype = ci
     L.rh_batch_compute.argtypes = [vp]
@@ -127,6 +134,19 @@ def tri_offset(n, i):
     return i * (2 * (n + 1) - i - 1) // 2
 
 
+def index_pairs(pairs):
+    """(seqs, first, second) of a list of (s1, s2) pairs: identical strings once, in the order of their first appearance, and
+    pair p = (seqs[first[p]], seqs[second[p]]) -- the arguments of Context.batch_upload_indexed."""
+    slot, seqs, first, second = {}, [], [], []
+    for a, b in pairs:
+        for s, out in ((a, first), (b, second)):
+            if s not in slot:
+                slot[s] = len(seqs)
+                seqs.append(s)
+            out.append(slot[s])
+    return seqs, first, second
+
+
 class Context:
     """One rh_ctx: one GPU, one host thread."""
 
@@ -145,6 +165,7 @@ class Context:
         if not self.h:
             raise RhError("rh_create failed: %s" % self.L.rh_last_error(None).decode())
         self._pairs = []
+        self._seq_lens = None   # lengths of the distinct sequences of an indexed upload (None: a plain one, 2 per pair)
 
     def vienna_semantics(self):
         """1 = ViennaRNA-1.8 loop energies, 2 = ViennaRNA-2.x (0: CONTRAfold model)."""
@@ -261,6 +282,40 @@ class Context:
             c2 = column(None if pairs_c is None else [c[1] for c in pairs_c])
             self._check(self.L.rh_batch_upload_constrained(self.h, np_, a, na, b, nb, c1, c2, column(co_constraints)))
         self._pairs = [(len(p[0]), len(p[1])) for p in pairs]
+        self._seq_lens = None
+
+    def batch_upload_indexed(self, seqs, index_pairs):
+        """Every string of `seqs` is folded once; pair p = (seqs[i], seqs[j]) for (i, j) = index_pairs[p] (rh_batch_upload_indexed).
+        The per-pair calls (batch_results, batch_candidates, batch_candidates_all, batch_logz) work as on the expanded batch."""
+        ns, np_ = len(seqs), len(index_pairs)
+        a = (ctypes.c_char_p * ns)(*[s.encode() for s in seqs])
+        na = (ctypes.c_int * ns)(*[len(s) for s in seqs])
+        first = (ctypes.c_int * max(np_, 1))(*[int(p[0]) for p in index_pairs])
+        second = (ctypes.c_int * max(np_, 1))(*[int(p[1]) for p in index_pairs])
+        self._check(self.L.rh_batch_upload_indexed(self.h, ns, a, na, np_, first, second))
+        self._pairs = [(len(seqs[p[0]]), len(seqs[p[1]])) for p in index_pairs]
+        self._seq_lens = [len(s) for s in seqs]
+
+    def batch_index(self):
+        """(nseq, [(first, second)] per pair) of the last upload; for batch_upload: nseq = 2 npairs and the pairs (2p, 2p+1)."""
+        ns, np_ = ctypes.c_int(), ctypes.c_int()
+        self._check(self.L.rh_batch_index(self.h, ctypes.byref(ns), ctypes.byref(np_), None, None))
+        first, second = (ctypes.c_int * max(np_.value, 1))(), (ctypes.c_int * max(np_.value, 1))()
+        self._check(self.L.rh_batch_index(self.h, None, None, first, second))
+        return ns.value, [(first[p], second[p]) for p in range(np_.value)]
+
+    def batch_candidates_seq_all(self, what, threshold, cap=1 << 22):
+        """Candidates per DISTINCT sequence: what = 0 the bp lists, 1 the up lists (records, first) with nseq+1 offsets -- the form of
+        batch_candidates_all that does not repeat a sequence's list for every pair that uses it."""
+        if getattr(self, "_cand_buf", None) is None or self._cand_buf.size < cap:
+            self._cand_buf = np.empty(cap, dtype=self.CAND_DTYPE)
+        ns = len(self._seq_lens) if self._seq_lens is not None else 2 * len(self._pairs)
+        first = np.empty(ns + 1, dtype=np.int32)
+        k = self._check(self.L.rh_batch_candidates_seq_all(self.h, what, ctypes.c_float(threshold), self._cand_buf.ctypes.data,
+                                                           cap, first.ctypes.data))
+        if k > cap:
+            raise RhError("candidate buffer too small: %d > %d" % (k, cap))
+        return self._cand_buf[:k], first
 
     def debug_allow_mask(self, which, k):
         """The allowed-pair mask of the last upload as the kernels read it (rh_debug_batch_allow_mask): which = 0, sequence k
@@ -314,11 +369,20 @@ class Context:
         return self._cand_buf[:k], first
 
     def batch_results_all(self):
-        """Dense results of all pairs (three device-to-host copies), unpacked into per-pair dicts."""
+        """Dense results of all pairs (three device-to-host copies), unpacked into per-pair dicts.  After batch_upload_indexed the
+        folds are per distinct sequence: one dict(bp=[nseq tables], up=[nseq], hp=[npairs matrices], logZ=(npairs, 3))."""
         ts, hs = ctypes.c_size_t(), ctypes.c_size_t()
         uld, hld = ctypes.c_int(), ctypes.c_int()
         self._check(self.L.rh_batch_layout(self.h, ctypes.byref(ts), ctypes.byref(uld), ctypes.byref(hs), ctypes.byref(hld)))
         np_ = len(self._pairs)
+        if getattr(self, "_seq_lens", None) is not None:
+            lens, w = self._seq_lens, self.max_w
+            bp = np.empty((len(lens), ts.value)); up = np.empty((len(lens), uld.value)); hp = np.empty((np_, hs.value)); z = np.empty((np_, 3))
+            self._check(self.L.rh_batch_results_all(self.h, bp.ctypes.data, up.ctypes.data, hp.ctypes.data, z.ctypes.data))
+            return dict(bp=[bp[k][:tri_size(n)] for k, n in enumerate(lens)],
+                        up=[up[k][:n * w] if w == 1 else up[k][:n * w].reshape(n, w) for k, n in enumerate(lens)],
+                        hp=[hp[p][:(n1 + 1) * hld.value].reshape(n1 + 1, hld.value)[:, :n2 + 1] for p, (n1, n2) in enumerate(self._pairs)],
+                        logZ=z)
         bp = np.empty((2 * np_, ts.value)); up = np.empty((2 * np_, uld.value)); hp = np.empty((np_, hs.value)); z = np.empty((np_, 3))
         self._check(self.L.rh_batch_results_all(self.h, bp.ctypes.data, up.ctypes.data, hp.ctypes.data, z.ctypes.data))
         out = []
@@ -357,7 +421,8 @@ class Context:
         uld, hld = ctypes.c_int(), ctypes.c_int()
         self._check(self.L.rh_batch_layout(self.h, ctypes.byref(ts), ctypes.byref(uld), ctypes.byref(hs), ctypes.byref(hld)))
         np_ = len(self._pairs)
-        shapes = ((2 * np_, ts.value), (2 * np_, uld.value), (np_, hs.value), (np_, 3))
+        ns = len(self._seq_lens) if getattr(self, "_seq_lens", None) is not None else 2 * np_
+        shapes = ((ns, ts.value), (ns, uld.value), (np_, hs.value), (np_, 3))
         if bufs is None or tuple(b.shape for b in bufs) != shapes:
             for b in bufs or ():          # the layout changed: the buffers this call replaces are released, not kept until close()
                 self.pinned_free(b)

@@ -109,6 +109,38 @@ def predict(s1, s2, model="vienna", duplex=False, device=0, options=None, ctx=No
             ctx.close()
 
 
+def screen(queries, targets, model="vienna", duplex=False, device=0, options=None, ctx=None):
+    """The joint structures of the cross product queries x targets from ONE indexed batch: every distinct string is uploaded and
+    folded once (hot.index_pairs, Context.batch_upload_indexed), every (query, target) gets its hp.  Returns one list per query
+    with predict()'s result for each target; model / duplex / options as in predict."""
+    pairs = [(q, t) for q in queries for t in targets]
+    if not pairs:
+        return [[] for _ in queries]
+    own = ctx is None
+    if own:
+        ctx = hot.Context(device=device, model=hot.RH_MODEL_VIENNA_BL if model == "vienna" else hot.RH_MODEL_CONTRAFOLD)
+    try:
+        opt = options or (ilp.Options() if model == "vienna" else ilp.Options(min_w=0))
+        if model == "vienna":
+            ctx.set_max_w(max(1, opt.max_w))
+            ctx.set_hybrid(not duplex)
+        seqs, first, second = hot.index_pairs(pairs)
+        ctx.batch_upload_indexed(seqs, list(zip(first, second)))
+        ctx.batch_compute()
+        out = []
+        for qi in range(len(queries)):
+            row = []
+            for ti in range(len(targets)):
+                (s1, s2), r = pairs[qi * len(targets) + ti], ctx.batch_results(qi * len(targets) + ti)
+                up1, up2 = (r["up1"], r["up2"]) if model == "vienna" else (None, None)
+                row.append(ilp.solve(s1, s2, r["bp1"], r["bp2"], r["hp"], up1, up2, opt))
+            out.append(row)
+        return out
+    finally:
+        if own:
+            ctx.close()
+
+
 def _energies(s1, s2, mats, opt):
     """One iteration of what RactIP::run does with show_energy_/z-score on (src/ractip.cpp:1599-1601, 1645-1650): the joint
     programme with e1, e2, e3 and the two single-sequence programmes with e1s, e2s (all float, like the reference)."""
@@ -125,7 +157,7 @@ def _energies(s1, s2, mats, opt):
 def zscore(s1, s2, mode=12, num_shuffling=1000, seed=1, options=None, matrices=None, device=0):
     """The z-score loop of RactIP::run (src/ractip.cpp:1624-1670) on the default path: the native pair and `num_shuffling`
     dinucleotide shuffles (the reference's own RNG order, ractip_amd/shard.py), ALL probability matrices in one device
-    pass, then the programmes and energies per iteration on the host with the reference's float accumulation order.
+    pass (modes 1 and 2 shuffle one molecule only: an indexed batch folds the other one once, with the bits it has in every pair), then the programmes and energies per iteration on the host with the reference's float accumulation order.
     `matrices(pairs) -> list of dicts` overrides the probability source (tests)."""
     opt = options or ilp.Options()
     pairs = [(s1, s2)] + shard.zscore_shuffles(s1, s2, mode, num_shuffling, seed)
@@ -134,9 +166,17 @@ def zscore(s1, s2, mode=12, num_shuffling=1000, seed=1, options=None, matrices=N
         try:
             ctx.set_max_w(max(1, opt.max_w))
             ctx.set_hybrid(True)
-            ctx.batch_upload(pairs)
-            ctx.batch_compute()
-            mats = ctx.batch_results_all()
+            if mode in (1, 2):
+                seqs, first, second = hot.index_pairs(pairs)
+                ctx.batch_upload_indexed(seqs, list(zip(first, second)))
+                ctx.batch_compute()
+                res = ctx.batch_results_all()
+                mats = [dict(bp1=res["bp"][i], bp2=res["bp"][j], up1=res["up"][i], up2=res["up"][j], hp=res["hp"][p], logZ=res["logZ"][p])
+                        for p, (i, j) in enumerate(zip(first, second))]
+            else:
+                ctx.batch_upload(pairs)
+                ctx.batch_compute()
+                mats = ctx.batch_results_all()
         finally:
             ctx.close()
     else:
