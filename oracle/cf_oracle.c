@@ -185,6 +185,7 @@ static int nuc_code(char c)
         default: return 4;
     }
 }
+int cfo_nuc_code(int c) { return nuc_code((char)c); } /* for the tests that compare the product's encoding with this one */
 static int complementary(int a, int b)
 { /* AU, GU, CG both ways (ipp:391-396) */
     return (a == 0 && b == 3) || (a == 3 && b == 0) || (a == 2 && b == 3) ||

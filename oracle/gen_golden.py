@@ -12,6 +12,8 @@ random ones) and the reference's outputs for them in double precision:
 Also the float-engine logZ (what RactIP itself instantiates, ractip.cpp:200-201).
 A second fixture, tests/golden/contrafold_planted_loops.npz (GOLDEN_ONLY=planted_loops writes it alone): log Z and the two
 stem posteriors of the 528 planted single-loop inputs of tests/_contrafold_cases.py (shape_set).
+A third, tests/golden/contrafold_unknown_letters.npz (GOLDEN_ONLY=unknown_letters): both engines on the inputs with N, T and lower-case
+letters of tests/_alphabet_cases.py (fixture_inputs).
 """
 import ctypes, glob, os, random, sys
 import numpy as np
@@ -60,6 +62,65 @@ def golden_planted_loops():
     print("wrote", os.path.normpath(dst), os.path.getsize(dst), "bytes; stem posteriors within the budget >= %.4f / %.4f"
           % (min(o for o, c in zip(outer, shapes) if c.l1 + c.l2 <= 30), min(i for i, c in zip(inner, shapes) if c.l1 + c.l2 <= 30)))
 
+
+def save_npz_fixed_dates(dst, arrays):
+    """np.savez_compressed with every member dated 1980-01-01: the same arrays give the same bytes on every run"""
+    import zipfile
+    with zipfile.ZipFile(dst, "w", zipfile.ZIP_DEFLATED) as z:
+        for name, a in arrays.items():
+            info = zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            with z.open(info, "w") as f:
+                np.lib.format.write_array(f, np.asanyarray(a), allow_pickle=False)
+
+
+def golden_unknown_letters():
+    """tests/golden/contrafold_unknown_letters.npz: InferenceEngine<double> and DuplexEngine<double> on inputs with N, T and lower-case
+    letters (the generators: tests/_alphabet_cases.py, fixture_inputs).  Every role x loop input: log Z and both stem posteriors; the
+    mixed sequences and pairs: log Z and the posterior entries above 1e-3 as index / value."""
+    sys.path.insert(0, os.path.join(here, "..", "tests"))
+    import _alphabet_cases as ac
+    import _contrafold_cases as edges
+    subs, seqs, pairs = ac.fixture_inputs()
+    out = {"role/seq": np.array([s.seq.encode() for s in subs])}
+    logz, outer, inner = [], [], []
+    for s in subs:
+        n = len(s.seq)
+        post = np.zeros((n + 1) * (n + 2) // 2)
+        logz.append(lib.ref_inference(s.seq.encode(), 0, post.ctypes.data, None, None))
+        p = edges.stem_probs(post, s.case)
+        outer.append(p[0])
+        inner.append(p[1])
+    out.update({"role/logZ": np.array(logz), "role/outer": np.array(outer), "role/inner": np.array(inner)})
+    out["mixed/seq"] = np.array([s.encode() for s in seqs])
+    out["mixed/logZ"] = np.zeros(len(seqs))
+    for k, s in enumerate(seqs):
+        n = len(s)
+        post = np.zeros((n + 1) * (n + 2) // 2)
+        out["mixed/logZ"][k] = lib.ref_inference(s.encode(), 0, post.ctypes.data, None, None)
+        idx = np.flatnonzero(post > 1e-3)
+        out["mixed/%d/idx" % k] = idx.astype(np.int32)
+        out["mixed/%d/val" % k] = post[idx]
+    out["pair/s1"] = np.array([a.encode() for a, _ in pairs])
+    out["pair/s2"] = np.array([b.encode() for _, b in pairs])
+    out["pair/logZ2"] = np.zeros((len(pairs), 2))
+    for k, (a, b) in enumerate(pairs):
+        post = np.zeros((len(a) + 1) * (len(b) + 1))
+        z2 = np.zeros(2)
+        lib.ref_duplex(a.encode(), b.encode(), 0, post.ctypes.data, None, None, z2.ctypes.data)
+        out["pair/logZ2"][k] = z2
+        idx = np.flatnonzero(post > 1e-3)
+        out["pair/%d/idx" % k] = idx.astype(np.int32)
+        out["pair/%d/val" % k] = post[idx]
+    dst = os.path.join(here, "..", "tests", "golden", "contrafold_unknown_letters.npz")
+    save_npz_fixed_dates(dst, out)
+    print("wrote", os.path.normpath(dst), os.path.getsize(dst), "bytes; %d role inputs, %d mixed sequences, %d mixed pairs"
+          % (len(subs), len(seqs), len(pairs)))
+
+
+if os.environ.get("GOLDEN_ONLY") == "unknown_letters":
+    golden_unknown_letters()
+    sys.exit(0)
 
 if os.environ.get("GOLDEN_ONLY") == "planted_loops":
     golden_planted_loops()

@@ -153,6 +153,7 @@ static int vcode(char c)
         default: return 0;
     }
 }
+int vo_code(int c) { return vcode((char)c); } /* for the tests that compare the product's encoding with this one */
 /* pair types CG=1 GC=2 GU=3 UG=4 AU=5 UA=6 (boltzmann_param.c:22) */
 static int ptype(int a, int b)
 {

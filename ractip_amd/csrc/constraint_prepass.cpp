@@ -6,6 +6,17 @@
 
 namespace rh::host {
 
+uint8_t nuc_code(char ch)
+{  // InferenceEngine.ipp:379-384: case-insensitive ACGU, anything else (incl. T, N) is code 4
+    switch (ch) {
+        case 'A': case 'a': return 0;
+        case 'C': case 'c': return 1;
+        case 'G': case 'g': return 2;
+        case 'U': case 'u': return 3;
+        default: return 4;
+    }
+}
+
 uint8_t vienna_code(char ch)
 {
     switch (ch) {

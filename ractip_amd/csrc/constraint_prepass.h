@@ -31,6 +31,7 @@ RH_HOST_DEVICE inline bool allow_pair(int a, int b, int n, const uint8_t* ch, co
     return P[a] == b || (P[a] == 0 && P[b] == 0 && enc[a] == enc[b]);   // the forced pair itself, or two free letters of one loop
 }
 
+uint8_t nuc_code(char ch);      // CONTRAfold model: A,C,G,U -> 0..3 in either case, anything else (T and N included) 4; host only, here so that a CPU program can call it
 uint8_t vienna_code(char ch);   // ViennaRNA encode_char with energy_set 0: A,C,G,U -> 1..4 (T reads as U), anything else 0
 
 // Fills ch / P / enc at 1..n (the caller presets '.' / 0 / 0 everywhere else).  cons may be shorter or longer than n.

@@ -14,17 +14,6 @@
 
 namespace rh::host {
 
-uint8_t nuc_code(char ch)
-{  // InferenceEngine.ipp:379-384: case-insensitive ACGU, anything else (incl. T, N) is code 4
-    switch (ch) {
-        case 'A': case 'a': return 0;
-        case 'C': case 'c': return 1;
-        case 'G': case 'g': return 2;
-        case 'U': case 'u': return 3;
-        default: return 4;
-    }
-}
-
 // The per-letter values of `count` constraint strings (constraint_prepass.h), [count][lds] each, as allow_mask_build reads them
 struct ConsPass {
     std::vector<uint8_t> ch;
