@@ -109,6 +109,8 @@ struct McLinArgs {   // launch_mc_lin: one phase (0 inside, 1 outside) of the CO
     SweepPlan plan_sweep, plan_short;
     int routed, n_small, nmax_sweep, short_count, nmax_short;
     int phase, pin, strip_xcd;
+    int f5_pass, f5_jlo;       // strips: the exterior sums by lin_f5i_pass / lin_f5o_pass (0: the serial kernels, same bits); the first F5i
+                               // entry the bootstrap diagonals do not leave behind
     McLinArgs() { std::memset(this, 0, sizeof *this); }
 };
 
@@ -245,6 +247,8 @@ struct Ctx {   // (the fields of rh_ctx, below)
     int acc_final_t = 1;           // Vienna-BL accessibility: vlin_acc_final_t (one thread per letter, all widths; RH_ACC_FINAL_T=0: one thread per letter and width)
     int acc_wide = 1;              // Vienna-BL accessibility: vlin_acc_gaps_wide for the gap lengths 3..30 (RH_ACC_WIDE=0: vlin_acc_gaps for all)
     int strip_xcd = 1;             // groups of one sequence consecutive on one XCD (RH_STRIP_XCD=0: sequence-major launch order only)
+    int f5_pass = 1;               // exterior sums of the strip sweeps in one pass per direction; RH_F5_PASS=0: lin_f5i_tail / lin_f5o_head over the same
+                                   // ranges, one entry at a time (slow, the same bits: the reference of tests/test_gpu_f5_pass.py)
     int far_pk = 1;                // ... on packed operand tiles (lin_pack_tiles + lin_far_*_pk); RH_FAR_PK=0: gather per product
     int use_graphs = 1;            // RH_NO_GRAPH=1 launches every kernel from the host instead
     GraphSlot g_in, g_out, g_dx;
@@ -409,6 +413,7 @@ void far_inside_after(const SweepPass& S, int done);
 void far_outside_begin(SweepPass& S, int top);
 void far_outside_before(SweepPass& S, int d);
 std::vector<double> strip_weights(const LinModel& L, bool* ok_out = nullptr);
+size_t f5_pass_lds(int ld, int phase);
 // launch_vienna.hip
 int launch_mc_vienna(rh_ctx* c, int pin);
 SweepPlan plan_mc_vlin(const rh_ctx* c, int phase, bool co, int nmax);

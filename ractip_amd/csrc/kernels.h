@@ -28,11 +28,13 @@ template <int BS> __global__ void lin_far_outside(McBatch B, int D);
 __global__ void lin_far_inside_mfma(McBatch B, int D);
 __global__ void lin_far_outside_mfma(McBatch B, int D);
 template <int SWEEP> __global__ void lin_pack_tiles(McBatch B, int Dblk, int outside, int banded);
-template <int KD, int W, int FILT> __global__ void lin_inside_strip(McBatch B, const LinModel* __restrict__ L, const double* __restrict__ wT, int d0, int f5_lo, double lam_d0, int pin);
-template <int KD, int W, int FILT> __global__ void lin_outside_strip(McBatch B, const LinModel* __restrict__ L, const double* __restrict__ wT, int d0, int f5_hi, int f5_lo, int pin, int* __restrict__ bad);
+template <int KD, int W, int FILT> __global__ void lin_inside_strip(McBatch B, const LinModel* __restrict__ L, const double* __restrict__ wT, int d0, double lam_d0, int pin);
+template <int KD, int W, int FILT> __global__ void lin_outside_strip(McBatch B, const LinModel* __restrict__ L, const double* __restrict__ wT, int d0, int pin, int* __restrict__ bad);
 __global__ void lin_f5i_tail(McBatch B, const LinModel* __restrict__ L, int jlo);
+__global__ void lin_f5i_pass(McBatch B, const LinModel* __restrict__ L, int jlo);
 void launch_lin_small(const McBatch& B, const LinModel* L, const double* wpad, const int* list, int nlist, int* bad, hipStream_t stream);   // mccaskill_small.hip
 __global__ void lin_f5o_head(McBatch B, const LinModel* __restrict__ L, int khi, int klo);
+__global__ void lin_f5o_pass(McBatch B, const LinModel* __restrict__ L);
 __global__ void lin_far_inside_pk(McBatch B, int D, int l2);
 __global__ void lin_far_outside_pk(McBatch B, int D, int l2);
 __global__ void lin_far2_inside(McBatch B, int D2, int l2);

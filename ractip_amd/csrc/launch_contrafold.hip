@@ -210,7 +210,11 @@ static void inside_pairs(const SweepPass& S, const McLinArgs& A, int last)
         far_inside_after(S, d + 2);   // (the first one is due behind diagonal 47)
     }
 }
-// diagonals 0..31 by pairs (every row is "near" there), then strips of KD diagonals (mccaskill_strip.hip)
+// dynamic LDS of the exterior-sum passes (mccaskill_strip.hip): F5 and the partial sums; outside also the parked operands
+size_t f5_pass_lds(int ld, int phase) { return sizeof(double) * ((size_t)ld + 8 + (phase ? (size_t)((ld + 255) / 256) * 256 : 0)); }
+
+// diagonals 0..31 by pairs (every row is "near" there), then strips of KD diagonals (mccaskill_strip.hip); the bootstrap leaves
+// F5i[0..31], the rest is one pass behind the last strip (no inside cell reads F5i).  A.f5_pass = 0: the serial kernel instead.
 static void inside_strips(const SweepPass& S, const McLinArgs& A)
 {
     rh_ctx* c = S.c;
@@ -218,15 +222,15 @@ static void inside_strips(const SweepPass& S, const McLinArgs& A)
     constexpr int KD = 8, GS = 64 - (KD - 1);
     const auto strip = strip_kernels(S.P.W, S.P.filt).in.kern;
     inside_pairs(S, A, 30);
-    int d0 = 32;
-    for (; d0 <= B.nmax - 2; d0 += KD) {
-        const int groups = (std::max(B.nmax - 1 - d0, 0) + GS - 1) / GS + 1;
-        KLAUNCH(c, 0, strip, seq_grid(A.pin, B.ns, groups), dim3(64 * S.P.W), S.st, B, A.lin->d, A.lin->wT, d0, d0 == 32 ? 32 : d0 - KD + 2,
-                std::exp(-A.lin->h.s * d0), (A.pin && A.strip_xcd) ? 2 : A.pin);
+    for (int d0 = 32; d0 <= B.nmax - 2; d0 += KD) {
+        const int groups = (B.nmax - 1 - d0 + GS - 1) / GS;
+        KLAUNCH(c, 0, strip, seq_grid(A.pin, B.ns, groups), dim3(64 * S.P.W), S.st, B, A.lin->d, A.lin->wT, d0, std::exp(-A.lin->h.s * d0),
+                (A.pin && A.strip_xcd) ? 2 : A.pin);
         c->n_launch[0]++;
         far_inside_after(S, d0 + KD);
     }
-    hipLaunchKernelGGL(lin_f5i_tail, dim3(B.ns), dim3(256), 0, S.st, B, A.lin->d, d0 - KD + 2);
+    if (A.f5_pass) hipLaunchKernelGGL(lin_f5i_pass, dim3(B.ns), dim3(256), f5_pass_lds(B.ld, 0), S.st, B, A.lin->d, A.f5_jlo);
+    else hipLaunchKernelGGL(lin_f5i_tail, dim3(B.ns), dim3(256), 0, S.st, B, A.lin->d, A.f5_jlo);
 }
 // one launch per diagonal, or (ahead) look-ahead pairs of launches
 static void inside_diagonals(const SweepPass& S, const McLinArgs& A, bool ahead)
@@ -242,7 +246,8 @@ static void inside_diagonals(const SweepPass& S, const McLinArgs& A, bool ahead)
     }
 }
 
-// strips of KD diagonals from the top, aligned so that a sequence's strips do not depend on the batch
+// strips of KD diagonals from the top, aligned so that a sequence's strips do not depend on the batch.  F5o needs FCA and itself
+// only, so all of it is there before the first strip: one pass, or (A.f5_pass = 0) the serial kernel over the same range.
 static void outside_strips(SweepPass& S, const McLinArgs& A)
 {
     rh_ctx* c = S.c;
@@ -251,12 +256,12 @@ static void outside_strips(SweepPass& S, const McLinArgs& A)
     const auto strip = strip_kernels(S.P.W, S.P.filt).out.kern;
     const int d0_top = (B.nmax - 2) | (KD - 1);
     far_outside_begin(S, d0_top);
-    hipLaunchKernelGGL(lin_f5o_head, dim3(B.ns), dim3(256), 0, S.st, B, A.lin->d, B.nmax - 1, d0_top - 5);
+    if (A.f5_pass) hipLaunchKernelGGL(lin_f5o_pass, dim3(B.ns), dim3(256), f5_pass_lds(B.ld, 1), S.st, B, A.lin->d);
+    else hipLaunchKernelGGL(lin_f5o_head, dim3(B.ns), dim3(256), 0, S.st, B, A.lin->d, B.nmax - 1, 1);
     for (int d0 = d0_top; d0 >= KD - 1; d0 -= KD) {
         far_outside_before(S, d0);
-        const int groups = (std::max(B.nmax - 1 - (d0 - (KD - 1)), 0) + GS - 1) / GS + 1;
-        KLAUNCH(c, 2, strip, seq_grid(A.pin, B.ns, groups), dim3(64 * S.P.W), S.st, B, A.lin->d, A.lin->wT, d0, d0 - 6, d0 - 13,
-                (A.pin && A.strip_xcd) ? 2 : A.pin, A.bad);
+        const int groups = (B.nmax - 1 - (d0 - (KD - 1)) + GS - 1) / GS;
+        KLAUNCH(c, 2, strip, seq_grid(A.pin, B.ns, groups), dim3(64 * S.P.W), S.st, B, A.lin->d, A.lin->wT, d0, (A.pin && A.strip_xcd) ? 2 : A.pin, A.bad);
         c->n_launch[1]++;
     }
 }

@@ -207,12 +207,12 @@ struct InStripPlan {
 };
 
 // ---------------------------------------------------------------------------------------------------------------
-// inside, diagonals d0 .. d0+KD-1 (d0 >= 32, d0 % KD == 0).  Last group: F5i[f5_lo .. d0+1] (rows <= d0-1 of FCA).
+// inside, diagonals d0 .. d0+KD-1 (d0 >= 32, d0 % KD == 0).  Every workgroup is a strip group: F5i is lin_f5i_pass's, behind the last strip.
 // wT[l1*kWTS + t + 1] = shape_w(l1, t-l1) for 0 <= l1 <= t <= 30, else 0.
 constexpr int kWTS = 40;
 
 template <int KD, int W, int FILT>
-__global__ __launch_bounds__(64 * W, (W >= 8 ? 4 : 2)) void lin_inside_strip(McBatch B, const LinModel* __restrict__ L, const double* __restrict__ wT, int d0, int f5_lo,
+__global__ __launch_bounds__(64 * W, (W >= 8 ? 4 : 2)) void lin_inside_strip(McBatch B, const LinModel* __restrict__ L, const double* __restrict__ wT, int d0,
                                                               double lam_d0, int pin)
 {
     using P = InStripPlan<KD, W>;
@@ -221,7 +221,6 @@ __global__ __launch_bounds__(64 * W, (W >= 8 ? 4 : 2)) void lin_inside_strip(McB
     constexpr int TS = P::TS, KH = KD * TS / W;     // term sets; diagonals per wavefront in the pre-phase
     static_assert(KD % W == 0 && KD <= 8 && W % TS == 0 && KD % (W / TS) == 0 && (NM + 1) % W == 0, "8 terms per end and term set, 32/W staged rows per wavefront and region");
     __shared__ double lds[P::SZ];
-    __shared__ double red[W];
     constexpr bool FACT = FILT != 0 && W == 8 && KD == 8;
     __shared__ double fw[FACT ? 160 : 1];   // factored filter: W4[t+1][4] (A, wb, -, Rc), read by wave-uniform (broadcast) LDS loads
     // pin = 2 (batch size a multiple of 8): workgroups are dealt round-robin to the 8 XCDs in launch order, so sequence sq is
@@ -241,30 +240,9 @@ __global__ __launch_bounds__(64 * W, (W >= 8 ? 4 : 2)) void lin_inside_strip(McB
     const size_t ts = B.tab_stride;
     const uint8_t* __restrict__ s = B.seq + (size_t)sq * B.lds;
     double* __restrict__ tab = B.tab + (size_t)sq * B.seq_stride;
-    double* __restrict__ f5i = B.f5i + (size_t)sq * ld;
     const int ncell0 = n - 1 - d0 > 0 ? n - 1 - d0 : 0;
     const int ngroup = (ncell0 + GS - 1) / GS;
-    if (slot > ngroup) return;
-
-    if (slot == ngroup) {
-        // F5i[jj] = F5i[jj-1]*ext_unpaired + sum_{k<=jj-2} F5i[k]*FCA[k+1,jj-1]*ext_paired   (ipp:3692-3717)
-        const double* __restrict__ fca = tab + L_FCA * ts;
-#pragma unroll 1
-        for (int jj = f5_lo; jj <= d0 + 1; jj++) {
-            if (jj < 1 || jj > n) continue;
-            // fixed partition of the sum (256 threads, 4 partial sums) whatever W is: the bits of F5i do not depend on which
-            // kernel -- bootstrap, strip or tail -- computes an entry, i.e. not on the other sequences of the batch
-            double acc = 0.0;
-            if (threadIdx.x < 256)
-                for (int k = threadIdx.x; k <= jj - 2; k += 256) acc = fma(f5i[k], fca[(size_t)(jj - 2 - k) * ld + (k + 1)], acc);
-            acc = wsum(acc);
-            if (lane == 0) red[w] = acc;
-            __syncthreads();
-            if (threadIdx.x == 0) f5i[jj] = f5i[jj - 1] * L->w_eu + (red[0] + red[1] + red[2] + red[3]) * L->w_ep2;
-            __syncthreads();   // F5i[jj] is an operand of F5i[jj+1]
-        }
-        return;
-    }
+    if (slot >= ngroup) return;
 
 #ifdef RH_STAGGER
     {   // tuning build: offset the second workgroup of every CU by about half a workgroup lifetime (lock-step rounds)
@@ -742,7 +720,23 @@ __global__ __launch_bounds__(64 * W, (W >= 8 ? 4 : 2)) void lin_inside_strip(McB
     RH_TRACE(4);
 }
 
-// F5i[jj], jj = jlo .. n, once every row of FCA is final (after the last strip)
+// ---------------------------------------------------------------------------------------------------------------
+// Exterior sums F5i / F5o of the sequences the strips sweep, one pass per direction (256 threads, one workgroup per sequence):
+//   F5i[jj] = F5i[jj-1]*ext_unpaired + sum_{k<=jj-2} F5i[k]*FCA[k+1,jj-1]*ext_paired              (ipp:3692-3717)
+//   F5o[k]  = F5o[k+1]*ext_unpaired  + sum_{jj>=k+2} F5o[jj]*FCA[k+1,jj-1]*ext_paired, descending  (ipp:3751-3780, pulled)
+// Both need FCA (an inside table) and themselves, nothing else: F5i is first read by the outside sweep, F5o can be complete before
+// the first outside strip.  The partition of every sum is FIXED: thread t of 256 takes its terms t, t+256, .. ascending by fma from
+// 0, then wsum, then the four partial sums in order, then f5_entry -- the same in the bootstrap diagonals, in the pass kernels and
+// in the serial kernels, so the bits of an entry do not depend on which kernel computes it.
+__device__ __forceinline__ double f5_term(double f5, double fca, double acc) { return fma(f5, fca, acc); }
+// (spelled out: the compiler may contract prev*w_eu + sum*w_ep2 either way round)
+__device__ __forceinline__ double f5_entry(double prev, double r0, double r1, double r2, double r3, double w_eu, double w_ep2)
+{
+    return fma(prev, w_eu, (r0 + r1 + r2 + r3) * w_ep2);
+}
+
+// F5i[jj], jj = jlo .. n, once every row of FCA is final: the serial form, one entry at a time with its operands fetched inside the
+// chain.  Runs under RH_F5_PASS=0 only (the reference of tests/test_gpu_f5_pass.py).
 __global__ __launch_bounds__(256) void lin_f5i_tail(McBatch B, const LinModel* __restrict__ L, int jlo)
 {
     __shared__ double red[4];
@@ -755,15 +749,95 @@ __global__ __launch_bounds__(256) void lin_f5i_tail(McBatch B, const LinModel* _
 #pragma unroll 1
     for (int jj = jlo < 1 ? 1 : jlo; jj <= n; jj++) {
         double acc = 0.0;
-        for (int k = threadIdx.x; k <= jj - 2; k += 256) acc = fma(f5i[k], fca[(size_t)(jj - 2 - k) * ld + (k + 1)], acc);
+        for (int k = threadIdx.x; k <= jj - 2; k += 256) acc = f5_term(f5i[k], fca[(size_t)(jj - 2 - k) * ld + (k + 1)], acc);
         acc = wsum(acc);
         if (lane == 0) red[w] = acc;
         __syncthreads();
-        if (threadIdx.x == 0) f5i[jj] = f5i[jj - 1] * L->w_eu + (red[0] + red[1] + red[2] + red[3]) * L->w_ep2;
+        if (threadIdx.x == 0) f5i[jj] = f5_entry(f5i[jj - 1], red[0], red[1], red[2], red[3], L->w_eu, L->w_ep2);
         __syncthreads();
     }
 }
 
+// The pass kernels take the memory round trips out of that chain.  Entries go in blocks of kF5Blk: every FCA operand of a block is
+// fetched before its chain starts (none depends on an F5 value), the terms whose F5 operand is final are summed up front, F5 lives in
+// LDS, and a chain step is the at most one term per thread (F5o: threads 0..13, a few dependent FMAs) that needs an entry of the same
+// block, wsum, one barrier and f5_entry, which every thread evaluates for itself.
+constexpr int kF5Blk = 16;
+
+// dynamic LDS: F5i[ld], partial sums [2][4]
+__global__ __launch_bounds__(256) void lin_f5i_pass(McBatch B, const LinModel* __restrict__ L, int jlo)
+{
+    extern __shared__ double f5_lds[];
+    const int sq = blockIdx.x;
+    if (sq >= B.ns) return;
+    const int n = B.n[sq], ld = B.ld;
+    if (n < jlo) return;   // (a hidden sequence has length 0; shorter ones are complete behind the bootstrap diagonals)
+    const int t = threadIdx.x, w = t >> 6, lane = t & 63;
+    double* const f5s = f5_lds;
+    double* const red = f5_lds + ld;
+    double* __restrict__ f5i = B.f5i + (size_t)sq * ld;
+    const double* __restrict__ fca = B.tab + (size_t)sq * B.seq_stride + L_FCA * B.tab_stride;
+    const double w_eu = L->w_eu, w_ep2 = L->w_ep2;
+    for (int k = t; k < jlo; k += 256) f5s[k] = f5i[k];
+    __syncthreads();
+    double prev = f5s[jlo - 1];
+#pragma unroll 1
+    for (int jj0 = jlo; jj0 <= n; jj0 += kF5Blk) {
+        const int ne = n - jj0 + 1 < kF5Blk ? n - jj0 + 1 : kF5Blk;   // entries jj0 .. jj0+ne-1
+        const int kmax = jj0 + ne - 3;                                 // the last term of the last entry
+        double acc[kF5Blk], opin[kF5Blk];
+#pragma unroll
+        for (int e = 0; e < kF5Blk; e++) { acc[e] = 0.0; opin[e] = 0.0; }
+        int kin = 0x7fffffff;   // this thread's term whose F5i operand is an entry of this block (at most one: k >= jj0), its last
+        // term k of entry jj0+e is FCA[k+1, jj0+e-1] = row jj0+e-2-k, column k+1 of the diagonal-major table; it exists for k <= jj0+e-2
+        // (fetched raw at clamped addresses -- row 0 has a column for every k <= n-2 --; what does not exist is never summed)
+        auto fetch = [&](int k, double (&op)[kF5Blk]) {
+            const int kc = k <= kmax ? k : kmax;
+            const double* __restrict__ col = fca + (kc + 1);
+#pragma unroll
+            for (int e = 0; e < kF5Blk; e++) {
+                const int row = jj0 + (e < ne ? e : 0) - 2 - kc;
+                op[e] = col[(size_t)(row > 0 ? row : 0) * ld];
+            }
+        };
+        auto take = [&](int k, const double (&op)[kF5Blk]) {
+            if (k > kmax) return;
+            if (k < jj0) {
+                const double f = f5s[k];
+#pragma unroll
+                for (int e = 0; e < kF5Blk; e++) acc[e] = (e < ne && (e > 0 || k <= jj0 - 2)) ? f5_term(f, op[e], acc[e]) : acc[e];   // (k = jj0-1 is no term of entry jj0)
+            } else {
+                kin = k;
+#pragma unroll
+                for (int e = 2; e < kF5Blk; e++) opin[e] = op[e];   // (k >= jj0 is a term from entry jj0+2 on)
+            }
+        };
+#pragma unroll 1
+        for (int k = t; k <= kmax; k += 512) {   // two terms' operands in flight
+            double opa[kF5Blk], opb[kF5Blk];
+            fetch(k, opa);
+            fetch(k + 256, opb);
+            take(k, opa);
+            take(k + 256, opb);
+        }
+#pragma unroll
+        for (int e = 0; e < kF5Blk; e++) {
+            if (e < ne) {   // (workgroup-uniform)
+                const int jj = jj0 + e;
+                double a = acc[e];
+                if (e >= 2 && kin <= jj - 2) a = f5_term(f5s[kin], opin[e], a);   // F5i[kin] was written two barriers ago at the latest
+                a = wsum(a);
+                if (lane == 0) red[(e & 1) * 4 + w] = a;
+                lds_barrier();
+                const double* r = red + (e & 1) * 4;
+                prev = f5_entry(prev, r[0], r[1], r[2], r[3], w_eu, w_ep2);
+                if (t == 0) f5s[jj] = prev;
+            }
+        }
+        lds_barrier();   // the block's entries are operands of the next block's sums
+        if (t < ne) f5i[jj0 + t] = f5s[jj0 + t];
+    }
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 // outside (pull form) + posterior, diagonals d0, d0-1, .., d0-KD+1 (d0 % KD == KD-1); the mirror image of the inside strip:
@@ -772,7 +846,7 @@ __global__ __launch_bounds__(256) void lin_f5i_tail(McBatch B, const LinModel* _
 //   FCo gather: sum_t sum_l1 w(l1,t-l1) * FCoX[d+2+t][i-1-l1]                                                       ipp:4004-4024, pulled
 // The sliding rows are d0+1 .. d0+32 (final before the launch), the strip's own rows are reached to the LEFT (columns i-e), so
 // the trapezoid shrinks from lane 0: step k is valid for lanes >= k, a group stores lanes KD-1 .. 63 and groups advance by
-// 64-(KD-1) columns.  Last group: F5o[f5_hi .. f5_lo] (descending), what the NEXT launch's cells read.
+// 64-(KD-1) columns.  F5o is complete before the first strip (lin_f5o_pass).
 template <int KD, int W>
 struct OutStripPlan {
     static constexpr int GS = 64 - (KD - 1);
@@ -791,39 +865,105 @@ struct OutStripPlan {
     static_assert(SZ * 8 <= 80 * 1024, "two workgroups per CU");
 };
 
-// F5o[k] = F5o[k+1]*ext_unpaired + sum_{jj>=k+2} F5o[jj]*FCA[k+1,jj-1]*ext_paired, k = khi .. klo descending   (ipp:3751-3780, pulled)
-template <int W>
-__device__ __forceinline__ void f5o_range(const double* __restrict__ fca_tab, double* __restrict__ f5o, const LinModel* __restrict__ L, int n, int ld,
-                                          int khi, int klo, double* red)
-{
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll 1
-    for (int k = khi; k >= klo && k >= 1; k--) {
-        if (k > n - 1) continue;
-        const double* __restrict__ fca = fca_tab + (k + 1);
-        double acc = 0.0;   // fixed partition (256 threads, 4 partial sums) whatever W is: see the inside strip
-        if (threadIdx.x < 256)
-            for (int jj = k + 2 + threadIdx.x; jj <= n; jj += 256) acc = fma(f5o[jj], fca[(size_t)(jj - 2 - k) * ld], acc);
-        acc = wsum(acc);
-        if (lane == 0) red[w] = acc;
-        __syncthreads();
-        if (threadIdx.x == 0) f5o[k] = f5o[k + 1] * L->w_eu + (red[0] + red[1] + red[2] + red[3]) * L->w_ep2;
-        __syncthreads();   // F5o[k] is an operand of F5o[k-1]
-    }
-}
-
-// F5o[khi .. klo] of every sequence before the first outside strip
+// F5o[khi .. klo] (descending) of every sequence, the serial form: RH_F5_PASS=0 only
 __global__ __launch_bounds__(256) void lin_f5o_head(McBatch B, const LinModel* __restrict__ L, int khi, int klo)
 {
     __shared__ double red[4];
     const int sq = blockIdx.x;
     if (sq >= B.ns) return;
-    f5o_range<4>(B.tab + (size_t)sq * B.seq_stride + L_FCA * B.tab_stride, B.f5o + (size_t)sq * B.ld, L, B.n[sq], B.ld, khi, klo, red);
+    const int n = B.n[sq], ld = B.ld;
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const double* __restrict__ fca_tab = B.tab + (size_t)sq * B.seq_stride + L_FCA * B.tab_stride;
+    double* __restrict__ f5o = B.f5o + (size_t)sq * ld;
+#pragma unroll 1
+    for (int k = khi; k >= klo && k >= 1; k--) {
+        if (k > n - 1) continue;
+        const double* __restrict__ fca = fca_tab + (k + 1);
+        double acc = 0.0;
+        for (int jj = k + 2 + threadIdx.x; jj <= n; jj += 256) acc = f5_term(f5o[jj], fca[(size_t)(jj - 2 - k) * ld], acc);
+        acc = wsum(acc);
+        if (lane == 0) red[w] = acc;
+        __syncthreads();
+        if (threadIdx.x == 0) f5o[k] = f5_entry(f5o[k + 1], red[0], red[1], red[2], red[3], L->w_eu, L->w_ep2);
+        __syncthreads();   // F5o[k] is an operand of F5o[k-1]
+    }
+}
+
+// F5o[n-1 .. 1] before the first outside strip.  Term r = t + 256 q of entry k is F5o[k+2+r] * FCA row r, column k+1: a thread's
+// operands of a block are kF5Blk consecutive doubles of its own row.  The terms that need an entry of the same block are the FIRST
+// of threads 0..13 (r <= 13), so those threads sum such an entry inside the chain, from operands parked in LDS.
+// dynamic LDS: F5o[ld], partial sums [2][4], parked operands [ceil(ld/256)][kF5Blk][16]
+__global__ __launch_bounds__(256) void lin_f5o_pass(McBatch B, const LinModel* __restrict__ L)
+{
+    extern __shared__ double f5_lds[];
+    const int sq = blockIdx.x;
+    if (sq >= B.ns) return;
+    const int n = B.n[sq], ld = B.ld;
+    if (n < 2) return;   // (hidden, or F5o[n] alone: lin_init's)
+    const int t = threadIdx.x, w = t >> 6, lane = t & 63;
+    double* const f5s = f5_lds;
+    double* const red = f5_lds + ld;
+    double* const park = red + 8;
+    const double* __restrict__ fca = B.tab + (size_t)sq * B.seq_stride + L_FCA * B.tab_stride;
+    double* __restrict__ f5o = B.f5o + (size_t)sq * ld;
+    const double w_eu = L->w_eu, w_ep2 = L->w_ep2;
+    double prev = f5o[n];
+    if (t == 0) f5s[n] = prev;
+    __syncthreads();
+#pragma unroll 1
+    for (int k0 = n - 1; k0 >= 1; k0 -= kF5Blk) {
+        const int ne = k0 < kF5Blk ? k0 : kF5Blk;   // entries k0, k0-1, .., k0-ne+1 >= 1
+        const int rmax = n - 2 - (k0 - ne + 1);     // the last term of the last entry
+        double acc[kF5Blk];
+#pragma unroll
+        for (int e = 0; e < kF5Blk; e++) acc[e] = 0.0;
+        // (fetched raw at clamped addresses; what does not exist is never summed)
+        auto fetch = [&](int r, double (&op)[kF5Blk]) {
+            const double* __restrict__ row = fca + (size_t)(r <= rmax ? r : 0) * ld;
+#pragma unroll
+            for (int e = 0; e < kF5Blk; e++) op[e] = row[k0 - (e < ne ? e : 0) + 1];
+        };
+        auto take = [&](int q, int r, const double (&op)[kF5Blk]) {
+            if (r > rmax) return;
+#pragma unroll
+            for (int e = 0; e < kF5Blk; e++) {
+                if (e >= 2 && t <= e - 2) park[(q * kF5Blk + e) * 16 + t] = op[e];   // this thread sums entry e in the chain
+                else if (e < ne && k0 - e + 2 + r <= n) acc[e] = f5_term(f5s[k0 - e + 2 + r], op[e], acc[e]);
+            }
+        };
+#pragma unroll 1
+        for (int q = 0; t + 256 * q <= rmax; q += 2) {   // two terms' operands in flight
+            double opa[kF5Blk], opb[kF5Blk];
+            fetch(t + 256 * q, opa);
+            fetch(t + 256 * q + 256, opb);
+            take(q, t + 256 * q, opa);
+            take(q + 1, t + 256 * q + 256, opb);
+        }
+#pragma unroll
+        for (int e = 0; e < kF5Blk; e++) {
+            if (e < ne) {   // (workgroup-uniform)
+                const int k = k0 - e;
+                double a = acc[e];
+                if (e >= 2 && t <= e - 2) {   // F5o[k+2+t] is the entry of step e-2-t: written two barriers ago at the latest
+                    a = 0.0;
+                    for (int q = 0; k + 2 + t + 256 * q <= n; q++) a = f5_term(f5s[k + 2 + t + 256 * q], park[(q * kF5Blk + e) * 16 + t], a);
+                }
+                a = wsum(a);
+                if (lane == 0) red[(e & 1) * 4 + w] = a;
+                lds_barrier();
+                const double* r = red + (e & 1) * 4;
+                prev = f5_entry(prev, r[0], r[1], r[2], r[3], w_eu, w_ep2);
+                if (t == 0) f5s[k] = prev;
+            }
+        }
+        lds_barrier();   // the block's entries are operands of the next block's sums
+        if (t < ne) f5o[k0 - t] = f5s[k0 - t];
+    }
 }
 
 template <int KD, int W, int FILT>
-__global__ __launch_bounds__(64 * W, (W >= 8 ? 4 : 2)) void lin_outside_strip(McBatch B, const LinModel* __restrict__ L, const double* __restrict__ wT, int d0, int f5_hi,
-                                                                              int f5_lo, int pin, int* __restrict__ bad)
+__global__ __launch_bounds__(64 * W, (W >= 8 ? 4 : 2)) void lin_outside_strip(McBatch B, const LinModel* __restrict__ L, const double* __restrict__ wT, int d0,
+                                                                              int pin, int* __restrict__ bad)
 {
     using P = OutStripPlan<KD, W>;
     constexpr int GS = P::GS, NM = P::NM, CD = P::CD, CA = P::CA, CE = P::CE, CS = P::CS, PADL = P::PADL;
@@ -831,7 +971,6 @@ __global__ __launch_bounds__(64 * W, (W >= 8 ? 4 : 2)) void lin_outside_strip(Mc
     constexpr int TS = P::TS, KH = KD * TS / W;
     static_assert(KD % W == 0 && KD <= 8 && W % TS == 0 && KD % (W / TS) == 0 && (NM + 1) % W == 0, "8 terms per end and term set, 32/W staged rows per wavefront and region");
     __shared__ double lds[P::SZ];
-    __shared__ double red[W];
     constexpr bool FACT = FILT != 0 && W == 8 && KD == 8;
     __shared__ double fw[FACT ? 160 : 1];   // factored filter: W4[t+1][4] (A, wb, -, Rc), read by wave-uniform (broadcast) LDS loads
     // pin = 2 (batch size a multiple of 8): workgroups are dealt round-robin to the 8 XCDs in launch order, so sequence sq is
@@ -856,11 +995,7 @@ __global__ __launch_bounds__(64 * W, (W >= 8 ? 4 : 2)) void lin_outside_strip(Mc
     const int dlow = d0 - (KD - 1);                        // the longest diagonal of the strip
     const int ncell_max = n - 1 - dlow > 0 ? n - 1 - dlow : 0;
     const int ngroup = (ncell_max + GS - 1) / GS;
-    if (slot > ngroup) return;
-    if (slot == ngroup) {
-        f5o_range<W>(tab + L_FCA * ts, f5o, L, n, ld, f5_hi, f5_lo, red);
-        return;
-    }
+    if (slot >= ngroup) return;
 
 #ifdef RH_STAGGER
     {   // tuning build: offset the second workgroup of every CU by about half a workgroup lifetime (lock-step rounds)
@@ -1371,11 +1506,11 @@ __global__ __launch_bounds__(64 * W, (W >= 8 ? 4 : 2)) void lin_outside_strip(Mc
     RH_STAMPO(8);
 }
 
-template __global__ void lin_inside_strip<8, 4, 0>(McBatch, const LinModel*, const double*, int, int, double, int);
-template __global__ void lin_inside_strip<8, 8, 0>(McBatch, const LinModel*, const double*, int, int, double, int);
-template __global__ void lin_inside_strip<8, 8, 1>(McBatch, const LinModel*, const double*, int, int, double, int);
-template __global__ void lin_outside_strip<8, 4, 0>(McBatch, const LinModel*, const double*, int, int, int, int, int*);
-template __global__ void lin_outside_strip<8, 8, 0>(McBatch, const LinModel*, const double*, int, int, int, int, int*);
-template __global__ void lin_outside_strip<8, 8, 1>(McBatch, const LinModel*, const double*, int, int, int, int, int*);
+template __global__ void lin_inside_strip<8, 4, 0>(McBatch, const LinModel*, const double*, int, double, int);
+template __global__ void lin_inside_strip<8, 8, 0>(McBatch, const LinModel*, const double*, int, double, int);
+template __global__ void lin_inside_strip<8, 8, 1>(McBatch, const LinModel*, const double*, int, double, int);
+template __global__ void lin_outside_strip<8, 4, 0>(McBatch, const LinModel*, const double*, int, int, int*);
+template __global__ void lin_outside_strip<8, 8, 0>(McBatch, const LinModel*, const double*, int, int, int*);
+template __global__ void lin_outside_strip<8, 8, 1>(McBatch, const LinModel*, const double*, int, int, int*);
 
 }  // namespace rh

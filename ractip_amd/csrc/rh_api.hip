@@ -129,6 +129,7 @@ const EnvSwitch kEnvSwitches[] = {
     {"RH_SMALL", ENV_FLAG, &Ctx::small_on},
     {"RH_FAR2", ENV_INT, &Ctx::far2},
     {"RH_STRIP_XCD", ENV_INT, &Ctx::strip_xcd},
+    {"RH_F5_PASS", ENV_FLAG, &Ctx::f5_pass},
     {"RH_ACC_WIDE", ENV_INT, &Ctx::acc_wide},
     {"RH_ACC_FINAL_T", ENV_INT, &Ctx::acc_final_t},
     {"RH_CO_WINDOW", ENV_INT, &Ctx::co_window},
