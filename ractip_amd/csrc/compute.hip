@@ -70,7 +70,7 @@ McLinArgs mc_lin_args(const rh_ctx* c, int phase, const McBatch& B, const LinSet
     A.pin = xcd_pin(B.ns);
     A.strip_xcd = c->strip_xcd;
     A.f5_jlo = 32;   // inside_pairs(S, A, 30) ends with F5i[31]
-    A.f5_pass = c->f5_pass && f5_pass_lds(B.ld, 1) <= 64 * 1024;   // (F5 in LDS: up to about 4000 letters; longer batches keep the serial kernels)
+    A.f5_pass = c->f5_pass && f5_pass_fits(B.ld);   // (F5 in LDS: up to about 4300 letters; longer batches keep the serial kernels)
     return A;
 }
 

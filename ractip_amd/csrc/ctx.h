@@ -414,6 +414,7 @@ void far_outside_begin(SweepPass& S, int top);
 void far_outside_before(SweepPass& S, int d);
 std::vector<double> strip_weights(const LinModel& L, bool* ok_out = nullptr);
 size_t f5_pass_lds(int ld, int phase);
+bool f5_pass_fits(int ld);
 // launch_vienna.hip
 int launch_mc_vienna(rh_ctx* c, int pin);
 SweepPlan plan_mc_vlin(const rh_ctx* c, int phase, bool co, int nmax);

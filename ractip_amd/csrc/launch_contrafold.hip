@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "ctx.h"
+#include "f5_stage.h"
 #include "kernels.h"
 
 // log-space path: logZ = F5i[n] (InferenceEngine.ipp:4089-4094)
@@ -210,8 +211,10 @@ static void inside_pairs(const SweepPass& S, const McLinArgs& A, int last)
         far_inside_after(S, d + 2);   // (the first one is due behind diagonal 47)
     }
 }
-// dynamic LDS of the exterior-sum passes (mccaskill_strip.hip): F5 and the partial sums; outside also the parked operands
-size_t f5_pass_lds(int ld, int phase) { return sizeof(double) * ((size_t)ld + 8 + (phase ? (size_t)((ld + 255) / 256) * 256 : 0)); }
+// dynamic LDS of the exterior-sum passes (mccaskill_strip.hip): F5 and the partial sums, outside also the parked operands, and the
+// chunk buffer of staged FCA rows, which shrinks where the rest leaves less than kF5StageRows rows of 64 KB (f5_stage.h)
+size_t f5_pass_lds(int ld, int phase) { return sizeof(double) * (size_t)f5_lds_doubles(ld, phase); }
+bool f5_pass_fits(int ld) { return f5_stage_rows(ld, 1) >= kF5StageRowsMin; }
 
 // diagonals 0..31 by pairs (every row is "near" there), then strips of KD diagonals (mccaskill_strip.hip); the bootstrap leaves
 // F5i[0..31], the rest is one pass behind the last strip (no inside cell reads F5i).  A.f5_pass = 0: the serial kernel instead.

@@ -30,6 +30,7 @@
 
 #include "batch.h"
 #include "dev_util.h"
+#include "f5_stage.h"
 #include "lin_model.h"
 #include "kernels.h"
 
@@ -762,10 +763,35 @@ __global__ __launch_bounds__(256) void lin_f5i_tail(McBatch B, const LinModel* _
 // fetched before its chain starts (none depends on an F5 value), the terms whose F5 operand is final are summed up front, F5 lives in
 // LDS, and a chain step is the at most one term per thread (F5o: threads 0..13, a few dependent FMAs) that needs an entry of the same
 // block, wsum, one barrier and f5_entry, which every thread evaluates for itself.
-constexpr int kF5Blk = 16;
+// The operands of a block are kF5Blk consecutive columns of every table row of a band (f5_stage.h), so they are fetched as row
+// segments, 16 lanes per row, into a chunk buffer in LDS, and the thread that owns a term reads its operands from there: one or two
+// 128-byte lines per 16 lanes, where a thread fetching its own term's operands asks for a line per lane.  The next chunk's loads are
+// in flight while a chunk is summed.
 
-// dynamic LDS: F5i[ld], partial sums [2][4]
-__global__ __launch_bounds__(256) void lin_f5i_pass(McBatch B, const LinModel* __restrict__ L, int jlo)
+// One chunk's staging elements of this thread: entry e = t % 16 of the rows lo + t/16 + 16 i.  `cell` points at the thread's cell of
+// table row 0, `step` is the distance to the same entry one row on, rows up to `last` exist (and are inside the chunk).
+// Straight-line code: an element that does not exist fetches the cell (row 0, column 1), which every sequence of two letters has,
+// and its slot holds that value unread; loads behind per-lane branches would each be waited for before the next is issued.
+__device__ __forceinline__ void f5_stage_issue(const double* __restrict__ fca, const double* __restrict__ cell, ptrdiff_t step, int t, int lo, int last,
+                                               double (&v)[kF5StageLoads])
+{
+#pragma unroll
+    for (int i = 0; i < kF5StageLoads; i++) {
+        const int row = lo + f5_stage_row(t, i);
+        const double* __restrict__ p = cell + row * step;
+        v[i] = *(row <= last ? p : fca + 1);
+    }
+}
+// (R is a multiple of 16, so the instruction i is inside the buffer or outside it)
+__device__ __forceinline__ void f5_stage_store(double* stg, int t, int R, const double (&v)[kF5StageLoads])
+{
+#pragma unroll
+    for (int i = 0; i < kF5StageLoads; i++)
+        if (kF5Blk * i < R) stg[f5_stage_slot(f5_stage_row(t, i), f5_stage_entry(t))] = v[i];
+}
+
+// dynamic LDS: F5i[ld], partial sums [2][4], chunk buffer [f5_stage_rows(ld, 0)][kF5StageStride]
+__global__ __launch_bounds__(256, 4) void lin_f5i_pass(McBatch B, const LinModel* __restrict__ L, int jlo)
 {
     extern __shared__ double f5_lds[];
     const int sq = blockIdx.x;
@@ -773,59 +799,71 @@ __global__ __launch_bounds__(256) void lin_f5i_pass(McBatch B, const LinModel* _
     const int n = B.n[sq], ld = B.ld;
     if (n < jlo) return;   // (a hidden sequence has length 0; shorter ones are complete behind the bootstrap diagonals)
     const int t = threadIdx.x, w = t >> 6, lane = t & 63;
+    const int R = f5_stage_rows(ld, 0);
     double* const f5s = f5_lds;
     double* const red = f5_lds + ld;
+    double* const stg = f5_lds + f5_fixed_doubles(ld, 0);
     double* __restrict__ f5i = B.f5i + (size_t)sq * ld;
     const double* __restrict__ fca = B.tab + (size_t)sq * B.seq_stride + L_FCA * B.tab_stride;
     const double w_eu = L->w_eu, w_ep2 = L->w_ep2;
     for (int k = t; k < jlo; k += 256) f5s[k] = f5i[k];
     __syncthreads();
     double prev = f5s[jlo - 1];
+    double v[kF5StageLoads];
+    // chunk c of block jj0
+    const auto issue = [&](int jj0, int c, double (&v)[kF5StageLoads]) {
+        const int ne = n - jj0 + 1 < kF5Blk ? n - jj0 + 1 : kF5Blk, e = f5_stage_entry(t), dmax = f5i_last_row(jj0, ne, e);
+        const F5Chunk ch = f5i_chunk(jj0 + ne - 3, R, c);
+        f5_stage_issue(fca, fca + f5i_addr(ld, jj0, 0, e), (ptrdiff_t)f5i_addr(ld, jj0, 1, 0) - (ptrdiff_t)f5i_addr(ld, jj0, 0, 0), t, ch.lo, dmax < ch.hi ? dmax : ch.hi, v);
+    };
 #pragma unroll 1
-    for (int jj0 = jlo; jj0 <= n; jj0 += kF5Blk) {
+    for (int jb = jlo; jb <= n; jb += kF5Blk) {
+        const int jj0 = __builtin_amdgcn_readfirstlane(jb);   // (opaque: no induction variable per entry and address across the blocks)
         const int ne = n - jj0 + 1 < kF5Blk ? n - jj0 + 1 : kF5Blk;   // entries jj0 .. jj0+ne-1
-        const int kmax = jj0 + ne - 3;                                 // the last term of the last entry
-        double acc[kF5Blk], opin[kF5Blk];
+        const int top = jj0 + ne - 3;                                  // the row of term 0 of the last entry
+        double acc[kF5Blk];
 #pragma unroll
-        for (int e = 0; e < kF5Blk; e++) { acc[e] = 0.0; opin[e] = 0.0; }
-        int kin = 0x7fffffff;   // this thread's term whose F5i operand is an entry of this block (at most one: k >= jj0), its last
-        // term k of entry jj0+e is FCA[k+1, jj0+e-1] = row jj0+e-2-k, column k+1 of the diagonal-major table; it exists for k <= jj0+e-2
-        // (fetched raw at clamped addresses -- row 0 has a column for every k <= n-2 --; what does not exist is never summed)
-        auto fetch = [&](int k, double (&op)[kF5Blk]) {
-            const int kc = k <= kmax ? k : kmax;
-            const double* __restrict__ col = fca + (kc + 1);
-#pragma unroll
-            for (int e = 0; e < kF5Blk; e++) {
-                const int row = jj0 + (e < ne ? e : 0) - 2 - kc;
-                op[e] = col[(size_t)(row > 0 ? row : 0) * ld];
-            }
-        };
-        auto take = [&](int k, const double (&op)[kF5Blk]) {
-            if (k > kmax) return;
-            if (k < jj0) {
-                const double f = f5s[k];
-#pragma unroll
-                for (int e = 0; e < kF5Blk; e++) acc[e] = (e < ne && (e > 0 || k <= jj0 - 2)) ? f5_term(f, op[e], acc[e]) : acc[e];   // (k = jj0-1 is no term of entry jj0)
-            } else {
-                kin = k;
-#pragma unroll
-                for (int e = 2; e < kF5Blk; e++) opin[e] = op[e];   // (k >= jj0 is a term from entry jj0+2 on)
-            }
-        };
+        for (int e = 0; e < kF5Blk; e++) acc[e] = 0.0;
+        // this thread's term whose F5i operand is an entry of this block (at most one: k >= jj0), its last.  Its operands are in rows
+        // 0 .. 13, which the last chunk leaves in the buffer for the chain.
+        int kin = 0x7fffffff;
+        // term k of entry jj0+e is FCA[k+1, jj0+e-1] = row jj0+e-2-k, column k+1 of the diagonal-major table; it exists for 0 <= k <= jj0+e-2
+        const int nc = f5_chunks(top, R);
+        issue(jj0, 0, v);
 #pragma unroll 1
-        for (int k = t; k <= kmax; k += 512) {   // two terms' operands in flight
-            double opa[kF5Blk], opb[kF5Blk];
-            fetch(k, opa);
-            fetch(k + 256, opb);
-            take(k, opa);
-            take(k + 256, opb);
+        for (int c = 0; c < nc; c++) {   // rows from the top down: ascending k for every entry; the last chunk starts at row 0
+            const F5Chunk ch = f5i_chunk(top, R, c);
+            f5_stage_store(stg, t, R, v);
+            lds_barrier();
+            if (c + 1 < nc) issue(jj0, c + 1, v);
+            // volatile reads, four entries at a time, and selects: behind per-lane branches every entry would wait for its own LDS
+            // round trip.  What does not exist reads slot 0 and F5i[0] and is not summed.
+            lds_vp vstg = (lds_vp)stg, vf5 = (lds_vp)f5s;
+#pragma unroll
+            for (int e0 = 0; e0 < kF5Blk; e0 += 4) {
+                double op[4], f[4];
+                bool ex[4];
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    const int e = e0 + u, k = f5i_owned_term(jj0, ch.hi, e, t), d = f5i_term(jj0, k, e);   // (row and term swap places in the map)
+                    const bool own = e < ne && k >= 0 && d >= ch.lo;
+                    ex[u] = own && k < jj0;
+                    kin = own && k >= jj0 ? k : kin;   // (k >= jj0 is a term from entry jj0+2 on)
+                    op[u] = vstg[f5_stage_slot(own ? d - ch.lo : 0, e)];
+                    f[u] = vf5[ex[u] ? k : 0];
+                }
+#pragma unroll
+                for (int u = 0; u < 4; u++) acc[e0 + u] = ex[u] ? f5_term(f[u], op[u], acc[e0 + u]) : acc[e0 + u];
+                asm volatile("" : "+v"(acc[e0]), "+v"(acc[e0 + 1]), "+v"(acc[e0 + 2]), "+v"(acc[e0 + 3]));   // (the next four reads stay behind these sums: 128 registers, four workgroups per CU)
+            }
+            if (c + 1 < nc) lds_barrier();   // the buffer is rewritten
         }
 #pragma unroll
         for (int e = 0; e < kF5Blk; e++) {
             if (e < ne) {   // (workgroup-uniform)
                 const int jj = jj0 + e;
                 double a = acc[e];
-                if (e >= 2 && kin <= jj - 2) a = f5_term(f5s[kin], opin[e], a);   // F5i[kin] was written two barriers ago at the latest
+                if (e >= 2 && kin <= jj - 2) a = f5_term(f5s[kin], stg[f5_stage_slot(f5i_term(jj0, kin, e), e)], a);   // F5i[kin] was written two barriers ago at the latest
                 a = wsum(a);
                 if (lane == 0) red[(e & 1) * 4 + w] = a;
                 lds_barrier();
@@ -890,10 +928,11 @@ __global__ __launch_bounds__(256) void lin_f5o_head(McBatch B, const LinModel* _
 }
 
 // F5o[n-1 .. 1] before the first outside strip.  Term r = t + 256 q of entry k is F5o[k+2+r] * FCA row r, column k+1: a thread's
-// operands of a block are kF5Blk consecutive doubles of its own row.  The terms that need an entry of the same block are the FIRST
-// of threads 0..13 (r <= 13), so those threads sum such an entry inside the chain, from operands parked in LDS.
-// dynamic LDS: F5o[ld], partial sums [2][4], parked operands [ceil(ld/256)][kF5Blk][16]
-__global__ __launch_bounds__(256) void lin_f5o_pass(McBatch B, const LinModel* __restrict__ L)
+// operands of a block are kF5Blk consecutive doubles of its own row, read from the chunk buffer.  The terms that need an entry of
+// the same block are the FIRST of threads 0..13 (r <= 13), so those threads sum such an entry inside the chain, from operands parked
+// in LDS.
+// dynamic LDS: F5o[ld], partial sums [2][4], parked operands [ceil(ld/256)][14][14], chunk buffer [f5_stage_rows(ld, 1)][kF5StageStride]
+__global__ __launch_bounds__(256, 4) void lin_f5o_pass(McBatch B, const LinModel* __restrict__ L)
 {
     extern __shared__ double f5_lds[];
     const int sq = blockIdx.x;
@@ -901,43 +940,70 @@ __global__ __launch_bounds__(256) void lin_f5o_pass(McBatch B, const LinModel* _
     const int n = B.n[sq], ld = B.ld;
     if (n < 2) return;   // (hidden, or F5o[n] alone: lin_init's)
     const int t = threadIdx.x, w = t >> 6, lane = t & 63;
+    const int R = f5_stage_rows(ld, 1);
     double* const f5s = f5_lds;
     double* const red = f5_lds + ld;
     double* const park = red + 8;
+    double* const stg = f5_lds + f5_fixed_doubles(ld, 1);
     const double* __restrict__ fca = B.tab + (size_t)sq * B.seq_stride + L_FCA * B.tab_stride;
     double* __restrict__ f5o = B.f5o + (size_t)sq * ld;
     const double w_eu = L->w_eu, w_ep2 = L->w_ep2;
     double prev = f5o[n];
     if (t == 0) f5s[n] = prev;
     __syncthreads();
+    double v[kF5StageLoads];
+    // chunk c of block k0
+    const auto issue = [&](int k0, int c, double (&v)[kF5StageLoads]) {
+        const int ne = k0 < kF5Blk ? k0 : kF5Blk, e = f5_stage_entry(t), rlast = f5o_last_row(n, k0, ne, e);
+        const F5Chunk ch = f5o_chunk(n - 2 - (k0 - ne + 1), R, c);
+        f5_stage_issue(fca, fca + f5o_addr(ld, k0, 0, e), ld, t, ch.lo, rlast < ch.hi ? rlast : ch.hi, v);
+    };
 #pragma unroll 1
-    for (int k0 = n - 1; k0 >= 1; k0 -= kF5Blk) {
+    for (int kb = n - 1; kb >= 1; kb -= kF5Blk) {
+        const int k0 = __builtin_amdgcn_readfirstlane(kb);   // (opaque: no induction variable per entry and address across the blocks)
         const int ne = k0 < kF5Blk ? k0 : kF5Blk;   // entries k0, k0-1, .., k0-ne+1 >= 1
         const int rmax = n - 2 - (k0 - ne + 1);     // the last term of the last entry
         double acc[kF5Blk];
 #pragma unroll
         for (int e = 0; e < kF5Blk; e++) acc[e] = 0.0;
-        // (fetched raw at clamped addresses; what does not exist is never summed)
-        auto fetch = [&](int r, double (&op)[kF5Blk]) {
-            const double* __restrict__ row = fca + (size_t)(r <= rmax ? r : 0) * ld;
-#pragma unroll
-            for (int e = 0; e < kF5Blk; e++) op[e] = row[k0 - (e < ne ? e : 0) + 1];
-        };
-        auto take = [&](int q, int r, const double (&op)[kF5Blk]) {
-            if (r > rmax) return;
-#pragma unroll
-            for (int e = 0; e < kF5Blk; e++) {
-                if (e >= 2 && t <= e - 2) park[(q * kF5Blk + e) * 16 + t] = op[e];   // this thread sums entry e in the chain
-                else if (e < ne && k0 - e + 2 + r <= n) acc[e] = f5_term(f5s[k0 - e + 2 + r], op[e], acc[e]);
-            }
-        };
+        const auto exists = [&](int r, int e) { return r <= f5o_last_row(n, k0, ne, e); };
+        const int nc = f5_chunks(rmax, R);
+        issue(k0, 0, v);
 #pragma unroll 1
-        for (int q = 0; t + 256 * q <= rmax; q += 2) {   // two terms' operands in flight
-            double opa[kF5Blk], opb[kF5Blk];
-            fetch(t + 256 * q, opa);
-            fetch(t + 256 * q + 256, opb);
-            take(q, t + 256 * q, opa);
-            take(q + 1, t + 256 * q + 256, opb);
+        for (int c = 0; c < nc; c++) {   // rows from 0 up: ascending q for every thread
+            const F5Chunk ch = f5o_chunk(rmax, R, c);
+            f5_stage_store(stg, t, R, v);
+            lds_barrier();
+            if (c + 1 < nc) issue(k0, c + 1, v);
+            const int r = f5o_owned_row(ch.lo, t), q = r >> 8;
+            if (r <= ch.hi) {
+                // volatile reads, four entries at a time, and selects: behind per-lane branches every entry would wait for its own LDS
+                // round trip.  What does not exist reads its unread slot and F5o[n] and is not summed.
+                const double* const row = stg + f5_stage_slot(r - ch.lo, 0);
+                lds_vp vrow = (lds_vp)row, vf5 = (lds_vp)f5s;
+#pragma unroll
+                for (int e0 = 0; e0 < kF5Blk; e0 += 4) {
+                    double op[4], f[4];
+#pragma unroll
+                    for (int u = 0; u < 4; u++) {
+                        const int jj = k0 - (e0 + u) + 2 + r;
+                        op[u] = vrow[e0 + u];
+                        f[u] = vf5[jj <= n ? jj : n];
+                    }
+#pragma unroll
+                    for (int u = 0; u < 4; u++) {
+                        const int e = e0 + u;
+                        acc[e] = (exists(r, e) && !(e >= 2 && t <= e - 2)) ? f5_term(f[u], op[u], acc[e]) : acc[e];
+                    }
+                    asm volatile("" : "+v"(acc[e0]), "+v"(acc[e0 + 1]), "+v"(acc[e0 + 2]), "+v"(acc[e0 + 3]));   // (the next four reads stay behind these sums: 128 registers, four workgroups per CU)
+                }
+                if (t < kF5ParkT) {   // this thread sums entry e >= t+2 in the chain
+#pragma unroll
+                    for (int e = 2; e < kF5Blk; e++)
+                        if (t <= e - 2 && exists(r, e)) park[f5_park_slot(q, e, t)] = row[e];
+                }
+            }
+            lds_barrier();   // the buffer is rewritten
         }
 #pragma unroll
         for (int e = 0; e < kF5Blk; e++) {
@@ -946,7 +1012,7 @@ __global__ __launch_bounds__(256) void lin_f5o_pass(McBatch B, const LinModel* _
                 double a = acc[e];
                 if (e >= 2 && t <= e - 2) {   // F5o[k+2+t] is the entry of step e-2-t: written two barriers ago at the latest
                     a = 0.0;
-                    for (int q = 0; k + 2 + t + 256 * q <= n; q++) a = f5_term(f5s[k + 2 + t + 256 * q], park[(q * kF5Blk + e) * 16 + t], a);
+                    for (int q = 0; k + 2 + t + 256 * q <= n; q++) a = f5_term(f5s[k + 2 + t + 256 * q], park[f5_park_slot(q, e, t)], a);
                 }
                 a = wsum(a);
                 if (lane == 0) red[(e & 1) * 4 + w] = a;
