@@ -82,7 +82,11 @@ const char* rh_last_error(const rh_ctx* ctx);
 int rh_set_mode(rh_ctx* ctx, int mode);
 /* path taken by the last compute: 1 = linear, 2 = log-space, 3 = linear, then log-space fallback */
 int rh_last_path(const rh_ctx* ctx);
-/* the same for the sweeps that produced hp (duplex or two-molecule ensemble) */
+/* the same for the sweeps that produced hp (duplex or two-molecule ensemble); 3 also where these sweeps left the double range on
+ * the default scale exponent and another exponent on the linear kernels held them: CONTRAfold duplex pairs (rh_batch_fallbacks
+ * which = 3), and a Vienna-BL two-molecule ensemble that leaves the range while every single fold of the batch stays inside (two
+ * 1000-nt molecules with little structure: Z~ of each is 1e-114, Z~ of the pair 1e-220).  Two-molecule sweeps that only follow a
+ * flagged fold to another exponent keep reporting 1. */
 int rh_last_hybrid_path(const rh_ctx* ctx);
 /* Arithmetic path of the pf_duplex sweeps alone: the sweeps that produce hp under RH_HYBRID_DUPLEX (rh_duplex, the batched
  * form, the pf_duplex shim), either model, either semantics, independently of the McCaskill sweeps.  RH_MODE_INHERIT

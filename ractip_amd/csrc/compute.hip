@@ -437,19 +437,23 @@ int compute(rh_ctx* c)
     // (An attempt that failed leaves Inf / NaN in the tables of the flagged sequences; the next attempt runs over them without a clear.
     //  That is sound because the vlin kernels mask every operand by SELECT (`ok ? x : 0.0`), never by a multiplication with 0, and
     //  rewrite every interior cell they read before reading it -- the invariant `tests: test_vienna_bl_scale_exponent_ladder` and
-    //  tools/fuzz_ladder.py exercise: chains of hairpins that overflow the first exponent, results equal to the log-space path's.)
+    //  tools/fuzz_ladder.py exercise: chains of hairpins that overflow the first exponent, results equal to the log-space path's.
+    //  An attempt that UNDERFLOWED leaves zeros and denormals instead; tests/test_gpu_vanishing.py runs 0.7 and 1.8 over those before
+    //  s = 0 holds the batch, against the oracle.)
     int rc = RH_OK;
     // (the helper recomputes whole pairs and copies their folds back into the pairs' own rows: an indexed batch, whose fold rows are
     //  shared between pairs, runs the whole batch again instead)
     const bool per_pair = !c->is_helper && c->pair_helper && c->has_dx && c->np >= 4 && !c->mc.allow && !c->co.allow && !c->indexed;
     const auto sort_unique = [](std::vector<int>& v) { std::sort(v.begin(), v.end()); v.erase(std::unique(v.begin(), v.end()), v.end()); };
     std::vector<int> flagged_seqs;   // by the deferred attempts so far
+    bool pairs_alone = false;        // the first attempt flagged two-molecule sweeps and no fold: the joint ensemble left the range by itself
     for (size_t a = 0; a < order.size(); a++) {
         if ((rc = select_vlin(c, order[a]))) break;
         Attempt at;
         at.defer_log = a + 1 < order.size();
         if ((rc = run_attempt(c, &at))) break;
         flagged_seqs.insert(flagged_seqs.end(), at.flagged_seqs.begin(), at.flagged_seqs.end());
+        if (a == 0) pairs_alone = at.deferred && at.flagged_seqs.empty() && !at.flagged_pairs.empty() && c->hybrid == RH_HYBRID_COFOLD;
         if (at.deferred && a == 0 && per_pair) {
             sort_unique(at.flagged_pairs);
             // cost: the helper pays the launch latency of a few pairs (tens of ms per attempt at n = 500 - 1000, whatever the batch), a
@@ -464,6 +468,9 @@ int compute(rh_ctx* c)
         if (!at.deferred) {
             if (a > 0) {   // held by another exponent
                 c->last_path = 3;
+                // two-molecule sweeps that vanished (or overflowed) while every fold stayed inside, held by this exponent: the hybrid
+                // path says so as the path of the folds does (sweeps that only followed a flagged fold keep reporting 1)
+                if (pairs_alone && c->last_dx_path == 1) c->last_dx_path = 3;
                 sort_unique(flagged_seqs);
                 if (!at.went_log) {   // (the last attempt may still have ended in log space)
                     c->rescaled_mc = flagged_seqs;

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""tools/fuzz_ladder.py [seconds] [seed]: random streams of batches that mix ordinary sequences with chains of stable hairpins (outside the
-double range of the default scale exponent), both models, ragged lengths, on ONE context per model (so that the remembered exponent
-moves back and forth); every batch is compared with a context that has the ladder switched off (log-space fallback)."""
+"""tools/fuzz_ladder.py [seconds] [seed]: random streams of batches that mix ordinary sequences with chains of stable hairpins (Z~ above
+the double range of the default scale exponent) and with structured inserts in long poly-A flanks (Z~ below it: the ladders' downward
+rungs), both models, ragged lengths, on ONE context per model (so that the remembered exponent moves back and forth); every batch is
+compared with a context that has the ladder switched off (log-space fallback)."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -19,6 +20,13 @@ def hairpins(n, k):
         stem = "".join(rng.choice(list("GC"), size=k))
         s += stem + "AAAA" + "".join(comp[ch] for ch in reversed(stem)) + "A" * int(rng.integers(1, 5))
     return s[:n]
+
+def flanked(n, k):
+    """k letters over {A, C, G} (only G-C pairs form) somewhere inside n - k letters A, which have no partner: log Z stays that of the
+    insert while the scaled Z~ falls with n (tests/_vanishing_cases.py)"""
+    k = min(k, n)
+    f5 = int(rng.integers(0, n - k + 1))
+    return "A" * f5 + "".join(rng.choice(list("ACG"), size=k)) + "A" * (n - k - f5)
 
 def rnd(n):
     return "".join(rng.choice(list("ACGU"), size=n))
@@ -38,7 +46,10 @@ while time.time() - t0 < budget:
     npairs = int(rng.integers(1, 9))
     frac = rng.choice([0.0, 0.2, 0.6, 1.0])
     top = 1500 if model == "cf" else 1000
+    low = float(rng.choice([0.0, 0.0, 0.3]))   # share of flanked inserts, up to lengths at which Z~ vanishes (cf: n > 3800, vi: n > 1800)
     def one():
+        if rng.random() < low:
+            return flanked(int(rng.integers(top, 4200 if model == "cf" else 2100)), int(rng.integers(40, 100)))
         n = int(rng.integers(40, top))
         return hairpins(n, int(rng.integers(7, 12))) if rng.random() < frac else rnd(n)
     pairs = [(one(), one()) for _ in range(npairs)]
