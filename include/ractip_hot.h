@@ -187,8 +187,8 @@ int rh_batch_upload_constrained(rh_ctx* ctx, int npairs,
  * Every sequence is folded once (bp, up, log Z); every pair gets its hp.  A sequence may be used by any number of pairs, in
  * either role, or by none (it is folded all the same).  A 32 x 32 cross product is 1024 pairs over 64 folds, and its McCaskill
  * tables are those of 64 sequences; under RH_HYBRID_COFOLD the N + M folds seed the N x M two-molecule sweeps.
- * Both models; under RH_MODEL_VIENNA_BL both rh_set_hybrid sources.  Structure constraints on an indexed batch are not supported
- * (there is no _constrained form).
+ * Both models; under RH_MODEL_VIENNA_BL both rh_set_hybrid sources.  Structure constraints on an indexed batch:
+ * rh_batch_upload_indexed_constrained below.
  * An index outside [0, nseq), npairs < 1, nseq < 1, a NULL sequence or a length < 1 is RH_ERR_ARG.  All arguments are checked before
  * anything is staged: a rejected upload leaves the previous batch in place, as rh_batch_upload_constrained does.
  * rh_batch_upload IS the indexed upload with the identity index (nseq = 2*npairs, first[p] = 2p, second[p] = 2p+1), bit for bit:
@@ -202,9 +202,34 @@ int rh_batch_upload_constrained(rh_ctx* ctx, int npairs,
  *   per distinct sequence: rh_batch_layout, rh_batch_results_all and rh_batch_device_views describe bp [nseq][tri_stride],
  *     up [nseq][up_ld] and hp [npairs][hp_stride]; rh_batch_fallbacks which = 0 / 2 lists distinct-sequence indices, each once,
  *     which = 1 / 3 pair indices.  A sequence that leaves the double range flags every pair that references it.
- *   rh_debug_batch_allow_mask returns 1 (an indexed batch has no mask). */
+ *   rh_debug_batch_allow_mask: which = 0, k = distinct sequence k; which = 1, k = pair k.  It returns 1 when that mask does not
+ *     exist: always after rh_batch_upload_indexed, which takes no constraint. */
 int rh_batch_upload_indexed(rh_ctx* ctx, int nseq, const char* const* seqs, const int* lens,
                             int npairs, const int* first, const int* second);
+/* rh_batch_upload_indexed under structure constraints, given once per distinct sequence.  RH_MODEL_VIENNA_BL only: any other model
+ * with at least one non-NULL constraint is RH_ERR_UNSUPPORTED.
+ *   cons[k]: the constraint of the fold of sequence k, in the fold_constrained alphabet of rh_bpp.  The sequence is folded once,
+ *     under it; every pair that uses k reads that fold.
+ *   co_first[k], co_second[k]: sequence k's share of a joint constraint when it is s1 / s2 of a pair.  The joint constraint of
+ *     pair p is pad(co_first[first[p]], n1) + pad(co_second[second[p]], n2), pad cutting a string at the sequence's length and
+ *     filling it with '.', and means what co_cons[p] means to rh_batch_upload_constrained.  RactIP's translation (src/ractip.cpp:
+ *     409-440) writes '(' for '[' in the share of s1, ')' for ']' in the share of s2 and 'x' for letters paired inside their own
+ *     molecule; the whole alphabet is accepted: brackets matched inside one share stay pairs inside that molecule, and a '(' the
+ *     first share leaves open pairs with a ')' the second share leaves open, the last one open with the first one closing.  Under
+ *     RH_HYBRID_DUPLEX the shares are checked and otherwise unused, as co_cons is.
+ * Any of the three arrays, and any entry, may be NULL (no constraint).  With no constraint at all this IS rh_batch_upload_indexed:
+ * the same bits, no masks, the two-molecule sweeps seeded from the folds.  With masks the sweeps are not seeded.
+ * Everything is checked before anything is staged (RH_ERR_ARG; the previous batch stays in place): indices, lengths and sequences
+ * as rh_batch_upload_indexed does; a fold constraint as "sequence k: ..." with the text of rh_batch_upload_constrained; a joint
+ * constraint as "pair p: ..." for the first pair p whose string is unbalanced -- a ')' left open in the share of s1, a '(' in the
+ * share of s2, or different numbers left open by the two -- or forces a pair of non-complementary letters, inside a share or
+ * across the cut.  A share that no pair uses in its role is not reported.
+ * The fold masks come from one host pass per distinct sequence; the joint masks are composed on the device from one host pass per
+ * distinct sequence and role, the host's work per pair being O(open brackets).  Everything downstream works as on any indexed
+ * batch. */
+int rh_batch_upload_indexed_constrained(rh_ctx* ctx, int nseq, const char* const* seqs, const int* lens,
+                                        int npairs, const int* first, const int* second,
+                                        const char* const* cons, const char* const* co_first, const char* const* co_second);
 /* The index of the last upload (any pointer may be NULL; first / second hold npairs entries); for a plain rh_batch_upload:
  * nseq = 2*npairs, first[p] = 2p, second[p] = 2p+1. */
 int rh_batch_index(rh_ctx* ctx, int* nseq, int* npairs, int* first, int* second);
@@ -317,8 +342,8 @@ int rh_debug_vienna_cell(const char* param_file, int table, int i, int j, int k,
 int rh_debug_vienna_value(const char* defaults_file, int use_bl_param, const char* bl_path, const char* param_file, int semantics,
                           int table, int i, int j, int k, int l, double* out);
 
-/* The allowed-pair mask of the last upload as the kernels read it: which = 0, sequence k (2p = s1 of pair p), or which = 1, the
- * concatenation s1+s2 of pair k.  *ld receives the row pitch; out (or NULL, to ask for ld first) receives ld*ld bytes, byte
+/* The allowed-pair mask of the last upload as the kernels read it: which = 0, sequence k (2p = s1 of pair p; of an indexed batch:
+ * distinct sequence k), or which = 1, the concatenation s1+s2 of pair k.  *ld receives the row pitch; out (or NULL, to ask for ld first) receives ld*ld bytes, byte
  * [a*ld + b] != 0 iff letters a < b (1-based) may pair.  Returns 0, 1 if that batch has no mask, or an error. */
 int rh_debug_batch_allow_mask(rh_ctx* ctx, int which, int k, unsigned char* out, int* ld);
 

@@ -5,4 +5,4 @@ include/ractip_hot.h), host/ (C++ mirror of the RactIP::contrafold /
 contraduplex / rnaduplex call surface), hot.py (ctypes binding used by tests and
 bench.py) and data/ (the CONTRAfold weights).
 """
-from .hot import Context, RhError, index_pairs, load_library, tri_offset, tri_size  # noqa: F401
+from .hot import Context, RhError, index_pairs, index_pairs_structured, load_library, tri_offset, tri_size  # noqa: F401

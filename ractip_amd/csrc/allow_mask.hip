@@ -8,6 +8,10 @@
 // enc in LDS once (they are indexed by row and by column), then writes the 16-byte-aligned part of [lo, hi) with one 16-byte
 // store per lane and the few bytes in front of and behind it one by one: ld is even but no multiple of 16, so neither rows nor
 // sequences start on a 16-byte boundary, and every byte is decoded to its own (row, column).
+//
+// An indexed batch gives the joint constraint of a pair as two shares, one per distinct sequence and role: joint_cons_gather (below)
+// composes the three values per letter of every pair on the device, in the rows the host pass would have filled, and the same
+// allow_mask_build writes the masks from them.
 #include <hip/hip_runtime.h>
 
 #include "constraint_prepass.h"
@@ -67,6 +71,27 @@ __global__ __launch_bounds__(kAllowThreads) void allow_mask_build(uint8_t* __res
         }
         *reinterpret_cast<uint4*>(allow + f) = make_uint4(w[0], w[1], w[2], w[3]);
     }
+}
+
+// The joint constraints of an indexed batch: one workgroup per pair writes the pair's row of ch / P / enc, every entry of 0 ..
+// co_lds - 1 (the '.' / 0 / 0 of letter 0 and of the padding included: the buffer is reused across batches), from the two shares
+// the index names; allow_mask_build then turns the rows into the masks as it does for rows that came from the host.  Each thread
+// reads its own letter of one share once, consecutive threads consecutive letters, and at an open bracket one entry of the partner's
+// short open list: nothing is read twice, so the shares are not staged in LDS, and shares of any length take this one path.
+// The host has checked that both shares of every pair leave the same number of brackets open (joint_pair_check), which keeps the
+// reads of the open lists inside them.
+__global__ __launch_bounds__(kJointGatherThreads) void joint_cons_gather(JointShares S, uint8_t* __restrict__ ch, int* __restrict__ P,
+                                                                         int* __restrict__ enc)
+{
+    const int p = blockIdx.x;
+    const int a = S.idx[2 * p], b = S.ns + S.idx[2 * p + 1];   // the shares: sequence idx[2p] as s1, sequence idx[2p+1] as s2
+    const int n = S.con[p], n1 = S.con[S.np + p];
+    const int m = S.open_off[a + 1] - S.open_off[a];
+    const host::ShareRef A{S.ch + (size_t)a * S.lds, S.P + (size_t)a * S.lds, S.enc + (size_t)a * S.lds, S.open_pos + S.open_off[a]};
+    const host::ShareRef B{S.ch + (size_t)b * S.lds, S.P + (size_t)b * S.lds, S.enc + (size_t)b * S.lds, S.open_pos + S.open_off[b]};
+    const size_t row = (size_t)p * S.co_lds;
+    for (int j = threadIdx.x; j < S.co_lds; j += kJointGatherThreads)
+        host::compose_joint_letter(j, n1, n - n1, m, A, B, &ch[row + j], &P[row + j], &enc[row + j]);
 }
 
 }  // namespace rh

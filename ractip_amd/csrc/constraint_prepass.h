@@ -9,9 +9,11 @@
 //   P[k]    the forced partner of a matched bracket, 0 if none
 //   enc[k]  the opening letter of the innermost matched bracket pair that strictly encloses k, 0 if none
 // allow_pair below is the one statement of the rule: the kernel evaluates it per byte.
+// Second half of this file: the same three values for a joint string that is given as two shares (indexed batches).
 #pragma once
 #include <cstdint>
 #include <string>
+#include <vector>
 
 #if defined(__HIPCC__)
 #define RH_HOST_DEVICE __host__ __device__
@@ -37,5 +39,60 @@ uint8_t vienna_code(char ch);   // ViennaRNA encode_char with energy_set 0: A,C,
 // Fills ch / P / enc at 1..n (the caller presets '.' / 0 / 0 everywhere else).  cons may be shorter or longer than n.
 // Returns false for unbalanced brackets or a forced pair of non-complementary letters, with the reason in *why.
 bool constraint_prepass(const char* seq, int n, const char* cons, uint8_t* ch, int* P, int* enc, std::string* why);
+
+// ---- joint constraints by shares (indexed batches: rh_batch_upload_indexed_constrained)
+//
+// The joint constraint of a pair is first share (over s1, cut at n1, filled with '.') + second share (over s2).  A share is passed
+// once per distinct sequence and role, without knowing the partner; compose_joint_letter puts two shares together into the ch / P /
+// enc that constraint_prepass leaves for the materialised joint string, letter by letter, so the masks of all pairs are built on the
+// device from the shares of the distinct sequences (joint_cons_gather, allow_mask.hip).
+//
+// Open brackets of a share: a '(' of a first share without a ')' in it, a ')' of a second share without a '(' in it.  In the joint
+// string the open '(' are still on the stack when s2 begins, and every open ')' pops the innermost of them: the r-th open ')' from
+// the left pairs with the r-th open '(' from the right.  A first share must not leave a ')' open nor a second share a '(', and both
+// must leave the same number open (the joint string is unbalanced otherwise).
+//
+// Per letter k = 1..n of a share (the caller presets '.' / 0 / 0 elsewhere):
+//   ch[k]   the constraint character
+//   P[k]    > 0: the partner of a bracket matched inside the share (a position of the share);
+//           < 0: an open bracket, -P[k] = its place among the share's open brackets counted from the left (1 = leftmost); 0: no bracket
+//   enc[k]  > 0: the innermost bracket of the share that strictly encloses k -- a matched one or, first share, an open '(';
+//           < 0: second share, no bracket of the share encloses k: -enc[k] = the place (as above) of the next open ')' to the right of
+//                k, whose partner in the first share encloses k in the joint string;  0: nothing encloses k
+// open[]: the positions of the share's open brackets, ascending.
+struct ShareRef {
+    const uint8_t* ch;
+    const int* P;
+    const int* enc;
+    const int* open;
+};
+
+// ch / P / enc of letter j of the joint string of n1 + n2 letters, from the first share A (of s1) and the second share B (of s2),
+// which both leave m brackets open.  Outside 1..n1+n2: '.' / 0 / 0.  The kernel and the CPU check both call this.
+RH_HOST_DEVICE inline void compose_joint_letter(int j, int n1, int n2, int m, const ShareRef& A, const ShareRef& B, uint8_t* ch, int* P, int* enc)
+{
+    if (j < 1 || j > n1 + n2) { *ch = '.'; *P = 0; *enc = 0; return; }
+    if (j <= n1) {
+        const int p = A.P[j];
+        *ch = A.ch[j];
+        *P = p >= 0 ? p : n1 + B.open[m + p];   // open '(' number -p from the left = number m + p + 1 from the right: that open ')' of s2
+        *enc = A.enc[j];
+        return;
+    }
+    const int k = j - n1, p = B.P[k], e = B.enc[k];
+    *ch = B.ch[k];
+    *P = p > 0 ? n1 + p : p < 0 ? A.open[m + p] : 0;
+    *enc = e > 0 ? n1 + e : e < 0 ? A.open[m + e] : 0;
+}
+
+// role 0: `share` as the first share of a joint constraint over seq, role 1: as the second.  Fills ch / P / enc at 1..n and appends
+// the open positions to *open.  share may be nullptr (all '.'), shorter or longer than n.  Returns false, with the reason in *why,
+// for a share no joint string can hold in that role (a ')' left open in a first share, a '(' in a second) and for a forced pair of
+// non-complementary letters inside the share.
+bool share_prepass(const char* seq, int n, const char* share, int role, uint8_t* ch, int* P, int* enc, std::vector<int>* open, std::string* why);
+
+// What of a joint constraint only the pair shows: the two shares leave the same number of brackets open (m1 open '(' of s1 at open1,
+// m2 open ')' of s2 at open2) and the pairs they force across the cut are of complementary letters.  O(open brackets).
+bool joint_pair_check(const char* s1, const int* open1, int m1, const char* s2, const int* open2, int m2, std::string* why);
 
 }  // namespace rh::host

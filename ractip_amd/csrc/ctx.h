@@ -315,6 +315,7 @@ struct Ctx {   // (the fields of rh_ctx, below)
     DevBuf d_allow;   // structure-constraint masks [ns][ld*ld] bytes (Vienna-BL, optional)
     DevBuf d_coallow;   // the same for the s1+s2 batch
     DevBuf d_cons;    // per-letter values of the constraint strings the masks are built from: P, enc [count][lds] ints, ch [count][lds] bytes
+    DevBuf d_share;   // indexed batch under joint constraints: the shares of the distinct sequences in both roles (JointShares, kernels.h)
     DevBuf d_hplen;   // lam^d x hairpin length weight, d = 0..nmax (linear Vienna path)
     std::vector<double> h_hplen;
     // two-molecule (co_pf_fold) form of the hybridization matrix: one concatenated sequence s1+s2 per pair
@@ -370,7 +371,8 @@ int fail(rh_ctx* c, int code, const char* fmt, ...);
 int ensure(rh_ctx* c, DevBuf& buf, size_t bytes, bool zero);
 // staging.hip
 int stage(rh_ctx* c, int ns, const char* const* seqs, const int* lens, bool with_mc, bool with_dx, const char* const* cons = nullptr,
-          const char* const* co_cons = nullptr, int npairs = 0, const int* first = nullptr, const int* second = nullptr);
+          const char* const* co_cons = nullptr, int npairs = 0, const int* first = nullptr, const int* second = nullptr,
+          const char* const* co_first = nullptr, const char* const* co_second = nullptr);
 // sequence of the fold batch that is strand `side` (0: s1, 1: s2) of pair p: the one place that knows how pairs map to sequences
 inline int seq_of(const Ctx* c, int p, int side) { return c->pair_seq[2 * (size_t)p + side]; }
 // the pairs that use sequence k, appended to *pairs (a flagged sequence flags every pair that references it)

@@ -83,6 +83,21 @@ __global__ void mcv_extract_hp(McBatch B, double* __restrict__ hp, size_t hp_str
 constexpr int kAllowRows = 64, kAllowThreads = 256;
 __global__ void allow_mask_build(uint8_t* __restrict__ allow, const int* __restrict__ n_of, const uint8_t* __restrict__ g_ch,
                                  const int* __restrict__ g_P, const int* __restrict__ g_enc, int ld, int lds, int in_lds);
+// allow_mask.hip: the per-letter values of the joint constraints of an indexed batch, [np][co_lds] each as allow_mask_build reads
+// them, composed from the shares of the distinct sequences (constraint_prepass.h: share_prepass, compose_joint_letter); grid (np),
+// kJointGatherThreads threads.  Pair p = first share of sequence idx[2p] + second share of sequence idx[2p+1].
+struct JointShares {
+    const uint8_t* ch;     // [2][ns][lds]: role 0 = the sequence's share as s1, role 1 = as s2
+    const int* P;          // [2][ns][lds]
+    const int* enc;        // [2][ns][lds]
+    const int* open_off;   // [2 ns + 1]: share role * ns + k owns open_pos[open_off[.] .. open_off[. + 1])
+    const int* open_pos;   // positions of the open brackets, ascending per share
+    const int* idx;        // [2 np]
+    const int* con;        // [2][np]: joint lengths, cuts (pair_gather)
+    int ns, np, lds, co_lds;
+};
+constexpr int kJointGatherThreads = 256;
+__global__ void joint_cons_gather(JointShares S, uint8_t* __restrict__ ch, int* __restrict__ P, int* __restrict__ enc);
 // pair_index.hip: the pair-major image of an upload, built from the distinct sequences and the index (pair p = sequences
 // idx[2p], idx[2p+1]); grid (np, 2), kPairGatherThreads threads
 struct PairImage {

@@ -371,6 +371,22 @@ int rh_batch_upload_indexed(rh_ctx* c, int nseq, const char* const* seqs, const 
     return stage(c, nseq, seqs, lens, true, true, nullptr, nullptr, npairs, first, second);   // (checks every index before it changes the context)
 }
 
+int rh_batch_upload_indexed_constrained(rh_ctx* c, int nseq, const char* const* seqs, const int* lens, int npairs, const int* first, const int* second,
+                                        const char* const* cons, const char* const* co_first, const char* const* co_second)
+{
+    if (!c) return RH_ERR_ARG;
+    if (nseq < 1 || npairs < 1 || !seqs || !lens || !first || !second) return fail(c, RH_ERR_ARG, "bad indexed batch");
+    const char* const* arrays[3] = {cons, co_first, co_second};
+    for (auto& a : arrays) {   // an array whose entries are all NULL is no constraint: the batch of rh_batch_upload_indexed
+        bool any = false;
+        for (int k = 0; a && k < nseq; k++) any = any || a[k];
+        if (!any) a = nullptr;
+    }
+    if ((arrays[0] || arrays[1] || arrays[2]) && c->model != RH_MODEL_VIENNA_BL)
+        return fail(c, RH_ERR_UNSUPPORTED, "structure constraints apply to the Vienna-BL model only (RactIP::contrafold takes none)");
+    return stage(c, nseq, seqs, lens, true, true, arrays[0], nullptr, npairs, first, second, arrays[1], arrays[2]);
+}
+
 int rh_batch_index(rh_ctx* c, int* nseq, int* npairs, int* first, int* second)
 {
     if (!c) return RH_ERR_ARG;

@@ -21,9 +21,20 @@ struct ConsPass {
     ConsPass(int count, int lds) : ch((size_t)count * lds, '.'), P((size_t)count * lds, 0), enc((size_t)count * lds, 0) {}
 };
 
-// The masks [count][ld][ld] of one batch, built on the device from the host pass: three small asynchronous copies and one launch on
-// s_mc, in front of the sweeps.  d_n: the lengths on the device.  The kernel writes every byte of the image.
-static int build_allow_masks(rh_ctx* c, const ConsPass& H, int count, int ld, int lds, const int* d_n, DevBuf& d_mask)
+// The shares of the ns distinct sequences of an indexed batch in both roles (share_prepass; share role * ns + k), the open brackets
+// of each, and why a share cannot stand in its role ("" = it can): O(letters of the distinct sequences), whatever the pairs.
+struct SharePass {
+    ConsPass L;
+    std::vector<int> off, pos;
+    std::vector<std::string> why;
+    SharePass(int ns, int lds) : L(2 * ns, lds), off(1, 0), why(2 * (size_t)ns) {}
+};
+
+// The masks [count][ld][ld] of one batch, built on the device from the per-letter values [count][lds]: H, the host pass over the
+// batch's own strings (three small asynchronous copies), or, H == nullptr, the rows joint_cons_gather composes from the shares S of
+// an indexed batch; then one launch on s_mc, in front of the sweeps.  d_n: the lengths on the device.  The kernel writes every
+// byte of the image.
+static int build_allow_masks(rh_ctx* c, const ConsPass* H, const JointShares* S, int count, int ld, int lds, const int* d_n, DevBuf& d_mask)
 {
     int rc;
     const size_t cells = (size_t)count * lds;
@@ -32,9 +43,14 @@ static int build_allow_masks(rh_ctx* c, const ConsPass& H, int count, int ld, in
     int* d_P = c->d_cons.as<int>();
     int* d_enc = d_P + cells;
     uint8_t* d_ch = reinterpret_cast<uint8_t*>(d_enc + cells);
-    HIP_TRY(c, hipMemcpyAsync(d_P, H.P.data(), cells * sizeof(int), hipMemcpyHostToDevice, c->s_mc));
-    HIP_TRY(c, hipMemcpyAsync(d_enc, H.enc.data(), cells * sizeof(int), hipMemcpyHostToDevice, c->s_mc));
-    HIP_TRY(c, hipMemcpyAsync(d_ch, H.ch.data(), cells, hipMemcpyHostToDevice, c->s_mc));
+    if (H) {
+        HIP_TRY(c, hipMemcpyAsync(d_P, H->P.data(), cells * sizeof(int), hipMemcpyHostToDevice, c->s_mc));
+        HIP_TRY(c, hipMemcpyAsync(d_enc, H->enc.data(), cells * sizeof(int), hipMemcpyHostToDevice, c->s_mc));
+        HIP_TRY(c, hipMemcpyAsync(d_ch, H->ch.data(), cells, hipMemcpyHostToDevice, c->s_mc));
+    } else {
+        hipLaunchKernelGGL(joint_cons_gather, dim3(count), dim3(kJointGatherThreads), 0, c->s_mc, *S, d_ch, d_P, d_enc);
+        HIP_TRY(c, hipGetLastError());
+    }
     const size_t lds_bytes = (size_t)lds * (2 * sizeof(int) + 1);
     const int in_lds = lds_bytes <= 64 * 1024;   // longer sequences: the kernel reads the three arrays from global memory
     hipLaunchKernelGGL(allow_mask_build, dim3(count, (ld + kAllowRows - 1) / kAllowRows), dim3(kAllowThreads), in_lds ? lds_bytes : 0, c->s_mc,
@@ -47,9 +63,11 @@ static int build_allow_masks(rh_ctx* c, const ConsPass& H, int count, int ld, in
 // Stage `ns` sequences; with_dx: pair p is (first[p], second[p]) of them, npairs pairs -- or, first == nullptr, the ns / 2 pairs
 // (2p, 2p+1).  Allocates what is needed.  cons: per-sequence structure constraints of
 // the single-molecule folds, co_cons: per-pair constraints over s1+s2 of the two-molecule ensemble (Vienna-BL; either, or any entry,
-// may be nullptr).  Every constraint is checked before the context changes: a rejected upload leaves the previous batch in place.
+// may be nullptr).  An indexed batch takes its joint constraints by shares instead: pair p's is co_first[first[p]] over s1 +
+// co_second[second[p]] over s2 (constraint_prepass.h), and its masks are composed on the device from one pass per distinct sequence
+// and role.  Every constraint is checked before the context changes: a rejected upload leaves the previous batch in place.
 int stage(rh_ctx* c, int ns, const char* const* seqs, const int* lens, bool with_mc, bool with_dx, const char* const* cons, const char* const* co_cons,
-          int npairs, const int* first, const int* second)
+          int npairs, const int* first, const int* second, const char* const* co_first, const char* const* co_second)
 {
     HIP_TRY(c, hipSetDevice(c->device));
     if (ns <= 0) return fail(c, RH_ERR_ARG, "empty batch");
@@ -76,9 +94,11 @@ int stage(rh_ctx* c, int ns, const char* const* seqs, const int* lens, bool with
     const int lds = (nmax + 3 + 15) & ~15;  // codes 0..n+2 readable
     const int co_lds = (n1max + n2max + 3 + 15) & ~15;
     const bool vienna = c->model == RH_MODEL_VIENNA_BL;
-    if (!with_mc || indexed) cons = nullptr;
-    if (indexed) co_cons = nullptr;
+    if (!with_mc) cons = nullptr;
+    if (indexed) co_cons = nullptr;   // (an indexed batch has no per-pair strings: its joint constraints come as shares)
     if (!with_dx || !vienna) co_cons = nullptr;
+    if (!indexed || !vienna) co_first = co_second = nullptr;
+    const bool shares = co_first || co_second;
     ConsPass H(cons ? ns : 0, lds), CH(co_cons ? npairs : 0, co_lds);
     std::string why;
     for (int k = 0; cons && k < ns; k++)
@@ -88,6 +108,25 @@ int stage(rh_ctx* c, int ns, const char* const* seqs, const int* lens, bool with
         const std::string joint = std::string(seqs[2 * p], lens[2 * p]) + std::string(seqs[2 * p + 1], lens[2 * p + 1]);
         if (!constraint_prepass(joint.c_str(), (int)joint.size(), co_cons[p], &CH.ch[(size_t)p * co_lds], &CH.P[(size_t)p * co_lds],
                                 &CH.enc[(size_t)p * co_lds], &why))
+            return fail(c, RH_ERR_ARG, "pair %d: %s", p, why.c_str());
+    }
+    SharePass SH(shares ? ns : 0, lds);
+    for (int r = 0; shares && r < 2; r++)
+        for (int k = 0; k < ns; k++) {
+            const char* const* from = r ? co_second : co_first;
+            const size_t sh = (size_t)r * ns + k;
+            std::vector<int> open;
+            if (from && from[k] &&
+                !share_prepass(seqs[k], lens[k], from[k], r, &SH.L.ch[sh * lds], &SH.L.P[sh * lds], &SH.L.enc[sh * lds], &open, &SH.why[sh]))
+                open.clear();   // (reported below if a pair puts the sequence in this role; its row is not read otherwise)
+            SH.pos.insert(SH.pos.end(), open.begin(), open.end());
+            SH.off.push_back((int)SH.pos.size());
+        }
+    for (int p = 0; shares && p < npairs; p++) {   // per pair only what the partner decides: O(open brackets)
+        const int a = pair_seq[2 * (size_t)p], b = ns + pair_seq[2 * (size_t)p + 1];
+        for (int sh : {a, b})
+            if (!SH.why[sh].empty()) return fail(c, RH_ERR_ARG, "pair %d: %s", p, SH.why[sh].c_str());
+        if (!joint_pair_check(seqs[a], SH.pos.data() + SH.off[a], SH.off[a + 1] - SH.off[a], seqs[b - ns], SH.pos.data() + SH.off[b], SH.off[b + 1] - SH.off[b], &why))
             return fail(c, RH_ERR_ARG, "pair %d: %s", p, why.c_str());
     }
     c->ns = ns; c->np = npairs;
@@ -175,7 +214,7 @@ int stage(rh_ctx* c, int ns, const char* const* seqs, const int* lens, bool with
         HIP_TRY(c, hipMemsetAsync(c->d_bp.p, 0, bp_bytes, c->s_mc));
         B.allow = nullptr;
         if (cons) {
-            if ((rc = build_allow_masks(c, H, ns, B.ld, lds, c->d_n.as<const int>(), c->d_allow))) return rc;
+            if ((rc = build_allow_masks(c, &H, nullptr, ns, B.ld, lds, c->d_n.as<const int>(), c->d_allow))) return rc;
             B.allow = c->d_allow.as<const uint8_t>();
         }
         if (c->tables_dirty) {
@@ -274,11 +313,30 @@ int stage(rh_ctx* c, int ns, const char* const* seqs, const int* lens, bool with
             const size_t fs = (size_t)C.ld * np;
             C.f5i = f; C.f5o = f + fs; C.xp = f + 2 * fs; C.xs = f + 3 * fs; C.xpo = f + 4 * fs; C.xso = f + 5 * fs;
             C.bp = c->d_cobp.as<double>(); C.up = nullptr;
-            if (co_cons) {
-                hipLaunchKernelGGL(pair_gather, dim3(npairs, 2), dim3(kPairGatherThreads), 0, c->s_dx, G);   // (the mask kernel on s_mc reads the joint lengths)
+            JointShares S{};
+            std::vector<int> blob;   // (dies with this scope: build_allow_masks synchronizes s_mc)
+            if (shares) {
+                // the shares go over once per distinct sequence and role, in one copy: P, enc, the open lists, then the characters
+                const size_t cells = 2 * (size_t)ns * lds, ints = 2 * cells + SH.off.size() + SH.pos.size();
+                blob.resize(ints + (cells + sizeof(int) - 1) / sizeof(int));
+                std::copy(SH.L.P.begin(), SH.L.P.end(), blob.begin());
+                std::copy(SH.L.enc.begin(), SH.L.enc.end(), blob.begin() + cells);
+                std::copy(SH.off.begin(), SH.off.end(), blob.begin() + 2 * cells);
+                std::copy(SH.pos.begin(), SH.pos.end(), blob.begin() + 2 * cells + SH.off.size());
+                std::memcpy(blob.data() + ints, SH.L.ch.data(), cells);
+                if ((rc = ensure(c, c->d_share, blob.size() * sizeof(int), false))) return rc;
+                HIP_TRY(c, hipMemcpyAsync(c->d_share.p, blob.data(), blob.size() * sizeof(int), hipMemcpyHostToDevice, c->s_mc));
+                const int* d = c->d_share.as<const int>();
+                S.P = d; S.enc = d + cells; S.open_off = d + 2 * cells; S.open_pos = S.open_off + SH.off.size();
+                S.ch = reinterpret_cast<const uint8_t*>(d + ints);
+                S.idx = c->d_pidx.as<const int>(); S.con = c->d_con.as<const int>();
+                S.ns = ns; S.np = np; S.lds = lds; S.co_lds = co_lds;
+            }
+            if (co_cons || shares) {
+                hipLaunchKernelGGL(pair_gather, dim3(npairs, 2), dim3(kPairGatherThreads), 0, c->s_dx, G);   // (the kernels on s_mc read the joint lengths)
                 HIP_TRY(c, hipStreamSynchronize(c->s_dx));
                 gathered = true;
-                if ((rc = build_allow_masks(c, CH, np, C.ld, co_lds, C.n, c->d_coallow))) return rc;
+                if ((rc = build_allow_masks(c, co_cons ? &CH : nullptr, &S, np, C.ld, co_lds, C.n, c->d_coallow))) return rc;
                 C.allow = c->d_coallow.as<const uint8_t>();
             }
         }

@@ -23,7 +23,7 @@ EXPORTS = [
     "rh_host_alloc", "rh_host_free", "rh_batch_fallbacks", "rh_create_vienna", "rh_vienna_semantics", "rh_set_scale_memory", "rh_set_kernel_timing", "rh_kernel_times",
     "rh_set_duplex_mode", "rh_get_duplex_mode",
     "rh_batch_upload_constrained", "rh_debug_batch_allow_mask",
-    "rh_batch_upload_indexed", "rh_batch_index", "rh_batch_candidates_seq_all",
+    "rh_batch_upload_indexed", "rh_batch_index", "rh_batch_candidates_seq_all", "rh_batch_upload_indexed_constrained",
     "rh_debug_vienna_cell", "rh_debug_vienna_value",   # loader inspection (host only; used by the CPU tests of the loader)
 ]
 
@@ -97,6 +97,8 @@ def load_library():
     L.rh_batch_upload_constrained.restype = ci
     L.rh_batch_upload_indexed.argtypes = [vp, ci, ctypes.POINTER(cp), ctypes.POINTER(ci), ci, ctypes.POINTER(ci), ctypes.POINTER(ci)]
     L.rh_batch_upload_indexed.restype = ci
+    L.rh_batch_upload_indexed_constrained.argtypes = L.rh_batch_upload_indexed.argtypes + [ctypes.POINTER(cp)] * 3
+    L.rh_batch_upload_indexed_constrained.restype = ci
     L.rh_batch_index.argtypes = [vp, vp, vp, vp, vp]
     L.rh_batch_index.restype = ci
     L.rh_batch_candidates_seq_all.argtypes = [vp, ci, ctypes.c_float, vp, ci, vp]
@@ -145,6 +147,21 @@ def index_pairs(pairs):
                 seqs.append(s)
             out.append(slot[s])
     return seqs, first, second
+
+
+def index_pairs_structured(pairs):
+    """index_pairs for sequences that come with a structure line: pairs = [((s1, t1), (s2, t2)), ...], t = the line or "".
+    Returns (seqs, structures, first, second); entries are distinct by (sequence, structure line), in the order of their first
+    appearance -- one sequence under two lines is two entries, each folded under its own constraint."""
+    slot, seqs, structures, first, second = {}, [], [], [], []
+    for a, b in pairs:
+        for (s, t), out in ((a, first), (b, second)):
+            if (s, t) not in slot:
+                slot[(s, t)] = len(seqs)
+                seqs.append(s)
+                structures.append(t)
+            out.append(slot[(s, t)])
+    return seqs, structures, first, second
 
 
 class Context:
@@ -284,15 +301,27 @@ class Context:
         self._pairs = [(len(p[0]), len(p[1])) for p in pairs]
         self._seq_lens = None
 
-    def batch_upload_indexed(self, seqs, index_pairs):
+    def batch_upload_indexed(self, seqs, index_pairs, constraints=None, co_first=None, co_second=None):
         """Every string of `seqs` is folded once; pair p = (seqs[i], seqs[j]) for (i, j) = index_pairs[p] (rh_batch_upload_indexed).
-        The per-pair calls (batch_results, batch_candidates, batch_candidates_all, batch_logz) work as on the expanded batch."""
+        The per-pair calls (batch_results, batch_candidates, batch_candidates_all, batch_logz) work as on the expanded batch.
+        constraints / co_first / co_second (rh_batch_upload_indexed_constrained, Vienna-BL model): one string or None per entry
+        of `seqs` -- the constraint of its fold, and its share of a pair's joint constraint when it is s1 / s2 of the pair."""
         ns, np_ = len(seqs), len(index_pairs)
         a = (ctypes.c_char_p * ns)(*[s.encode() for s in seqs])
         na = (ctypes.c_int * ns)(*[len(s) for s in seqs])
         first = (ctypes.c_int * max(np_, 1))(*[int(p[0]) for p in index_pairs])
         second = (ctypes.c_int * max(np_, 1))(*[int(p[1]) for p in index_pairs])
-        self._check(self.L.rh_batch_upload_indexed(self.h, ns, a, na, np_, first, second))
+        if constraints is None and co_first is None and co_second is None:
+            self._check(self.L.rh_batch_upload_indexed(self.h, ns, a, na, np_, first, second))
+        else:
+            def column(strings):
+                if strings is None:
+                    return None
+                if len(strings) != ns:
+                    raise RhError("%d constraints for %d sequences" % (len(strings), ns))
+                return (ctypes.c_char_p * ns)(*[None if x is None else x.encode() for x in strings])
+            self._check(self.L.rh_batch_upload_indexed_constrained(self.h, ns, a, na, np_, first, second, column(constraints),
+                                                                   column(co_first), column(co_second)))
         self._pairs = [(len(seqs[p[0]]), len(seqs[p[1]])) for p in index_pairs]
         self._seq_lens = [len(s) for s in seqs]
 
@@ -319,7 +348,7 @@ class Context:
 
     def debug_allow_mask(self, which, k):
         """The allowed-pair mask of the last upload as the kernels read it (rh_debug_batch_allow_mask): which = 0, sequence k
-        (2p = s1 of pair p), which = 1 the concatenation of pair k.  An (ld, ld) uint8 array, or None if that batch has no mask."""
+        (2p = s1 of pair p; indexed upload: distinct sequence k), which = 1 the concatenation of pair k.  An (ld, ld) uint8 array, or None if that batch has no mask."""
         ld = ctypes.c_int()
         if self._check(self.L.rh_debug_batch_allow_mask(self.h, which, k, None, ctypes.byref(ld))) == 1:
             return None

@@ -59,13 +59,19 @@ def fold_constraint(structure, n):
     return "".join("x" if ch in "[]e" else ch for ch in line) + "." * (n - len(line))
 
 
+def joint_share(structure, n, first):
+    """One molecule's part of joint_constraint: the structure line of s1 (first=True: '[' becomes '(') or of s2 (']' becomes ')');
+    '(' ')' 'l' 'x' become 'x', everything else '.', n characters.  What Context.batch_upload_indexed takes per sequence as
+    co_first / co_second."""
+    forced, to = ("[", "(") if first else ("]", ")")
+    line = structure[:n]
+    return "".join(to if ch == forced else "x" if ch in "()lx" else "." for ch in line) + "." * (n - len(line))
+
+
 def joint_constraint(str1, n1, str2, n2):
     """The structure lines of a pair as the default branch of RactIP::rnaduplex hands them to co_pf_fold over s1+s2
     (src/ractip.cpp:409-440): '[' of s1 becomes '(' and ']' of s2 becomes ')', '(' ')' 'l' 'x' become 'x', everything else '.'."""
-    def side(line, n, forced, to):
-        line = line[:n]
-        return "".join(to if ch == forced else "x" if ch in "()lx" else "." for ch in line) + "." * (n - len(line))
-    return side(str1, n1, "[", "(") + side(str2, n2, "]", ")")
+    return joint_share(str1, n1, True) + joint_share(str2, n2, False)
 
 
 def probabilities(ctx, s1, s2, structures=None):
@@ -109,13 +115,24 @@ def predict(s1, s2, model="vienna", duplex=False, device=0, options=None, ctx=No
             ctx.close()
 
 
-def screen(queries, targets, model="vienna", duplex=False, device=0, options=None, ctx=None):
+def screen(queries, targets, model="vienna", duplex=False, device=0, options=None, ctx=None, query_structures=None, target_structures=None):
     """The joint structures of the cross product queries x targets from ONE indexed batch: every distinct string is uploaded and
     folded once (hot.index_pairs, Context.batch_upload_indexed), every (query, target) gets its hp.  Returns one list per query
-    with predict()'s result for each target; model / duplex / options as in predict."""
+    with predict()'s result for each target; model / duplex / options as in predict.
+    query_structures / target_structures: one FASTA structure line per query / target ("" for none; a missing side is all ""), used
+    as predict uses structures= (--use-constraint; model "vienna" only).  A sequence is then folded once per distinct structure
+    line it comes with (hot.index_pairs_structured), and the joint constraints are built on the device from each line's two shares."""
+    structured = query_structures is not None or target_structures is not None
+    if structured and model != "vienna":
+        raise ValueError("structure constraints apply to the default (Vienna-BL) path only")
     pairs = [(q, t) for q in queries for t in targets]
     if not pairs:
         return [[] for _ in queries]
+    if structured:
+        tq = list(query_structures) if query_structures is not None else [""] * len(queries)
+        tt = list(target_structures) if target_structures is not None else [""] * len(targets)
+        if len(tq) != len(queries) or len(tt) != len(targets):
+            raise ValueError("one structure line per query and per target")
     own = ctx is None
     if own:
         ctx = hot.Context(device=device, model=hot.RH_MODEL_VIENNA_BL if model == "vienna" else hot.RH_MODEL_CONTRAFOLD)
@@ -124,8 +141,15 @@ def screen(queries, targets, model="vienna", duplex=False, device=0, options=Non
         if model == "vienna":
             ctx.set_max_w(max(1, opt.max_w))
             ctx.set_hybrid(not duplex)
-        seqs, first, second = hot.index_pairs(pairs)
-        ctx.batch_upload_indexed(seqs, list(zip(first, second)))
+        if structured:
+            seqs, lines, first, second = hot.index_pairs_structured([((q, a), (t, b)) for q, a in zip(queries, tq) for t, b in zip(targets, tt)])
+            ctx.batch_upload_indexed(seqs, list(zip(first, second)),
+                                     constraints=[fold_constraint(t, len(s)) for s, t in zip(seqs, lines)],
+                                     co_first=[joint_share(t, len(s), True) for s, t in zip(seqs, lines)],
+                                     co_second=[joint_share(t, len(s), False) for s, t in zip(seqs, lines)])
+        else:
+            seqs, first, second = hot.index_pairs(pairs)
+            ctx.batch_upload_indexed(seqs, list(zip(first, second)))
         ctx.batch_compute()
         out = []
         for qi in range(len(queries)):
