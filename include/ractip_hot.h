@@ -164,6 +164,8 @@ int rh_cofold_constrained(rh_ctx* ctx, const char* s1, int n1, const char* s2, i
  *   rh_batch_results  : copy dense results of pair `p` to caller buffers (any may be NULL)
  *   rh_batch_candidates: thresholded sparse results of pair `p` -- the scans of
  *                       src/ractip.cpp:557-568, 578-589, 598-608, 621-627 done on device.
+ * An upload whose arguments are rejected (RH_ERR_ARG, RH_ERR_UNSUPPORTED) leaves the previous batch in place; one that fails
+ * afterwards (RH_ERR_OOM, RH_ERR_HIP) leaves the context without a batch until the next successful upload.
  */
 int rh_batch_upload(rh_ctx* ctx, int npairs,
                     const char* const* s1, const int* n1,

@@ -13,6 +13,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <cmath>
+
 namespace rh {
 
 // ---- McCaskill tables (gap-indexed cell (i,j): letters i+1..j inside; FC assumes
@@ -166,5 +168,62 @@ struct DxLinBatch {
     double pw4[4];       // dxl_sweep4: (lam*e^eu)^(4*step+k) * lam^2, k = 0..3 (the same for both directions)
     double pw8[8];       // dxl_strip8: (lam*e^eu)^(8*step+k) * lam^2, k = 0..7
 };
+
+// ---- The layout of every table kind, stated once: the upload (staging.hip), the sub-batches of the scale-exponent ladder
+// (fallbacks.hip) and the CPU check (tools/batch_request_check.cpp) all size and stride by these.  Host functions; each returns
+// zeroed storage with the shape fields filled (an argument of a captured graph is hashed by its bytes) and no pointer bound.
+inline size_t tri_size(int n) { return (size_t)(n + 1) * (n + 2) / 2; }
+inline int seq_lds(int nmax) { return (nmax + 3 + 15) & ~15; }   // row pitch of the letter codes: 0..n+2 readable
+
+// ns sequences of at most nmax letters with `tables` square tables each (T_COUNT, or VM_COUNT: Vienna-BL, one molecule or s1+s2)
+inline McBatch mc_layout(int ns, int nmax, int tables)
+{
+    McBatch B{};
+    B.ns = ns; B.nmax = nmax;
+    B.lds = seq_lds(nmax);
+    B.ld = (nmax + 2 + 1) & ~1;
+    B.tab_stride = (size_t)B.ld * B.ld;
+    B.seq_stride = B.tab_stride * tables;
+    B.tri_stride = (tri_size(nmax) + 1) & ~(size_t)1;
+    B.nb = (nmax - 1) / 16 + 1;
+    B.pk_stride = (size_t)B.nb * (B.nb + 1) / 2 * 256;
+    return B;
+}
+
+// np pairs of at most n1max x n2max letters, `tables` tables of (n1max+2) x ldd each; lds: the row pitch of the codes
+inline DxBatch dx_layout(int np, int n1max, int n2max, int lds, int tables)
+{
+    DxBatch D{};
+    D.np = np; D.n1max = n1max; D.n2max = n2max; D.lds = lds;
+    D.ldd = (n2max + 2 + 1) & ~1;
+    D.tab_stride = (size_t)(n1max + 2) * D.ldd;
+    D.pair_stride = D.tab_stride * tables;
+    return D;
+}
+
+// the same pairs on the linear path: `tables` anti-diagonal-major tables of n1max+n2max+3 rows, kDxPad zero columns on both sides of
+// every row and a slack behind the last one (the staged 96-column segments may run past it); ldd: of the posterior they write
+inline DxLinBatch dxl_layout(int np, int n1max, int n2max, int lds, int ldd, int tables)
+{
+    DxLinBatch X{};
+    X.np = np; X.n1max = n1max; X.n2max = n2max; X.lds = lds; X.ldd = ldd;
+    X.lda = (n1max + 2 + 2 * kDxPad + 1) & ~1;
+    const size_t rows = (size_t)n1max + n2max + 3;
+    X.tab_stride = rows * X.lda + 128;
+    X.pair_stride = X.tab_stride * tables;
+    return X;
+}
+
+// chunks of kLzRows = 16 anti-diagonals of the duplex log Z sums
+inline int lz_chunks(int n1max, int n2max) { return (n1max + n2max - 1 + 15) / 16; }
+
+// out[d], d < count: the weight of a hairpin of d unpaired letters (beyond 30 as part_func.c extrapolates) x lam^d.  Model: VLinModel
+// (vienna_model.h; a template so that this header, and a CPU program that includes it, needs no HIP)
+template <class Model>
+inline void hairpin_length_weights(const Model& H, int count, double* out)
+{
+    for (int d = 0; d < count; d++)
+        out[d] = (d <= 30 ? H.E_hairpin[d] : std::exp(H.hairpin30 - H.lxc * std::log(d / 30.0))) * std::exp(-H.s * d);
+}
 
 }  // namespace rh

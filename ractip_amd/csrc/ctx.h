@@ -12,6 +12,7 @@
 
 #include "../../include/ractip_hot.h"
 #include "batch.h"
+#include "batch_request.h"
 #include "score_model.h"
 #include "lin_model.h"
 #include "vienna_model.h"
@@ -263,7 +264,7 @@ struct Ctx {   // (the fields of rh_ctx, below)
     SweepPlan plan[3];             // of the linear first pass over the batch as uploaded: inside, outside, hybridization (run_attempt)
     int max_w = 1;                 // accessibility widths 1..max_w (src/ractip.cpp:370-375); the CONTRAfold path has width 1 only
 
-    // current batch (host mirror)
+    // current batch (host mirror): published by stage() as its last step, all zero / false while it works and after it failed
     int np = 0, ns = 0;
     // the index of the upload: pair p = sequences pair_seq[2p] (s1) and pair_seq[2p+1] (s2) of the fold batch.  rh_batch_upload
     // stages the identity (2p, 2p+1); rh_batch_upload_indexed any pairs of the ns distinct sequences.  Read through seq_of().
@@ -364,15 +365,13 @@ struct rh_ctx : rh::host::Ctx {};   // the opaque context of include/ractip_hot.
 
 namespace rh::host {
 
-inline size_t tri_size(int n) { return (size_t)(n + 1) * (n + 2) / 2; }
-
 // rh_api.hip
 int fail(rh_ctx* c, int code, const char* fmt, ...);
 int ensure(rh_ctx* c, DevBuf& buf, size_t bytes, bool zero);
-// staging.hip
-int stage(rh_ctx* c, int ns, const char* const* seqs, const int* lens, bool with_mc, bool with_dx, const char* const* cons = nullptr,
-          const char* const* co_cons = nullptr, int npairs = 0, const int* first = nullptr, const int* second = nullptr,
-          const char* const* co_first = nullptr, const char* const* co_second = nullptr);
+// staging.hip: check_batch (batch_request.h), then the tables of the request.  A request the checks reject leaves the previous
+// batch in place; from the first change to the context until RH_OK the context holds no batch (ns = np = 0, nothing computed), so
+// after a failure past the checks (RH_ERR_OOM, a HIP error) rh_batch_compute and the fetches answer "no ... batch".
+int stage(rh_ctx* c, const BatchRequest& r);
 // sequence of the fold batch that is strand `side` (0: s1, 1: s2) of pair p: the one place that knows how pairs map to sequences
 inline int seq_of(const Ctx* c, int p, int side) { return c->pair_seq[2 * (size_t)p + side]; }
 // the pairs that use sequence k, appended to *pairs (a flagged sequence flags every pair that references it)

@@ -258,11 +258,8 @@ int retry_dx_lin_rungs(rh_ctx* c, std::vector<int>* rest)
         const int nsub = sub.nsub, n1max = sub.nmax[0], n2max = sub.nmax[1];
         DxLinArgs A = dx_lin_args(c);   // (d_zpart / d_zbar of the main batch: large enough, the sub-batch has no more chunks)
         DxLinBatch& X = A.X;   // lds, ldd, hp_stride as in the main batch: results scatter back row for row
-        X.np = nsub; X.n1max = n1max; X.n2max = n2max;
-        X.lda = (n1max + 2 + 2 * kDxPad + 1) & ~1;
-        const size_t rows = (size_t)n1max + n2max + 3;
-        X.tab_stride = rows * X.lda + 128;
-        X.pair_stride = X.tab_stride * (int)DL_COUNT;
+        X = dxl_layout(nsub, n1max, n2max, X.lds, X.ldd, (int)DL_COUNT);
+        X.hp_stride = D.tab_stride;
         const size_t tab_d = X.pair_stride * nsub, hp_d = D.tab_stride * nsub;
         const size_t own_bytes = sizeof(double) * (tab_d + hp_d + nsub + 1) + sizeof(int) * nsub;   // tables, hp, log Z, flags
         if ((rc = stage_dx_sub(c, sub, own_bytes))) return rc;
@@ -275,7 +272,7 @@ int retry_dx_lin_rungs(rh_ctx* c, std::vector<int>* rest)
         X.seq = c->d_subdseq.as<const uint8_t>(); X.n = c->d_subdn.as<const int>(); X.tab = sub_tab; X.hp = sub_hp;
         A.plan = plan_dx_lin(c, 4);   // (always the four-wavefront organisation, whatever RH_DX_W chose for the first pass: see ADVICE.md)
         A.dm = c->d_dxlin_r[r]; A.hm = &c->h_dxlin_r[r];
-        A.lz_chunks = (n1max + n2max - 1 + 15) / 16;
+        A.lz_chunks = lz_chunks(n1max, n2max);
         A.logz = sub_logz; A.bad = sub_bad;
         if ((rc = launch_dx_lin(c, A))) return rc;
         if ((rc = flagged(c, sub_bad, nsub, c->s_dx, &bad))) return rc;
@@ -322,7 +319,10 @@ int recompute_pairs_on_helper(rh_ctx* c, const std::vector<int>& P)
             ptr[2 * k + hh] = t.c_str(); lens[2 * k + hh] = n;
         }
     int rc;
-    if ((rc = stage(h, 2 * nsub, ptr.data(), lens.data(), true, true, nullptr, nullptr))) return fail(c, rc, "helper upload: %s", h->err.c_str());
+    BatchRequest r;
+    r.ns = 2 * nsub; r.seqs = ptr.data(); r.lens = lens.data();
+    r.with_mc = r.with_dx = true;
+    if ((rc = stage(h, r))) return fail(c, rc, "helper upload: %s", h->err.c_str());
     if ((rc = compute(h))) return fail(c, rc, "helper compute: %s", h->err.c_str());
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->s_mc));

@@ -217,9 +217,7 @@ int select_vlin(rh_ctx* c, int model)
     c->d_vlin = v.d;
     c->vlin_cur = model;
     // hairpin length weights x lam^d (kernel arguments of the inside sweeps; the device copy serves the accessibility)
-    const VLinModel& H = *c->h_vlin;
-    for (size_t d = 0; d < c->h_hplen.size(); d++)
-        c->h_hplen[d] = (d <= 30 ? H.E_hairpin[d] : std::exp(H.hairpin30 - H.lxc * std::log(d / 30.0))) * std::exp(-H.s * (double)d);
+    hairpin_length_weights(*c->h_vlin, (int)c->h_hplen.size(), c->h_hplen.data());
     if (c->d_hplen.p && c->has_mc) {
         HIP_TRY(c, hipMemcpyAsync(c->d_hplen.p, c->h_hplen.data(), sizeof(double) * std::min((size_t)c->mc.ld, c->h_hplen.size()), hipMemcpyHostToDevice, c->s_mc));
         HIP_TRY(c, hipStreamSynchronize(c->s_mc));

@@ -272,12 +272,16 @@ const char* rh_last_error(const rh_ctx* c) { return c ? c->err.c_str() : g_creat
 static int fold_one(rh_ctx* c, const char* seq, int n, const char* constraint, double* bp_tri, double* up, double* logZ)
 {
     if (!c) return RH_ERR_ARG;
-    if (constraint && c->model != RH_MODEL_VIENNA_BL)
-        return fail(c, RH_ERR_UNSUPPORTED, "structure constraints apply to the Vienna-BL model only (RactIP::contrafold takes none)");
+    BatchRequest r;
+    r.ns = 1; r.seqs = &seq; r.lens = &n;
+    r.with_mc = true;
+    r.fold_cons = &constraint;
+    int rc;
+    std::string why;
+    if ((rc = check_model(r, c->model == RH_MODEL_VIENNA_BL, &why))) return fail(c, rc, "%s", why.c_str());   // (answers before the sequence is looked at)
     if (!seq || n < 0) return fail(c, RH_ERR_ARG, "bad sequence");
     if (n == 0) { if (bp_tri) bp_tri[0] = 0.0; if (logZ) *logZ = 0.0; return RH_OK; }
-    int rc;
-    if ((rc = stage(c, 1, &seq, &n, true, false, constraint ? &constraint : nullptr))) return rc;
+    if ((rc = stage(c, r))) return rc;
     if ((rc = compute(c))) return rc;
     if (bp_tri && (rc = fetch_bp(c, 0, bp_tri))) return rc;
     if (up && (rc = fetch_up(c, 0, up))) return rc;
@@ -316,9 +320,13 @@ static int pair_one(rh_ctx* c, bool cofold, const char* s1, int n1, const char* 
     if (!s1 || !s2 || n1 < 1 || n2 < 1) return fail(c, RH_ERR_ARG, "bad sequence");
     const char* seqs[2] = {s1, s2};
     const int lens[2] = {n1, n2};
+    BatchRequest r;
+    r.ns = 2; r.seqs = seqs; r.lens = lens;
+    r.with_dx = true;
+    r.joint_cons = &constraint;
     const int keep = c->hybrid;
     if (cofold) c->hybrid = RH_HYBRID_COFOLD;
-    int rc = stage(c, 2, seqs, lens, false, true, nullptr, constraint ? &constraint : nullptr);
+    int rc = stage(c, r);
     if (!rc) rc = compute(c);
     if (!rc) rc = fetch_hp(c, 0, hp, logZ);
     if (cofold) { c->hybrid = keep; c->ns = 0; c->computed = false; }
@@ -350,25 +358,22 @@ int rh_batch_upload_constrained(rh_ctx* c, int npairs, const char* const* s1, co
     if (npairs < 1 || !s1 || !s2 || !n1 || !n2) return fail(c, RH_ERR_ARG, "bad batch");
     std::vector<const char*> seqs(2 * (size_t)npairs), cons(2 * (size_t)npairs, nullptr);
     std::vector<int> lens(2 * (size_t)npairs);
-    bool any = false, any_co = false;   // an array whose entries are all NULL is no constraint: the batch of rh_batch_upload
     for (int p = 0; p < npairs; p++) {
         seqs[2 * p] = s1[p]; seqs[2 * p + 1] = s2[p];
         lens[2 * p] = n1[p]; lens[2 * p + 1] = n2[p];
         if (cons1) cons[2 * p] = cons1[p];
         if (cons2) cons[2 * p + 1] = cons2[p];
-        any = any || cons[2 * p] || cons[2 * p + 1];
-        any_co = any_co || (co_cons && co_cons[p]);
     }
-    if ((any || any_co) && c->model != RH_MODEL_VIENNA_BL)
-        return fail(c, RH_ERR_UNSUPPORTED, "structure constraints apply to the Vienna-BL model only (RactIP::contrafold takes none)");
-    return stage(c, 2 * npairs, seqs.data(), lens.data(), true, true, any ? cons.data() : nullptr, any_co ? co_cons : nullptr);
+    BatchRequest r;   // (constraint arrays whose entries are all NULL: the batch of rh_batch_upload)
+    r.ns = 2 * npairs; r.seqs = seqs.data(); r.lens = lens.data();
+    r.with_mc = r.with_dx = true;
+    r.fold_cons = cons.data(); r.joint_cons = co_cons;
+    return stage(c, r);
 }
 
 int rh_batch_upload_indexed(rh_ctx* c, int nseq, const char* const* seqs, const int* lens, int npairs, const int* first, const int* second)
 {
-    if (!c) return RH_ERR_ARG;
-    if (nseq < 1 || npairs < 1 || !seqs || !lens || !first || !second) return fail(c, RH_ERR_ARG, "bad indexed batch");
-    return stage(c, nseq, seqs, lens, true, true, nullptr, nullptr, npairs, first, second);   // (checks every index before it changes the context)
+    return rh_batch_upload_indexed_constrained(c, nseq, seqs, lens, npairs, first, second, nullptr, nullptr, nullptr);
 }
 
 int rh_batch_upload_indexed_constrained(rh_ctx* c, int nseq, const char* const* seqs, const int* lens, int npairs, const int* first, const int* second,
@@ -376,15 +381,13 @@ int rh_batch_upload_indexed_constrained(rh_ctx* c, int nseq, const char* const* 
 {
     if (!c) return RH_ERR_ARG;
     if (nseq < 1 || npairs < 1 || !seqs || !lens || !first || !second) return fail(c, RH_ERR_ARG, "bad indexed batch");
-    const char* const* arrays[3] = {cons, co_first, co_second};
-    for (auto& a : arrays) {   // an array whose entries are all NULL is no constraint: the batch of rh_batch_upload_indexed
-        bool any = false;
-        for (int k = 0; a && k < nseq; k++) any = any || a[k];
-        if (!any) a = nullptr;
-    }
-    if ((arrays[0] || arrays[1] || arrays[2]) && c->model != RH_MODEL_VIENNA_BL)
-        return fail(c, RH_ERR_UNSUPPORTED, "structure constraints apply to the Vienna-BL model only (RactIP::contrafold takes none)");
-    return stage(c, nseq, seqs, lens, true, true, arrays[0], nullptr, npairs, first, second, arrays[1], arrays[2]);
+    BatchRequest r;   // (stage() checks every index and constraint before it changes the context)
+    r.ns = nseq; r.seqs = seqs; r.lens = lens;
+    r.with_mc = r.with_dx = true;
+    r.fold_cons = cons;
+    r.npairs = npairs; r.first = first; r.second = second;
+    r.share_first = co_first; r.share_second = co_second;
+    return stage(c, r);
 }
 
 int rh_batch_index(rh_ctx* c, int* nseq, int* npairs, int* first, int* second)
