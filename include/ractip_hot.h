@@ -270,6 +270,28 @@ int rh_batch_candidates_seq_all(rh_ctx* ctx, int what, float threshold, rh_cand*
 int rh_batch_layout(rh_ctx* ctx, size_t* tri_stride, int* up_ld, size_t* hp_stride, int* hp_ld);
 int rh_batch_results_all(rh_ctx* ctx, double* bp, double* up, double* hp, double* logz);
 
+/* ---- dense results at the width the reference stores them: packed float32, narrowed on the device ----
+ * The reference keeps every probability as float (VF, VVF, pair_info::p: src/ractip.cpp:82-83).  The packed image is three arrays
+ * of floats, each a row of blocks at their tight sizes in the layouts at the top of this file:
+ *   bp: sequence k owns T(n_k) floats at bp_off[k];  up: n_k*max_w floats at up_off[k];  hp: pair p owns (n1+1)*(n2+1) floats at
+ *   hp_off[p], row-major, 1-based, row 0 / column 0 zero -- what rh_batch_results hands back per pair, as floats.
+ * Sequences are those of rh_batch_layout: 2p = s1, 2p+1 = s2 of pair p after rh_batch_upload, the distinct sequences after
+ * rh_batch_upload_indexed (bp / up per distinct sequence, hp per pair).  Offsets count elements, are 64-bit (512 pairs of n = 2000
+ * hold 2.05e9 hp entries, 8.2e9 bytes) and multiples of 4 (16 bytes); the floats between the end of one block and the start of the next
+ * are padding and hold 0, so equal results give equal images byte for byte.  totals[k] (= the last entry of each offset array) is
+ * the number of floats of the bp, up and hp image. */
+/* element offsets of the packed float image of the last upload (known from the lengths: valid after the upload, before the compute) */
+int rh_batch_packed_layout(rh_ctx* ctx, size_t* bp_off /*nseq+1*/, size_t* up_off /*nseq+1*/, size_t* hp_off /*npairs+1*/, size_t totals[3]);
+/* bp, up, hp of the whole batch narrowed to float on the device, packed as rh_batch_packed_layout says; any pointer may be NULL; logz as rh_batch_results_all.
+ * Element e of every block equals (float) of the corresponding double of rh_batch_results bit for bit (one IEEE conversion, round
+ * to nearest, float subnormals kept), whichever path computed it.  Both models, both rh_set_hybrid sources, every kind of upload;
+ * errors as rh_batch_results_all ("no computed pair batch").  Half the bytes of rh_batch_results_all cross the bus, and the host
+ * narrows nothing.  The first call allocates a device staging buffer as large as the images asked for (about 0.5 GB per 256 pairs
+ * of n = 500); it is kept, grows only, and goes with the context.  A table of 2^31 entries or more is RH_ERR_UNSUPPORTED. */
+int rh_batch_results_packed_f32(rh_ctx* ctx, float* bp, float* up, float* hp, double* logz);
+/* Measurement aid: device time (ms, one HIP event pair) of the pack kernel of the last rh_batch_results_packed_f32 that fetched a table. */
+int rh_batch_pack_time(rh_ctx* ctx, double* ms);
+
 /* Page-locked host memory for result buffers (hipHostMalloc): device-to-host copies into it run at the full DMA rate and,
  * issued from two contexts, overlap the other context's kernels (the reference's result containers are plain std::vector,
  * src/ractip.cpp:82-83; a host that wants the dense matrices at PCIe speed hands these buffers to rh_batch_results_all).

@@ -214,6 +214,29 @@ inline DxLinBatch dxl_layout(int np, int n1max, int n2max, int lds, int ldd, int
     return X;
 }
 
+// ---- The packed float image of a batch's dense results (rh_batch_packed_layout; written by pack_results.hip, checked on the CPU by
+// tools/packed_layout_check.cpp): three arrays of floats, each a row of blocks at their tight sizes in the reference's layouts --
+//   bp: sequence k owns tri_size(n_k) floats, the triangular table for ITS n;  up: n_k * max_w floats, up[i*max_w + w];
+//   hp: pair p owns (n1+1) * (n2+1) floats, row-major, 1-based, row 0 and column 0 zero (pair p = sequences pair_seq[2p], pair_seq[2p+1]).
+// Every block starts at a multiple of kPackAlign elements (16 bytes); the floats between the end of a block and the start of the next
+// one (behind the last block: the total) are padding and hold 0.  Offsets and totals count elements and are 64-bit: 512 pairs of
+// 2000 + 2000 letters hold 2.05e9 hp entries (8.2e9 bytes), 2048 of them more than 2^32.  bp_off / up_off have nseq + 1 entries, hp_off npairs + 1; the last entry of
+// each is its total.
+constexpr size_t kPackAlign = 4;
+inline size_t pack_pad(size_t elements) { return (elements + kPackAlign - 1) & ~(kPackAlign - 1); }
+inline void packed_layout(int nseq, const int* lens, int npairs, const int* pair_seq, int max_w, size_t* bp_off, size_t* up_off, size_t* hp_off,
+                          size_t totals[3])
+{
+    bp_off[0] = up_off[0] = hp_off[0] = 0;
+    for (int k = 0; k < nseq; k++) {
+        bp_off[k + 1] = bp_off[k] + pack_pad(tri_size(lens[k]));
+        up_off[k + 1] = up_off[k] + pack_pad((size_t)lens[k] * max_w);
+    }
+    for (int p = 0; p < npairs; p++)
+        hp_off[p + 1] = hp_off[p] + pack_pad(((size_t)lens[pair_seq[2 * p]] + 1) * ((size_t)lens[pair_seq[2 * p + 1]] + 1));
+    totals[0] = bp_off[nseq]; totals[1] = up_off[nseq]; totals[2] = hp_off[npairs];
+}
+
 // chunks of kLzRows = 16 anti-diagonals of the duplex log Z sums
 inline int lz_chunks(int n1max, int n2max) { return (n1max + n2max - 1 + 15) / 16; }
 

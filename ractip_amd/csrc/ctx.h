@@ -317,6 +317,14 @@ struct Ctx {   // (the fields of rh_ctx, below)
     DevBuf d_coallow;   // the same for the s1+s2 batch
     DevBuf d_cons;    // per-letter values of the constraint strings the masks are built from: P, enc [count][lds] ints, ch [count][lds] bytes
     DevBuf d_share;   // indexed batch under joint constraints: the shares of the distinct sequences in both roles (JointShares, kernels.h)
+    // rh_batch_results_packed_f32 only (a context that never calls it allocates none of this): the staging buffer of the packed float
+    // image (as large as the kinds asked for: about 0.5 GB per 256 pairs of n = 500), the offsets on the device with their host copy,
+    // and the event pair around the pack kernel (rh_batch_pack_time)
+    DevBuf d_pack;
+    DevBuf d_packoff;
+    std::vector<size_t> pack_off;
+    hipEvent_t pack_ev[2] = {nullptr, nullptr};
+    bool pack_timed = false;
     DevBuf d_hplen;   // lam^d x hairpin length weight, d = 0..nmax (linear Vienna path)
     std::vector<double> h_hplen;
     // two-molecule (co_pf_fold) form of the hybridization matrix: one concatenated sequence s1+s2 per pair

@@ -113,6 +113,24 @@ struct PairImage {
 constexpr int kPairGatherThreads = 256;
 __global__ void pair_gather(PairImage G);
 __global__ void vlin_co_seed(McBatch B, McBatch S, const int* __restrict__ idx);
+// pack_results.hip: the dense results of a computed batch narrowed to float into the packed image of packed_layout (batch.h); grid
+// (blocks of the kinds asked for: bp, up, hp in this order; chunks of a block), kPackThreads threads.  A kind whose source is nullptr
+// is left out of the grid.
+struct PackArgs {
+    const double* bp;      // [nseq][tri_stride]
+    const double* up;      // [nseq][up_stride], n * max_w entries used
+    const double* hp;      // [np][hp_stride], row pitch ldd
+    const int* n;          // [nseq]
+    const int* pn;         // [2 np]: the lengths of pair p's sequences
+    const size_t* off;     // bp_off [nseq + 1], up_off [nseq + 1], hp_off [np + 1], one behind the other
+    float* dst_bp;         // the three images (each 16-byte aligned)
+    float* dst_up;
+    float* dst_hp;
+    size_t tri_stride, up_stride, hp_stride;
+    int nseq, np, max_w, ldd;
+};
+constexpr int kPackThreads = 256, kPackGroupsPerThread = 4;
+__global__ void pack_results_f32(PackArgs A);
 }  // namespace rh
 
 // defined by the host units (global namespace)

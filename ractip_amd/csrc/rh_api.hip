@@ -261,6 +261,7 @@ void rh_destroy(rh_ctx* c)
     for (GraphSlot* g : {&c->g_in, &c->g_out, &c->g_dx}) if (g->exec) (void)hipGraphExecDestroy(g->exec);
     for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : c->tev) if (e) (void)hipEventDestroy(e);
+    for (auto& e : c->pack_ev) if (e) (void)hipEventDestroy(e);
     if (c->s_mc) (void)hipStreamDestroy(c->s_mc);
     if (c->s_dx) (void)hipStreamDestroy(c->s_dx);
     delete c;   // device buffers and host models go with their owners (ctx.h)
@@ -478,6 +479,89 @@ int rh_batch_results_all(rh_ctx* c, double* bp, double* up, double* hp, double* 
     if (hp) HIP_TRY(c, hipMemcpyAsync(hp, c->d_hp.p, sizeof(double) * c->dx.tab_stride * c->np, hipMemcpyDeviceToHost, c->s_mc));
     HIP_TRY(c, hipStreamSynchronize(c->s_mc));
     if (logz) return rh_batch_logz(c, logz);
+    return RH_OK;
+}
+
+// the offsets of the packed float image of the staged batch (packed_layout, batch.h) in c->pack_off: bp_off, up_off, hp_off one behind
+// the other, as the pack kernel reads them
+static void packed_offsets(rh_ctx* c, size_t totals[3])
+{
+    c->pack_off.resize(2 * ((size_t)c->ns + 1) + c->np + 1);
+    size_t* off = c->pack_off.data();
+    packed_layout(c->ns, c->n.data(), c->np, c->pair_seq.data(), c->max_w, off, off + c->ns + 1, off + 2 * ((size_t)c->ns + 1), totals);
+}
+
+int rh_batch_packed_layout(rh_ctx* c, size_t* bp_off, size_t* up_off, size_t* hp_off, size_t totals[3])
+{
+    if (!c) return RH_ERR_ARG;
+    if (c->ns == 0 || !c->has_mc || !c->has_dx) return fail(c, RH_ERR_ARG, "no pair batch");
+    size_t tot[3];
+    packed_offsets(c, tot);
+    const size_t* off = c->pack_off.data();
+    const size_t ns1 = (size_t)c->ns + 1;
+    if (bp_off) std::copy(off, off + ns1, bp_off);
+    if (up_off) std::copy(off + ns1, off + 2 * ns1, up_off);
+    if (hp_off) std::copy(off + 2 * ns1, off + 2 * ns1 + c->np + 1, hp_off);
+    if (totals) std::copy(tot, tot + 3, totals);
+    return RH_OK;
+}
+
+int rh_batch_results_packed_f32(rh_ctx* c, float* bp, float* up, float* hp, double* logz)
+{
+    if (!c) return RH_ERR_ARG;
+    if (!c->computed || !c->has_mc || !c->has_dx) return fail(c, RH_ERR_ARG, "no computed pair batch");
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->pack_timed = false;
+    if (bp || up || hp) {
+        int rc;
+        size_t tot[3];
+        packed_offsets(c, tot);
+        // the grid: a row of workgroups per block of the kinds asked for, as many as the largest block needs
+        size_t largest = 0;
+        for (int k = 0; k < c->ns; k++) largest = std::max(largest, std::max(bp ? tri_size(c->n[k]) : 0, up ? (size_t)c->n[k] * c->max_w : 0));
+        for (int p = 0; hp && p < c->np; p++) largest = std::max(largest, ((size_t)c->n[seq_of(c, p, 0)] + 1) * ((size_t)c->n[seq_of(c, p, 1)] + 1));
+        if (largest >= ((size_t)1 << 31)) return fail(c, RH_ERR_UNSUPPORTED, "a table of %zu entries is too large for the packed fetch", largest);
+        const size_t blocks = (bp ? (size_t)c->ns : 0) + (up ? (size_t)c->ns : 0) + (hp ? (size_t)c->np : 0);
+        if (blocks >= ((size_t)1 << 31)) return fail(c, RH_ERR_UNSUPPORTED, "%zu tables are too many for the packed fetch", blocks);
+        const size_t per_wg = (size_t)kPackThreads * kPackGroupsPerThread * kPackAlign;
+        const unsigned chunks = (unsigned)std::min<size_t>(65535, std::max<size_t>(1, (largest + per_wg - 1) / per_wg));
+        // the staging buffer holds the images asked for, one behind the other (every total is a multiple of 16 bytes)
+        const size_t at_up = bp ? tot[0] : 0, at_hp = at_up + (up ? tot[1] : 0), floats = at_hp + (hp ? tot[2] : 0);
+        if ((rc = ensure(c, c->d_pack, sizeof(float) * floats, false))) return rc;
+        if ((rc = ensure(c, c->d_packoff, sizeof(size_t) * c->pack_off.size(), false))) return rc;
+        for (hipEvent_t& e : c->pack_ev) if (!e) HIP_TRY(c, hipEventCreate(&e));
+        HIP_TRY(c, hipMemcpyAsync(c->d_packoff.p, c->pack_off.data(), sizeof(size_t) * c->pack_off.size(), hipMemcpyHostToDevice, c->s_mc));
+        PackArgs A{};
+        A.bp = bp ? c->d_bp.as<const double>() : nullptr;
+        A.up = up ? c->d_up.as<const double>() : nullptr;
+        A.hp = hp ? c->d_hp.as<const double>() : nullptr;
+        A.n = c->d_n.as<const int>(); A.pn = c->d_pn.as<const int>();
+        A.off = c->d_packoff.as<const size_t>();
+        A.dst_bp = c->d_pack.as<float>(); A.dst_up = A.dst_bp + at_up; A.dst_hp = A.dst_bp + at_hp;
+        A.tri_stride = c->mc.tri_stride; A.up_stride = (size_t)c->mc.ld * c->max_w; A.hp_stride = c->dx.tab_stride;
+        A.nseq = c->ns; A.np = c->np; A.max_w = c->max_w; A.ldd = c->dx.ldd;
+        HIP_TRY(c, hipEventRecord(c->pack_ev[0], c->s_mc));
+        hipLaunchKernelGGL(pack_results_f32, dim3((unsigned)blocks, chunks), dim3(kPackThreads), 0, c->s_mc, A);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipEventRecord(c->pack_ev[1], c->s_mc));
+        if (bp) HIP_TRY(c, hipMemcpyAsync(bp, A.dst_bp, sizeof(float) * tot[0], hipMemcpyDeviceToHost, c->s_mc));
+        if (up) HIP_TRY(c, hipMemcpyAsync(up, A.dst_up, sizeof(float) * tot[1], hipMemcpyDeviceToHost, c->s_mc));
+        if (hp) HIP_TRY(c, hipMemcpyAsync(hp, A.dst_hp, sizeof(float) * tot[2], hipMemcpyDeviceToHost, c->s_mc));
+        HIP_TRY(c, hipStreamSynchronize(c->s_mc));
+        c->pack_timed = true;
+    }
+    if (logz) return rh_batch_logz(c, logz);
+    return RH_OK;
+}
+
+int rh_batch_pack_time(rh_ctx* c, double* ms)
+{
+    if (!c || !ms) return RH_ERR_ARG;
+    if (!c->pack_timed) return fail(c, RH_ERR_ARG, "no packed fetch to time");
+    float t = 0.f;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipEventElapsedTime(&t, c->pack_ev[0], c->pack_ev[1]));
+    *ms = t;
     return RH_OK;
 }
 

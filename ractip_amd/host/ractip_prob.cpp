@@ -36,8 +36,37 @@ ProbabilityEngine::ProbabilityEngine(const std::vector<int>& devices, float th_h
 
 ProbabilityEngine::~ProbabilityEngine()
 {
-    for (rh_ctx* c : ctxs_) rh_destroy(c);
-    for (rh_ctx* c : vctxs_) rh_destroy(c);
+    for (rh_ctx* c : ctxs_) { release_buffers(c); rh_destroy(c); }
+    for (rh_ctx* c : vctxs_) { release_buffers(c); rh_destroy(c); }
+}
+
+// this context's page-locked buffers, grown to hold `totals` floats of bp, up and hp
+ProbabilityEngine::PackedBuffers& ProbabilityEngine::packed_buffers(rh_ctx* ctx, const size_t totals[3]) const
+{
+    PackedBuffers* b;
+    {
+        std::lock_guard<std::mutex> hold(packed_lock_);
+        b = &packed_[ctx];   // (a map keeps its entries in place; a context is driven by one thread at a time)
+    }
+    for (int k = 0; k < 3; ++k) {
+        if (totals[k] <= b->cap[k]) continue;
+        if (b->p[k]) rh_host_free(ctx, b->p[k]);
+        b->cap[k] = 0;
+        b->p[k] = static_cast<float*>(rh_host_alloc(ctx, sizeof(float) * totals[k]));
+        if (!b->p[k]) throw std::logic_error(std::string("ractip_amd::solve_probabilities: ") + rh_last_error(ctx));
+        b->cap[k] = totals[k];
+    }
+    return *b;
+}
+
+void ProbabilityEngine::release_buffers(rh_ctx* ctx) const
+{
+    if (!ctx) return;
+    std::lock_guard<std::mutex> hold(packed_lock_);
+    const auto it = packed_.find(ctx);
+    if (it == packed_.end()) return;
+    for (float* p : it->second.p) if (p) rh_host_free(ctx, p);
+    packed_.erase(it);
 }
 
 rh_ctx* ProbabilityEngine::vienna() const
@@ -58,7 +87,7 @@ rh_ctx* ProbabilityEngine::vienna() const
 void ProbabilityEngine::set_vienna_parameters(const std::string& defaults_file, bool use_bl_param, const std::string& param_file, int semantics)
 {
     v_defaults_ = defaults_file; v_use_bl_ = use_bl_param; v_param_ = param_file; v_semantics_ = semantics;
-    for (rh_ctx*& c : vctxs_) { if (c) rh_destroy(c); c = nullptr; }
+    for (rh_ctx*& c : vctxs_) { if (c) { release_buffers(c); rh_destroy(c); } c = nullptr; }
     vctx_ = nullptr;
 }
 
@@ -413,34 +442,36 @@ std::vector<PairProbabilities> ProbabilityEngine::compute_and_unpack(rh_ctx* ctx
     std::vector<PairProbabilities> out(np);
     auto raise_ctx = [&](const char* where) { throw std::logic_error(std::string("ractip_amd::") + where + ": " + rh_last_error(ctx)); };
     if (rh_batch_compute(ctx) != RH_OK) raise_ctx("solve_probabilities");
-    // three device-to-host copies for the whole batch, then unpack the padded layout on the host
-    size_t tri_stride = 0, hp_stride = 0;
-    int up_ld = 0, hp_ld = 0;
-    if (rh_batch_layout(ctx, &tri_stride, &up_ld, &hp_stride, &hp_ld) != RH_OK) raise_ctx("solve_probabilities");
-    std::vector<double> bp((size_t)nseq * tri_stride), up((size_t)nseq * up_ld), hp((size_t)np * hp_stride), z((size_t)3 * np);
-    if (rh_batch_results_all(ctx, bp.data(), up.data(), hp.data(), z.data()) != RH_OK) raise_ctx("solve_probabilities");
+    // the whole batch at the width the containers store (VF / VVF are float): narrowed and packed on the device, three copies into this
+    // context's page-locked buffers, then block copies into the members
+    std::vector<size_t> bp_off((size_t)nseq + 1), up_off((size_t)nseq + 1), hp_off((size_t)np + 1);
+    size_t totals[3];
+    if (rh_batch_packed_layout(ctx, bp_off.data(), up_off.data(), hp_off.data(), totals) != RH_OK) raise_ctx("solve_probabilities");
+    const PackedBuffers& buf = packed_buffers(ctx, totals);
+    std::vector<double> z((size_t)3 * np);
+    if (rh_batch_results_packed_f32(ctx, buf.p[0], buf.p[1], buf.p[2], z.data()) != RH_OK) raise_ctx("solve_probabilities");
+    const auto rows = [max_w](const float* u, uint n, VVF& up) {
+        up.resize(n);
+        for (uint i = 0; i < n; ++i) up[i].assign(u + (size_t)i * max_w, u + (size_t)(i + 1) * max_w);
+    };
     for (int p = 0; p < np; ++p) {
         const uint n1 = na[p], n2 = nb[p];
         PairProbabilities& r = out[p];
-        const double* b1 = bp.data() + (size_t)first[p] * tri_stride;
-        const double* b2 = bp.data() + (size_t)second[p] * tri_stride;
-        r.bp1.resize((size_t)(n1 + 1) * (n1 + 2) / 2);
-        r.bp2.resize((size_t)(n2 + 1) * (n2 + 2) / 2);
-        std::transform(b1, b1 + r.bp1.size(), r.bp1.begin(), [](double v) { return (float)v; });
-        std::transform(b2, b2 + r.bp2.size(), r.bp2.begin(), [](double v) { return (float)v; });
-        r.up1.assign(n1, VF(max_w)); r.up2.assign(n2, VF(max_w));
-        for (uint i = 0; i < n1; ++i)
-            for (uint w = 0; w < max_w; ++w) r.up1[i][w] = (float)up[(size_t)first[p] * up_ld + (size_t)i * max_w + w];
-        for (uint i = 0; i < n2; ++i)
-            for (uint w = 0; w < max_w; ++w) r.up2[i][w] = (float)up[(size_t)second[p] * up_ld + (size_t)i * max_w + w];
+        const float* b1 = buf.p[0] + bp_off[first[p]];
+        const float* b2 = buf.p[0] + bp_off[second[p]];
+        r.bp1.assign(b1, b1 + (size_t)(n1 + 1) * (n1 + 2) / 2);
+        r.bp2.assign(b2, b2 + (size_t)(n2 + 1) * (n2 + 2) / 2);
+        rows(buf.p[1] + up_off[first[p]], n1, r.up1);
+        rows(buf.p[1] + up_off[second[p]], n2, r.up2);
         r.offset1 = make_offsets(n1); r.offset2 = make_offsets(n2);
-        r.hp.assign(n1 + 1, VF(n2 + 1));
-        const double* h = hp.data() + (size_t)p * hp_stride;
-        for (uint i = 0; i <= n1; ++i)
-            for (uint j = 0; j <= n2; ++j) {
-                const float v = (float)h[(size_t)i * hp_ld + j];
-                r.hp[i][j] = (!threshold_hp || v > th_hy_) ? v : 0.0f;   // plist entries with p > th_hy (:451-454)
-            }
+        const float* h = buf.p[2] + hp_off[p];
+        r.hp.resize(n1 + 1);
+        for (uint i = 0; i <= n1; ++i) {
+            VF& row = r.hp[i];
+            row.assign(h + (size_t)i * (n2 + 1), h + (size_t)(i + 1) * (n2 + 1));
+            if (threshold_hp)
+                for (float& v : row) if (!(v > th_hy_)) v = 0.0f;   // plist entries with p > th_hy (:451-454)
+        }
         r.logZ1 = z[3 * p]; r.logZ2 = z[3 * p + 1]; r.logZd = z[3 * p + 2];
     }
     return out;

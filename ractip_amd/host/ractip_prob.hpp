@@ -12,6 +12,8 @@
 // two-line patch.  Failures surface as std::logic_error, which RactIP's main() already
 // catches (:1684-1691).
 #pragma once
+#include <map>
+#include <mutex>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -68,7 +70,9 @@ public:
     // becomes ')' (the interaction is forced), and '(' ')' 'l' 'x' become 'x' (letters paired inside their own molecule)
     void rnaduplex_cofold(const std::string& seq1, const std::string& str1, const std::string& seq2, const std::string& str2, VVF& hp) const;
 
-    // batched form for the z-score loop (:1638-1657): all DPs of all pairs in one device pass
+    // batched form for the z-score loop (:1638-1657): all DPs of all pairs in one device pass.  The batched members fetch the dense
+    // tables as floats, narrowed on the device (rh_batch_results_packed_f32: the bits of (float)x on the host, half the bytes),
+    // into page-locked buffers the engine keeps per context, and copy the blocks into the members
     std::vector<PairProbabilities> solve_probabilities(const std::vector<std::pair<std::string, std::string>>& pairs) const;
     // the same for the DEFAULT path (:544-548): rnafold(fa, bp, offset, up, max(1, max_w)) x2 + the co_pf_fold branch of
     // rnaduplex (hp entries with p > th_hy, :451-454) for every pair, Vienna-BL model; duplex = true: the --duplex branch
@@ -122,6 +126,16 @@ private:
                                                  uint max_w, bool threshold_hp) const;
     std::vector<PairProbabilities> compute_and_unpack(rh_ctx* ctx, int nseq, const std::vector<int>& first, const std::vector<int>& second,
                                                       const std::vector<int>& n1, const std::vector<int>& n2, uint max_w, bool threshold_hp) const;
+    // page-locked float buffers of the batched members (rh_host_alloc), one set per context: bp, up, hp images of
+    // rh_batch_results_packed_f32.  Grow-only; released before their context is destroyed.
+    struct PackedBuffers {
+        float* p[3] = {nullptr, nullptr, nullptr};
+        size_t cap[3] = {0, 0, 0};   // floats
+    };
+    PackedBuffers& packed_buffers(rh_ctx* ctx, const size_t totals[3]) const;
+    void release_buffers(rh_ctx* ctx) const;
+    mutable std::map<rh_ctx*, PackedBuffers> packed_;
+    mutable std::mutex packed_lock_;       // (the shards of one call look their sets up from their own threads)
     rh_ctx* ctx_;                          // first device's CONTRAfold context
     mutable rh_ctx* vctx_ = nullptr;       // first device's Vienna-BL context (created on first use)
     std::vector<int> devices_;

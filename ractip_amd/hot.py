@@ -24,6 +24,7 @@ EXPORTS = [
     "rh_set_duplex_mode", "rh_get_duplex_mode",
     "rh_batch_upload_constrained", "rh_debug_batch_allow_mask",
     "rh_batch_upload_indexed", "rh_batch_index", "rh_batch_candidates_seq_all", "rh_batch_upload_indexed_constrained",
+    "rh_batch_packed_layout", "rh_batch_results_packed_f32", "rh_batch_pack_time",
     "rh_debug_vienna_cell", "rh_debug_vienna_value",   # loader inspection (host only; used by the CPU tests of the loader)
 ]
 
@@ -116,6 +117,12 @@ def load_library():
     L.rh_batch_device_views.argtypes = [vp, vp, vp, vp, vp, vp]
     L.rh_batch_fallbacks.argtypes = [vp, ci, vp, ci]
     L.rh_batch_fallbacks.restype = ci
+    L.rh_batch_packed_layout.argtypes = [vp, vp, vp, vp, vp]
+    L.rh_batch_packed_layout.restype = ci
+    L.rh_batch_results_packed_f32.argtypes = [vp, vp, vp, vp, vp]
+    L.rh_batch_results_packed_f32.restype = ci
+    L.rh_batch_pack_time.argtypes = [vp, vp]
+    L.rh_batch_pack_time.restype = ci
     L.rh_host_alloc.restype = vp
     L.rh_host_alloc.argtypes = [vp, ctypes.c_size_t]
     L.rh_host_free.restype = None
@@ -458,6 +465,46 @@ class Context:
             bufs = tuple(self.pinned_empty(sh) for sh in shapes)
         self._check(self.L.rh_batch_results_all(self.h, *[b.ctypes.data for b in bufs]))
         return bufs
+
+    def batch_packed_layout(self):
+        """(bp_off, up_off, hp_off, totals) of the packed float image of the last upload (rh_batch_packed_layout): element offsets as
+        uint64 arrays of nseq+1, nseq+1 and npairs+1 entries, and the three totals.  Valid after the upload, before the compute."""
+        np_ = len(self._pairs)
+        ns = len(self._seq_lens) if getattr(self, "_seq_lens", None) is not None else 2 * np_
+        bo, uo, ho = np.zeros(ns + 1, dtype=np.uint64), np.zeros(ns + 1, dtype=np.uint64), np.zeros(np_ + 1, dtype=np.uint64)
+        tot = np.zeros(3, dtype=np.uint64)
+        self._check(self.L.rh_batch_packed_layout(self.h, bo.ctypes.data, uo.ctypes.data, ho.ctypes.data, tot.ctypes.data))
+        return bo, uo, ho, tot
+
+    def batch_results_packed_f32(self, bufs=None, want=("bp", "up", "hp", "logz")):
+        """Dense results of the whole batch as float32, narrowed and packed on the device (rh_batch_results_packed_f32): half the bytes
+        of batch_results_all_into, no host conversion.  Returns dict(bp=[per sequence], up=[per sequence], hp=[per pair], logZ=(npairs, 3),
+        bufs=(bp, up, hp, logz)): the lists hold views -- slices, not copies -- of the page-locked float32 buffers `bufs`, which a
+        later call reuses when handed back with unchanged totals.  Sequences are 2p = s1, 2p+1 = s2 of pair p, or the distinct ones of an
+        indexed upload; hp[p] is (n1+1, n2+1), up[k] is (n, max_w) when max_w > 1.  A kind not named in `want` is not fetched (NULL
+        to the C call) and its buffer keeps what it held."""
+        bo, uo, ho, tot = self.batch_packed_layout()
+        np_, w = len(self._pairs), self.max_w
+        lens = self._seq_lens if getattr(self, "_seq_lens", None) is not None else [n for pr in self._pairs for n in pr]
+        shapes = ((int(tot[0]),), (int(tot[1]),), (int(tot[2]),), (np_, 3))
+        if bufs is None or tuple(b.shape for b in bufs) != shapes:
+            for b in bufs or ():          # the totals changed: the buffers this call replaces are released, not kept until close()
+                self.pinned_free(b)
+            bufs = tuple(self.pinned_empty(sh, np.float32 if k < 3 else np.float64) for k, sh in enumerate(shapes))
+        ptr = [b.ctypes.data if name in want else None for b, name in zip(bufs, ("bp", "up", "hp", "logz"))]
+        self._check(self.L.rh_batch_results_packed_f32(self.h, *ptr))
+        bp, up, hp, z = bufs
+        ups = [up[int(uo[k]):int(uo[k]) + n * w] for k, n in enumerate(lens)]
+        return dict(bp=[bp[int(bo[k]):int(bo[k]) + tri_size(n)] for k, n in enumerate(lens)],
+                    up=ups if w == 1 else [u.reshape(n, w) for u, n in zip(ups, lens)],
+                    hp=[hp[int(ho[p]):int(ho[p]) + (n1 + 1) * (n2 + 1)].reshape(n1 + 1, n2 + 1) for p, (n1, n2) in enumerate(self._pairs)],
+                    logZ=z, bufs=bufs)
+
+    def batch_pack_time(self):
+        """Device time (ms) of the pack kernel of the last batch_results_packed_f32 (rh_batch_pack_time)."""
+        ms = ctypes.c_double()
+        self._check(self.L.rh_batch_pack_time(self.h, ctypes.byref(ms)))
+        return ms.value
 
     def batch_fallbacks(self, which=0):
         """Indices of the sequences (which=0) / pairs (which=1) the last compute recomputed in log space; which=2: the sequences it
