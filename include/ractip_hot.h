@@ -114,7 +114,7 @@ int rh_bpp(rh_ctx* ctx, const char* seq, int n, const char* constraint,
            double* bp_tri, double* logZ);
 
 /* Accessibility, up[i*max_w+w] = P(letters i..i+w unpaired), n*max_w doubles.  RH_MODEL_CONTRAFOLD: max_w must be 1
- * (src/ractip.cpp:213-222, up[i] = max(0, 1 - sum_j bp(i,j))).  RH_MODEL_VIENNA_BL: any 1 <= max_w <= 64; replaces
+ * (src/ractip.cpp:213-222, up[i] = max(0, 1 - sum_j bp(i,j))) unless rh_set_region_accessibility is on.  RH_MODEL_VIENNA_BL: any 1 <= max_w <= 64; replaces
  * pf_unstru and the H+I+M+E sum of src/ractip.cpp:370-375.  Sets the context's max_w (see rh_set_max_w). */
 int rh_unpaired(rh_ctx* ctx, const char* seq, int n, int max_w, double* up);
 
@@ -123,6 +123,19 @@ int rh_unpaired(rh_ctx* ctx, const char* seq, int n, int max_w, double* up);
  * RH_MODEL_VIENNA_BL.  Takes effect at the next upload / single-sequence call. */
 int rh_set_max_w(rh_ctx* ctx, int max_w);
 int rh_get_max_w(const rh_ctx* ctx);
+
+/* Region accessibility under RH_MODEL_CONTRAFOLD (an extension: the reference refuses widths with --contrafold,
+ * src/ractip.cpp:1511-1517).  Off (the default): everything as described above, max_w must be 1.  On: rh_set_max_w and
+ * rh_unpaired take 1..64, and rh_fold, the batched forms and their fetches carry n*max_w entries per sequence.
+ *   up[i*max_w+w] = Z(letters i..i+w forbidden to pair) / Z, Z the sum over the derivations the CONTRAfold inside recurrences
+ *   count (the quantity whose width-1 column is 1 - sum_j bp(i,j)); entries whose region runs past the end hold 0.
+ * Column 0 keeps the width-1 arithmetic, max(0, 1 - sum_j bp(i,j)), bit for bit, and bp, hp and log Z do not change.
+ * Turning it off sets max_w back to 1.  On a RH_MODEL_VIENNA_BL context the call is accepted and changes nothing. */
+int rh_set_region_accessibility(rh_ctx* ctx, int on);
+int rh_get_region_accessibility(const rh_ctx* ctx);
+/* Measurement aid: device time (ms, one HIP event pair) of the region-accessibility kernels of the last rh_batch_compute, over the
+ * batch as uploaded (sequences recomputed with another scale exponent or in log space are not in it). */
+int rh_batch_acc_time(rh_ctx* ctx, double* ms);
 
 /* Source of the hybridization matrix hp under RH_MODEL_VIENNA_BL (rh_duplex and the batched form):
  *   RH_HYBRID_DUPLEX (default): pf_duplex -- duplexes only, the --duplex branch (src/ractip.cpp:390-398);

@@ -70,6 +70,7 @@ McLinArgs mc_lin_args(const rh_ctx* c, int phase, const McBatch& B, const LinSet
     A.pin = xcd_pin(B.ns);
     A.strip_xcd = c->strip_xcd;
     A.f5_jlo = 32;   // inside_pairs(S, A, 30) ends with F5i[31]
+    A.up_w = c->max_w;
     A.f5_pass = c->f5_pass && f5_pass_fits(B.ld);   // (F5 in LDS: up to about 4300 letters; longer batches keep the serial kernels)
     return A;
 }
@@ -207,6 +208,7 @@ static int schedule_contrafold(rh_ctx* c, int dx_mode)
         if ((rc = run_graphed(c, c->g_in, c->s_mc, 0, launch_mc_lin, mc_lin_args(c, 0, c->mc, lin, true)))) return rc;
         HIP_TRY(c, hipEventRecord(c->ev[kEvMcInside], c->s_mc));
         if ((rc = run_graphed(c, c->g_out, c->s_mc, 1, launch_mc_lin, mc_lin_args(c, 1, c->mc, lin, true)))) return rc;
+        if ((rc = launch_mc_acc(c, c->mc, lin, true))) return rc;   // (region accessibility, when it is on: outside the graph)
         c->last_path = 1;
         if (c->mode == RH_MODE_AUTO) {  // did every sequence stay inside the double range?
             if ((rc = flagged(c, c->d_bad.as<int>(), c->mc.ns, c->s_mc, &c->fallback_mc))) return rc;
@@ -225,7 +227,10 @@ static int schedule_contrafold(rh_ctx* c, int dx_mode)
     } else {
         HIP_TRY(c, hipEventRecord(c->ev[kEvMcInside], c->s_mc));
     }
-    if (need_log && (rc = restart_mc_log(c, [&] { return launch_mc_log(c, xcd_pin(c->mc.ns), c->mc, c->d_mclogz.as<double>()); }))) return rc;
+    if (need_log && (rc = restart_mc_log(c, [&] {
+            const int r = launch_mc_log(c, xcd_pin(c->mc.ns), c->mc, c->d_mclogz.as<double>());
+            return r ? r : launch_mc_acc(c, c->mc, nullptr, true);
+        }))) return rc;
     HIP_TRY(c, hipEventRecord(c->ev[kEvMcEnd], c->s_mc));
 
     if (dx_lin) {
@@ -393,6 +398,7 @@ static int run_attempt(rh_ctx* c, Attempt* at)
     c->n_far[0] = c->n_far[1] = c->n_far[2] = 0;
     c->last_path = 0;
     c->last_went_log = false;
+    c->acc_timed = false;
     c->fallback_mc.clear(); c->fallback_dx.clear(); c->rescaled_mc.clear(); c->rescaled_dx.clear();
     const bool vienna = c->model == RH_MODEL_VIENNA_BL, cofold = vienna && c->hybrid == RH_HYBRID_COFOLD;
     // the organisation of each sweep's linear first pass: decided here, on every compute (a replayed graph does not call its launcher);

@@ -112,6 +112,7 @@ struct McLinArgs {   // launch_mc_lin: one phase (0 inside, 1 outside) of the CO
     int phase, pin, strip_xcd;
     int f5_pass, f5_jlo;       // strips: the exterior sums by lin_f5i_pass / lin_f5o_pass (0: the serial kernels, same bits); the first F5i
                                // entry the bootstrap diagonals do not leave behind
+    int up_w, pad_;            // row pitch of B.up (the context's max_w): mc_unpaired writes column 0
     McLinArgs() { std::memset(this, 0, sizeof *this); }
 };
 
@@ -262,7 +263,11 @@ struct Ctx {   // (the fields of rh_ctx, below)
     bool last_went_log = false;    // Vienna-BL: the last compute ended with the folds or the two-molecule sweeps on the log-space kernels
                                    // (recompute_pairs_on_helper reads it from the helper context, to list its pairs under the right mechanism)
     SweepPlan plan[3];             // of the linear first pass over the batch as uploaded: inside, outside, hybridization (run_attempt)
-    int max_w = 1;                 // accessibility widths 1..max_w (src/ractip.cpp:370-375); the CONTRAfold path has width 1 only
+    int max_w = 1;                 // accessibility widths 1..max_w (src/ractip.cpp:370-375); the CONTRAfold path has width 1 only ...
+    int region_acc = 0;            // ... unless rh_set_region_accessibility turned the wider widths on (mccaskill_acc.hip, launch_mc_acc)
+    DevBuf d_acc;                  // scratch of launch_mc_acc: [ns][acc_scratch_doubles(ld)], allocated by the first compute that needs it
+    hipEvent_t acc_ev[2] = {nullptr, nullptr};   // around the accessibility kernels of the batch as uploaded (rh_batch_acc_time)
+    bool acc_timed = false;
 
     // current batch (host mirror): published by stage() as its last step, all zero / false while it works and after it failed
     int np = 0, ns = 0;
@@ -416,6 +421,7 @@ struct SweepPass {
 int launch_mc_log(rh_ctx* c, int pin, const McBatch& B, double* logz_out);
 SweepPlan plan_mc_lin(const rh_ctx* c, int phase, int nmax);
 int launch_mc_lin(rh_ctx* c, const McLinArgs& A);
+int launch_mc_acc(rh_ctx* c, const McBatch& B, const LinSet* lin, bool timed);
 void far_products(const rh_ctx* c, int phase, int nmax, bool mfma, SweepPlan* P);
 const char* far_name(SweepPlan::Far far, int BS, int phase);
 void far_inside_after(const SweepPass& S, int done);

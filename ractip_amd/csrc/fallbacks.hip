@@ -113,6 +113,7 @@ int recompute_mc_subset_log(rh_ctx* c, const std::vector<int>& F)
     // (no table is cleared: the tables of the linear pass are dead, and the log-space kernels run over them as they are)
     double* sub_logz = c->d_subup.as<double>() + (size_t)c->mc.ld * c->max_w * nsub;
     if ((rc = launch_mc_log(c, xcd_pin(nsub), S, sub_logz))) return rc;
+    if ((rc = launch_mc_acc(c, S, nullptr, false))) return rc;
     for (int k = 0; k < nsub; k++) {   // scatter to the flagged sequences' slots
         HIP_TRY(c, scatter_mc(c, k, F[k]));
         HIP_TRY(c, hipMemcpyAsync(c->d_mclogz.as<double>() + F[k], sub_logz + k, sizeof(double), hipMemcpyDeviceToDevice, c->s_mc));
@@ -184,6 +185,7 @@ int retry_mc_lin_rungs(rh_ctx* c, int first_model, std::vector<int>* rest, int (
         const int saved_nl[2] = {c->n_launch[0], c->n_launch[1]}, saved_nf[2] = {c->n_far[0], c->n_far[1]};
         rc = launch_mc_lin(c, mc_lin_args(c, 0, S, lin, false));
         if (!rc) rc = launch_mc_lin(c, mc_lin_args(c, 1, S, lin, false));
+        if (!rc) rc = launch_mc_acc(c, S, lin, false);
         for (int q = 0; q < 2; q++) { c->n_launch[q] = saved_nl[q]; c->n_far[q] = saved_nf[q]; }
         if (rc) return rc;
         // flags and log Z of the sub-batch are the first nsub entries of d_bad / d_mclogz

@@ -14,7 +14,25 @@ namespace rh {
 __global__ void mc_init(McBatch B);
 __global__ void mc_inside_diag(McBatch B, const ScoreModel* __restrict__ M, int d, int pin);
 __global__ void mc_outside_diag(McBatch B, const ScoreModel* __restrict__ M, int d, int pin);
-__global__ void mc_unpaired(McBatch B);
+__global__ void mc_unpaired(McBatch B, int max_w);   // writes column 0 of up[.][max_w]
+// mccaskill_acc.hip: region accessibility of the CONTRAfold model, widths 2..max_w, from the finished tables.  PATH 0: the scaled
+// linear tables (A.lin), PATH 1: the log-space tables (A.score).  Scratch per sequence: three square tables and the gap weights.
+struct AccArgs {
+    const LinModel* lin;
+    const ScoreModel* score;
+    double* scratch;   // [ns][acc_scratch_doubles(ld)]
+    int max_w, pad_;
+};
+constexpr int kAccTile = 64, kAccK = 16;   // cf_acc_link: output tile, K tile
+constexpr size_t acc_scratch_doubles(int ld) { return 3 * (size_t)ld * ld + 2 * 31 * (size_t)ld; }
+template <int PATH> __global__ void cf_acc_hrows(McBatch B, AccArgs A);
+template <int PATH> __global__ void cf_acc_hcols(McBatch B, AccArgs A);
+template <int PATH> __global__ void cf_acc_gaps(McBatch B, AccArgs A);
+template <int PATH> __global__ void cf_acc_final(McBatch B, AccArgs A);
+template <int PATH> __global__ void cf_acc_sbuild(McBatch B, AccArgs A);
+template <int PATH> __global__ void cf_acc_seed(McBatch B, AccArgs A);
+template <int PATH> __global__ void cf_acc_link(McBatch B, AccArgs A, int flip);
+template <int PATH> __global__ void cf_acc_close(McBatch B, AccArgs A, int j, int flip);
 __global__ void dx_sweep_diag(DxBatch B, const ScoreModel* __restrict__ M, int t);
 __global__ void dx_logz(DxBatch B, const ScoreModel* __restrict__ M);
 __global__ void dx_posterior(DxBatch B);

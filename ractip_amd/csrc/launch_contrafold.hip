@@ -37,7 +37,53 @@ int launch_mc_log(rh_ctx* c, int pin, const McBatch& B, double* logz_out)
         c->n_launch[1]++;
     }
     hipLaunchKernelGGL(log_finish, dim3((B.ns + 63) / 64), dim3(64), 0, c->s_mc, B, logz_out);
-    hipLaunchKernelGGL(mc_unpaired, dim3((B.nmax + 63) / 64, B.ns), dim3(256), 0, c->s_mc, B);
+    hipLaunchKernelGGL(mc_unpaired, dim3((B.nmax + 63) / 64, B.ns), dim3(256), 0, c->s_mc, B, c->max_w);
+    return RH_OK;
+}
+
+// ---- region accessibility, widths 2..max_w (rh_set_region_accessibility; mccaskill_acc.hip): behind the outside sweep of the
+// sequences B, on the tables that sweep left -- the scaled linear ones at the exponent of `lin`, or (lin == nullptr) the log-space
+// ones -- and before anything else writes them.  Column 0 of up is mc_unpaired's.  Launched from the host, outside the captured
+// graphs: the scratch is allocated here, and `timed` brackets the kernels with the event pair rh_batch_acc_time reads.
+template <int PATH>
+static void acc_kernels(const McBatch& B, const AccArgs& A, hipStream_t st)
+{
+    const int n = B.nmax, ns = B.ns, w = A.max_w;
+    hipLaunchKernelGGL(cf_acc_hrows<PATH>, dim3((n + 255) / 256, ns), dim3(256), 0, st, B, A);
+    hipLaunchKernelGGL(cf_acc_hcols<PATH>, dim3((n + 255) / 256, ns), dim3(256), 0, st, B, A);
+    hipLaunchKernelGGL(cf_acc_gaps<PATH>, dim3((n + 127) / 128, 2 * kMaxSingle, ns), dim3(128), 0, st, B, A);
+    hipLaunchKernelGGL(cf_acc_final<PATH>, dim3((n + 127) / 128, w - 1, ns), dim3(128), 0, st, B, A);
+    if (n < 5) return;   // (no multiloop, no chain)
+    hipLaunchKernelGGL(cf_acc_sbuild<PATH>, dim3(ns), dim3(1024), 0, st, B, A);
+    hipLaunchKernelGGL(cf_acc_seed<PATH>, dim3((n + 255) / 256, n - 1, ns), dim3(256), 0, st, B, A);   // (behind cf_acc_final: it reuses the hairpin sums' table)
+    const int tiles = (n - 1) / kAccTile + 1;
+    for (int j = 1; j < w; j++) {   // A_j = mu A_{j-1} S, then its term of width j + 1
+        hipLaunchKernelGGL(cf_acc_link<PATH>, dim3(tiles, tiles, ns), dim3(256), 0, st, B, A, (j - 1) & 1);
+        hipLaunchKernelGGL(cf_acc_close<PATH>, dim3((n + 3) / 4, ns), dim3(256), 0, st, B, A, j, j & 1);
+    }
+}
+
+int launch_mc_acc(rh_ctx* c, const McBatch& B, const LinSet* lin, bool timed)
+{
+    if (!c->region_acc || c->model != RH_MODEL_CONTRAFOLD || c->max_w <= 1 || B.ns <= 0 || B.nmax < 1) return RH_OK;
+    if (B.ns > 65535 || B.nmax > 65535) return fail(c, RH_ERR_UNSUPPORTED, "region accessibility: more than 65535 sequences (or letters) in one batch");
+    if (int rc = ensure(c, c->d_acc, sizeof(double) * acc_scratch_doubles(B.ld) * B.ns, false)) return rc;
+    AccArgs A{};
+    A.lin = lin ? (const LinModel*)lin->d : nullptr;
+    A.score = c->d_model;
+    A.scratch = c->d_acc.as<double>();
+    A.max_w = c->max_w;
+    if (timed) {
+        for (auto& e : c->acc_ev) if (!e) HIP_TRY(c, hipEventCreate(&e));
+        HIP_TRY(c, hipEventRecord(c->acc_ev[0], c->s_mc));
+    }
+    if (lin) acc_kernels<0>(B, A, c->s_mc);
+    else acc_kernels<1>(B, A, c->s_mc);
+    HIP_TRY(c, hipGetLastError());
+    if (timed) {
+        HIP_TRY(c, hipEventRecord(c->acc_ev[1], c->s_mc));
+        c->acc_timed = true;
+    }
     return RH_OK;
 }
 
@@ -325,7 +371,7 @@ int launch_mc_lin(rh_ctx* c, const McLinArgs& A)
         sweep(BR, A.plan);
     if (phase == 1) {
         hipLaunchKernelGGL(lin_finish, dim3((BR.ns + 63) / 64), dim3(64), 0, c->s_mc, BR, A.lin->d, A.logz, A.bad);
-        hipLaunchKernelGGL(mc_unpaired, dim3((BR.nmax + 63) / 64, BR.ns), dim3(256), 0, c->s_mc, BR);
+        hipLaunchKernelGGL(mc_unpaired, dim3((BR.nmax + 63) / 64, BR.ns), dim3(256), 0, c->s_mc, BR, A.up_w);
     }
     return RH_OK;
 }

@@ -316,7 +316,8 @@ __global__ __launch_bounds__(256) void mc_outside_diag(McBatch B, const ScoreMod
 // rows b = 1+w, 5+w, ..: every load is a contiguous 512-byte run of a row of the triangular table (the per-letter form read the
 // column with a stride of a row: one 128-byte line per element).  Row part (pairs (a, b), b > a): wavefront w takes the letters
 // a0+1+w, +4, ..; lanes run along the row.  Fixed summation order: the bits of up do not depend on the batch.
-__global__ __launch_bounds__(256) void mc_unpaired(McBatch B)
+// max_w: the row pitch of up (1 unless region accessibility is on: then this is column 0 of up[.][max_w], the same bits).
+__global__ __launch_bounds__(256) void mc_unpaired(McBatch B, int max_w)
 {
     __shared__ double colsum[4][64];
     __shared__ double rowsum[64];
@@ -344,7 +345,7 @@ __global__ __launch_bounds__(256) void mc_unpaired(McBatch B)
     }
     __syncthreads();
     if (w == 0 && a0 + 1 + lane <= n)
-        B.up[(size_t)sq * B.ld + a0 + lane] = fmax(0.0, 1.0 - (((colsum[0][lane] + colsum[1][lane]) + (colsum[2][lane] + colsum[3][lane])) + rowsum[lane]));
+        B.up[((size_t)sq * B.ld + a0 + lane) * max_w] = fmax(0.0, 1.0 - (((colsum[0][lane] + colsum[1][lane]) + (colsum[2][lane] + colsum[3][lane])) + rowsum[lane]));
 }
 
 }  // namespace rh

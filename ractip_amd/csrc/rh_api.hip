@@ -262,6 +262,7 @@ void rh_destroy(rh_ctx* c)
     for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : c->tev) if (e) (void)hipEventDestroy(e);
     for (auto& e : c->pack_ev) if (e) (void)hipEventDestroy(e);
+    for (auto& e : c->acc_ev) if (e) (void)hipEventDestroy(e);
     if (c->s_mc) (void)hipStreamDestroy(c->s_mc);
     if (c->s_dx) (void)hipStreamDestroy(c->s_dx);
     delete c;   // device buffers and host models go with their owners (ctx.h)
@@ -585,12 +586,35 @@ int rh_set_max_w(rh_ctx* c, int max_w)
 {
     if (!c) return RH_ERR_ARG;
     if (max_w < 1 || max_w > 64) return fail(c, RH_ERR_ARG, "max_w=%d out of range [1,64]", max_w);
-    if (c->model == RH_MODEL_CONTRAFOLD && max_w != 1)
-        return fail(c, RH_ERR_UNSUPPORTED, "max_w=%d: the CONTRAfold path has width-1 accessibility only (src/ractip.cpp:213-222)", max_w);
+    if (c->model == RH_MODEL_CONTRAFOLD && max_w != 1 && !c->region_acc)
+        return fail(c, RH_ERR_UNSUPPORTED, "max_w=%d: the CONTRAfold path has width-1 accessibility only (src/ractip.cpp:213-222) unless rh_set_region_accessibility is on", max_w);
     if (max_w != c->max_w) { c->max_w = max_w; c->computed = false; c->ns = 0; }   // buffers are sized at upload
     return RH_OK;
 }
 int rh_get_max_w(const rh_ctx* c) { return c ? c->max_w : RH_ERR_ARG; }
+
+int rh_set_region_accessibility(rh_ctx* c, int on)
+{
+    if (!c) return RH_ERR_ARG;
+    on = on != 0;
+    if (c->model != RH_MODEL_CONTRAFOLD) return RH_OK;   // Vienna-BL computes every width already: accepted, nothing changes
+    if (on == c->region_acc) return RH_OK;
+    c->region_acc = on;
+    if (!on && c->max_w != 1) { c->max_w = 1; c->computed = false; c->ns = 0; }   // back to the width the default path has
+    return RH_OK;
+}
+int rh_get_region_accessibility(const rh_ctx* c) { return c ? c->region_acc : RH_ERR_ARG; }
+
+int rh_batch_acc_time(rh_ctx* c, double* ms)
+{
+    if (!c || !ms) return RH_ERR_ARG;
+    if (!c->computed || !c->acc_timed) return fail(c, RH_ERR_ARG, "no region accessibility phase to time");
+    float t = 0.f;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipEventElapsedTime(&t, c->acc_ev[0], c->acc_ev[1]));
+    *ms = t;
+    return RH_OK;
+}
 
 int rh_set_hybrid(rh_ctx* c, int hybrid)
 {

@@ -68,7 +68,7 @@ static int stage_sequences(rh_ctx* c, const BatchRequest& r, const BatchShape& S
         nsw.assign(lens, lens + ns); nsh.assign(ns, 0);
         int nmax_rest = 0;
         for (int k = 0; k < ns; k++) {
-            if (c->small_on && lens[k] >= kSmallMin && lens[k] <= kSmallMax) { c->small_list.push_back(k); nsw[k] = 0; }
+            if (c->small_on && !(c->region_acc && c->max_w > 1) && lens[k] >= kSmallMin && lens[k] <= kSmallMax) { c->small_list.push_back(k); nsw[k] = 0; }
             else nmax_rest = std::max(nmax_rest, lens[k]);
         }
         if (nmax_rest >= kStripMinN)   // some sequence runs in strips: the ones below that length get their own pass

@@ -160,6 +160,25 @@ void ProbabilityEngine::contrafold(const std::string& seq, VF& bp, VI& offset, V
     narrow_up(dup, up);
 }
 
+void ProbabilityEngine::contrafold(const std::string& seq, VF& bp, VI& offset, VVF& up, uint max_w) const
+{
+    const uint L = seq.size();
+    if (max_w < 1) max_w = 1;
+    std::vector<double> dbp((size_t)(L + 1) * (L + 2) / 2, 0.0), dup((size_t)L * max_w, 0.0);
+    offset = make_offsets(L);
+    if (L > 0) {
+        const bool ok = rh_set_region_accessibility(ctx_, 1) == RH_OK && rh_set_max_w(ctx_, (int)max_w) == RH_OK &&
+                        rh_fold(ctx_, seq.c_str(), (int)L, dbp.data(), dup.data(), nullptr) == RH_OK;
+        const std::string why = ok ? "" : rh_last_error(ctx_);
+        rh_set_region_accessibility(ctx_, 0);   // (max_w goes back to 1 with it)
+        if (!ok) throw std::logic_error("ractip_amd::contrafold: " + why);
+    }
+    narrow_bp(dbp, bp);
+    up.assign(L, VF(max_w));
+    for (uint i = 0; i < L; ++i)
+        for (uint w = 0; w < max_w; ++w) up[i][w] = (float)dup[(size_t)i * max_w + w];
+}
+
 void ProbabilityEngine::rnafold(const std::string& seq, VF& bp, VI& offset) const
 {
     const uint L = seq.size();

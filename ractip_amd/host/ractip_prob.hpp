@@ -3,6 +3,7 @@
 // error behaviour as the reference's private members (/root/reference/src/ractip.cpp):
 //
 //   void contrafold(const std::string& seq, VF& bp, VI& offset, VVF& up) const;   // :195-223
+//   void contrafold(const std::string& seq, VF& bp, VI& offset, VVF& up, uint max_w) const;   // (no counterpart: region accessibility)
 //   void contraduplex(const std::string& s1, const std::string& s2, VVF& hp) const; // :225-245
 //   void rnaduplex(const std::string& s1, const std::string& s2, VVF& hp) const;  // :384-399 (--duplex branch)
 //   void rnafold(const std::string& seq, VF& bp, VI& offset) const;                // :248-306  (Fasta::seq() of the original)
@@ -50,6 +51,10 @@ public:
     ProbabilityEngine& operator=(const ProbabilityEngine&) = delete;
 
     void contrafold(const std::string& seq, VF& bp, VI& offset, VVF& up) const;
+    // an extension (the reference refuses widths with --contrafold, :1511-1517): the same with region accessibility
+    // up[i][w] = P(letters i..i+w unpaired), w < max_w, under the CONTRAfold model (rh_set_region_accessibility), in the layout
+    // of the rnafold overload below.  The option is turned on for this call only: every other member sees width 1 as before.
+    void contrafold(const std::string& seq, VF& bp, VI& offset, VVF& up, uint max_w) const;
     void contraduplex(const std::string& seq1, const std::string& seq2, VVF& hp) const;
     // the --duplex branch of RactIP::rnaduplex: pf_duplex() + pr_duplex copy (:390-398)
     void rnaduplex(const std::string& seq1, const std::string& seq2, VVF& hp) const;

@@ -25,6 +25,7 @@ EXPORTS = [
     "rh_batch_upload_constrained", "rh_debug_batch_allow_mask",
     "rh_batch_upload_indexed", "rh_batch_index", "rh_batch_candidates_seq_all", "rh_batch_upload_indexed_constrained",
     "rh_batch_packed_layout", "rh_batch_results_packed_f32", "rh_batch_pack_time",
+    "rh_set_region_accessibility", "rh_get_region_accessibility", "rh_batch_acc_time",
     "rh_debug_vienna_cell", "rh_debug_vienna_value",   # loader inspection (host only; used by the CPU tests of the loader)
 ]
 
@@ -123,6 +124,12 @@ def load_library():
     L.rh_batch_results_packed_f32.restype = ci
     L.rh_batch_pack_time.argtypes = [vp, vp]
     L.rh_batch_pack_time.restype = ci
+    L.rh_set_region_accessibility.argtypes = [vp, ci]
+    L.rh_set_region_accessibility.restype = ci
+    L.rh_get_region_accessibility.argtypes = [vp]
+    L.rh_get_region_accessibility.restype = ci
+    L.rh_batch_acc_time.argtypes = [vp, vp]
+    L.rh_batch_acc_time.restype = ci
     L.rh_host_alloc.restype = vp
     L.rh_host_alloc.argtypes = [vp, ctypes.c_size_t]
     L.rh_host_free.restype = None
@@ -242,6 +249,20 @@ class Context:
     @property
     def max_w(self):
         return self.L.rh_get_max_w(self.h)
+
+    def set_region_accessibility(self, on):
+        """CONTRAfold model: accessibility of regions wider than one letter (off by default; see rh_set_region_accessibility)."""
+        self._check(self.L.rh_set_region_accessibility(self.h, 1 if on else 0))
+
+    @property
+    def region_accessibility(self):
+        return bool(self.L.rh_get_region_accessibility(self.h))
+
+    def batch_acc_time(self):
+        """Device time (ms) of the region-accessibility kernels of the last batch_compute (rh_batch_acc_time)."""
+        ms = ctypes.c_double()
+        self._check(self.L.rh_batch_acc_time(self.h, ctypes.byref(ms)))
+        return ms.value
 
     # ---- single-problem calls
     def bpp(self, seq, constraint=None):

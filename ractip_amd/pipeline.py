@@ -85,11 +85,13 @@ def probabilities(ctx, s1, s2, structures=None):
     return ctx.batch_results(0)
 
 
-def predict(s1, s2, model="vienna", duplex=False, device=0, options=None, ctx=None, rip_path=None, structures=None):
+def predict(s1, s2, model="vienna", duplex=False, device=0, options=None, ctx=None, rip_path=None, structures=None, accessibility=False):
     """model "vienna": RactIP's default path (rnafold + rnaduplex; duplex=True = --duplex, else co_pf_fold), parity
     unpinned; model "contrafold": the --contrafold path (bp from the CONTRAfold engine, width-1 up, accessibility off as
     src/ractip.cpp:1511-1517 demands), hp from the CONTRAfold duplex engine.  structures = (str1, str2): the FASTA structure
-    lines, used as constraints (--use-constraint; model "vienna" only)."""
+    lines, used as constraints (--use-constraint; model "vienna" only).  accessibility=True with model "contrafold" (an extension:
+    the reference has no such combination) turns the context's region accessibility on and hands up[i][w], widths 1..options.max_w,
+    to the ILP as the default path does."""
     if structures is not None and model != "vienna":
         raise ValueError("structure constraints apply to the default (Vienna-BL) path only")
     own = ctx is None
@@ -104,9 +106,14 @@ def predict(s1, s2, model="vienna", duplex=False, device=0, options=None, ctx=No
             if rip_path:
                 rip.write_rip(rip_path, s1, s2, r["bp1"], r["bp2"], r["hp"])
             return ilp.solve(s1, s2, r["bp1"], r["bp2"], r["hp"], r["up1"], r["up2"], opt)
+        if accessibility:
+            ctx.set_region_accessibility(True)
+            ctx.set_max_w(max(1, opt.max_w))
         r = probabilities(ctx, s1, s2)
         if rip_path:
             rip.write_rip(rip_path, s1, s2, r["bp1"], r["bp2"], r["hp"])
+        if accessibility:
+            return ilp.solve(s1, s2, r["bp1"], r["bp2"], r["hp"], r["up1"].reshape(len(s1), -1), r["up2"].reshape(len(s2), -1), opt)
         if options is None:
             opt = ilp.Options(min_w=0)
         return ilp.solve(s1, s2, r["bp1"], r["bp2"], r["hp"], None, None, opt)
@@ -115,10 +122,11 @@ def predict(s1, s2, model="vienna", duplex=False, device=0, options=None, ctx=No
             ctx.close()
 
 
-def screen(queries, targets, model="vienna", duplex=False, device=0, options=None, ctx=None, query_structures=None, target_structures=None):
+def screen(queries, targets, model="vienna", duplex=False, device=0, options=None, ctx=None, query_structures=None, target_structures=None,
+           accessibility=False):
     """The joint structures of the cross product queries x targets from ONE indexed batch: every distinct string is uploaded and
     folded once (hot.index_pairs, Context.batch_upload_indexed), every (query, target) gets its hp.  Returns one list per query
-    with predict()'s result for each target; model / duplex / options as in predict.
+    with predict()'s result for each target; model / duplex / options / accessibility as in predict.
     query_structures / target_structures: one FASTA structure line per query / target ("" for none; a missing side is all ""), used
     as predict uses structures= (--use-constraint; model "vienna" only).  A sequence is then folded once per distinct structure
     line it comes with (hot.index_pairs_structured), and the joint constraints are built on the device from each line's two shares."""
@@ -137,10 +145,14 @@ def screen(queries, targets, model="vienna", duplex=False, device=0, options=Non
     if own:
         ctx = hot.Context(device=device, model=hot.RH_MODEL_VIENNA_BL if model == "vienna" else hot.RH_MODEL_CONTRAFOLD)
     try:
-        opt = options or (ilp.Options() if model == "vienna" else ilp.Options(min_w=0))
+        with_up = model == "vienna" or accessibility
+        opt = options or (ilp.Options() if with_up else ilp.Options(min_w=0))
         if model == "vienna":
             ctx.set_max_w(max(1, opt.max_w))
             ctx.set_hybrid(not duplex)
+        elif accessibility:
+            ctx.set_region_accessibility(True)
+            ctx.set_max_w(max(1, opt.max_w))
         if structured:
             seqs, lines, first, second = hot.index_pairs_structured([((q, a), (t, b)) for q, a in zip(queries, tq) for t, b in zip(targets, tt)])
             ctx.batch_upload_indexed(seqs, list(zip(first, second)),
@@ -156,7 +168,9 @@ def screen(queries, targets, model="vienna", duplex=False, device=0, options=Non
             row = []
             for ti in range(len(targets)):
                 (s1, s2), r = pairs[qi * len(targets) + ti], ctx.batch_results(qi * len(targets) + ti)
-                up1, up2 = (r["up1"], r["up2"]) if model == "vienna" else (None, None)
+                up1, up2 = (r["up1"], r["up2"]) if with_up else (None, None)
+                if model != "vienna" and with_up:
+                    up1, up2 = up1.reshape(len(s1), -1), up2.reshape(len(s2), -1)
                 row.append(ilp.solve(s1, s2, r["bp1"], r["bp2"], r["hp"], up1, up2, opt))
             out.append(row)
         return out
