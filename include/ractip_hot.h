@@ -365,6 +365,46 @@ int rh_set_scale_memory(rh_ctx* ctx, int on);
 int rh_batch_device_views(rh_ctx* ctx, const double** bp, size_t* tri_stride,
                           const double** hp, size_t* hp_stride, int* hp_ld);
 
+/* ---- local folding: window-averaged bp and accessibility of a long sequence (the quantity RNAplfold defines; an extension, the
+ * reference folds a sequence only as a whole) ----
+ * A sequence of n letters, a window of W >= 2 letters and a step 1 <= S <= W; We = min(W, n).  n <= W: one window, start 0, n letters.
+ * Otherwise m = ceil((n - W) / S) windows start at 0, S, .., (m-1) S and a last one at n - W, so that it ends at the last letter:
+ * nw = m + 1 distinct, increasing starts.  Every window is folded as a sequence of its own (its end letters have no neighbour, as in
+ * rh_fold) under the context's model, arithmetic mode, max_w and region-accessibility setting; no structure constraint applies.
+ * Letters 0-based; a run of len letters from i lies in window k iff start[k] <= i and i + len <= start[k] + We.
+ *   bp_loc(i, j), 1 <= j - i < We: the mean of bp_k(i - start[k], j - start[k]) over the windows that contain i..j; 0 if none does.
+ *   up_loc[i][w]: the mean of up_k[i - start[k]][w] over the windows that contain i..i+w; 0 if none does or i + w >= n.
+ *   logz_win[k]: log Z of window k.
+ * A mean is a plain double sum in increasing window order followed by ONE division by the count: the order is part of the interface,
+ * and the result bits do not depend on how the windows were chunked (each window's bits depend on its own letters only; under
+ * RH_MODEL_VIENNA_BL that holds while no window leaves the double range on the default scale exponent, see rh_batch_fallbacks).
+ * With S > 1 a run of more than We - S + 1 letters may lie in no window: its entry is 0, not a probability.
+ * Layouts (offsets are size_t: n = 1e6, W = 1000 is 1e9 doubles):
+ *   bp_band: n rows of ld = We doubles, bp_band[i*ld + d] = bp_loc(i, i + d); column 0 and every entry with i + d >= n hold 0;
+ *   up: n * max_w doubles, up[i*max_w + w], as everywhere else;  logz_win: nw doubles.
+ *
+ * rh_local_fold checks its arguments first: a rejected call (RH_ERR_ARG) leaves the previous local result and the previous batch in
+ * place.  Then it folds the windows in chunks of consecutive windows, each a fold-only batch, adds every chunk's tables into band
+ * accumulators on the device and divides by the counts behind the last chunk; nothing but the letters crosses the bus.  Afterwards
+ * the context's batch is the last chunk, a fold-only batch as after rh_fold (the pair fetches answer "no computed pair batch"); the
+ * local result lives in buffers of its own, which grow only and go with the context, and stays valid until the next rh_local_fold.
+ * A failure behind the checks (RH_ERR_OOM, RH_ERR_HIP) leaves no local result. */
+int rh_local_fold(rh_ctx* ctx, const char* seq, int n, int window, int step);
+/* shape of the last local result; any pointer may be NULL, starts receives nw entries */
+int rh_local_layout(rh_ctx* ctx, int* n, int* ld, int* nw, int* max_w, int* starts);
+/* the last local result in the layouts above; any pointer may be NULL */
+int rh_local_results(rh_ctx* ctx, double* bp_band, double* up, double* logz_win);
+/* Thresholded lists of the last local result, scanned on the device over the band: what = 0: bp_loc, records with 1-based letters
+ * i < j of the long sequence; what = 1: up_loc, i = 0-based position, j = width index (all n * max_w entries).  Row-major order, the
+ * float narrowing and the p > threshold comparison of rh_batch_candidates.  Writes at most `cap` records, returns the total found. */
+int rh_local_candidates(rh_ctx* ctx, int what, float threshold, rh_cand* out, int cap);
+/* Test and measurement aid: windows per chunk of rh_local_fold, 1..32768; 0 (default) = automatic, the largest chunk whose McCaskill
+ * tables stay under the byte budget kLocalChunkBytes of ractip_amd/csrc/ctx.h (4 GiB).  Results are unchanged. */
+int rh_set_local_chunk(rh_ctx* ctx, int windows);
+/* Measurement aid: device time (ms, HIP event pairs) of the last rh_local_fold: ms[0] the folds (the computes of its chunks), ms[1]
+ * the accumulate and finish kernels, plus the scan kernels of the rh_local_candidates calls since. */
+int rh_local_times(rh_ctx* ctx, double ms[2]);
+
 /* ---- loader inspection (host only, no GPU, no context) ----
  * What the parameter loader holds after binding its sources, for checks of the binding itself (tests/test_bl_cells.py,
  * tests/test_vienna_par.py); not needed by a caller of the probability path.  Return 0, -1 (bad index / NULL) or

@@ -13,6 +13,7 @@
 #include "../../include/ractip_hot.h"
 #include "batch.h"
 #include "batch_request.h"
+#include "local_windows.h"
 #include "score_model.h"
 #include "lin_model.h"
 #include "vienna_model.h"
@@ -61,6 +62,13 @@ struct VLinSet {
     DevObj<VLinModel> d;
     ~VLinSet() { delete h; }
 };
+
+// Local folding (local_fold.hip): the windows of a long sequence are folded in chunks of consecutive windows, each chunk a fold-only
+// batch.  Automatic chunking takes the largest chunk whose McCaskill tables (DP tables, operand tiles, posteriors) stay under this
+// many bytes: 4 GiB hold about 700 windows of 200 letters, several workgroups for each of the 256 CUs in every sweep launch, and
+// leave most of the HBM to the caller's other contexts.  A chunk has at most kLocalChunkMax windows (a batch is one grid dimension).
+constexpr size_t kLocalChunkBytes = (size_t)4 << 30;
+constexpr int kLocalChunkMax = 32768;
 
 struct GraphSlot {   // one captured launch sequence (see run_graphed)
     hipGraphExec_t exec = nullptr;
@@ -346,6 +354,14 @@ struct Ctx {   // (the fields of rh_ctx, below)
     int n_far[3] = {0, 0, 0};      // of which block-product launches (mccaskill_far.hip)
     bool overlap = true;           // false: duplex, inside and outside sweeps run one after the other (isolated phase timings)
     int time_cls = -1;             // rh_set_kernel_timing: sweep-kernel class whose launches are bracketed by event pairs (-1: none)
+    // rh_local_fold only: the last local result -- its shape, the band bp_band [n][ld], up [n][loc_max_w] and log Z per window on the
+    // device (grow-only, kept until the next rh_local_fold), and the device times rh_local_times reports
+    LocalPlan loc;
+    bool loc_valid = false;
+    int loc_max_w = 1;
+    int loc_chunk = 0;             // rh_set_local_chunk: windows per chunk (0: by kLocalChunkBytes)
+    DevBuf d_loc_bp, d_loc_up, d_loc_logz;
+    double loc_ms[2] = {0, 0};     // folds (sum of the chunks' computes); accumulate + finish + scans since
     std::vector<hipEvent_t> tev;   // event pool of the timed class (pairs), tev_n used by the last compute
     size_t tev_n = 0;
     Ctx() = default;

@@ -1,0 +1,313 @@
+// local_fold.hip -- local folding of a long sequence (rh_local_fold and the rh_local_* fetches): the windows of local_windows.h go
+// through stage() and compute() chunk by chunk as fold-only batches, and the kernels here add each chunk's bp and up tables into
+// band accumulators that stay on the device, divide by the window counts behind the last chunk, and scan the band for candidates.
+//
+// The mean of an entry is a plain double sum over the windows that contain it, in increasing window order, and one division by their
+// number.  The accumulate kernel is a gather: a workgroup owns a row of the band, a lane an entry, and the lane adds its windows in
+// order, carrying the partial sum from chunk to chunk in the accumulator -- so the result does not depend on the chunking, and no
+// atomics are needed.  Row i - start(k) of window k's triangular table is contiguous in j, hence in d = j - i: reads and writes are
+// coalesced, and every table entry of every window is read once.  A row starts from 0 in the first chunk that holds one of its
+// windows (every letter lies in some window), so the accumulators are never cleared as a whole.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "ctx.h"
+#include "kernels.h"
+
+using namespace rh;
+using namespace rh::host;
+
+namespace {
+
+constexpr int kLocalThreads = 256;
+
+struct LocalAcc {
+    LocalPlan P;
+    const double* bp;    // the chunk's posteriors [k1 - k0][tri_stride], each the triangular table of We letters
+    const double* up;    // [k1 - k0][up_stride], We * max_w entries used
+    double* acc_bp;      // [n][ld]
+    double* acc_up;      // [n][max_w]
+    size_t tri_stride, up_stride;
+    int k0, k1;          // the chunk: windows k0 .. k1 - 1
+    int row0;            // first letter of window k0: workgroup b owns row row0 + b
+    int max_w;
+};
+
+// the windows of the chunk that contain letters i .. i+len-1
+__device__ __forceinline__ void chunk_range(const LocalAcc& A, int i, int len, int* lo, int* hi)
+{
+    local_window_range(A.P, i, len, lo, hi);
+    if (*lo < A.k0) *lo = A.k0;
+    if (*hi > A.k1 - 1) *hi = A.k1 - 1;
+}
+
+// grid: the rows row0 .. start(k1 - 1) + We - 1, which the windows of the chunk cover without a gap (S <= W)
+__global__ __launch_bounds__(kLocalThreads) void local_accumulate(LocalAcc A)
+{
+    const int i = A.row0 + blockIdx.x;
+    if (i >= A.P.n) return;
+    int lo1, hi1;
+    local_window_range(A.P, i, 1, &lo1, &hi1);
+    const bool fresh = lo1 >= A.k0;   // the first chunk that touches this row: the sums start from 0
+    const int We = A.P.We;
+    for (int d = threadIdx.x; d < A.P.ld; d += kLocalThreads) {
+        double* out = A.acc_bp + (size_t)i * A.P.ld + d;
+        double s = fresh ? 0.0 : *out;
+        int lo = 1, hi = 0;
+        if (d >= 1) chunk_range(A, i, d + 1, &lo, &hi);
+#pragma unroll 4
+        for (int k = lo; k <= hi; k++) {
+            const int ia = i - local_start(A.P, k) + 1;   // 1-based letter of the window; the pair is (ia, ia + d), ia + d <= We
+            s += A.bp[(size_t)(k - A.k0) * A.tri_stride + (size_t)ia * (size_t)(2 * (We + 1) - ia - 1) / 2 + ia + d];
+        }
+        *out = s;
+    }
+    for (int w = threadIdx.x; w < A.max_w; w += kLocalThreads) {
+        double* out = A.acc_up + (size_t)i * A.max_w + w;
+        double s = fresh ? 0.0 : *out;
+        int lo, hi;
+        chunk_range(A, i, w + 1, &lo, &hi);
+#pragma unroll 4
+        for (int k = lo; k <= hi; k++)
+            s += A.up[(size_t)(k - A.k0) * A.up_stride + (size_t)(i - local_start(A.P, k)) * A.max_w + w];
+        *out = s;
+    }
+}
+
+// sum -> mean, in place: grid (n), one division by the number of windows that contain the run; 0 where none does
+__global__ __launch_bounds__(kLocalThreads) void local_finish(LocalPlan P, int max_w, double* __restrict__ bp, double* __restrict__ up)
+{
+    const int i = blockIdx.x;
+    for (int d = threadIdx.x; d < P.ld + max_w; d += kLocalThreads) {
+        const bool is_up = d >= P.ld;
+        const int len = (is_up ? d - P.ld : d) + 1;
+        double* v = is_up ? up + (size_t)i * max_w + (d - P.ld) : bp + (size_t)i * P.ld + d;
+        int lo, hi;
+        local_window_range(P, i, len, &lo, &hi);
+        *v = hi >= lo ? *v / (double)(hi - lo + 1) : 0.0;
+    }
+}
+
+// ---- ordered threshold compaction over the band or over up, as candidates.hip does it for a batch: one wavefront per row, the
+// probability narrowed to float before the comparison.  Row i holds the entries e0 .. min(width - 1, last - i) at base[i*pitch + e];
+// bp: e = d, e0 = 1, last = n - 1, record (i + 1, i + 1 + d); up: e = w, e0 = 0, last = any, record (i, w).
+struct LocalScan {
+    const double* base;
+    int n, pitch, width, e0, last, is_up;
+    float th;
+};
+__device__ __forceinline__ int scan_end(const LocalScan& V, int i) { return min(V.width - 1, V.last - i); }
+
+__global__ __launch_bounds__(256) void local_cand_count(LocalScan V, int* __restrict__ counts)
+{
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (i >= V.n) return;
+    const double* p = V.base + (size_t)i * V.pitch;
+    const int e1 = scan_end(V, i);
+    int c = 0;
+    for (int e = V.e0 + lane; e <= e1; e += 64) c += ((float)p[e] > V.th) ? 1 : 0;
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    if (lane == 0) counts[i] = c;
+}
+__global__ __launch_bounds__(256) void local_cand_write(LocalScan V, const int* __restrict__ counts, const int* __restrict__ offsets,
+                                                        rh_cand* __restrict__ out, int cap)
+{
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (i >= V.n) return;
+    if (counts[i] == 0) return;
+    const double* p = V.base + (size_t)i * V.pitch;
+    const int e1 = scan_end(V, i);
+    int pos = offsets[i];
+    for (int eb = V.e0; eb <= e1; eb += 64) {
+        const int e = eb + lane;
+        const float pf = e <= e1 ? (float)p[e] : 0.0f;
+        const bool hit = e <= e1 && pf > V.th;
+        const unsigned long long m = __ballot(hit);
+        if (hit) {
+            const int k = pos + __popcll(m & ((1ull << lane) - 1ull));
+            if (k < cap) {
+                rh_cand r;
+                r.i = V.is_up ? i : i + 1;
+                r.j = V.is_up ? e : i + 1 + e;
+                r.p = pf;
+                out[k] = r;
+            }
+        }
+        pos += __popcll(m);
+    }
+}
+
+// an event pair that goes with its scope
+struct EventPair {
+    hipEvent_t a = nullptr, b = nullptr;
+    hipError_t create() { hipError_t e = hipEventCreate(&a); return e != hipSuccess ? e : hipEventCreate(&b); }
+    ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+};
+
+// windows per chunk: what rh_set_local_chunk asked for, or the largest count whose McCaskill tables stay under kLocalChunkBytes
+int chunk_windows(const rh_ctx* c, const LocalPlan& P)
+{
+    int chunk = c->loc_chunk;
+    if (chunk <= 0) {
+        const McBatch B = mc_layout(1, P.We, c->model == RH_MODEL_VIENNA_BL ? (int)VM_COUNT : (int)T_COUNT);
+        const size_t per_window = sizeof(double) * (B.seq_stride + B.pk_stride * kPkCopies + B.tri_stride);
+        chunk = (int)std::min<size_t>(kLocalChunkMax, std::max<size_t>(1, kLocalChunkBytes / per_window));
+        if (chunk > 8) chunk &= ~7;   // (a multiple of the XCD count: xcd_pin)
+    }
+    return std::min(chunk, P.nw);
+}
+
+int local_ready(rh_ctx* c)
+{
+    if (!c->loc_valid) return fail(c, RH_ERR_ARG, "no local fold result");
+    return RH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rh_set_local_chunk(rh_ctx* c, int windows)
+{
+    if (!c) return RH_ERR_ARG;
+    if (windows < 0 || windows > kLocalChunkMax) return fail(c, RH_ERR_ARG, "rh_set_local_chunk: %d windows outside [0, %d]", windows, kLocalChunkMax);
+    c->loc_chunk = windows;
+    return RH_OK;
+}
+
+int rh_local_fold(rh_ctx* c, const char* seq, int n, int window, int step)
+{
+    if (!c) return RH_ERR_ARG;
+    LocalPlan P;
+    std::string why;
+    int rc;
+    if ((rc = local_check(seq, n, window, step, &P, &why))) return fail(c, rc, "%s", why.c_str());
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->loc_valid = false;
+    const int max_w = c->max_w;
+    if ((rc = ensure(c, c->d_loc_bp, sizeof(double) * local_band_size(P), false))) return rc;
+    if ((rc = ensure(c, c->d_loc_up, sizeof(double) * local_up_size(P, max_w), false))) return rc;
+    if ((rc = ensure(c, c->d_loc_logz, sizeof(double) * P.nw, false))) return rc;
+    EventPair ev;
+    HIP_TRY(c, ev.create());
+    const int chunk = chunk_windows(c, P);
+    std::vector<const char*> seqs((size_t)chunk);
+    const std::vector<int> lens((size_t)chunk, P.We);
+    double ms_fold = 0.0, ms_acc = 0.0;
+    float t = 0.f;
+    for (int k0 = 0; k0 < P.nw; k0 += chunk) {
+        const int k1 = std::min(P.nw, k0 + chunk);
+        for (int k = k0; k < k1; k++) seqs[k - k0] = seq + local_start(P, k);
+        BatchRequest r;
+        r.ns = k1 - k0; r.seqs = seqs.data(); r.lens = lens.data();
+        r.with_mc = true;
+        if ((rc = stage(c, r))) return rc;
+        if ((rc = compute(c))) return rc;
+        ms_fold += c->ms[3];
+        LocalAcc A{};
+        A.P = P;
+        A.bp = c->d_bp.as<const double>(); A.up = c->d_up.as<const double>();
+        A.acc_bp = c->d_loc_bp.as<double>(); A.acc_up = c->d_loc_up.as<double>();
+        A.tri_stride = c->mc.tri_stride; A.up_stride = (size_t)c->mc.ld * max_w;
+        A.k0 = k0; A.k1 = k1; A.row0 = local_start(P, k0); A.max_w = max_w;
+        const int rows = local_start(P, k1 - 1) + P.We - A.row0;
+        HIP_TRY(c, hipEventRecord(ev.a, c->s_mc));
+        hipLaunchKernelGGL(local_accumulate, dim3(rows), dim3(kLocalThreads), 0, c->s_mc, A);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(c->d_loc_logz.as<double>() + k0, c->d_mclogz.p, sizeof(double) * (k1 - k0), hipMemcpyDeviceToDevice, c->s_mc));
+        if (k1 == P.nw) {
+            hipLaunchKernelGGL(local_finish, dim3(P.n), dim3(kLocalThreads), 0, c->s_mc, P, max_w, A.acc_bp, A.acc_up);
+            HIP_TRY(c, hipGetLastError());
+        }
+        HIP_TRY(c, hipEventRecord(ev.b, c->s_mc));
+        HIP_TRY(c, hipStreamSynchronize(c->s_mc));   // (the next chunk's stage() reuses the tables this one read)
+        HIP_TRY(c, hipEventElapsedTime(&t, ev.a, ev.b));
+        ms_acc += t;
+    }
+    c->loc = P; c->loc_max_w = max_w;
+    c->loc_ms[0] = ms_fold; c->loc_ms[1] = ms_acc;
+    c->loc_valid = true;
+    return RH_OK;
+}
+
+int rh_local_layout(rh_ctx* c, int* n, int* ld, int* nw, int* max_w, int* starts)
+{
+    if (!c) return RH_ERR_ARG;
+    if (int rc = local_ready(c)) return rc;
+    if (n) *n = c->loc.n;
+    if (ld) *ld = c->loc.ld;
+    if (nw) *nw = c->loc.nw;
+    if (max_w) *max_w = c->loc_max_w;
+    for (int k = 0; starts && k < c->loc.nw; k++) starts[k] = local_start(c->loc, k);
+    return RH_OK;
+}
+
+int rh_local_results(rh_ctx* c, double* bp_band, double* up, double* logz_win)
+{
+    if (!c) return RH_ERR_ARG;
+    if (int rc = local_ready(c)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (bp_band) HIP_TRY(c, hipMemcpyAsync(bp_band, c->d_loc_bp.p, sizeof(double) * local_band_size(c->loc), hipMemcpyDeviceToHost, c->s_mc));
+    if (up) HIP_TRY(c, hipMemcpyAsync(up, c->d_loc_up.p, sizeof(double) * local_up_size(c->loc, c->loc_max_w), hipMemcpyDeviceToHost, c->s_mc));
+    if (logz_win) HIP_TRY(c, hipMemcpyAsync(logz_win, c->d_loc_logz.p, sizeof(double) * c->loc.nw, hipMemcpyDeviceToHost, c->s_mc));
+    HIP_TRY(c, hipStreamSynchronize(c->s_mc));
+    return RH_OK;
+}
+
+int rh_local_candidates(rh_ctx* c, int what, float threshold, rh_cand* out, int cap)
+{
+    if (!c) return RH_ERR_ARG;
+    if (int rc = local_ready(c)) return rc;
+    if ((what != 0 && what != 1) || cap < 0 || (cap > 0 && !out)) return fail(c, RH_ERR_ARG, "rh_local_candidates: bad what/cap");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const LocalPlan& P = c->loc;
+    const int n = P.n;
+    const LocalScan V = what == 0 ? LocalScan{c->d_loc_bp.as<const double>(), n, P.ld, P.ld, 1, n - 1, 0, threshold}
+                                  : LocalScan{c->d_loc_up.as<const double>(), n, c->loc_max_w, c->loc_max_w, 0, n - 1 + c->loc_max_w, 1, threshold};
+    int rc;
+    if ((rc = ensure(c, c->d_cnt, sizeof(int) * 2 * ((size_t)n + 1), false))) return rc;
+    int* d_counts = c->d_cnt.as<int>();
+    int* d_offsets = d_counts + (n + 1);
+    EventPair ev;
+    HIP_TRY(c, ev.create());
+    float t = 0.f;
+    HIP_TRY(c, hipEventRecord(ev.a, c->s_mc));
+    hipLaunchKernelGGL(local_cand_count, dim3((n + 3) / 4), dim3(256), 0, c->s_mc, V, d_counts);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(ev.b, c->s_mc));
+    std::vector<int> counts(n), offsets(n);
+    HIP_TRY(c, hipMemcpyAsync(counts.data(), d_counts, sizeof(int) * n, hipMemcpyDeviceToHost, c->s_mc));
+    HIP_TRY(c, hipStreamSynchronize(c->s_mc));
+    HIP_TRY(c, hipEventElapsedTime(&t, ev.a, ev.b));
+    c->loc_ms[1] += t;
+    long long found = 0;
+    for (int i = 0; i < n; i++) { offsets[i] = (int)std::min<long long>(found, cap); found += counts[i]; }
+    if (found > 0x7fffffffLL) return fail(c, RH_ERR_UNSUPPORTED, "rh_local_candidates: %lld entries above the threshold", found);
+    const int take = (int)std::min<long long>(found, cap);
+    if (take > 0) {
+        if ((rc = ensure(c, c->d_cand, sizeof(rh_cand) * (size_t)take, false))) return rc;
+        HIP_TRY(c, hipMemcpyAsync(d_offsets, offsets.data(), sizeof(int) * n, hipMemcpyHostToDevice, c->s_mc));
+        HIP_TRY(c, hipEventRecord(ev.a, c->s_mc));
+        hipLaunchKernelGGL(local_cand_write, dim3((n + 3) / 4), dim3(256), 0, c->s_mc, V, d_counts, d_offsets, c->d_cand.as<rh_cand>(), take);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipEventRecord(ev.b, c->s_mc));
+        HIP_TRY(c, hipMemcpyAsync(out, c->d_cand.p, sizeof(rh_cand) * (size_t)take, hipMemcpyDeviceToHost, c->s_mc));
+        HIP_TRY(c, hipStreamSynchronize(c->s_mc));
+        HIP_TRY(c, hipEventElapsedTime(&t, ev.a, ev.b));
+        c->loc_ms[1] += t;
+    }
+    return (int)found;
+}
+
+int rh_local_times(rh_ctx* c, double ms[2])
+{
+    if (!c || !ms) return RH_ERR_ARG;
+    if (int rc = local_ready(c)) return rc;
+    ms[0] = c->loc_ms[0]; ms[1] = c->loc_ms[1];
+    return RH_OK;
+}
+
+}  // extern "C"

@@ -26,6 +26,7 @@ EXPORTS = [
     "rh_batch_upload_indexed", "rh_batch_index", "rh_batch_candidates_seq_all", "rh_batch_upload_indexed_constrained",
     "rh_batch_packed_layout", "rh_batch_results_packed_f32", "rh_batch_pack_time",
     "rh_set_region_accessibility", "rh_get_region_accessibility", "rh_batch_acc_time",
+    "rh_local_fold", "rh_local_layout", "rh_local_results", "rh_local_candidates", "rh_set_local_chunk", "rh_local_times",
     "rh_debug_vienna_cell", "rh_debug_vienna_value",   # loader inspection (host only; used by the CPU tests of the loader)
 ]
 
@@ -130,6 +131,18 @@ def load_library():
     L.rh_get_region_accessibility.restype = ci
     L.rh_batch_acc_time.argtypes = [vp, vp]
     L.rh_batch_acc_time.restype = ci
+    L.rh_local_fold.argtypes = [vp, cp, ci, ci, ci]
+    L.rh_local_fold.restype = ci
+    L.rh_local_layout.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.rh_local_layout.restype = ci
+    L.rh_local_results.argtypes = [vp, vp, vp, vp]
+    L.rh_local_results.restype = ci
+    L.rh_local_candidates.argtypes = [vp, ci, ctypes.c_float, vp, ci]
+    L.rh_local_candidates.restype = ci
+    L.rh_set_local_chunk.argtypes = [vp, ci]
+    L.rh_set_local_chunk.restype = ci
+    L.rh_local_times.argtypes = [vp, vp]
+    L.rh_local_times.restype = ci
     L.rh_host_alloc.restype = vp
     L.rh_host_alloc.argtypes = [vp, ctypes.c_size_t]
     L.rh_host_free.restype = None
@@ -148,6 +161,20 @@ def tri_size(n):
 
 def tri_offset(n, i):
     return i * (2 * (n + 1) - i - 1) // 2
+
+
+def band_to_tri(bp_band):
+    """The reference's triangular layout (tri_size(n) doubles, pair (i, j) 1-based at tri_offset(n, i) + j) of a band
+    bp_band[i, d] = bp(i, i + d), 0-based i, as Context.local_fold returns it -- for n small enough to hold the triangle.  Pairs
+    further apart than the band is wide are 0."""
+    band = np.asarray(bp_band)
+    n, ld = band.shape
+    tri = np.zeros(tri_size(n), dtype=band.dtype)
+    for i in range(n):
+        m = min(ld - 1, n - 1 - i)
+        at = tri_offset(n, i + 1) + i + 2
+        tri[at:at + m] = band[i, 1:1 + m]
+    return tri
 
 
 def index_pairs(pairs):
@@ -303,6 +330,43 @@ class Context:
         self._check(self.L.rh_cofold_constrained(self.h, s1.encode(), len(s1), s2.encode(), len(s2),
                                                  constraint.encode() if constraint is not None else None, hp.ctypes.data, ctypes.addressof(z)))
         return hp, z.value
+
+    # ---- local folding
+    def local_fold(self, seq, window, step=1):
+        """Window-averaged bp and accessibility of a long sequence (rh_local_fold): every window of `window` letters, one every
+        `step` letters and a last one that ends at the last letter, is folded on its own, and each probability is the mean over the
+        windows that contain it.  Returns (bp_band, up, logz, starts): bp_band (n, ld) with bp_band[i, d] = bp(i, i + d), 0-based,
+        ld = min(window, n); up (n, max_w); log Z and start of every window.  band_to_tri gives the triangular layout."""
+        self._check(self.L.rh_local_fold(self.h, seq.encode(), len(seq), window, step))
+        return self.local_results()
+
+    def local_results(self):
+        """(bp_band, up, logz, starts) of the last local_fold, which stays fetchable until the next one (rh_local_results)."""
+        n, ld, nw, w = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        self._check(self.L.rh_local_layout(self.h, ctypes.byref(n), ctypes.byref(ld), ctypes.byref(nw), ctypes.byref(w), None))
+        band, up = np.empty((n.value, ld.value)), np.empty((n.value, w.value))
+        logz, starts = np.empty(nw.value), np.empty(nw.value, dtype=np.int32)
+        self._check(self.L.rh_local_layout(self.h, None, None, None, None, starts.ctypes.data))
+        self._check(self.L.rh_local_results(self.h, band.ctypes.data, up.ctypes.data, logz.ctypes.data))
+        return band, up, logz, starts
+
+    def local_candidates(self, what, threshold, cap=1 << 22):
+        """Thresholded list of the last local_fold, scanned on the device (rh_local_candidates): what = 0 the pairs (1-based i < j),
+        1 the accessibilities (0-based position, width index).  Returns (records, total): a structured array (i, j, p) of
+        min(total, cap) records in row-major order, and the number found."""
+        buf = np.empty(max(cap, 1), dtype=self.CAND_DTYPE)
+        k = self._check(self.L.rh_local_candidates(self.h, what, ctypes.c_float(threshold), buf.ctypes.data, cap))
+        return buf[:min(k, cap)], k
+
+    def set_local_chunk(self, windows):
+        """Windows per chunk of local_fold (0: automatic, by the byte budget of the McCaskill tables); results are unchanged."""
+        self._check(self.L.rh_set_local_chunk(self.h, windows))
+
+    def local_times(self):
+        """Device time (ms) of the last local_fold: (folds, accumulate + finish + the scans since)."""
+        ms = (ctypes.c_double * 2)()
+        self._check(self.L.rh_local_times(self.h, ms))
+        return ms[0], ms[1]
 
     # ---- batched calls
     def batch_upload(self, pairs, constraints=None, co_constraints=None):

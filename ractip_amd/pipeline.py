@@ -2,10 +2,12 @@
 integer programme (ractip_amd/ilp.py).  What `ractip s1.fa s2.fa` prints (/root/reference/src/ractip.cpp:1561-1610),
 without z-scores and energies.
 
-  python -m ractip_amd.pipeline [--contrafold] [--duplex] [--use-constraint] [--write-rip FILE] a.fa b.fa
+  python -m ractip_amd.pipeline [--contrafold] [--duplex] [--use-constraint] [--window W [--step S]] [--write-rip FILE] a.fa b.fa
 
 --use-constraint: the structure line that follows each sequence in its FASTA file constrains the folds and the two-molecule
 ensemble, as RactIP's -c does (src/ractip.cpp:271-291, 405-447); default path only.
+--window W [--step S]: local folding -- bp and up of both molecules are averages over windows of W letters, one every S letters
+(Context.local_fold: the quantity RNAplfold defines), for targets too long to fold as a whole; hp comes from the pair as before.
 --write-rip FILE: also write bp1, bp2, hp as RIP tables (ractip_amd/rip.py) for a stock `ractip --rip FILE --min-w 0`.
 """
 import sys
@@ -85,20 +87,68 @@ def probabilities(ctx, s1, s2, structures=None):
     return ctx.batch_results(0)
 
 
-def predict(s1, s2, model="vienna", duplex=False, device=0, options=None, ctx=None, rip_path=None, structures=None, accessibility=False):
+def _set_up(ctx, model, opt, duplex, accessibility):
+    """the context's settings for one of predict's paths"""
+    if model == "vienna":
+        ctx.set_max_w(max(1, opt.max_w))
+        ctx.set_hybrid(not duplex)
+    elif accessibility:
+        ctx.set_region_accessibility(True)
+        ctx.set_max_w(max(1, opt.max_w))
+
+
+def local_fold(seq, window, step=1, model="vienna", accessibility=False, device=0, options=None, ctx=None):
+    """Window-averaged probabilities of one long sequence: dict(bp_band (n, ld), up (n, max_w), logz, starts) of
+    Context.local_fold under predict's settings of model / accessibility / options.max_w."""
+    own = ctx is None
+    if own:
+        ctx = hot.Context(device=device, model=hot.RH_MODEL_VIENNA_BL if model == "vienna" else hot.RH_MODEL_CONTRAFOLD)
+    try:
+        _set_up(ctx, model, options or ilp.Options(), False, accessibility)
+        band, up, logz, starts = ctx.local_fold(seq, window, step)
+        return dict(bp_band=band, up=up, logz=logz, starts=starts)
+    finally:
+        if own:
+            ctx.close()
+
+
+def _predict_local(ctx, s1, s2, model, duplex, opt, default_options, rip_path, accessibility, window, step):
+    """predict with bp and up of both molecules from local folds; hp from the pair path as before"""
+    _set_up(ctx, model, opt, duplex, accessibility)
+    hp = probabilities(ctx, s1, s2)["hp"]   # (fetched before the local folds take the context's batch)
+    bp, up = [], []
+    for s in (s1, s2):
+        band, u, _, _ = ctx.local_fold(s, window, step)
+        bp.append(hot.band_to_tri(band))
+        up.append(u)
+    if rip_path:
+        rip.write_rip(rip_path, s1, s2, bp[0], bp[1], hp)
+    if model == "vienna" or accessibility:
+        return ilp.solve(s1, s2, bp[0], bp[1], hp, up[0], up[1], opt)
+    return ilp.solve(s1, s2, bp[0], bp[1], hp, None, None, ilp.Options(min_w=0) if default_options else opt)
+
+
+def predict(s1, s2, model="vienna", duplex=False, device=0, options=None, ctx=None, rip_path=None, structures=None, accessibility=False,
+            window=None, step=1):
     """model "vienna": RactIP's default path (rnafold + rnaduplex; duplex=True = --duplex, else co_pf_fold), parity
     unpinned; model "contrafold": the --contrafold path (bp from the CONTRAfold engine, width-1 up, accessibility off as
     src/ractip.cpp:1511-1517 demands), hp from the CONTRAfold duplex engine.  structures = (str1, str2): the FASTA structure
     lines, used as constraints (--use-constraint; model "vienna" only).  accessibility=True with model "contrafold" (an extension:
     the reference has no such combination) turns the context's region accessibility on and hands up[i][w], widths 1..options.max_w,
-    to the ILP as the default path does."""
+    to the ILP as the default path does.  window=W (and step): bp and up of both molecules are window averages from
+    Context.local_fold instead of whole-sequence folds (no structure constraints); with W no shorter than either molecule the
+    probabilities, and so the structures, are those of the whole-sequence folds."""
     if structures is not None and model != "vienna":
         raise ValueError("structure constraints apply to the default (Vienna-BL) path only")
+    if structures is not None and window is not None:
+        raise ValueError("local folding takes no structure constraints")
     own = ctx is None
     if own:
         ctx = hot.Context(device=device, model=hot.RH_MODEL_VIENNA_BL if model == "vienna" else hot.RH_MODEL_CONTRAFOLD)
     try:
         opt = options or ilp.Options()
+        if window is not None:
+            return _predict_local(ctx, s1, s2, model, duplex, opt, options is None, rip_path, accessibility, window, step)
         if model == "vienna":
             ctx.set_max_w(max(1, opt.max_w))
             ctx.set_hybrid(not duplex)
@@ -244,6 +294,15 @@ def main(argv):
         k = argv.index("--write-rip")
         rip_path = argv[k + 1]
         argv = argv[:k] + argv[k + 2:]
+    window, step = None, 1
+    for flag in ("--window", "--step"):
+        if flag in argv:
+            k = argv.index(flag)
+            if flag == "--window":
+                window = int(argv[k + 1])
+            else:
+                step = int(argv[k + 1])
+            argv = argv[:k] + argv[k + 2:]
     flags = [a for a in argv if a.startswith("--")]
     files = [a for a in argv if not a.startswith("--")]
     if len(files) != 2:
@@ -251,7 +310,7 @@ def main(argv):
     (n1, s1, t1), (n2, s2, t2) = read_fasta_with_structure(files[0]), read_fasta_with_structure(files[1])
     structures = (t1, t2) if "--use-constraint" in flags else None
     r1, r2, _ = predict(s1, s2, model="contrafold" if "--contrafold" in flags else "vienna", duplex="--duplex" in flags, rip_path=rip_path,
-                        structures=structures)
+                        structures=structures, window=window, step=step)
     print(">%s\n%s\n%s\n>%s\n%s\n%s" % (n1, s1, r1, n2, s2, r2))   # src/ractip.cpp:1607-1610
 
 
