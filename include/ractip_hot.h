@@ -399,11 +399,48 @@ int rh_local_results(rh_ctx* ctx, double* bp_band, double* up, double* logz_win)
  * float narrowing and the p > threshold comparison of rh_batch_candidates.  Writes at most `cap` records, returns the total found. */
 int rh_local_candidates(rh_ctx* ctx, int what, float threshold, rh_cand* out, int cap);
 /* Test and measurement aid: windows per chunk of rh_local_fold, 1..32768; 0 (default) = automatic, the largest chunk whose McCaskill
- * tables stay under the byte budget kLocalChunkBytes of ractip_amd/csrc/ctx.h (4 GiB).  Results are unchanged. */
+ * tables stay under the byte budget kLocalChunkBytes of ractip_amd/csrc/local_windows.h (4 GiB).  Under rh_local_duplex a window's
+ * bytes also count its pair (hybridization tables, hp block, under RH_HYBRID_COFOLD the tables of query + window), the query's fold
+ * counts once per chunk, and a chunk has at most 32767 windows.  Results are unchanged. */
 int rh_set_local_chunk(rh_ctx* ctx, int windows);
 /* Measurement aid: device time (ms, HIP event pairs) of the last rh_local_fold: ms[0] the folds (the computes of its chunks), ms[1]
  * the accumulate and finish kernels, plus the scan kernels of the rh_local_candidates calls since. */
 int rh_local_times(rh_ctx* ctx, double ms[2]);
+
+/* ---- local hybridization: window-averaged hp of a query on a long target ----
+ * Two molecules s1 (n1 letters) and s2 (n2 letters).  `windowed` (1 or 2) names the one that is cut into the windows of rh_local_fold
+ * (same W, S, We, starts); the other one, the query, is always whole.  For window k the engine computes hp_k of the pair
+ * (query, window k) if windowed = 2, (window k, query) if windowed = 1, under the context's model, arithmetic mode, rh_set_hybrid and
+ * rh_set_duplex_mode settings, without constraints.
+ *   hp_loc(i, j), 1-based letters of s1 and s2: the mean of hp_k at the translated coordinates over the windows that contain the
+ *     windowed molecule's letter -- a plain double sum in increasing window order, then ONE division by the count, the rule of bp_loc;
+ *     the order is part of the interface and the bits do not depend on the chunking.  Every letter lies in a window: no holes.
+ *   logz_pair[k]: log Z of the two-molecule or duplex ensemble of window k.
+ * Layout of hp: (n1+1) * (n2+1) doubles, row-major, 1-based, row 0 and column 0 zero -- what rh_duplex returns; offsets are size_t.
+ * WHAT THE MEAN MEANS depends on the hybridization source.  Under the duplex-only sources (the CONTRAfold DuplexEngine, Vienna
+ * pf_duplex) each window's ensemble is normalized over the duplexes inside that window: a window without the true site still spends
+ * its whole probability somewhere, and the mean is a probability GIVEN THAT THE QUERY BINDS IN THE WINDOW.  Under RH_HYBRID_COFOLD
+ * the ensemble of a window includes the unbound state, and the mean is a probability in RNAplfold's sense.  No Z-weighted
+ * combination of the windows is offered for the duplex sources.
+ *
+ * rh_local_duplex checks its arguments first ("local duplex: ..."): a rejected call (RH_ERR_ARG) leaves the previous local result,
+ * the previous local hp result and the previous batch in place.  Then it runs chunks of consecutive windows, each an indexed batch
+ * (rh_batch_upload_indexed) whose sequence 0 is the query and whose sequences 1..c are windows, paired (0, k) or (k, 0).  For the
+ * windowed molecule the call is also rh_local_fold: bp_band, up and logz_win of that molecule carry the bits a plain rh_local_fold
+ * gives and are served by rh_local_layout / rh_local_results / rh_local_candidates / rh_local_times (whose accumulate time then
+ * includes the hp kernels).  The query's own bp / up are not part of the local result (rh_fold).  Afterwards the context's batch is
+ * the last chunk, an ordinary computed indexed batch.
+ * One window (W >= the windowed molecule): hp and logz_pair[0] have the bits of rh_duplex(s1, s2) under the same settings.  Under
+ * RH_HYBRID_COFOLD that call's two-molecule sweeps are not seeded from folds (it has none), so the one compute of a one-window call
+ * is not either; with two windows or more the chunks are seeded like every batch with folds, whose hp differs from the unseeded
+ * one in the last bits on the scaled linear path. */
+int rh_local_duplex(rh_ctx* ctx, const char* s1, int n1, const char* s2, int n2, int windowed, int window, int step);
+/* shape of the last local hp result; any pointer may be NULL.  "no local hybridization result" before the first rh_local_duplex and
+ * after a later rh_local_fold, which replaces the fold part and drops the hp part. */
+int rh_local_hp_layout(rh_ctx* ctx, int* n1, int* n2, int* windowed, int* nw);
+/* hp_loc and logz_pair (nw doubles) in the layout above; any pointer may be NULL.  rh_local_candidates(what = 2) scans hp_loc on the
+ * device: records (i, j) 1-based over 1..n1 x 1..n2 in row-major order, narrowed to float before p > threshold. */
+int rh_local_hp_results(rh_ctx* ctx, double* hp, double* logz_pair);
 
 /* ---- loader inspection (host only, no GPU, no context) ----
  * What the parameter loader holds after binding its sources, for checks of the binding itself (tests/test_bl_cells.py,

@@ -63,13 +63,6 @@ struct VLinSet {
     ~VLinSet() { delete h; }
 };
 
-// Local folding (local_fold.hip): the windows of a long sequence are folded in chunks of consecutive windows, each chunk a fold-only
-// batch.  Automatic chunking takes the largest chunk whose McCaskill tables (DP tables, operand tiles, posteriors) stay under this
-// many bytes: 4 GiB hold about 700 windows of 200 letters, several workgroups for each of the 256 CUs in every sweep launch, and
-// leave most of the HBM to the caller's other contexts.  A chunk has at most kLocalChunkMax windows (a batch is one grid dimension).
-constexpr size_t kLocalChunkBytes = (size_t)4 << 30;
-constexpr int kLocalChunkMax = 32768;
-
 struct GraphSlot {   // one captured launch sequence (see run_graphed)
     hipGraphExec_t exec = nullptr;
     size_t key = 0;   // hash of the argument(s) it was captured with
@@ -361,6 +354,11 @@ struct Ctx {   // (the fields of rh_ctx, below)
     int loc_max_w = 1;
     int loc_chunk = 0;             // rh_set_local_chunk: windows per chunk (0: by kLocalChunkBytes)
     DevBuf d_loc_bp, d_loc_up, d_loc_logz;
+    // rh_local_duplex only: the hp part of the last local result -- hp_loc [(n1+1)][(n2+1)] and log Z per window pair on the device;
+    // dropped by the next rh_local_fold, replaced by the next rh_local_duplex
+    LocalDuplexPlan loc_hp;
+    bool loc_hp_valid = false;
+    DevBuf d_loc_hp, d_loc_logzp;
     double loc_ms[2] = {0, 0};     // folds (sum of the chunks' computes); accumulate + finish + scans since
     std::vector<hipEvent_t> tev;   // event pool of the timed class (pairs), tev_n used by the last compute
     size_t tev_n = 0;

@@ -8,6 +8,10 @@
 // atomics are needed.  Row i - start(k) of window k's triangular table is contiguous in j, hence in d = j - i: reads and writes are
 // coalesced, and every table entry of every window is read once.  A row starts from 0 in the first chunk that holds one of its
 // windows (every letter lies in some window), so the accumulators are never cleared as a whole.
+//
+// Local hybridization (rh_local_duplex) runs the same chunks with a query in front of the windows: sequence 0 of every chunk is the
+// query, pair k the query with window k, and local_hp_accumulate / local_hp_finish average the chunk's hp blocks into hp_loc by the
+// same rule, next to the band of the windowed molecule, which the kernels above accumulate from sequences 1..c.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -23,6 +27,7 @@ using namespace rh::host;
 namespace {
 
 constexpr int kLocalThreads = 256;
+constexpr int kLocalGridRows = 65535;   // second grid dimension of the hp kernels: rows beyond it are walked
 
 struct LocalAcc {
     LocalPlan P;
@@ -91,12 +96,71 @@ __global__ __launch_bounds__(kLocalThreads) void local_finish(LocalPlan P, int m
     }
 }
 
+// ---- hp_loc [(n1+1)][(n2+1)], row-major, 1-based, from the hp blocks of the chunk's pairs [k1 - k0][hp_stride] (row pitch ldd, 1-based:
+// DxBatch::hp).  A lane owns one entry (i, j), lanes consecutive in j.  windowed = 2: pair k is (query, window k) and the lane reads
+// block k at (i, j - start(k)); windowed = 1: (window k, query), read at (i - start(k), j).  Either way the reads of a wavefront are
+// contiguous in j, like its writes.
+struct LocalHpAcc {
+    LocalPlan P;         // of the windowed molecule
+    const double* hp;
+    double* acc;
+    size_t hp_stride;
+    int ldd, n1, n2, windowed;
+    int k0, k1;          // the chunk: windows k0 .. k1 - 1
+    int t0, nt;          // the letters (0-based) of the windowed molecule its windows cover: t0 .. t0 + nt - 1, without a gap
+};
+
+// grid (column blocks, rows): only the columns (windowed = 2) or rows (windowed = 1) of the chunk's letters; rows beyond the grid's
+// second dimension are walked
+__global__ __launch_bounds__(kLocalThreads) void local_hp_accumulate(LocalHpAcc A)
+{
+    const bool w2 = A.windowed == 2;
+    const int cols = w2 ? A.nt : A.n2, rows = w2 ? A.n1 : A.nt;
+    const int col = blockIdx.x * kLocalThreads + threadIdx.x;
+    if (col >= cols) return;
+    const int j = (w2 ? A.t0 : 0) + 1 + col;
+    for (int r = blockIdx.y; r < rows; r += gridDim.y) {
+        const int i = (w2 ? 0 : A.t0) + 1 + r;
+        int lo, hi;
+        local_window_range(A.P, (w2 ? j : i) - 1, 1, &lo, &hi);
+        const bool fresh = lo >= A.k0;   // the first chunk that holds one of the letter's windows: the sum starts from 0
+        if (lo < A.k0) lo = A.k0;
+        if (hi > A.k1 - 1) hi = A.k1 - 1;
+        double* out = A.acc + (size_t)i * ((size_t)A.n2 + 1) + j;
+        double s = fresh ? 0.0 : *out;
+#pragma unroll 4
+        for (int k = lo; k <= hi; k++) {
+            const int st = local_start(A.P, k);
+            const double* blk = A.hp + (size_t)(k - A.k0) * A.hp_stride;
+            s += w2 ? blk[(size_t)i * A.ldd + (j - st)] : blk[(size_t)(i - st) * A.ldd + j];
+        }
+        *out = s;
+    }
+}
+
+// sum -> mean, in place, over all of (0..n1) x (0..n2): one division by the number of windows that contain the letter (at least one);
+// row 0 and column 0 are written as 0
+__global__ __launch_bounds__(kLocalThreads) void local_hp_finish(LocalPlan P, int n1, int n2, int windowed, double* __restrict__ hp)
+{
+    const int j = blockIdx.x * kLocalThreads + threadIdx.x;
+    if (j > n2) return;
+    for (int i = blockIdx.y; i <= n1; i += gridDim.y) {
+        double* v = hp + (size_t)i * ((size_t)n2 + 1) + j;
+        if (i == 0 || j == 0) { *v = 0.0; continue; }
+        int lo, hi;
+        local_window_range(P, (windowed == 2 ? j : i) - 1, 1, &lo, &hi);
+        *v = *v / (double)(hi - lo + 1);
+    }
+}
+
 // ---- ordered threshold compaction over the band or over up, as candidates.hip does it for a batch: one wavefront per row, the
 // probability narrowed to float before the comparison.  Row i holds the entries e0 .. min(width - 1, last - i) at base[i*pitch + e];
-// bp: e = d, e0 = 1, last = n - 1, record (i + 1, i + 1 + d); up: e = w, e0 = 0, last = any, record (i, w).
+// bp: e = d, e0 = 1, last = n - 1, record (i + 1, i + 1 + d); up: e = w, e0 = 0, last = any, record (i, w); hp: the rows 1..n1 of
+// hp_loc (base = its row 1), e = j, e0 = 1, last = any, record (i + 1, j).
+enum LocalScanKind { kScanBp = 0, kScanUp, kScanHp };
 struct LocalScan {
     const double* base;
-    int n, pitch, width, e0, last, is_up;
+    int n, pitch, width, e0, last, kind;
     float th;
 };
 __device__ __forceinline__ int scan_end(const LocalScan& V, int i) { return min(V.width - 1, V.last - i); }
@@ -130,8 +194,8 @@ __global__ __launch_bounds__(256) void local_cand_write(LocalScan V, const int* 
             const int k = pos + __popcll(m & ((1ull << lane) - 1ull));
             if (k < cap) {
                 rh_cand r;
-                r.i = V.is_up ? i : i + 1;
-                r.j = V.is_up ? e : i + 1 + e;
+                r.i = V.kind == kScanUp ? i : i + 1;
+                r.j = V.kind == kScanBp ? i + 1 + e : e;
                 r.p = pf;
                 out[k] = r;
             }
@@ -147,22 +211,126 @@ struct EventPair {
     ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
 };
 
-// windows per chunk: what rh_set_local_chunk asked for, or the largest count whose McCaskill tables stay under kLocalChunkBytes
-int chunk_windows(const rh_ctx* c, const LocalPlan& P)
+// the table counts the context's model sizes a chunk by (staging.hip)
+LocalTables local_tables(const rh_ctx* c)
+{
+    const bool vienna = c->model == RH_MODEL_VIENNA_BL;
+    LocalTables T;
+    T.fold = vienna ? (int)VM_COUNT : (int)T_COUNT;
+    T.dx = std::max((int)D_COUNT, (int)V_COUNT);
+    T.dxl = !vienna ? (int)DL_COUNT : c->vienna_sem == kViennaSem20 ? (int)VD_COUNT20 : (int)VD_COUNT;
+    T.cofold = vienna && c->hybrid == RH_HYBRID_COFOLD;
+    return T;
+}
+
+// windows per chunk: what rh_set_local_chunk asked for, or the largest count whose tables stay under kLocalChunkBytes; D: the chunks
+// of rh_local_duplex, which hold the query as well
+int chunk_windows(const rh_ctx* c, const LocalPlan& P, const LocalDuplexPlan* D)
 {
     int chunk = c->loc_chunk;
-    if (chunk <= 0) {
-        const McBatch B = mc_layout(1, P.We, c->model == RH_MODEL_VIENNA_BL ? (int)VM_COUNT : (int)T_COUNT);
-        const size_t per_window = sizeof(double) * (B.seq_stride + B.pk_stride * kPkCopies + B.tri_stride);
-        chunk = (int)std::min<size_t>(kLocalChunkMax, std::max<size_t>(1, kLocalChunkBytes / per_window));
-        if (chunk > 8) chunk &= ~7;   // (a multiple of the XCD count: xcd_pin)
-    }
+    if (chunk <= 0) chunk = D ? local_duplex_chunk_auto(*D, local_tables(c)) : local_chunk_auto(P, local_tables(c));
+    if (D) chunk = std::min(chunk, kLocalChunkMax - 1);
     return std::min(chunk, P.nw);
 }
 
 int local_ready(rh_ctx* c)
 {
     if (!c->loc_valid) return fail(c, RH_ERR_ARG, "no local fold result");
+    return RH_OK;
+}
+
+int local_hp_ready(rh_ctx* c)
+{
+    if (!c->loc_valid || !c->loc_hp_valid) return fail(c, RH_ERR_ARG, "no local hybridization result");
+    return RH_OK;
+}
+
+// The scheduler of rh_local_fold (D == nullptr) and rh_local_duplex over checked arguments: chunks of consecutive windows of `seq`,
+// each one batch through stage() and compute() -- fold-only, or indexed with the query as sequence 0 and the pairs (0, k) / (k, 0) --
+// and behind each compute the accumulate kernels, behind the last one the finish kernels.
+int local_run(rh_ctx* c, const LocalPlan& P, const char* seq, const LocalDuplexPlan* D, const char* query)
+{
+    int rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->loc_valid = c->loc_hp_valid = false;
+    const int max_w = c->max_w;
+    const int q = D ? 1 : 0;   // sequences in front of the windows
+    if ((rc = ensure(c, c->d_loc_bp, sizeof(double) * local_band_size(P), false))) return rc;
+    if ((rc = ensure(c, c->d_loc_up, sizeof(double) * local_up_size(P, max_w), false))) return rc;
+    if ((rc = ensure(c, c->d_loc_logz, sizeof(double) * P.nw, false))) return rc;
+    if (D && (rc = ensure(c, c->d_loc_hp, sizeof(double) * local_hp_size(*D), false))) return rc;
+    if (D && (rc = ensure(c, c->d_loc_logzp, sizeof(double) * P.nw, false))) return rc;
+    EventPair ev;
+    HIP_TRY(c, ev.create());
+    const int chunk = chunk_windows(c, P, D);
+    std::vector<const char*> seqs((size_t)chunk + q);
+    std::vector<int> lens((size_t)chunk + q, P.We), first, second;
+    if (D) {
+        seqs[0] = query; lens[0] = D->nq;
+        first.assign((size_t)chunk, 0); second.assign((size_t)chunk, 0);
+        std::vector<int>& win = D->windowed == 2 ? second : first;
+        for (int k = 0; k < chunk; k++) win[k] = 1 + k;
+    }
+    double ms_fold = 0.0, ms_acc = 0.0;
+    float t = 0.f;
+    for (int k0 = 0; k0 < P.nw; k0 += chunk) {
+        const int k1 = std::min(P.nw, k0 + chunk);
+        for (int k = k0; k < k1; k++) seqs[q + k - k0] = seq + local_start(P, k);
+        BatchRequest r;
+        r.ns = q + k1 - k0; r.seqs = seqs.data(); r.lens = lens.data();
+        r.with_mc = true;
+        if (D) { r.with_dx = true; r.npairs = k1 - k0; r.first = first.data(); r.second = second.data(); }
+        if ((rc = stage(c, r))) return rc;
+        // One window (W >= n) is the pair itself, and the call answers with the bits of rh_duplex: under RH_HYBRID_COFOLD that call
+        // has no folds to seed its two-molecule sweeps from, and seeded sweeps differ from it in the last bits on the scaled linear
+        // kernels -- so this one compute runs them unseeded too.  With two windows or more every chunk is seeded, like any batch.
+        const int seed = c->co_seed;
+        if (D && P.nw == 1) c->co_seed = 0;
+        rc = compute(c);
+        c->co_seed = seed;
+        if (rc) return rc;
+        ms_fold += c->ms[3];
+        LocalAcc A{};
+        A.P = P;
+        A.tri_stride = c->mc.tri_stride; A.up_stride = (size_t)c->mc.ld * max_w;
+        A.bp = c->d_bp.as<const double>() + q * A.tri_stride; A.up = c->d_up.as<const double>() + q * A.up_stride;
+        A.acc_bp = c->d_loc_bp.as<double>(); A.acc_up = c->d_loc_up.as<double>();
+        A.k0 = k0; A.k1 = k1; A.row0 = local_start(P, k0); A.max_w = max_w;
+        const int rows = local_start(P, k1 - 1) + P.We - A.row0;
+        HIP_TRY(c, hipEventRecord(ev.a, c->s_mc));
+        hipLaunchKernelGGL(local_accumulate, dim3(rows), dim3(kLocalThreads), 0, c->s_mc, A);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(c->d_loc_logz.as<double>() + k0, c->d_mclogz.as<const double>() + q, sizeof(double) * (k1 - k0), hipMemcpyDeviceToDevice, c->s_mc));
+        if (D) {
+            LocalHpAcc H{};
+            H.P = P;
+            H.hp = c->d_hp.as<const double>(); H.acc = c->d_loc_hp.as<double>();
+            H.hp_stride = c->dx.tab_stride; H.ldd = c->dx.ldd;
+            H.n1 = D->n1; H.n2 = D->n2; H.windowed = D->windowed;
+            H.k0 = k0; H.k1 = k1; H.t0 = A.row0; H.nt = rows;
+            const int cols = D->windowed == 2 ? rows : D->n2, lines = D->windowed == 2 ? D->n1 : rows;
+            hipLaunchKernelGGL(local_hp_accumulate, dim3((cols + kLocalThreads - 1) / kLocalThreads, std::min(lines, kLocalGridRows)), dim3(kLocalThreads), 0, c->s_mc, H);
+            HIP_TRY(c, hipGetLastError());
+            HIP_TRY(c, hipMemcpyAsync(c->d_loc_logzp.as<double>() + k0, c->d_logz.p, sizeof(double) * (k1 - k0), hipMemcpyDeviceToDevice, c->s_mc));
+        }
+        if (k1 == P.nw) {
+            hipLaunchKernelGGL(local_finish, dim3(P.n), dim3(kLocalThreads), 0, c->s_mc, P, max_w, A.acc_bp, A.acc_up);
+            HIP_TRY(c, hipGetLastError());
+            if (D) {
+                hipLaunchKernelGGL(local_hp_finish, dim3((D->n2 + 1 + kLocalThreads - 1) / kLocalThreads, std::min(D->n1 + 1, kLocalGridRows)), dim3(kLocalThreads), 0,
+                                   c->s_mc, P, D->n1, D->n2, D->windowed, c->d_loc_hp.as<double>());
+                HIP_TRY(c, hipGetLastError());
+            }
+        }
+        HIP_TRY(c, hipEventRecord(ev.b, c->s_mc));
+        HIP_TRY(c, hipStreamSynchronize(c->s_mc));   // (the next chunk's stage() reuses the tables this one read)
+        HIP_TRY(c, hipEventElapsedTime(&t, ev.a, ev.b));
+        ms_acc += t;
+    }
+    c->loc = P; c->loc_max_w = max_w;
+    c->loc_ms[0] = ms_fold; c->loc_ms[1] = ms_acc;
+    c->loc_valid = true;
+    if (D) { c->loc_hp = *D; c->loc_hp_valid = true; }
     return RH_OK;
 }
 
@@ -183,53 +351,38 @@ int rh_local_fold(rh_ctx* c, const char* seq, int n, int window, int step)
     if (!c) return RH_ERR_ARG;
     LocalPlan P;
     std::string why;
-    int rc;
-    if ((rc = local_check(seq, n, window, step, &P, &why))) return fail(c, rc, "%s", why.c_str());
+    if (int rc = local_check(seq, n, window, step, &P, &why)) return fail(c, rc, "%s", why.c_str());
+    return local_run(c, P, seq, nullptr, nullptr);
+}
+
+int rh_local_duplex(rh_ctx* c, const char* s1, int n1, const char* s2, int n2, int windowed, int window, int step)
+{
+    if (!c) return RH_ERR_ARG;
+    LocalDuplexPlan D;
+    std::string why;
+    if (int rc = local_duplex_check(s1, n1, s2, n2, windowed, window, step, &D, &why)) return fail(c, rc, "%s", why.c_str());
+    return local_run(c, D.P, windowed == 1 ? s1 : s2, &D, windowed == 1 ? s2 : s1);
+}
+
+int rh_local_hp_layout(rh_ctx* c, int* n1, int* n2, int* windowed, int* nw)
+{
+    if (!c) return RH_ERR_ARG;
+    if (int rc = local_hp_ready(c)) return rc;
+    if (n1) *n1 = c->loc_hp.n1;
+    if (n2) *n2 = c->loc_hp.n2;
+    if (windowed) *windowed = c->loc_hp.windowed;
+    if (nw) *nw = c->loc_hp.P.nw;
+    return RH_OK;
+}
+
+int rh_local_hp_results(rh_ctx* c, double* hp, double* logz_pair)
+{
+    if (!c) return RH_ERR_ARG;
+    if (int rc = local_hp_ready(c)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    c->loc_valid = false;
-    const int max_w = c->max_w;
-    if ((rc = ensure(c, c->d_loc_bp, sizeof(double) * local_band_size(P), false))) return rc;
-    if ((rc = ensure(c, c->d_loc_up, sizeof(double) * local_up_size(P, max_w), false))) return rc;
-    if ((rc = ensure(c, c->d_loc_logz, sizeof(double) * P.nw, false))) return rc;
-    EventPair ev;
-    HIP_TRY(c, ev.create());
-    const int chunk = chunk_windows(c, P);
-    std::vector<const char*> seqs((size_t)chunk);
-    const std::vector<int> lens((size_t)chunk, P.We);
-    double ms_fold = 0.0, ms_acc = 0.0;
-    float t = 0.f;
-    for (int k0 = 0; k0 < P.nw; k0 += chunk) {
-        const int k1 = std::min(P.nw, k0 + chunk);
-        for (int k = k0; k < k1; k++) seqs[k - k0] = seq + local_start(P, k);
-        BatchRequest r;
-        r.ns = k1 - k0; r.seqs = seqs.data(); r.lens = lens.data();
-        r.with_mc = true;
-        if ((rc = stage(c, r))) return rc;
-        if ((rc = compute(c))) return rc;
-        ms_fold += c->ms[3];
-        LocalAcc A{};
-        A.P = P;
-        A.bp = c->d_bp.as<const double>(); A.up = c->d_up.as<const double>();
-        A.acc_bp = c->d_loc_bp.as<double>(); A.acc_up = c->d_loc_up.as<double>();
-        A.tri_stride = c->mc.tri_stride; A.up_stride = (size_t)c->mc.ld * max_w;
-        A.k0 = k0; A.k1 = k1; A.row0 = local_start(P, k0); A.max_w = max_w;
-        const int rows = local_start(P, k1 - 1) + P.We - A.row0;
-        HIP_TRY(c, hipEventRecord(ev.a, c->s_mc));
-        hipLaunchKernelGGL(local_accumulate, dim3(rows), dim3(kLocalThreads), 0, c->s_mc, A);
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipMemcpyAsync(c->d_loc_logz.as<double>() + k0, c->d_mclogz.p, sizeof(double) * (k1 - k0), hipMemcpyDeviceToDevice, c->s_mc));
-        if (k1 == P.nw) {
-            hipLaunchKernelGGL(local_finish, dim3(P.n), dim3(kLocalThreads), 0, c->s_mc, P, max_w, A.acc_bp, A.acc_up);
-            HIP_TRY(c, hipGetLastError());
-        }
-        HIP_TRY(c, hipEventRecord(ev.b, c->s_mc));
-        HIP_TRY(c, hipStreamSynchronize(c->s_mc));   // (the next chunk's stage() reuses the tables this one read)
-        HIP_TRY(c, hipEventElapsedTime(&t, ev.a, ev.b));
-        ms_acc += t;
-    }
-    c->loc = P; c->loc_max_w = max_w;
-    c->loc_ms[0] = ms_fold; c->loc_ms[1] = ms_acc;
-    c->loc_valid = true;
+    if (hp) HIP_TRY(c, hipMemcpyAsync(hp, c->d_loc_hp.p, sizeof(double) * local_hp_size(c->loc_hp), hipMemcpyDeviceToHost, c->s_mc));
+    if (logz_pair) HIP_TRY(c, hipMemcpyAsync(logz_pair, c->d_loc_logzp.p, sizeof(double) * c->loc_hp.P.nw, hipMemcpyDeviceToHost, c->s_mc));
+    HIP_TRY(c, hipStreamSynchronize(c->s_mc));
     return RH_OK;
 }
 
@@ -260,13 +413,15 @@ int rh_local_results(rh_ctx* c, double* bp_band, double* up, double* logz_win)
 int rh_local_candidates(rh_ctx* c, int what, float threshold, rh_cand* out, int cap)
 {
     if (!c) return RH_ERR_ARG;
-    if (int rc = local_ready(c)) return rc;
-    if ((what != 0 && what != 1) || cap < 0 || (cap > 0 && !out)) return fail(c, RH_ERR_ARG, "rh_local_candidates: bad what/cap");
+    if (int rc = what == 2 ? local_hp_ready(c) : local_ready(c)) return rc;
+    if (what < 0 || what > 2 || cap < 0 || (cap > 0 && !out)) return fail(c, RH_ERR_ARG, "rh_local_candidates: bad what/cap");
     HIP_TRY(c, hipSetDevice(c->device));
     const LocalPlan& P = c->loc;
-    const int n = P.n;
-    const LocalScan V = what == 0 ? LocalScan{c->d_loc_bp.as<const double>(), n, P.ld, P.ld, 1, n - 1, 0, threshold}
-                                  : LocalScan{c->d_loc_up.as<const double>(), n, c->loc_max_w, c->loc_max_w, 0, n - 1 + c->loc_max_w, 1, threshold};
+    const int hp_ld = c->loc_hp.n2 + 1;
+    const int n = what == 2 ? c->loc_hp.n1 : P.n;   // rows of the scan
+    const LocalScan V = what == 0   ? LocalScan{c->d_loc_bp.as<const double>(), n, P.ld, P.ld, 1, n - 1, kScanBp, threshold}
+                        : what == 1 ? LocalScan{c->d_loc_up.as<const double>(), n, c->loc_max_w, c->loc_max_w, 0, n - 1 + c->loc_max_w, kScanUp, threshold}
+                                    : LocalScan{c->d_loc_hp.as<const double>() + hp_ld, n, hp_ld, hp_ld, 1, 0x3fffffff, kScanHp, threshold};
     int rc;
     if ((rc = ensure(c, c->d_cnt, sizeof(int) * 2 * ((size_t)n + 1), false))) return rc;
     int* d_counts = c->d_cnt.as<int>();

@@ -1,5 +1,5 @@
-// local_windows.h -- the window arithmetic of local folding (rh_local_fold), host only: no HIP, no context (local_windows.cpp;
-// checked on the CPU by tools/local_windows_check.cpp).  The two functions the accumulate and finish kernels of local_fold.hip need
+// local_windows.h -- the window arithmetic of local folding and local hybridization (rh_local_fold, rh_local_duplex), host only: no
+// HIP, no context (local_windows.cpp; checked on the CPU by tools/local_windows_check.cpp and tools/local_duplex_check.cpp).  The two functions the accumulate and finish kernels of local_fold.hip need
 // as well -- the start of a window, the windows that contain a run of letters -- are inline here and compile for both sides.
 //
 // A sequence of n letters is folded in windows of W letters every S letters, We = min(W, n):
@@ -11,6 +11,8 @@
 #pragma once
 #include <cstddef>
 #include <string>
+
+#include "batch.h"
 
 #if defined(__HIPCC__)
 #define RH_LW_HD __host__ __device__ inline
@@ -48,5 +50,46 @@ RH_LW_HD void local_window_range(const LocalPlan& P, int i, int len, int* lo, in
     }
     *lo = l; *hi = h;
 }
+
+// ---- local hybridization (rh_local_duplex): one of two molecules is windowed as above, the other one -- the query -- is whole, and
+// window k is hybridized with it as the pair (query, window k) (windowed = 2) or (window k, query) (windowed = 1).  hp_loc(i, j),
+// 1-based letters of s1 and s2, is the mean of the windows' hp over the windows that contain the windowed molecule's letter: every
+// letter lies in one, so the matrix has no holes.
+struct LocalDuplexPlan {
+    LocalPlan P;               // of the windowed molecule
+    int n1 = 0, n2 = 0;        // letters of s1 and s2
+    int windowed = 0;          // 1 or 2
+    int nq = 0;                // letters of the query = the other molecule
+};
+
+// RH_OK with *D filled, or RH_ERR_ARG with the reason in *why; reads nothing of s1 / s2 but whether they are NULL
+int local_duplex_check(const char* s1, int n1, const char* s2, int n2, int windowed, int window, int step, LocalDuplexPlan* D, std::string* why);
+// doubles of hp_loc: (n1+1) x (n2+1), row-major, 1-based (n1 = 200, n2 = 1e6: 2e8 doubles)
+inline size_t local_hp_size(const LocalDuplexPlan& D) { return ((size_t)D.n1 + 1) * ((size_t)D.n2 + 1); }
+// longest s1 / s2 of a chunk's pairs
+inline int local_n1max(const LocalDuplexPlan& D) { return D.windowed == 1 ? D.P.We : D.nq; }
+inline int local_n2max(const LocalDuplexPlan& D) { return D.windowed == 2 ? D.P.We : D.nq; }
+
+// ---- chunks.  The windows go through the engine in chunks of consecutive windows, each chunk one batch.  Automatic chunking takes
+// the largest chunk whose tables stay under kLocalChunkBytes: 4 GiB hold about 700 fold-only windows of 200 letters, several
+// workgroups for each of the 256 CUs in every sweep launch, and leave most of the HBM to the caller's other contexts.  A batch is
+// one grid dimension: at most kLocalChunkMax sequences, so kLocalChunkMax - 1 windows next to a query.  The sizes come from the
+// layout functions of batch.h, with the table counts of the context's model.
+constexpr size_t kLocalChunkBytes = (size_t)4 << 30;
+constexpr int kLocalChunkMax = 32768;
+
+struct LocalTables {
+    int fold = 0;              // square tables per folded sequence (T_COUNT / VM_COUNT)
+    int dx = 0, dxl = 0;       // tables per pair of the log-space and of the linear hybridization kernels, which share one buffer
+    bool cofold = false;       // hp from the two-molecule ensemble: VM_COUNT tables over query + window per pair as well
+};
+// bytes of one folded sequence in a batch whose longest sequence has nmax letters: DP tables, operand tiles, posterior
+size_t local_fold_bytes(int nmax, const LocalTables& T);
+// bytes of one pair: the hybridization tables, the hp block, and under cofold the tables of the concatenation with their tile copies
+size_t local_pair_bytes(int n1max, int n2max, const LocalTables& T);
+// windows per automatic chunk of rh_local_fold ...
+int local_chunk_auto(const LocalPlan& P, const LocalTables& T);
+// ... and of rh_local_duplex, where the query's fold counts once per chunk and every window brings its pair
+int local_duplex_chunk_auto(const LocalDuplexPlan& D, const LocalTables& T);
 
 }  // namespace rh::host

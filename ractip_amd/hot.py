@@ -27,6 +27,7 @@ EXPORTS = [
     "rh_batch_packed_layout", "rh_batch_results_packed_f32", "rh_batch_pack_time",
     "rh_set_region_accessibility", "rh_get_region_accessibility", "rh_batch_acc_time",
     "rh_local_fold", "rh_local_layout", "rh_local_results", "rh_local_candidates", "rh_set_local_chunk", "rh_local_times",
+    "rh_local_duplex", "rh_local_hp_layout", "rh_local_hp_results",
     "rh_debug_vienna_cell", "rh_debug_vienna_value",   # loader inspection (host only; used by the CPU tests of the loader)
 ]
 
@@ -143,6 +144,12 @@ def load_library():
     L.rh_set_local_chunk.restype = ci
     L.rh_local_times.argtypes = [vp, vp]
     L.rh_local_times.restype = ci
+    L.rh_local_duplex.argtypes = [vp, cp, ci, cp, ci, ci, ci, ci]
+    L.rh_local_duplex.restype = ci
+    L.rh_local_hp_layout.argtypes = [vp, vp, vp, vp, vp]
+    L.rh_local_hp_layout.restype = ci
+    L.rh_local_hp_results.argtypes = [vp, vp, vp]
+    L.rh_local_hp_results.restype = ci
     L.rh_host_alloc.restype = vp
     L.rh_host_alloc.argtypes = [vp, ctypes.c_size_t]
     L.rh_host_free.restype = None
@@ -350,9 +357,34 @@ class Context:
         self._check(self.L.rh_local_results(self.h, band.ctypes.data, up.ctypes.data, logz.ctypes.data))
         return band, up, logz, starts
 
+    def local_duplex(self, s1, s2, window, step=1, windowed=2):
+        """Window-averaged hybridization matrix of a query on a long target (rh_local_duplex): molecule `windowed` (1 or 2) is cut into
+        the windows of local_fold, the other one is whole, and every window is hybridized with it under the context's settings.
+        Returns (hp, logz_pair, starts): hp (n1+1, n2+1), 1-based, the mean over the windows that contain the windowed molecule's
+        letter; log Z of every window pair; the window starts.  The call is also local_fold of the windowed molecule
+        (local_results), and it leaves the last chunk as the context's batch: query + windows, indexed."""
+        self._check(self.L.rh_local_duplex(self.h, s1.encode(), len(s1), s2.encode(), len(s2), windowed, window, step))
+        ns, index = self.batch_index()
+        nq, we = (len(s1), min(window, len(s2))) if windowed == 2 else (len(s2), min(window, len(s1)))
+        self._seq_lens = [nq] + [we] * (ns - 1)
+        self._pairs = [(self._seq_lens[a], self._seq_lens[b]) for a, b in index]
+        hp, logz = self.local_hp_results()
+        starts = np.empty(logz.shape[0], dtype=np.int32)
+        self._check(self.L.rh_local_layout(self.h, None, None, None, None, starts.ctypes.data))
+        return hp, logz, starts
+
+    def local_hp_results(self):
+        """(hp, logz_pair) of the last local_duplex (rh_local_hp_results); a later local_fold drops them."""
+        n1, n2, nw = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        self._check(self.L.rh_local_hp_layout(self.h, ctypes.byref(n1), ctypes.byref(n2), None, ctypes.byref(nw)))
+        hp, logz = np.empty((n1.value + 1, n2.value + 1)), np.empty(nw.value)
+        self._check(self.L.rh_local_hp_results(self.h, hp.ctypes.data, logz.ctypes.data))
+        return hp, logz
+
     def local_candidates(self, what, threshold, cap=1 << 22):
         """Thresholded list of the last local_fold, scanned on the device (rh_local_candidates): what = 0 the pairs (1-based i < j),
-        1 the accessibilities (0-based position, width index).  Returns (records, total): a structured array (i, j, p) of
+        1 the accessibilities (0-based position, width index), 2 the hybridization matrix of the last local_duplex (1-based letters
+        of s1 and s2).  Returns (records, total): a structured array (i, j, p) of
         min(total, cap) records in row-major order, and the number found."""
         buf = np.empty(max(cap, 1), dtype=self.CAND_DTYPE)
         k = self._check(self.L.rh_local_candidates(self.h, what, ctypes.c_float(threshold), buf.ctypes.data, cap))

@@ -2,12 +2,14 @@
 integer programme (ractip_amd/ilp.py).  What `ractip s1.fa s2.fa` prints (/root/reference/src/ractip.cpp:1561-1610),
 without z-scores and energies.
 
-  python -m ractip_amd.pipeline [--contrafold] [--duplex] [--use-constraint] [--window W [--step S]] [--write-rip FILE] a.fa b.fa
+  python -m ractip_amd.pipeline [--contrafold] [--duplex] [--use-constraint] [--window W [--step S] [--local-hp]] [--write-rip FILE] a.fa b.fa
 
 --use-constraint: the structure line that follows each sequence in its FASTA file constrains the folds and the two-molecule
 ensemble, as RactIP's -c does (src/ractip.cpp:271-291, 405-447); default path only.
 --window W [--step S]: local folding -- bp and up of both molecules are averages over windows of W letters, one every S letters
 (Context.local_fold: the quantity RNAplfold defines), for targets too long to fold as a whole; hp comes from the pair as before.
+--local-hp (with --window): hp too is a window average -- the longer molecule is windowed and every window hybridized with the whole
+shorter one (Context.local_duplex), so nothing is computed over the whole pair.
 --write-rip FILE: also write bp1, bp2, hp as RIP tables (ractip_amd/rip.py) for a stock `ractip --rip FILE --min-w 0`.
 """
 import sys
@@ -112,15 +114,39 @@ def local_fold(seq, window, step=1, model="vienna", accessibility=False, device=
             ctx.close()
 
 
-def _predict_local(ctx, s1, s2, model, duplex, opt, default_options, rip_path, accessibility, window, step):
-    """predict with bp and up of both molecules from local folds; hp from the pair path as before"""
+def local_duplex(s1, s2, window, step=1, windowed=2, model="vienna", duplex=False, accessibility=False, device=0, options=None, ctx=None):
+    """Window-averaged hybridization of a query on a long target: dict(hp (n1+1, n2+1), logz_pair, starts, bp_band, up, logz) of
+    Context.local_duplex under predict's settings of model / duplex / accessibility / options.max_w; bp_band, up and logz are the
+    local fold of the windowed molecule, which the same call yields."""
+    own = ctx is None
+    if own:
+        ctx = hot.Context(device=device, model=hot.RH_MODEL_VIENNA_BL if model == "vienna" else hot.RH_MODEL_CONTRAFOLD)
+    try:
+        _set_up(ctx, model, options or ilp.Options(), duplex, accessibility)
+        hp, logz_pair, starts = ctx.local_duplex(s1, s2, window, step, windowed)
+        band, up, logz, _ = ctx.local_results()
+        return dict(hp=hp, logz_pair=logz_pair, starts=starts, bp_band=band, up=up, logz=logz)
+    finally:
+        if own:
+            ctx.close()
+
+
+def _predict_local(ctx, s1, s2, model, duplex, opt, default_options, rip_path, accessibility, window, step, local_hp=False):
+    """predict with bp and up of both molecules from local folds; hp from the pair path as before, or (local_hp) from local_duplex
+    with the longer molecule windowed (s2 on a tie), which also yields that molecule's bp and up"""
     _set_up(ctx, model, opt, duplex, accessibility)
-    hp = probabilities(ctx, s1, s2)["hp"]   # (fetched before the local folds take the context's batch)
-    bp, up = [], []
-    for s in (s1, s2):
-        band, u, _, _ = ctx.local_fold(s, window, step)
-        bp.append(hot.band_to_tri(band))
-        up.append(u)
+    bp, up = [None, None], [None, None]
+    if local_hp:
+        windowed = 1 if len(s1) > len(s2) else 2
+        hp, _, _ = ctx.local_duplex(s1, s2, window, step, windowed)
+        band, u, _, _ = ctx.local_results()
+        bp[windowed - 1], up[windowed - 1] = hot.band_to_tri(band), u
+    else:
+        hp = probabilities(ctx, s1, s2)["hp"]   # (fetched before the local folds take the context's batch)
+    for k, s in enumerate((s1, s2)):
+        if bp[k] is None:
+            band, u, _, _ = ctx.local_fold(s, window, step)
+            bp[k], up[k] = hot.band_to_tri(band), u
     if rip_path:
         rip.write_rip(rip_path, s1, s2, bp[0], bp[1], hp)
     if model == "vienna" or accessibility:
@@ -129,7 +155,7 @@ def _predict_local(ctx, s1, s2, model, duplex, opt, default_options, rip_path, a
 
 
 def predict(s1, s2, model="vienna", duplex=False, device=0, options=None, ctx=None, rip_path=None, structures=None, accessibility=False,
-            window=None, step=1):
+            window=None, step=1, local_hp=False):
     """model "vienna": RactIP's default path (rnafold + rnaduplex; duplex=True = --duplex, else co_pf_fold), parity
     unpinned; model "contrafold": the --contrafold path (bp from the CONTRAfold engine, width-1 up, accessibility off as
     src/ractip.cpp:1511-1517 demands), hp from the CONTRAfold duplex engine.  structures = (str1, str2): the FASTA structure
@@ -137,7 +163,11 @@ def predict(s1, s2, model="vienna", duplex=False, device=0, options=None, ctx=No
     the reference has no such combination) turns the context's region accessibility on and hands up[i][w], widths 1..options.max_w,
     to the ILP as the default path does.  window=W (and step): bp and up of both molecules are window averages from
     Context.local_fold instead of whole-sequence folds (no structure constraints); with W no shorter than either molecule the
-    probabilities, and so the structures, are those of the whole-sequence folds."""
+    probabilities, and so the structures, are those of the whole-sequence folds.  local_hp=True (needs window): hp too is a window
+    average, from one Context.local_duplex call that windows the longer molecule (s2 on a tie) against the whole shorter one and
+    also yields the windowed molecule's bp and up; the other molecule's come from local_fold as before."""
+    if local_hp and window is None:
+        raise ValueError("local_hp needs a window")
     if structures is not None and model != "vienna":
         raise ValueError("structure constraints apply to the default (Vienna-BL) path only")
     if structures is not None and window is not None:
@@ -148,7 +178,7 @@ def predict(s1, s2, model="vienna", duplex=False, device=0, options=None, ctx=No
     try:
         opt = options or ilp.Options()
         if window is not None:
-            return _predict_local(ctx, s1, s2, model, duplex, opt, options is None, rip_path, accessibility, window, step)
+            return _predict_local(ctx, s1, s2, model, duplex, opt, options is None, rip_path, accessibility, window, step, local_hp)
         if model == "vienna":
             ctx.set_max_w(max(1, opt.max_w))
             ctx.set_hybrid(not duplex)
@@ -307,10 +337,12 @@ def main(argv):
     files = [a for a in argv if not a.startswith("--")]
     if len(files) != 2:
         raise SystemExit(__doc__)
+    if "--local-hp" in flags and window is None:
+        raise SystemExit("--local-hp requires --window")
     (n1, s1, t1), (n2, s2, t2) = read_fasta_with_structure(files[0]), read_fasta_with_structure(files[1])
     structures = (t1, t2) if "--use-constraint" in flags else None
     r1, r2, _ = predict(s1, s2, model="contrafold" if "--contrafold" in flags else "vienna", duplex="--duplex" in flags, rip_path=rip_path,
-                        structures=structures, window=window, step=step)
+                        structures=structures, window=window, step=step, local_hp="--local-hp" in flags)
     print(">%s\n%s\n%s\n>%s\n%s\n%s" % (n1, s1, r1, n2, s2, r2))   # src/ractip.cpp:1607-1610
 
 
