@@ -442,6 +442,59 @@ int rh_local_hp_layout(rh_ctx* ctx, int* n1, int* n2, int* windowed, int* nw);
  * device: records (i, j) 1-based over 1..n1 x 1..n2 in row-major order, narrowed to float before p > threshold. */
 int rh_local_hp_results(rh_ctx* ctx, double* hp, double* logz_pair);
 
+/* ---- local hybridization of two long molecules: both cut into windows ----
+ * s1 (n1 letters) is cut into the windows of rh_local_fold with (window1, step1): We1 = min(window1, n1), starts a_0 < .. < a_{nw1-1};
+ * s2 (n2 letters) with (window2, step2): We2, starts b_0 < .. < b_{nw2-1}.  For every (k, l) the engine computes h_kl, the hp matrix of
+ * the pair (window k of s1, window l of s2), under the context's model, arithmetic mode, rh_set_hybrid and rh_set_duplex_mode
+ * settings, without constraints; logz_pair[k*nw2 + l] is that pair's log Z.
+ *   hp_loc2(i, j), 1-based letters of s1 and s2, is a SUM OF ROW SUMS followed by one division:
+ *     acc = 0
+ *     for k in increasing order over the windows of s1 that contain letter i:
+ *         r = 0
+ *         for l in increasing order over the windows of s2 that contain letter j:  r += h_kl(i - a_k, j - b_l)
+ *         acc += r
+ *     hp_loc2(i, j) = acc / (c1(i) * c2(j))        c1, c2: the numbers of containing windows; their product is exact in double
+ * All sums are plain double sums.  The association -- row sums first, not one running sum over (k, l) -- is part of the interface: it
+ * lets the grid of window pairs be cut into rectangular tiles (a per-k row buffer is carried across the column tiles of a row block,
+ * then added in increasing k), so that rows x cols pairs cost rows + cols folds and the result bits do not depend on the tiling.
+ * Every letter lies in a window: no holes.  Layout of hp: (n1+1) * (n2+1) doubles, row-major, 1-based, row 0 and column 0 zero;
+ * offsets are size_t (n1 = n2 = 1e5 is 1e10 doubles).  nw1 * nw2 must fit an int.
+ * WHAT THE MEAN MEANS, as for rh_local_duplex: under the duplex-only sources each window pair's ensemble is normalized inside that
+ * pair, so the mean is a probability GIVEN THAT THE MOLECULES BIND IN THAT PAIR OF WINDOWS; under RH_HYBRID_COFOLD each pair's
+ * ensemble contains the unbound state.  Under every source the sum of a letter's row over the whole other molecule is NOT bounded by
+ * 1: different columns are averaged over different window pairs, whose ensembles are separate (the letters of a planted site reach
+ * 1.06 under cofold when computed on the CPU).  The values are evidence for the ILP, not a distribution over partners.
+ *
+ * rh_local_duplex2 checks its arguments first ("local duplex2: ..."): a rejected call (RH_ERR_ARG) leaves every previous result and
+ * the previous batch in place.  Then it walks tiles of `rows` consecutive k by `cols` consecutive l -- row blocks in increasing k,
+ * inside a row block column tiles in increasing l -- each one indexed batch WITH folds (rh_batch_upload_indexed): sequences
+ * 0..rows-1 the windows of s1, rows..rows+cols-1 those of s2, pair a*cols + b = (a, rows + b).  A pair so has the bits it has in any
+ * indexed batch with folds (under RH_HYBRID_COFOLD the two-molecule sweeps are seeded from the folds); only a call with one window
+ * pair (nw1 * nw2 == 1) runs its one compute unseeded and answers with the bits of rh_duplex, as rh_local_duplex does.  The folds of
+ * the windows are not part of the result (rh_local_fold).  The result lives in buffers of its own, which grow only and go with the
+ * context, and stays valid until the next rh_local_duplex2: rh_local_fold and rh_local_duplex neither read nor drop it, and it
+ * leaves theirs alone.  Afterwards the context's batch is the last tile, an ordinary computed indexed batch.  A failure behind the
+ * checks (RH_ERR_OOM, RH_ERR_HIP) leaves no result of this kind. */
+int rh_local_duplex2(rh_ctx* ctx, const char* s1, int n1, const char* s2, int n2, int window1, int step1, int window2, int step2);
+/* shape of the last rh_local_duplex2; any pointer may be NULL, starts1 / starts2 receive nw1 / nw2 entries.  "no local hybridization
+ * result of two windowed molecules" before the first call. */
+int rh_local_hp2_layout(rh_ctx* ctx, int* n1, int* n2, int* nw1, int* nw2, int* starts1, int* starts2);
+/* hp_loc2 and logz_pair (nw1 * nw2 doubles, row-major) in the layout above; any pointer may be NULL */
+int rh_local_hp2_results(rh_ctx* ctx, double* hp, double* logz_pair);
+/* Thresholded list of hp_loc2, scanned on the device: records (i, j) 1-based over 1..n1 x 1..n2 in row-major order, narrowed to float
+ * before p > threshold, as rh_local_candidates(what = 2).  Writes at most `cap` records, returns the total found. */
+int rh_local_hp2_candidates(rh_ctx* ctx, float threshold, rh_cand* out, int cap);
+/* Test and measurement aid: the tile of rh_local_duplex2, rows x cols windows; (0, 0) (default) = automatic: the largest t with
+ * 2t fold + t^2 pair + t rowbuf bytes under kLocalChunkBytes of ractip_amd/csrc/local_windows.h (rowbuf = (We1+1) * (n2+1) doubles,
+ * the row buffer of one k), rows = min(t, nw1), cols = min(t, nw2), the unclipped side grown while the sum still fits.  Otherwise
+ * rows, cols >= 1, rows + cols <= 32768 and rows * cols <= 32767; each is clipped to nw1 / nw2 at run time.  Results are unchanged.
+ * rh_set_local_chunk does not apply to rh_local_duplex2.  rh_local_hp2_tile: the tile the last call ran, clipped. */
+int rh_set_local_tile(rh_ctx* ctx, int rows, int cols);
+int rh_local_hp2_tile(rh_ctx* ctx, int* rows, int* cols);
+/* Measurement aid: device time (ms, HIP event pairs) of the last rh_local_duplex2: ms[0] the computes of its tiles, ms[1] the row, add
+ * and finish kernels with the log Z copies, plus the scan kernels of the rh_local_hp2_candidates calls since. */
+int rh_local_hp2_times(rh_ctx* ctx, double ms[2]);
+
 /* ---- loader inspection (host only, no GPU, no context) ----
  * What the parameter loader holds after binding its sources, for checks of the binding itself (tests/test_bl_cells.py,
  * tests/test_vienna_par.py); not needed by a caller of the probability path.  Return 0, -1 (bad index / NULL) or

@@ -360,6 +360,14 @@ struct Ctx {   // (the fields of rh_ctx, below)
     bool loc_hp_valid = false;
     DevBuf d_loc_hp, d_loc_logzp;
     double loc_ms[2] = {0, 0};     // folds (sum of the chunks' computes); accumulate + finish + scans since
+    // rh_local_duplex2 only: the last result of two windowed molecules -- hp_loc2 [(n1+1)][(n2+1)], log Z [nw1][nw2] and the row buffer
+    // of one row block on the device (grow-only), kept until the next rh_local_duplex2; the other local calls neither read nor drop it
+    LocalDuplex2Plan loc2;
+    bool loc2_valid = false;
+    int loc2_tile[2] = {0, 0};     // rh_set_local_tile: rows, cols of a tile (0, 0: local_tile_auto)
+    int loc2_used[2] = {0, 0};     // the tile the last call ran
+    DevBuf d_loc2_hp, d_loc2_rows, d_loc2_logz;
+    double loc2_ms[2] = {0, 0};    // the tiles' computes; row + add + finish kernels and the scans since
     std::vector<hipEvent_t> tev;   // event pool of the timed class (pairs), tev_n used by the last compute
     size_t tev_n = 0;
     Ctx() = default;

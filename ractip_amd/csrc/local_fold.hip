@@ -12,6 +12,11 @@
 // Local hybridization (rh_local_duplex) runs the same chunks with a query in front of the windows: sequence 0 of every chunk is the
 // query, pair k the query with window k, and local_hp_accumulate / local_hp_finish average the chunk's hp blocks into hp_loc by the
 // same rule, next to the band of the windowed molecule, which the kernels above accumulate from sequences 1..c.
+//
+// Local hybridization of two windowed molecules (rh_local_duplex2) walks the grid of window pairs in rectangular tiles, each an
+// indexed batch of windows of s1 followed by windows of s2 with all their pairs, and local_hp2_rows / local_hp2_add_rows /
+// local_hp2_finish average the tiles' hp blocks into hp_loc2 in two levels -- per window of s1 the sum over the windows of s2 in a
+// row buffer, then the sum of the finished rows -- so that the bits do not depend on the tiling.  Its result has buffers of its own.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -150,6 +155,88 @@ __global__ __launch_bounds__(kLocalThreads) void local_hp_finish(LocalPlan P, in
         int lo, hi;
         local_window_range(P, (windowed == 2 ? j : i) - 1, 1, &lo, &hi);
         *v = *v / (double)(hi - lo + 1);
+    }
+}
+
+// ---- hp_loc2 of two windowed molecules (rh_local_duplex2): the two-level form of the kernels above.  A tile holds the pairs of the
+// windows kA .. kB-1 of s1 with the windows lA .. lB-1 of s2, pair (k - kA) * (lB - lA) + (l - lA), in the hp blocks of its batch.
+// The sum over l goes into the row buffer R[a][ia][j] (a = k - kA, ia = 1..We1 the letter of window k, j = 0..n2, pitch n2 + 1) and
+// is carried there across the column tiles of a row block; behind the last column tile the rows of the block are added into hp_loc2
+// in increasing k, which carries the sum over k from row block to row block.  Both are gathers with lanes consecutive in j.
+struct LocalHp2 {
+    LocalPlan P1, P2;    // of s1 and of s2
+    const double* hp;    // the tile's hp blocks [(kB - kA) * (lB - lA)][hp_stride], row pitch ldd, 1-based
+    double* R;           // [kB - kA][We1 + 1][n2 + 1]
+    double* acc;         // hp_loc2 [(n1+1)][(n2+1)]
+    size_t hp_stride;
+    int ldd;
+    int kA, kB, lA, lB;
+};
+
+// grid (column blocks, lines): only the columns the tile's windows of s2 cover, which they do without a gap; a line is one (a, ia),
+// lines beyond the grid's second dimension are walked.  A column starts from 0 in the first column tile that holds one of its windows.
+__global__ __launch_bounds__(kLocalThreads) void local_hp2_rows(LocalHp2 A)
+{
+    const int t0 = local_start(A.P2, A.lA), nt = local_start(A.P2, A.lB - 1) + A.P2.We - t0;
+    const int col = blockIdx.x * kLocalThreads + threadIdx.x;
+    if (col >= nt) return;
+    const int j = t0 + 1 + col;
+    int lo, hi;
+    local_window_range(A.P2, j - 1, 1, &lo, &hi);
+    const bool fresh = lo >= A.lA;
+    if (lo < A.lA) lo = A.lA;
+    if (hi > A.lB - 1) hi = A.lB - 1;
+    const int nc = A.lB - A.lA, We1 = A.P1.We, lines = (A.kB - A.kA) * We1;
+    const size_t pitch = (size_t)A.P2.n + 1;
+    for (int r = blockIdx.y; r < lines; r += gridDim.y) {
+        const int a = r / We1, ia = r - a * We1 + 1;
+        double* out = A.R + ((size_t)a * (size_t)(We1 + 1) + ia) * pitch + j;
+        double s = fresh ? 0.0 : *out;
+#pragma unroll 4
+        for (int l = lo; l <= hi; l++)
+            s += A.hp[((size_t)a * nc + (l - A.lA)) * A.hp_stride + (size_t)ia * A.ldd + (j - local_start(A.P2, l))];
+        *out = s;
+    }
+}
+
+// grid (column blocks over 1..n2, rows): the rows of s1 the block's windows cover, without a gap; rows beyond the grid's second
+// dimension are walked.  A row starts from 0 in the first row block that holds one of its windows.
+__global__ __launch_bounds__(kLocalThreads) void local_hp2_add_rows(LocalHp2 A)
+{
+    const int j = 1 + blockIdx.x * kLocalThreads + threadIdx.x;
+    if (j > A.P2.n) return;
+    const int i0 = local_start(A.P1, A.kA), ni = local_start(A.P1, A.kB - 1) + A.P1.We - i0, We1 = A.P1.We;
+    const size_t pitch = (size_t)A.P2.n + 1;
+    for (int r = blockIdx.y; r < ni; r += gridDim.y) {
+        const int i = i0 + 1 + r;
+        int lo, hi;
+        local_window_range(A.P1, i - 1, 1, &lo, &hi);
+        const bool fresh = lo >= A.kA;
+        if (lo < A.kA) lo = A.kA;
+        if (hi > A.kB - 1) hi = A.kB - 1;
+        double* out = A.acc + (size_t)i * pitch + j;
+        double s = fresh ? 0.0 : *out;
+#pragma unroll 4
+        for (int k = lo; k <= hi; k++)
+            s += A.R[((size_t)(k - A.kA) * (size_t)(We1 + 1) + (i - local_start(A.P1, k))) * pitch + j];
+        *out = s;
+    }
+}
+
+// sum -> mean, in place, over all of (0..n1) x (0..n2): one division by the product of the two window counts (each at least one, the
+// product exact in double); row 0 and column 0 are written as 0
+__global__ __launch_bounds__(kLocalThreads) void local_hp2_finish(LocalPlan P1, LocalPlan P2, double* __restrict__ hp)
+{
+    const int j = blockIdx.x * kLocalThreads + threadIdx.x;
+    if (j > P2.n) return;
+    int lo, hi;
+    local_window_range(P2, j - 1, 1, &lo, &hi);
+    const double c2 = (double)(hi - lo + 1);
+    for (int i = blockIdx.y; i <= P1.n; i += gridDim.y) {
+        double* v = hp + (size_t)i * ((size_t)P2.n + 1) + j;
+        if (i == 0 || j == 0) { *v = 0.0; continue; }
+        local_window_range(P1, i - 1, 1, &lo, &hi);
+        *v = *v / ((double)(hi - lo + 1) * c2);
     }
 }
 
@@ -334,6 +421,127 @@ int local_run(rh_ctx* c, const LocalPlan& P, const char* seq, const LocalDuplexP
     return RH_OK;
 }
 
+int local_hp2_ready(rh_ctx* c)
+{
+    if (!c->loc2_valid) return fail(c, RH_ERR_ARG, "no local hybridization result of two windowed molecules");
+    return RH_OK;
+}
+
+// The scheduler of rh_local_duplex2 over checked arguments: the tiles of local_windows.h, row blocks in increasing k and inside a row
+// block column tiles in increasing l, each one indexed batch with folds through stage() and compute() -- sequences 0..nr-1 the
+// windows of s1, nr..nr+nc-1 those of s2, pair a * nc + b = (a, nr + b).  Behind every compute the row kernel and the copy of the
+// tile's log Z, behind the last column tile of a row block the add kernel, behind the last row block the finish kernel.
+int local2_run(rh_ctx* c, const LocalDuplex2Plan& D, const char* s1, const char* s2)
+{
+    int rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->loc2_valid = false;
+    const LocalPlan &P1 = D.P1, &P2 = D.P2;
+    int rows = c->loc2_tile[0], cols = c->loc2_tile[1];
+    if (rows <= 0 || cols <= 0) local_tile_auto(D, local_tables(c), &rows, &cols);
+    rows = std::min(rows, P1.nw); cols = std::min(cols, P2.nw);
+    if ((rc = ensure(c, c->d_loc2_hp, sizeof(double) * local_hp2_size(D), false))) return rc;
+    if ((rc = ensure(c, c->d_loc2_rows, sizeof(double) * local_hp2_rowbuf_size(D, rows), false))) return rc;
+    if ((rc = ensure(c, c->d_loc2_logz, sizeof(double) * local_hp2_logz_size(D), false))) return rc;
+    EventPair ev;
+    HIP_TRY(c, ev.create());
+    std::vector<const char*> seqs((size_t)rows + cols);
+    std::vector<int> lens((size_t)rows + cols), first((size_t)rows * cols), second((size_t)rows * cols);
+    LocalHp2 A{};
+    A.P1 = P1; A.P2 = P2;
+    A.R = c->d_loc2_rows.as<double>(); A.acc = c->d_loc2_hp.as<double>();
+    const int col_blocks = (P2.n + kLocalThreads - 1) / kLocalThreads;
+    double ms_compute = 0.0, ms_acc = 0.0;
+    float t = 0.f;
+    LocalTile tile;
+    for (size_t ti = 0; local_tile_at(D, rows, cols, ti, &tile); ti++) {
+        const int kA = tile.kA, kB = tile.kB, lA = tile.lA, lB = tile.lB, nr = kB - kA, nc = lB - lA;
+        for (int a = 0; a < nr; a++) { seqs[a] = s1 + local_start(P1, kA + a); lens[a] = P1.We; }
+        for (int b = 0; b < nc; b++) { seqs[nr + b] = s2 + local_start(P2, lA + b); lens[nr + b] = P2.We; }
+        for (int a = 0; a < nr; a++)
+            for (int b = 0; b < nc; b++) { first[(size_t)a * nc + b] = a; second[(size_t)a * nc + b] = nr + b; }
+        BatchRequest r;
+        r.ns = nr + nc; r.seqs = seqs.data(); r.lens = lens.data();
+        r.with_mc = true; r.with_dx = true;
+        r.npairs = nr * nc; r.first = first.data(); r.second = second.data();
+        if ((rc = stage(c, r))) return rc;
+        // one window pair is the pair itself and answers with the bits of rh_duplex: its one compute runs unseeded, as in local_run
+        const int seed = c->co_seed;
+        if (P1.nw == 1 && P2.nw == 1) c->co_seed = 0;
+        rc = compute(c);
+        c->co_seed = seed;
+        if (rc) return rc;
+        ms_compute += c->ms[3];
+        A.hp = c->d_hp.as<const double>(); A.hp_stride = c->dx.tab_stride; A.ldd = c->dx.ldd;
+        A.kA = kA; A.kB = kB; A.lA = lA; A.lB = lB;
+        const int nt = local_start(P2, lB - 1) + P2.We - local_start(P2, lA);
+        HIP_TRY(c, hipEventRecord(ev.a, c->s_mc));
+        hipLaunchKernelGGL(local_hp2_rows, dim3((nt + kLocalThreads - 1) / kLocalThreads, std::min(nr * P1.We, kLocalGridRows)), dim3(kLocalThreads), 0,
+                           c->s_mc, A);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpy2DAsync(c->d_loc2_logz.as<double>() + (size_t)kA * P2.nw + lA, sizeof(double) * P2.nw, c->d_logz.p, sizeof(double) * nc,
+                                    sizeof(double) * nc, nr, hipMemcpyDeviceToDevice, c->s_mc));
+        if (lB == P2.nw) {
+            const int ni = local_start(P1, kB - 1) + P1.We - local_start(P1, kA);
+            hipLaunchKernelGGL(local_hp2_add_rows, dim3(col_blocks, std::min(ni, kLocalGridRows)), dim3(kLocalThreads), 0, c->s_mc, A);
+            HIP_TRY(c, hipGetLastError());
+            if (kB == P1.nw) {
+                hipLaunchKernelGGL(local_hp2_finish, dim3((P2.n + 1 + kLocalThreads - 1) / kLocalThreads, std::min(P1.n + 1, kLocalGridRows)),
+                                   dim3(kLocalThreads), 0, c->s_mc, P1, P2, A.acc);
+                HIP_TRY(c, hipGetLastError());
+            }
+        }
+        HIP_TRY(c, hipEventRecord(ev.b, c->s_mc));
+        HIP_TRY(c, hipStreamSynchronize(c->s_mc));   // (the next tile's stage() reuses the tables this one read)
+        HIP_TRY(c, hipEventElapsedTime(&t, ev.a, ev.b));
+        ms_acc += t;
+    }
+    c->loc2 = D;
+    c->loc2_used[0] = rows; c->loc2_used[1] = cols;
+    c->loc2_ms[0] = ms_compute; c->loc2_ms[1] = ms_acc;
+    c->loc2_valid = true;
+    return RH_OK;
+}
+
+// count, prefix on the host, ordered write: the scan V into out[0 .. cap), the kernel time added to *ms; returns the total found
+int scan_candidates(rh_ctx* c, const LocalScan& V, rh_cand* out, int cap, double* ms, const char* who)
+{
+    const int n = V.n;
+    int rc;
+    if ((rc = ensure(c, c->d_cnt, sizeof(int) * 2 * ((size_t)n + 1), false))) return rc;
+    int* d_counts = c->d_cnt.as<int>();
+    int* d_offsets = d_counts + (n + 1);
+    EventPair ev;
+    HIP_TRY(c, ev.create());
+    float t = 0.f;
+    HIP_TRY(c, hipEventRecord(ev.a, c->s_mc));
+    hipLaunchKernelGGL(local_cand_count, dim3((n + 3) / 4), dim3(256), 0, c->s_mc, V, d_counts);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(ev.b, c->s_mc));
+    std::vector<int> counts(n), offsets(n);
+    HIP_TRY(c, hipMemcpyAsync(counts.data(), d_counts, sizeof(int) * n, hipMemcpyDeviceToHost, c->s_mc));
+    HIP_TRY(c, hipStreamSynchronize(c->s_mc));
+    HIP_TRY(c, hipEventElapsedTime(&t, ev.a, ev.b));
+    *ms += t;
+    long long found = 0;
+    for (int i = 0; i < n; i++) { offsets[i] = (int)std::min<long long>(found, cap); found += counts[i]; }
+    if (found > 0x7fffffffLL) return fail(c, RH_ERR_UNSUPPORTED, "%s: %lld entries above the threshold", who, found);
+    const int take = (int)std::min<long long>(found, cap);
+    if (take > 0) {
+        if ((rc = ensure(c, c->d_cand, sizeof(rh_cand) * (size_t)take, false))) return rc;
+        HIP_TRY(c, hipMemcpyAsync(d_offsets, offsets.data(), sizeof(int) * n, hipMemcpyHostToDevice, c->s_mc));
+        HIP_TRY(c, hipEventRecord(ev.a, c->s_mc));
+        hipLaunchKernelGGL(local_cand_write, dim3((n + 3) / 4), dim3(256), 0, c->s_mc, V, d_counts, d_offsets, c->d_cand.as<rh_cand>(), take);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipEventRecord(ev.b, c->s_mc));
+        HIP_TRY(c, hipMemcpyAsync(out, c->d_cand.p, sizeof(rh_cand) * (size_t)take, hipMemcpyDeviceToHost, c->s_mc));
+        HIP_TRY(c, hipStreamSynchronize(c->s_mc));
+        HIP_TRY(c, hipEventElapsedTime(&t, ev.a, ev.b));
+        *ms += t;
+    }
+    return (int)found;
+}
+
 }  // namespace
 
 extern "C" {
@@ -422,39 +630,7 @@ int rh_local_candidates(rh_ctx* c, int what, float threshold, rh_cand* out, int 
     const LocalScan V = what == 0   ? LocalScan{c->d_loc_bp.as<const double>(), n, P.ld, P.ld, 1, n - 1, kScanBp, threshold}
                         : what == 1 ? LocalScan{c->d_loc_up.as<const double>(), n, c->loc_max_w, c->loc_max_w, 0, n - 1 + c->loc_max_w, kScanUp, threshold}
                                     : LocalScan{c->d_loc_hp.as<const double>() + hp_ld, n, hp_ld, hp_ld, 1, 0x3fffffff, kScanHp, threshold};
-    int rc;
-    if ((rc = ensure(c, c->d_cnt, sizeof(int) * 2 * ((size_t)n + 1), false))) return rc;
-    int* d_counts = c->d_cnt.as<int>();
-    int* d_offsets = d_counts + (n + 1);
-    EventPair ev;
-    HIP_TRY(c, ev.create());
-    float t = 0.f;
-    HIP_TRY(c, hipEventRecord(ev.a, c->s_mc));
-    hipLaunchKernelGGL(local_cand_count, dim3((n + 3) / 4), dim3(256), 0, c->s_mc, V, d_counts);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipEventRecord(ev.b, c->s_mc));
-    std::vector<int> counts(n), offsets(n);
-    HIP_TRY(c, hipMemcpyAsync(counts.data(), d_counts, sizeof(int) * n, hipMemcpyDeviceToHost, c->s_mc));
-    HIP_TRY(c, hipStreamSynchronize(c->s_mc));
-    HIP_TRY(c, hipEventElapsedTime(&t, ev.a, ev.b));
-    c->loc_ms[1] += t;
-    long long found = 0;
-    for (int i = 0; i < n; i++) { offsets[i] = (int)std::min<long long>(found, cap); found += counts[i]; }
-    if (found > 0x7fffffffLL) return fail(c, RH_ERR_UNSUPPORTED, "rh_local_candidates: %lld entries above the threshold", found);
-    const int take = (int)std::min<long long>(found, cap);
-    if (take > 0) {
-        if ((rc = ensure(c, c->d_cand, sizeof(rh_cand) * (size_t)take, false))) return rc;
-        HIP_TRY(c, hipMemcpyAsync(d_offsets, offsets.data(), sizeof(int) * n, hipMemcpyHostToDevice, c->s_mc));
-        HIP_TRY(c, hipEventRecord(ev.a, c->s_mc));
-        hipLaunchKernelGGL(local_cand_write, dim3((n + 3) / 4), dim3(256), 0, c->s_mc, V, d_counts, d_offsets, c->d_cand.as<rh_cand>(), take);
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipEventRecord(ev.b, c->s_mc));
-        HIP_TRY(c, hipMemcpyAsync(out, c->d_cand.p, sizeof(rh_cand) * (size_t)take, hipMemcpyDeviceToHost, c->s_mc));
-        HIP_TRY(c, hipStreamSynchronize(c->s_mc));
-        HIP_TRY(c, hipEventElapsedTime(&t, ev.a, ev.b));
-        c->loc_ms[1] += t;
-    }
-    return (int)found;
+    return scan_candidates(c, V, out, cap, &c->loc_ms[1], "rh_local_candidates");
 }
 
 int rh_local_times(rh_ctx* c, double ms[2])
@@ -462,6 +638,79 @@ int rh_local_times(rh_ctx* c, double ms[2])
     if (!c || !ms) return RH_ERR_ARG;
     if (int rc = local_ready(c)) return rc;
     ms[0] = c->loc_ms[0]; ms[1] = c->loc_ms[1];
+    return RH_OK;
+}
+
+int rh_set_local_tile(rh_ctx* c, int rows, int cols)
+{
+    if (!c) return RH_ERR_ARG;
+    const bool automatic = rows == 0 && cols == 0;
+    if (!automatic && (rows < 1 || cols < 1 || (long long)rows + cols > kLocalChunkMax || (long long)rows * cols > kLocalChunkMax - 1))
+        return fail(c, RH_ERR_ARG, "rh_set_local_tile: %d x %d windows (0, 0, or rows + cols <= %d and rows * cols <= %d)", rows, cols, kLocalChunkMax,
+                    kLocalChunkMax - 1);
+    c->loc2_tile[0] = rows; c->loc2_tile[1] = cols;
+    return RH_OK;
+}
+
+int rh_local_duplex2(rh_ctx* c, const char* s1, int n1, const char* s2, int n2, int window1, int step1, int window2, int step2)
+{
+    if (!c) return RH_ERR_ARG;
+    LocalDuplex2Plan D;
+    std::string why;
+    if (int rc = local_duplex2_check(s1, n1, s2, n2, window1, step1, window2, step2, &D, &why)) return fail(c, rc, "%s", why.c_str());
+    return local2_run(c, D, s1, s2);
+}
+
+int rh_local_hp2_layout(rh_ctx* c, int* n1, int* n2, int* nw1, int* nw2, int* starts1, int* starts2)
+{
+    if (!c) return RH_ERR_ARG;
+    if (int rc = local_hp2_ready(c)) return rc;
+    const LocalPlan &P1 = c->loc2.P1, &P2 = c->loc2.P2;
+    if (n1) *n1 = P1.n;
+    if (n2) *n2 = P2.n;
+    if (nw1) *nw1 = P1.nw;
+    if (nw2) *nw2 = P2.nw;
+    for (int k = 0; starts1 && k < P1.nw; k++) starts1[k] = local_start(P1, k);
+    for (int l = 0; starts2 && l < P2.nw; l++) starts2[l] = local_start(P2, l);
+    return RH_OK;
+}
+
+int rh_local_hp2_results(rh_ctx* c, double* hp, double* logz_pair)
+{
+    if (!c) return RH_ERR_ARG;
+    if (int rc = local_hp2_ready(c)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (hp) HIP_TRY(c, hipMemcpyAsync(hp, c->d_loc2_hp.p, sizeof(double) * local_hp2_size(c->loc2), hipMemcpyDeviceToHost, c->s_mc));
+    if (logz_pair) HIP_TRY(c, hipMemcpyAsync(logz_pair, c->d_loc2_logz.p, sizeof(double) * local_hp2_logz_size(c->loc2), hipMemcpyDeviceToHost, c->s_mc));
+    HIP_TRY(c, hipStreamSynchronize(c->s_mc));
+    return RH_OK;
+}
+
+int rh_local_hp2_candidates(rh_ctx* c, float threshold, rh_cand* out, int cap)
+{
+    if (!c) return RH_ERR_ARG;
+    if (int rc = local_hp2_ready(c)) return rc;
+    if (cap < 0 || (cap > 0 && !out)) return fail(c, RH_ERR_ARG, "rh_local_hp2_candidates: bad cap");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int n1 = c->loc2.P1.n, hp_ld = c->loc2.P2.n + 1;
+    const LocalScan V{c->d_loc2_hp.as<const double>() + hp_ld, n1, hp_ld, hp_ld, 1, 0x3fffffff, kScanHp, threshold};
+    return scan_candidates(c, V, out, cap, &c->loc2_ms[1], "rh_local_hp2_candidates");
+}
+
+int rh_local_hp2_tile(rh_ctx* c, int* rows, int* cols)
+{
+    if (!c) return RH_ERR_ARG;
+    if (int rc = local_hp2_ready(c)) return rc;
+    if (rows) *rows = c->loc2_used[0];
+    if (cols) *cols = c->loc2_used[1];
+    return RH_OK;
+}
+
+int rh_local_hp2_times(rh_ctx* c, double ms[2])
+{
+    if (!c || !ms) return RH_ERR_ARG;
+    if (int rc = local_hp2_ready(c)) return rc;
+    ms[0] = c->loc2_ms[0]; ms[1] = c->loc2_ms[1];
     return RH_OK;
 }
 

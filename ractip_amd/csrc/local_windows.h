@@ -1,5 +1,6 @@
-// local_windows.h -- the window arithmetic of local folding and local hybridization (rh_local_fold, rh_local_duplex), host only: no
-// HIP, no context (local_windows.cpp; checked on the CPU by tools/local_windows_check.cpp and tools/local_duplex_check.cpp).  The two functions the accumulate and finish kernels of local_fold.hip need
+// local_windows.h -- the window arithmetic of local folding and local hybridization (rh_local_fold, rh_local_duplex, rh_local_duplex2),
+// host only: no HIP, no context (local_windows.cpp; checked on the CPU by tools/local_windows_check.cpp, tools/local_duplex_check.cpp
+// and tools/local_duplex2_check.cpp).  The two functions the accumulate and finish kernels of local_fold.hip need
 // as well -- the start of a window, the windows that contain a run of letters -- are inline here and compile for both sides.
 //
 // A sequence of n letters is folded in windows of W letters every S letters, We = min(W, n):
@@ -91,5 +92,43 @@ size_t local_pair_bytes(int n1max, int n2max, const LocalTables& T);
 int local_chunk_auto(const LocalPlan& P, const LocalTables& T);
 // ... and of rh_local_duplex, where the query's fold counts once per chunk and every window brings its pair
 int local_duplex_chunk_auto(const LocalDuplexPlan& D, const LocalTables& T);
+
+// ---- local hybridization of two windowed molecules (rh_local_duplex2): s1 and s2 are both cut into windows as above, each with a
+// window and a step of its own, and every window k of s1 is hybridized with every window l of s2.  hp_loc2(i, j), 1-based letters of
+// s1 and s2, is a sum of row sums -- over the windows k that contain i, in increasing k, of the sum over the windows l that contain
+// j, in increasing l, of h_kl at the translated coordinates -- divided once by the product of the two window counts.
+struct LocalDuplex2Plan {
+    LocalPlan P1, P2;          // of s1 and of s2
+};
+
+// RH_OK with *D filled, or RH_ERR_ARG with the reason in *why; reads nothing of s1 / s2 but whether they are NULL.  Rejects a grid of
+// more window pairs than an int indexes (logz_pair[k*nw2 + l]); the product is taken in 64 bits.
+int local_duplex2_check(const char* s1, int n1, const char* s2, int n2, int window1, int step1, int window2, int step2, LocalDuplex2Plan* D,
+                        std::string* why);
+// doubles of hp_loc2: (n1+1) x (n2+1), row-major, 1-based (n1 = n2 = 1e5: 1e10 doubles) ...
+inline size_t local_hp2_size(const LocalDuplex2Plan& D) { return ((size_t)D.P1.n + 1) * ((size_t)D.P2.n + 1); }
+// ... of logz_pair [nw1][nw2] ...
+inline size_t local_hp2_logz_size(const LocalDuplex2Plan& D) { return (size_t)D.P1.nw * (size_t)D.P2.nw; }
+// ... and of the row buffer R[a][ia][j] of `rows` windows of s1: ia = 0..We1 (row 0 unused), j = 0..n2, pitch n2 + 1
+inline size_t local_hp2_rowbuf_size(const LocalDuplex2Plan& D, int rows) { return (size_t)rows * ((size_t)D.P1.We + 1) * ((size_t)D.P2.n + 1); }
+
+// Tiles.  The nw1 x nw2 grid of window pairs is walked in rectangles of `rows` consecutive k by `cols` consecutive l -- row blocks in
+// increasing k, inside a row block column tiles in increasing l -- each tile one indexed batch of rows + cols folded windows and
+// rows x cols pairs.  The automatic tile: the largest t >= 1 with 2t fold + t^2 pair + t rowbuf <= kLocalChunkBytes (rowbuf = the
+// row buffer of one k), rows = min(t, nw1), cols = min(t, nw2); where one side was clipped the other one grows while the same sum
+// with the actual rows and cols still fits.  Throughout rows + cols <= kLocalChunkMax (the sequences of a batch) and rows x cols <=
+// kLocalChunkMax - 1 (the pairs a chunk of rh_local_duplex reaches); (1, 1) when nothing fits.
+struct LocalTile { int kA = 0, kB = 0, lA = 0, lB = 0; };   // windows kA .. kB-1 of s1 with lA .. lB-1 of s2
+// tile t of the walk under (rows, cols), both already clipped to nw1 / nw2; false behind the last one
+inline bool local_tile_at(const LocalDuplex2Plan& D, int rows, int cols, size_t t, LocalTile* out)
+{
+    const size_t per_block = ((size_t)D.P2.nw + cols - 1) / cols, kA = t / per_block * rows, lA = t % per_block * cols;
+    if (kA >= (size_t)D.P1.nw) return false;
+    out->kA = (int)kA; out->kB = D.P1.nw - (int)kA < rows ? D.P1.nw : (int)kA + rows;
+    out->lA = (int)lA; out->lB = D.P2.nw - (int)lA < cols ? D.P2.nw : (int)lA + cols;
+    return true;
+}
+bool local_tile_fits(const LocalDuplex2Plan& D, const LocalTables& T, size_t rows, size_t cols);
+void local_tile_auto(const LocalDuplex2Plan& D, const LocalTables& T, int* rows, int* cols);
 
 }  // namespace rh::host

@@ -28,6 +28,8 @@ EXPORTS = [
     "rh_set_region_accessibility", "rh_get_region_accessibility", "rh_batch_acc_time",
     "rh_local_fold", "rh_local_layout", "rh_local_results", "rh_local_candidates", "rh_set_local_chunk", "rh_local_times",
     "rh_local_duplex", "rh_local_hp_layout", "rh_local_hp_results",
+    "rh_local_duplex2", "rh_local_hp2_layout", "rh_local_hp2_results", "rh_local_hp2_candidates", "rh_set_local_tile", "rh_local_hp2_tile",
+    "rh_local_hp2_times",
     "rh_debug_vienna_cell", "rh_debug_vienna_value",   # loader inspection (host only; used by the CPU tests of the loader)
 ]
 
@@ -150,6 +152,20 @@ def load_library():
     L.rh_local_hp_layout.restype = ci
     L.rh_local_hp_results.argtypes = [vp, vp, vp]
     L.rh_local_hp_results.restype = ci
+    L.rh_local_duplex2.argtypes = [vp, cp, ci, cp, ci, ci, ci, ci, ci]
+    L.rh_local_duplex2.restype = ci
+    L.rh_local_hp2_layout.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.rh_local_hp2_layout.restype = ci
+    L.rh_local_hp2_results.argtypes = [vp, vp, vp]
+    L.rh_local_hp2_results.restype = ci
+    L.rh_local_hp2_candidates.argtypes = [vp, ctypes.c_float, vp, ci]
+    L.rh_local_hp2_candidates.restype = ci
+    L.rh_set_local_tile.argtypes = [vp, ci, ci]
+    L.rh_set_local_tile.restype = ci
+    L.rh_local_hp2_tile.argtypes = [vp, vp, vp]
+    L.rh_local_hp2_tile.restype = ci
+    L.rh_local_hp2_times.argtypes = [vp, vp]
+    L.rh_local_hp2_times.restype = ci
     L.rh_host_alloc.restype = vp
     L.rh_host_alloc.argtypes = [vp, ctypes.c_size_t]
     L.rh_host_free.restype = None
@@ -398,6 +414,57 @@ class Context:
         """Device time (ms) of the last local_fold: (folds, accumulate + finish + the scans since)."""
         ms = (ctypes.c_double * 2)()
         self._check(self.L.rh_local_times(self.h, ms))
+        return ms[0], ms[1]
+
+    # ---- local hybridization of two windowed molecules
+    def local_duplex2(self, s1, s2, window1, step1=1, window2=None, step2=None):
+        """Window-averaged hybridization matrix of two long molecules (rh_local_duplex2): s1 is cut into windows (window1, step1), s2
+        into (window2, step2) -- by default the same pair -- and every window of s1 is hybridized with every window of s2 under the
+        context's settings.  Returns (hp, logz_pair, starts1, starts2): hp (n1+1, n2+1), 1-based, per entry the sum over the windows
+        of s1 that contain the row's letter, in increasing order, of the sums over the windows of s2 that contain the column's letter,
+        divided once by the product of the two counts; log Z of every window pair, (nw1, nw2); the window starts.  The result stays
+        fetchable until the next local_duplex2, whatever local_fold and local_duplex do meanwhile.  The call leaves its last tile as the
+        context's batch: the tile's windows of s1, then those of s2, indexed."""
+        window2 = window1 if window2 is None else window2
+        step2 = step1 if step2 is None else step2
+        self._check(self.L.rh_local_duplex2(self.h, s1.encode(), len(s1), s2.encode(), len(s2), window1, step1, window2, step2))
+        ns, index = self.batch_index()
+        rows = index[0][1] if index else 0                      # pair 0 = (0, rows)
+        self._seq_lens = [min(window1, len(s1))] * rows + [min(window2, len(s2))] * (ns - rows)
+        self._pairs = [(self._seq_lens[a], self._seq_lens[b]) for a, b in index]
+        return self.local_hp2_results()
+
+    def local_hp2_results(self):
+        """(hp, logz_pair (nw1, nw2), starts1, starts2) of the last local_duplex2 (rh_local_hp2_results)."""
+        n1, n2, nw1, nw2 = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        self._check(self.L.rh_local_hp2_layout(self.h, ctypes.byref(n1), ctypes.byref(n2), ctypes.byref(nw1), ctypes.byref(nw2), None, None))
+        hp, logz = np.empty((n1.value + 1, n2.value + 1)), np.empty((nw1.value, nw2.value))
+        starts1, starts2 = np.empty(nw1.value, dtype=np.int32), np.empty(nw2.value, dtype=np.int32)
+        self._check(self.L.rh_local_hp2_layout(self.h, None, None, None, None, starts1.ctypes.data, starts2.ctypes.data))
+        self._check(self.L.rh_local_hp2_results(self.h, hp.ctypes.data, logz.ctypes.data))
+        return hp, logz, starts1, starts2
+
+    def local_hp2_candidates(self, threshold, cap=1 << 22):
+        """Thresholded list of the last local_duplex2's hp, scanned on the device (rh_local_hp2_candidates): (records, total) as
+        local_candidates(2, ...) returns them, 1-based letters of s1 and s2 in row-major order."""
+        buf = np.empty(max(cap, 1), dtype=self.CAND_DTYPE)
+        k = self._check(self.L.rh_local_hp2_candidates(self.h, ctypes.c_float(threshold), buf.ctypes.data, cap))
+        return buf[:min(k, cap)], k
+
+    def set_local_tile(self, rows, cols):
+        """Windows of s1 x windows of s2 per tile of local_duplex2 ((0, 0): automatic, by the byte budget); results are unchanged."""
+        self._check(self.L.rh_set_local_tile(self.h, rows, cols))
+
+    def local_hp2_tile(self):
+        """(rows, cols) of the tile the last local_duplex2 ran."""
+        rows, cols = ctypes.c_int(), ctypes.c_int()
+        self._check(self.L.rh_local_hp2_tile(self.h, ctypes.byref(rows), ctypes.byref(cols)))
+        return rows.value, cols.value
+
+    def local_hp2_times(self):
+        """Device time (ms) of the last local_duplex2: (the tiles' computes, row + add + finish kernels and the scans since)."""
+        ms = (ctypes.c_double * 2)()
+        self._check(self.L.rh_local_hp2_times(self.h, ms))
         return ms[0], ms[1]
 
     # ---- batched calls

@@ -2,7 +2,7 @@
 integer programme (ractip_amd/ilp.py).  What `ractip s1.fa s2.fa` prints (/root/reference/src/ractip.cpp:1561-1610),
 without z-scores and energies.
 
-  python -m ractip_amd.pipeline [--contrafold] [--duplex] [--use-constraint] [--window W [--step S] [--local-hp]] [--write-rip FILE] a.fa b.fa
+  python -m ractip_amd.pipeline [--contrafold] [--duplex] [--use-constraint] [--window W [--step S] [--local-hp | --local-hp-both]] [--write-rip FILE] a.fa b.fa
 
 --use-constraint: the structure line that follows each sequence in its FASTA file constrains the folds and the two-molecule
 ensemble, as RactIP's -c does (src/ractip.cpp:271-291, 405-447); default path only.
@@ -10,6 +10,8 @@ ensemble, as RactIP's -c does (src/ractip.cpp:271-291, 405-447); default path on
 (Context.local_fold: the quantity RNAplfold defines), for targets too long to fold as a whole; hp comes from the pair as before.
 --local-hp (with --window): hp too is a window average -- the longer molecule is windowed and every window hybridized with the whole
 shorter one (Context.local_duplex), so nothing is computed over the whole pair.
+--local-hp-both (with --window): both molecules are windowed and every window of one is hybridized with every window of the other
+(Context.local_duplex2): the route for two long molecules, where not even one of them is folded whole.
 --write-rip FILE: also write bp1, bp2, hp as RIP tables (ractip_amd/rip.py) for a stock `ractip --rip FILE --min-w 0`.
 """
 import sys
@@ -131,12 +133,30 @@ def local_duplex(s1, s2, window, step=1, windowed=2, model="vienna", duplex=Fals
             ctx.close()
 
 
-def _predict_local(ctx, s1, s2, model, duplex, opt, default_options, rip_path, accessibility, window, step, local_hp=False):
+def local_duplex2(s1, s2, window1, step1=1, window2=None, step2=None, model="vienna", duplex=False, device=0, options=None, ctx=None):
+    """Window-averaged hybridization of two long molecules, both cut into windows: dict(hp (n1+1, n2+1), logz_pair (nw1, nw2),
+    starts1, starts2) of Context.local_duplex2 under predict's settings of model / duplex / options.max_w."""
+    own = ctx is None
+    if own:
+        ctx = hot.Context(device=device, model=hot.RH_MODEL_VIENNA_BL if model == "vienna" else hot.RH_MODEL_CONTRAFOLD)
+    try:
+        _set_up(ctx, model, options or ilp.Options(), duplex, False)
+        hp, logz_pair, starts1, starts2 = ctx.local_duplex2(s1, s2, window1, step1, window2, step2)
+        return dict(hp=hp, logz_pair=logz_pair, starts1=starts1, starts2=starts2)
+    finally:
+        if own:
+            ctx.close()
+
+
+def _predict_local(ctx, s1, s2, model, duplex, opt, default_options, rip_path, accessibility, window, step, local_hp=False, local_hp_both=False):
     """predict with bp and up of both molecules from local folds; hp from the pair path as before, or (local_hp) from local_duplex
-    with the longer molecule windowed (s2 on a tie), which also yields that molecule's bp and up"""
+    with the longer molecule windowed (s2 on a tie), which also yields that molecule's bp and up, or (local_hp_both) from
+    local_duplex2 with both molecules windowed, whose result the local folds behind it leave alone"""
     _set_up(ctx, model, opt, duplex, accessibility)
     bp, up = [None, None], [None, None]
-    if local_hp:
+    if local_hp_both:
+        hp = ctx.local_duplex2(s1, s2, window, step)[0]
+    elif local_hp:
         windowed = 1 if len(s1) > len(s2) else 2
         hp, _, _ = ctx.local_duplex(s1, s2, window, step, windowed)
         band, u, _, _ = ctx.local_results()
@@ -155,7 +175,7 @@ def _predict_local(ctx, s1, s2, model, duplex, opt, default_options, rip_path, a
 
 
 def predict(s1, s2, model="vienna", duplex=False, device=0, options=None, ctx=None, rip_path=None, structures=None, accessibility=False,
-            window=None, step=1, local_hp=False):
+            window=None, step=1, local_hp=False, local_hp_both=False):
     """model "vienna": RactIP's default path (rnafold + rnaduplex; duplex=True = --duplex, else co_pf_fold), parity
     unpinned; model "contrafold": the --contrafold path (bp from the CONTRAfold engine, width-1 up, accessibility off as
     src/ractip.cpp:1511-1517 demands), hp from the CONTRAfold duplex engine.  structures = (str1, str2): the FASTA structure
@@ -165,7 +185,13 @@ def predict(s1, s2, model="vienna", duplex=False, device=0, options=None, ctx=No
     Context.local_fold instead of whole-sequence folds (no structure constraints); with W no shorter than either molecule the
     probabilities, and so the structures, are those of the whole-sequence folds.  local_hp=True (needs window): hp too is a window
     average, from one Context.local_duplex call that windows the longer molecule (s2 on a tie) against the whole shorter one and
-    also yields the windowed molecule's bp and up; the other molecule's come from local_fold as before."""
+    also yields the windowed molecule's bp and up; the other molecule's come from local_fold as before.  local_hp_both=True (needs
+    window, excludes local_hp): hp is the window average of Context.local_duplex2 with (window, step) on BOTH molecules -- the route
+    for two long molecules, where no whole molecule is folded anywhere; bp and up of both come from local_fold."""
+    if local_hp_both and window is None:
+        raise ValueError("local_hp_both needs a window")
+    if local_hp_both and local_hp:
+        raise ValueError("local_hp_both and local_hp exclude each other")
     if local_hp and window is None:
         raise ValueError("local_hp needs a window")
     if structures is not None and model != "vienna":
@@ -178,7 +204,7 @@ def predict(s1, s2, model="vienna", duplex=False, device=0, options=None, ctx=No
     try:
         opt = options or ilp.Options()
         if window is not None:
-            return _predict_local(ctx, s1, s2, model, duplex, opt, options is None, rip_path, accessibility, window, step, local_hp)
+            return _predict_local(ctx, s1, s2, model, duplex, opt, options is None, rip_path, accessibility, window, step, local_hp, local_hp_both)
         if model == "vienna":
             ctx.set_max_w(max(1, opt.max_w))
             ctx.set_hybrid(not duplex)
@@ -339,10 +365,13 @@ def main(argv):
         raise SystemExit(__doc__)
     if "--local-hp" in flags and window is None:
         raise SystemExit("--local-hp requires --window")
+    if "--local-hp-both" in flags and window is None:
+        raise SystemExit("--local-hp-both requires --window")
     (n1, s1, t1), (n2, s2, t2) = read_fasta_with_structure(files[0]), read_fasta_with_structure(files[1])
     structures = (t1, t2) if "--use-constraint" in flags else None
     r1, r2, _ = predict(s1, s2, model="contrafold" if "--contrafold" in flags else "vienna", duplex="--duplex" in flags, rip_path=rip_path,
-                        structures=structures, window=window, step=step, local_hp="--local-hp" in flags)
+                        structures=structures, window=window, step=step, local_hp="--local-hp" in flags,
+                        local_hp_both="--local-hp-both" in flags)
     print(">%s\n%s\n%s\n>%s\n%s\n%s" % (n1, s1, r1, n2, s2, r2))   # src/ractip.cpp:1607-1610
 
 
