@@ -48,6 +48,17 @@ struct DevObj : DevBuf {
     }
 };
 
+// The hp result of a local hybridization (local_fold.hip): hp_loc [(n1+1)][(n2+1)] and log Z per window pair [nw1][nw2] on the device,
+// grow-only.  A molecule that was not cut into windows (the query of rh_local_duplex) is the one window of its plan.
+struct LocalHp {
+    LocalDuplex2Plan D;            // of s1 and of s2
+    int windowed = 0;              // rh_local_duplex: the molecule it cut, as rh_local_hp_layout reports it
+    bool valid = false;
+    DevBuf hp, logz;
+    int tile[2] = {0, 0};          // rows, cols of the tile the call ran
+    double ms[2] = {0, 0};         // rh_local_duplex2: the tiles' computes; gather + finish kernels and the scans since
+};
+
 // CONTRAfold linear path: the model at one scale exponent -- host copy, device copy and the transposed, zero-padded single-branch
 // weights wT[l1][t+1] of the strip kernels.  McLinArgs::lin names the one a pass runs on.
 struct LinSet {
@@ -354,20 +365,15 @@ struct Ctx {   // (the fields of rh_ctx, below)
     int loc_max_w = 1;
     int loc_chunk = 0;             // rh_set_local_chunk: windows per chunk (0: by kLocalChunkBytes)
     DevBuf d_loc_bp, d_loc_up, d_loc_logz;
-    // rh_local_duplex only: the hp part of the last local result -- hp_loc [(n1+1)][(n2+1)] and log Z per window pair on the device;
-    // dropped by the next rh_local_fold, replaced by the next rh_local_duplex
-    LocalDuplexPlan loc_hp;
-    bool loc_hp_valid = false;
-    DevBuf d_loc_hp, d_loc_logzp;
     double loc_ms[2] = {0, 0};     // folds (sum of the chunks' computes); accumulate + finish + scans since
-    // rh_local_duplex2 only: the last result of two windowed molecules -- hp_loc2 [(n1+1)][(n2+1)], log Z [nw1][nw2] and the row buffer
-    // of one row block on the device (grow-only), kept until the next rh_local_duplex2; the other local calls neither read nor drop it
-    LocalDuplex2Plan loc2;
-    bool loc2_valid = false;
+    // rh_local_duplex only: the hp part of the last local result, whose times are in loc_ms with the band's; dropped by the next
+    // rh_local_fold, replaced by the next rh_local_duplex
+    LocalHp loc_hp;
+    // rh_local_duplex2 only: the last result of two windowed molecules, kept until the next rh_local_duplex2; the other local calls
+    // neither read nor drop it
+    LocalHp loc_hp2;
     int loc2_tile[2] = {0, 0};     // rh_set_local_tile: rows, cols of a tile (0, 0: local_tile_auto)
-    int loc2_used[2] = {0, 0};     // the tile the last call ran
-    DevBuf d_loc2_hp, d_loc2_rows, d_loc2_logz;
-    double loc2_ms[2] = {0, 0};    // the tiles' computes; row + add + finish kernels and the scans since
+    DevBuf d_loc_rows;             // the row buffer of one row block of a walk with several windows on both sides (grow-only)
     std::vector<hipEvent_t> tev;   // event pool of the timed class (pairs), tev_n used by the last compute
     size_t tev_n = 0;
     Ctx() = default;

@@ -1,25 +1,27 @@
-// local_fold.hip -- local folding of a long sequence (rh_local_fold and the rh_local_* fetches): the windows of local_windows.h go
-// through stage() and compute() chunk by chunk as fold-only batches, and the kernels here add each chunk's bp and up tables into
-// band accumulators that stay on the device, divide by the window counts behind the last chunk, and scan the band for candidates.
+// local_fold.hip -- the local calls (rh_local_fold, rh_local_duplex, rh_local_duplex2 and the rh_local_* fetches): one walk over tiles of
+// windows, the kernels that average what each tile computed into results that stay on the device, and the candidate scans of those.
 //
-// The mean of an entry is a plain double sum over the windows that contain it, in increasing window order, and one division by their
-// number.  The accumulate kernel is a gather: a workgroup owns a row of the band, a lane an entry, and the lane adds its windows in
-// order, carrying the partial sum from chunk to chunk in the accumulator -- so the result does not depend on the chunking, and no
-// atomics are needed.  Row i - start(k) of window k's triangular table is contiguous in j, hence in d = j - i: reads and writes are
-// coalesced, and every table entry of every window is read once.  A row starts from 0 in the first chunk that holds one of its
-// windows (every letter lies in some window), so the accumulators are never cleared as a whole.
+// The walk (local_walk) covers the grid of (window k of s1, window l of s2) in tiles of `rows` x `cols` windows (local_windows.h), each
+// tile one batch through stage() and compute(): its windows as sequences, all their pairs.  rh_local_duplex2 is that walk as it
+// stands.  rh_local_duplex is the walk with the query as the one window of its molecule, in tiles of 1 x chunk or chunk x 1 windows;
+// rh_local_fold is the walk without a second molecule, in fold-only chunks of windows of s1.
 //
-// Local hybridization (rh_local_duplex) runs the same chunks with a query in front of the windows: sequence 0 of every chunk is the
-// query, pair k the query with window k, and local_hp_accumulate / local_hp_finish average the chunk's hp blocks into hp_loc by the
-// same rule, next to the band of the windowed molecule, which the kernels above accumulate from sequences 1..c.
+// Band.  The mean of an entry of bp_band / up is a plain double sum over the windows that contain it, in increasing window order, and
+// one division by their number.  The accumulate kernel is a gather: a workgroup owns a row of the band, a lane an entry, and the lane
+// adds its windows in order, carrying the partial sum from chunk to chunk in the accumulator -- so the result does not depend on the
+// chunking, and no atomics are needed.  Row i - start(k) of window k's triangular table is contiguous in j, hence in d = j - i: reads
+// and writes are coalesced, and every table entry of every window is read once.  A row starts from 0 in the first chunk that holds one
+// of its windows (every letter lies in some window), so the accumulators are never cleared as a whole.  rh_local_fold accumulates the
+// band of its molecule, rh_local_duplex that of the molecule it cuts, next to hp.
 //
-// Local hybridization of two windowed molecules (rh_local_duplex2) walks the grid of window pairs in rectangular tiles, each an
-// indexed batch of windows of s1 followed by windows of s2 with all their pairs, and local_hp2_rows / local_hp2_add_rows /
-// local_hp2_finish average the tiles' hp blocks into hp_loc2 in two levels -- per window of s1 the sum over the windows of s2 in a
-// row buffer, then the sum of the finished rows -- so that the bits do not depend on the tiling.  Its result has buffers of its own.
+// hp.  hp_loc(i, j) is a sum in two levels -- per window of s1 the sum over the windows of s2 that contain j, then the sum of those
+// rows over the windows of s1 that contain i, each in increasing window order -- and one division by the product of the two counts, so
+// that the bits do not depend on the tiling.  Two gathers by the rule of the band (column gather, row gather) and a finish kernel do
+// it; where a molecule has one window its level adds one term to 0.0 and is skipped (the three routes: local_walk).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cassert>
 #include <string>
 #include <vector>
 
@@ -101,81 +103,25 @@ __global__ __launch_bounds__(kLocalThreads) void local_finish(LocalPlan P, int m
     }
 }
 
-// ---- hp_loc [(n1+1)][(n2+1)], row-major, 1-based, from the hp blocks of the chunk's pairs [k1 - k0][hp_stride] (row pitch ldd, 1-based:
-// DxBatch::hp).  A lane owns one entry (i, j), lanes consecutive in j.  windowed = 2: pair k is (query, window k) and the lane reads
-// block k at (i, j - start(k)); windowed = 1: (window k, query), read at (i - start(k), j).  Either way the reads of a wavefront are
-// contiguous in j, like its writes.
-struct LocalHpAcc {
-    LocalPlan P;         // of the windowed molecule
-    const double* hp;
-    double* acc;
-    size_t hp_stride;
-    int ldd, n1, n2, windowed;
-    int k0, k1;          // the chunk: windows k0 .. k1 - 1
-    int t0, nt;          // the letters (0-based) of the windowed molecule its windows cover: t0 .. t0 + nt - 1, without a gap
-};
-
-// grid (column blocks, rows): only the columns (windowed = 2) or rows (windowed = 1) of the chunk's letters; rows beyond the grid's
-// second dimension are walked
-__global__ __launch_bounds__(kLocalThreads) void local_hp_accumulate(LocalHpAcc A)
-{
-    const bool w2 = A.windowed == 2;
-    const int cols = w2 ? A.nt : A.n2, rows = w2 ? A.n1 : A.nt;
-    const int col = blockIdx.x * kLocalThreads + threadIdx.x;
-    if (col >= cols) return;
-    const int j = (w2 ? A.t0 : 0) + 1 + col;
-    for (int r = blockIdx.y; r < rows; r += gridDim.y) {
-        const int i = (w2 ? 0 : A.t0) + 1 + r;
-        int lo, hi;
-        local_window_range(A.P, (w2 ? j : i) - 1, 1, &lo, &hi);
-        const bool fresh = lo >= A.k0;   // the first chunk that holds one of the letter's windows: the sum starts from 0
-        if (lo < A.k0) lo = A.k0;
-        if (hi > A.k1 - 1) hi = A.k1 - 1;
-        double* out = A.acc + (size_t)i * ((size_t)A.n2 + 1) + j;
-        double s = fresh ? 0.0 : *out;
-#pragma unroll 4
-        for (int k = lo; k <= hi; k++) {
-            const int st = local_start(A.P, k);
-            const double* blk = A.hp + (size_t)(k - A.k0) * A.hp_stride;
-            s += w2 ? blk[(size_t)i * A.ldd + (j - st)] : blk[(size_t)(i - st) * A.ldd + j];
-        }
-        *out = s;
-    }
-}
-
-// sum -> mean, in place, over all of (0..n1) x (0..n2): one division by the number of windows that contain the letter (at least one);
-// row 0 and column 0 are written as 0
-__global__ __launch_bounds__(kLocalThreads) void local_hp_finish(LocalPlan P, int n1, int n2, int windowed, double* __restrict__ hp)
-{
-    const int j = blockIdx.x * kLocalThreads + threadIdx.x;
-    if (j > n2) return;
-    for (int i = blockIdx.y; i <= n1; i += gridDim.y) {
-        double* v = hp + (size_t)i * ((size_t)n2 + 1) + j;
-        if (i == 0 || j == 0) { *v = 0.0; continue; }
-        int lo, hi;
-        local_window_range(P, (windowed == 2 ? j : i) - 1, 1, &lo, &hi);
-        *v = *v / (double)(hi - lo + 1);
-    }
-}
-
-// ---- hp_loc2 of two windowed molecules (rh_local_duplex2): the two-level form of the kernels above.  A tile holds the pairs of the
-// windows kA .. kB-1 of s1 with the windows lA .. lB-1 of s2, pair (k - kA) * (lB - lA) + (l - lA), in the hp blocks of its batch.
-// The sum over l goes into the row buffer R[a][ia][j] (a = k - kA, ia = 1..We1 the letter of window k, j = 0..n2, pitch n2 + 1) and
-// is carried there across the column tiles of a row block; behind the last column tile the rows of the block are added into hp_loc2
-// in increasing k, which carries the sum over k from row block to row block.  Both are gathers with lanes consecutive in j.
-struct LocalHp2 {
+// ---- hp_loc [(n1+1)][(n2+1)], row-major, 1-based, pitch n2 + 1.  A tile holds the pairs of the windows kA .. kB-1 of s1 with the
+// windows lA .. lB-1 of s2, pair (k - kA) * (lB - lA) + (l - lA), in the hp blocks of its batch (row pitch ldd, 1-based: DxBatch::hp).
+// The sum over l makes rows[a][ia][j] (a = k - kA, ia = 1..We1 the letter of window k, j = 0..n2, pitch n2 + 1), carried across the
+// column tiles of a row block; behind the last column tile the rows of the block are added into hp_loc in increasing k, which
+// carries the sum over k from row block to row block.  Both are gathers: a lane owns one entry, lanes consecutive in j, so the reads
+// of a wavefront are contiguous like its writes.
+struct LocalHpGather {
     LocalPlan P1, P2;    // of s1 and of s2
-    const double* hp;    // the tile's hp blocks [(kB - kA) * (lB - lA)][hp_stride], row pitch ldd, 1-based
-    double* R;           // [kB - kA][We1 + 1][n2 + 1]
-    double* acc;         // hp_loc2 [(n1+1)][(n2+1)]
-    size_t hp_stride;
-    int ldd;
+    const double* src;   // blocks of src_stride doubles, row pitch src_pitch, 1-based: the column gather reads the tile's hp blocks
+    size_t src_stride;   // [(kB - kA) * (lB - lA)], the row gather the finished rows of the row block [kB - kA]
+    int src_pitch;
+    double* dst;         // column gather: the rows, a-th block at dst + a * dst_stride; row gather: hp_loc
+    size_t dst_stride;
     int kA, kB, lA, lB;
 };
 
 // grid (column blocks, lines): only the columns the tile's windows of s2 cover, which they do without a gap; a line is one (a, ia),
 // lines beyond the grid's second dimension are walked.  A column starts from 0 in the first column tile that holds one of its windows.
-__global__ __launch_bounds__(kLocalThreads) void local_hp2_rows(LocalHp2 A)
+__global__ __launch_bounds__(kLocalThreads) void local_hp_col_gather(LocalHpGather A)
 {
     const int t0 = local_start(A.P2, A.lA), nt = local_start(A.P2, A.lB - 1) + A.P2.We - t0;
     const int col = blockIdx.x * kLocalThreads + threadIdx.x;
@@ -190,22 +136,22 @@ __global__ __launch_bounds__(kLocalThreads) void local_hp2_rows(LocalHp2 A)
     const size_t pitch = (size_t)A.P2.n + 1;
     for (int r = blockIdx.y; r < lines; r += gridDim.y) {
         const int a = r / We1, ia = r - a * We1 + 1;
-        double* out = A.R + ((size_t)a * (size_t)(We1 + 1) + ia) * pitch + j;
+        double* out = A.dst + (size_t)a * A.dst_stride + (size_t)ia * pitch + j;
         double s = fresh ? 0.0 : *out;
 #pragma unroll 4
         for (int l = lo; l <= hi; l++)
-            s += A.hp[((size_t)a * nc + (l - A.lA)) * A.hp_stride + (size_t)ia * A.ldd + (j - local_start(A.P2, l))];
+            s += A.src[((size_t)a * nc + (l - A.lA)) * A.src_stride + (size_t)ia * A.src_pitch + (j - local_start(A.P2, l))];
         *out = s;
     }
 }
 
 // grid (column blocks over 1..n2, rows): the rows of s1 the block's windows cover, without a gap; rows beyond the grid's second
 // dimension are walked.  A row starts from 0 in the first row block that holds one of its windows.
-__global__ __launch_bounds__(kLocalThreads) void local_hp2_add_rows(LocalHp2 A)
+__global__ __launch_bounds__(kLocalThreads) void local_hp_row_gather(LocalHpGather A)
 {
     const int j = 1 + blockIdx.x * kLocalThreads + threadIdx.x;
     if (j > A.P2.n) return;
-    const int i0 = local_start(A.P1, A.kA), ni = local_start(A.P1, A.kB - 1) + A.P1.We - i0, We1 = A.P1.We;
+    const int i0 = local_start(A.P1, A.kA), ni = local_start(A.P1, A.kB - 1) + A.P1.We - i0;
     const size_t pitch = (size_t)A.P2.n + 1;
     for (int r = blockIdx.y; r < ni; r += gridDim.y) {
         const int i = i0 + 1 + r;
@@ -214,17 +160,17 @@ __global__ __launch_bounds__(kLocalThreads) void local_hp2_add_rows(LocalHp2 A)
         const bool fresh = lo >= A.kA;
         if (lo < A.kA) lo = A.kA;
         if (hi > A.kB - 1) hi = A.kB - 1;
-        double* out = A.acc + (size_t)i * pitch + j;
+        double* out = A.dst + (size_t)i * pitch + j;
         double s = fresh ? 0.0 : *out;
 #pragma unroll 4
         for (int k = lo; k <= hi; k++)
-            s += A.R[((size_t)(k - A.kA) * (size_t)(We1 + 1) + (i - local_start(A.P1, k))) * pitch + j];
+            s += A.src[(size_t)(k - A.kA) * A.src_stride + (size_t)(i - local_start(A.P1, k)) * A.src_pitch + j];
         *out = s;
     }
 }
 
 // sum -> mean, in place, over all of (0..n1) x (0..n2): one division by the product of the two window counts (each at least one, the
-// product exact in double); row 0 and column 0 are written as 0
+// product exact in double, and the other count itself where one of them is 1); row 0 and column 0 are written as 0
 __global__ __launch_bounds__(kLocalThreads) void local_hp2_finish(LocalPlan P1, LocalPlan P2, double* __restrict__ hp)
 {
     const int j = blockIdx.x * kLocalThreads + threadIdx.x;
@@ -328,166 +274,128 @@ int local_ready(rh_ctx* c)
 
 int local_hp_ready(rh_ctx* c)
 {
-    if (!c->loc_valid || !c->loc_hp_valid) return fail(c, RH_ERR_ARG, "no local hybridization result");
-    return RH_OK;
-}
-
-// The scheduler of rh_local_fold (D == nullptr) and rh_local_duplex over checked arguments: chunks of consecutive windows of `seq`,
-// each one batch through stage() and compute() -- fold-only, or indexed with the query as sequence 0 and the pairs (0, k) / (k, 0) --
-// and behind each compute the accumulate kernels, behind the last one the finish kernels.
-int local_run(rh_ctx* c, const LocalPlan& P, const char* seq, const LocalDuplexPlan* D, const char* query)
-{
-    int rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    c->loc_valid = c->loc_hp_valid = false;
-    const int max_w = c->max_w;
-    const int q = D ? 1 : 0;   // sequences in front of the windows
-    if ((rc = ensure(c, c->d_loc_bp, sizeof(double) * local_band_size(P), false))) return rc;
-    if ((rc = ensure(c, c->d_loc_up, sizeof(double) * local_up_size(P, max_w), false))) return rc;
-    if ((rc = ensure(c, c->d_loc_logz, sizeof(double) * P.nw, false))) return rc;
-    if (D && (rc = ensure(c, c->d_loc_hp, sizeof(double) * local_hp_size(*D), false))) return rc;
-    if (D && (rc = ensure(c, c->d_loc_logzp, sizeof(double) * P.nw, false))) return rc;
-    EventPair ev;
-    HIP_TRY(c, ev.create());
-    const int chunk = chunk_windows(c, P, D);
-    std::vector<const char*> seqs((size_t)chunk + q);
-    std::vector<int> lens((size_t)chunk + q, P.We), first, second;
-    if (D) {
-        seqs[0] = query; lens[0] = D->nq;
-        first.assign((size_t)chunk, 0); second.assign((size_t)chunk, 0);
-        std::vector<int>& win = D->windowed == 2 ? second : first;
-        for (int k = 0; k < chunk; k++) win[k] = 1 + k;
-    }
-    double ms_fold = 0.0, ms_acc = 0.0;
-    float t = 0.f;
-    for (int k0 = 0; k0 < P.nw; k0 += chunk) {
-        const int k1 = std::min(P.nw, k0 + chunk);
-        for (int k = k0; k < k1; k++) seqs[q + k - k0] = seq + local_start(P, k);
-        BatchRequest r;
-        r.ns = q + k1 - k0; r.seqs = seqs.data(); r.lens = lens.data();
-        r.with_mc = true;
-        if (D) { r.with_dx = true; r.npairs = k1 - k0; r.first = first.data(); r.second = second.data(); }
-        if ((rc = stage(c, r))) return rc;
-        // One window (W >= n) is the pair itself, and the call answers with the bits of rh_duplex: under RH_HYBRID_COFOLD that call
-        // has no folds to seed its two-molecule sweeps from, and seeded sweeps differ from it in the last bits on the scaled linear
-        // kernels -- so this one compute runs them unseeded too.  With two windows or more every chunk is seeded, like any batch.
-        const int seed = c->co_seed;
-        if (D && P.nw == 1) c->co_seed = 0;
-        rc = compute(c);
-        c->co_seed = seed;
-        if (rc) return rc;
-        ms_fold += c->ms[3];
-        LocalAcc A{};
-        A.P = P;
-        A.tri_stride = c->mc.tri_stride; A.up_stride = (size_t)c->mc.ld * max_w;
-        A.bp = c->d_bp.as<const double>() + q * A.tri_stride; A.up = c->d_up.as<const double>() + q * A.up_stride;
-        A.acc_bp = c->d_loc_bp.as<double>(); A.acc_up = c->d_loc_up.as<double>();
-        A.k0 = k0; A.k1 = k1; A.row0 = local_start(P, k0); A.max_w = max_w;
-        const int rows = local_start(P, k1 - 1) + P.We - A.row0;
-        HIP_TRY(c, hipEventRecord(ev.a, c->s_mc));
-        hipLaunchKernelGGL(local_accumulate, dim3(rows), dim3(kLocalThreads), 0, c->s_mc, A);
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipMemcpyAsync(c->d_loc_logz.as<double>() + k0, c->d_mclogz.as<const double>() + q, sizeof(double) * (k1 - k0), hipMemcpyDeviceToDevice, c->s_mc));
-        if (D) {
-            LocalHpAcc H{};
-            H.P = P;
-            H.hp = c->d_hp.as<const double>(); H.acc = c->d_loc_hp.as<double>();
-            H.hp_stride = c->dx.tab_stride; H.ldd = c->dx.ldd;
-            H.n1 = D->n1; H.n2 = D->n2; H.windowed = D->windowed;
-            H.k0 = k0; H.k1 = k1; H.t0 = A.row0; H.nt = rows;
-            const int cols = D->windowed == 2 ? rows : D->n2, lines = D->windowed == 2 ? D->n1 : rows;
-            hipLaunchKernelGGL(local_hp_accumulate, dim3((cols + kLocalThreads - 1) / kLocalThreads, std::min(lines, kLocalGridRows)), dim3(kLocalThreads), 0, c->s_mc, H);
-            HIP_TRY(c, hipGetLastError());
-            HIP_TRY(c, hipMemcpyAsync(c->d_loc_logzp.as<double>() + k0, c->d_logz.p, sizeof(double) * (k1 - k0), hipMemcpyDeviceToDevice, c->s_mc));
-        }
-        if (k1 == P.nw) {
-            hipLaunchKernelGGL(local_finish, dim3(P.n), dim3(kLocalThreads), 0, c->s_mc, P, max_w, A.acc_bp, A.acc_up);
-            HIP_TRY(c, hipGetLastError());
-            if (D) {
-                hipLaunchKernelGGL(local_hp_finish, dim3((D->n2 + 1 + kLocalThreads - 1) / kLocalThreads, std::min(D->n1 + 1, kLocalGridRows)), dim3(kLocalThreads), 0,
-                                   c->s_mc, P, D->n1, D->n2, D->windowed, c->d_loc_hp.as<double>());
-                HIP_TRY(c, hipGetLastError());
-            }
-        }
-        HIP_TRY(c, hipEventRecord(ev.b, c->s_mc));
-        HIP_TRY(c, hipStreamSynchronize(c->s_mc));   // (the next chunk's stage() reuses the tables this one read)
-        HIP_TRY(c, hipEventElapsedTime(&t, ev.a, ev.b));
-        ms_acc += t;
-    }
-    c->loc = P; c->loc_max_w = max_w;
-    c->loc_ms[0] = ms_fold; c->loc_ms[1] = ms_acc;
-    c->loc_valid = true;
-    if (D) { c->loc_hp = *D; c->loc_hp_valid = true; }
+    if (!c->loc_valid || !c->loc_hp.valid) return fail(c, RH_ERR_ARG, "no local hybridization result");
     return RH_OK;
 }
 
 int local_hp2_ready(rh_ctx* c)
 {
-    if (!c->loc2_valid) return fail(c, RH_ERR_ARG, "no local hybridization result of two windowed molecules");
+    if (!c->loc_hp2.valid) return fail(c, RH_ERR_ARG, "no local hybridization result of two windowed molecules");
     return RH_OK;
 }
 
-// The scheduler of rh_local_duplex2 over checked arguments: the tiles of local_windows.h, row blocks in increasing k and inside a row
-// block column tiles in increasing l, each one indexed batch with folds through stage() and compute() -- sequences 0..nr-1 the
-// windows of s1, nr..nr+nc-1 those of s2, pair a * nc + b = (a, nr + b).  Behind every compute the row kernel and the copy of the
-// tile's log Z, behind the last column tile of a row block the add kernel, behind the last row block the finish kernel.
-int local2_run(rh_ctx* c, const LocalDuplex2Plan& D, const char* s1, const char* s2)
+// What a local call asks of the walk, over checked arguments.
+struct LocalWalk {
+    LocalDuplex2Plan D;          // of s1 and of s2; P2.nw = 0: no second molecule, fold-only batches without pairs
+    const char* s1 = nullptr;
+    const char* s2 = nullptr;
+    int rows = 0, cols = 0;      // windows of s1 x windows of s2 in a tile, clipped to nw1 / nw2
+    int band = 0;                // the side (1 or 2; 0: none) whose windows also go into the band accumulators, as rh_local_fold's do
+    int front = 1;               // the side whose windows stand first in a tile's batch
+    LocalHp* out = nullptr;      // the hp result it writes (none without a second molecule) ...
+    double* ms = nullptr;        // ... and its time pair: the tiles' computes, the kernels here
+};
+
+// The scheduler of the three local calls: row blocks in increasing k and inside a row block column tiles in increasing l
+// (local_tile_at), each tile one batch with folds through stage() and compute().  Pair a * nc + b is (window kA + a of s1, window
+// lA + b of s2); the windows of the front side are sequences 0.., those of the other side follow.  Behind every compute the
+// gathers and the copies of log Z, behind the last one the finish kernels.  hp takes one of three routes:
+//   nw1 = 1           the column gather writes hp_loc itself, which has the layout of the rows of the one window of s1 (We1 = n1);
+//   nw2 = 1, nw1 > 1  the finished rows are the tile's hp blocks (0.0 + x is x): the row gather reads them in place;
+//   both above 1      the column gather into the row buffer, behind the last column tile of a row block the row gather from it.
+// A band side needs each of its windows in one tile only, in increasing order: the other side has at most one window.
+int local_walk(rh_ctx* c, const LocalWalk& w)
 {
     int rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    c->loc2_valid = false;
-    const LocalPlan &P1 = D.P1, &P2 = D.P2;
-    int rows = c->loc2_tile[0], cols = c->loc2_tile[1];
-    if (rows <= 0 || cols <= 0) local_tile_auto(D, local_tables(c), &rows, &cols);
-    rows = std::min(rows, P1.nw); cols = std::min(cols, P2.nw);
-    if ((rc = ensure(c, c->d_loc2_hp, sizeof(double) * local_hp2_size(D), false))) return rc;
-    if ((rc = ensure(c, c->d_loc2_rows, sizeof(double) * local_hp2_rowbuf_size(D, rows), false))) return rc;
-    if ((rc = ensure(c, c->d_loc2_logz, sizeof(double) * local_hp2_logz_size(D), false))) return rc;
+    const LocalPlan &P1 = w.D.P1, &P2 = w.D.P2;
+    const LocalPlan& PB = w.band == 2 ? P2 : P1;   // of the band side
+    assert(w.band == 0 || (w.band == 1 ? P2.nw : P1.nw) <= 1);
+    LocalHp* out = w.out;
+    if (w.band) c->loc_valid = c->loc_hp.valid = false;   // (the hp result of rh_local_duplex goes with the band it came with)
+    if (out) out->valid = false;
+    const int max_w = c->max_w;
+    const bool two_level = P1.nw > 1 && P2.nw > 1;
+    const size_t pitch = (size_t)P2.n + 1, rows_stride = ((size_t)P1.We + 1) * pitch;   // of hp_loc; of the row buffer of one k
+    if (w.band && (rc = ensure(c, c->d_loc_bp, sizeof(double) * local_band_size(PB), false))) return rc;
+    if (w.band && (rc = ensure(c, c->d_loc_up, sizeof(double) * local_up_size(PB, max_w), false))) return rc;
+    if (w.band && (rc = ensure(c, c->d_loc_logz, sizeof(double) * PB.nw, false))) return rc;
+    if (out && (rc = ensure(c, out->hp, sizeof(double) * local_hp2_size(w.D), false))) return rc;
+    if (two_level && (rc = ensure(c, c->d_loc_rows, sizeof(double) * local_hp2_rowbuf_size(w.D, w.rows), false))) return rc;
+    if (out && (rc = ensure(c, out->logz, sizeof(double) * local_hp2_logz_size(w.D), false))) return rc;
     EventPair ev;
     HIP_TRY(c, ev.create());
-    std::vector<const char*> seqs((size_t)rows + cols);
-    std::vector<int> lens((size_t)rows + cols), first((size_t)rows * cols), second((size_t)rows * cols);
-    LocalHp2 A{};
-    A.P1 = P1; A.P2 = P2;
-    A.R = c->d_loc2_rows.as<double>(); A.acc = c->d_loc2_hp.as<double>();
-    const int col_blocks = (P2.n + kLocalThreads - 1) / kLocalThreads;
+    std::vector<const char*> seqs((size_t)w.rows + w.cols);
+    std::vector<int> lens((size_t)w.rows + w.cols), first((size_t)w.rows * w.cols), second((size_t)w.rows * w.cols);
     double ms_compute = 0.0, ms_acc = 0.0;
     float t = 0.f;
     LocalTile tile;
-    for (size_t ti = 0; local_tile_at(D, rows, cols, ti, &tile); ti++) {
+    for (size_t ti = 0; local_tile_at(w.D, w.rows, w.cols, ti, &tile); ti++) {
         const int kA = tile.kA, kB = tile.kB, lA = tile.lA, lB = tile.lB, nr = kB - kA, nc = lB - lA;
-        for (int a = 0; a < nr; a++) { seqs[a] = s1 + local_start(P1, kA + a); lens[a] = P1.We; }
-        for (int b = 0; b < nc; b++) { seqs[nr + b] = s2 + local_start(P2, lA + b); lens[nr + b] = P2.We; }
+        const int q1 = w.front == 1 ? 0 : nc, q2 = w.front == 1 ? nr : 0;   // the first sequence of either side
+        for (int a = 0; a < nr; a++) { seqs[q1 + a] = w.s1 + local_start(P1, kA + a); lens[q1 + a] = P1.We; }
+        for (int b = 0; b < nc; b++) { seqs[q2 + b] = w.s2 + local_start(P2, lA + b); lens[q2 + b] = P2.We; }
         for (int a = 0; a < nr; a++)
-            for (int b = 0; b < nc; b++) { first[(size_t)a * nc + b] = a; second[(size_t)a * nc + b] = nr + b; }
+            for (int b = 0; b < nc; b++) { first[(size_t)a * nc + b] = q1 + a; second[(size_t)a * nc + b] = q2 + b; }
         BatchRequest r;
         r.ns = nr + nc; r.seqs = seqs.data(); r.lens = lens.data();
-        r.with_mc = true; r.with_dx = true;
-        r.npairs = nr * nc; r.first = first.data(); r.second = second.data();
+        r.with_mc = true;
+        if (out) { r.with_dx = true; r.npairs = nr * nc; r.first = first.data(); r.second = second.data(); }
         if ((rc = stage(c, r))) return rc;
-        // one window pair is the pair itself and answers with the bits of rh_duplex: its one compute runs unseeded, as in local_run
+        // One window pair (W >= n on both sides) is the pair itself, and the call answers with the bits of rh_duplex: under
+        // RH_HYBRID_COFOLD that call has no folds to seed its two-molecule sweeps from, and seeded sweeps differ from it in the last
+        // bits on the scaled linear kernels -- so this one compute runs them unseeded too.  Every other tile is seeded, like any batch.
         const int seed = c->co_seed;
         if (P1.nw == 1 && P2.nw == 1) c->co_seed = 0;
         rc = compute(c);
         c->co_seed = seed;
         if (rc) return rc;
         ms_compute += c->ms[3];
-        A.hp = c->d_hp.as<const double>(); A.hp_stride = c->dx.tab_stride; A.ldd = c->dx.ldd;
-        A.kA = kA; A.kB = kB; A.lA = lA; A.lB = lB;
-        const int nt = local_start(P2, lB - 1) + P2.We - local_start(P2, lA);
+        const bool last = kB == P1.nw && lB == P2.nw;
         HIP_TRY(c, hipEventRecord(ev.a, c->s_mc));
-        hipLaunchKernelGGL(local_hp2_rows, dim3((nt + kLocalThreads - 1) / kLocalThreads, std::min(nr * P1.We, kLocalGridRows)), dim3(kLocalThreads), 0,
-                           c->s_mc, A);
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipMemcpy2DAsync(c->d_loc2_logz.as<double>() + (size_t)kA * P2.nw + lA, sizeof(double) * P2.nw, c->d_logz.p, sizeof(double) * nc,
-                                    sizeof(double) * nc, nr, hipMemcpyDeviceToDevice, c->s_mc));
-        if (lB == P2.nw) {
-            const int ni = local_start(P1, kB - 1) + P1.We - local_start(P1, kA);
-            hipLaunchKernelGGL(local_hp2_add_rows, dim3(col_blocks, std::min(ni, kLocalGridRows)), dim3(kLocalThreads), 0, c->s_mc, A);
+        if (w.band) {
+            const int q = w.band == 1 ? q1 : q2;
+            LocalAcc A{};
+            A.P = PB;
+            A.tri_stride = c->mc.tri_stride; A.up_stride = (size_t)c->mc.ld * max_w;
+            A.bp = c->d_bp.as<const double>() + q * A.tri_stride; A.up = c->d_up.as<const double>() + q * A.up_stride;
+            A.acc_bp = c->d_loc_bp.as<double>(); A.acc_up = c->d_loc_up.as<double>();
+            A.k0 = w.band == 1 ? kA : lA; A.k1 = w.band == 1 ? kB : lB; A.row0 = local_start(PB, A.k0); A.max_w = max_w;
+            const int rows = local_start(PB, A.k1 - 1) + PB.We - A.row0;
+            hipLaunchKernelGGL(local_accumulate, dim3(rows), dim3(kLocalThreads), 0, c->s_mc, A);
             HIP_TRY(c, hipGetLastError());
-            if (kB == P1.nw) {
+            HIP_TRY(c, hipMemcpyAsync(c->d_loc_logz.as<double>() + A.k0, c->d_mclogz.as<const double>() + q, sizeof(double) * (A.k1 - A.k0), hipMemcpyDeviceToDevice, c->s_mc));
+            if (last) {
+                hipLaunchKernelGGL(local_finish, dim3(PB.n), dim3(kLocalThreads), 0, c->s_mc, PB, max_w, A.acc_bp, A.acc_up);
+                HIP_TRY(c, hipGetLastError());
+            }
+        }
+        if (out) {
+            LocalHpGather G{};
+            G.P1 = P1; G.P2 = P2;
+            G.kA = kA; G.kB = kB; G.lA = lA; G.lB = lB;
+            if (P1.nw == 1 || two_level) {
+                G.src = c->d_hp.as<const double>(); G.src_stride = c->dx.tab_stride; G.src_pitch = c->dx.ldd;
+                G.dst = two_level ? c->d_loc_rows.as<double>() : out->hp.as<double>(); G.dst_stride = rows_stride;
+                const int nt = local_start(P2, lB - 1) + P2.We - local_start(P2, lA);
+                hipLaunchKernelGGL(local_hp_col_gather, dim3((nt + kLocalThreads - 1) / kLocalThreads, std::min(nr * P1.We, kLocalGridRows)), dim3(kLocalThreads),
+                                   0, c->s_mc, G);
+                HIP_TRY(c, hipGetLastError());
+            }
+            HIP_TRY(c, hipMemcpy2DAsync(out->logz.as<double>() + (size_t)kA * P2.nw + lA, sizeof(double) * P2.nw, c->d_logz.p, sizeof(double) * nc,
+                                        sizeof(double) * nc, nr, hipMemcpyDeviceToDevice, c->s_mc));
+            if (P1.nw > 1 && lB == P2.nw) {
+                G.src = two_level ? c->d_loc_rows.as<const double>() : c->d_hp.as<const double>();
+                G.src_stride = two_level ? rows_stride : c->dx.tab_stride; G.src_pitch = two_level ? (int)pitch : c->dx.ldd;
+                G.dst = out->hp.as<double>();
+                const int ni = local_start(P1, kB - 1) + P1.We - local_start(P1, kA);
+                hipLaunchKernelGGL(local_hp_row_gather, dim3((P2.n + kLocalThreads - 1) / kLocalThreads, std::min(ni, kLocalGridRows)), dim3(kLocalThreads), 0,
+                                   c->s_mc, G);
+                HIP_TRY(c, hipGetLastError());
+            }
+            if (last) {
                 hipLaunchKernelGGL(local_hp2_finish, dim3((P2.n + 1 + kLocalThreads - 1) / kLocalThreads, std::min(P1.n + 1, kLocalGridRows)),
-                                   dim3(kLocalThreads), 0, c->s_mc, P1, P2, A.acc);
+                                   dim3(kLocalThreads), 0, c->s_mc, P1, P2, out->hp.as<double>());
                 HIP_TRY(c, hipGetLastError());
             }
         }
@@ -496,10 +404,19 @@ int local2_run(rh_ctx* c, const LocalDuplex2Plan& D, const char* s1, const char*
         HIP_TRY(c, hipEventElapsedTime(&t, ev.a, ev.b));
         ms_acc += t;
     }
-    c->loc2 = D;
-    c->loc2_used[0] = rows; c->loc2_used[1] = cols;
-    c->loc2_ms[0] = ms_compute; c->loc2_ms[1] = ms_acc;
-    c->loc2_valid = true;
+    w.ms[0] = ms_compute; w.ms[1] = ms_acc;
+    if (w.band) { c->loc = PB; c->loc_max_w = max_w; c->loc_valid = true; }
+    if (out) { out->D = w.D; out->tile[0] = w.rows; out->tile[1] = w.cols; out->valid = true; }
+    return RH_OK;
+}
+
+// the fetch of an hp result
+int fetch_hp(rh_ctx* c, const LocalHp& R, double* hp, double* logz_pair)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (hp) HIP_TRY(c, hipMemcpyAsync(hp, R.hp.p, sizeof(double) * local_hp2_size(R.D), hipMemcpyDeviceToHost, c->s_mc));
+    if (logz_pair) HIP_TRY(c, hipMemcpyAsync(logz_pair, R.logz.p, sizeof(double) * local_hp2_logz_size(R.D), hipMemcpyDeviceToHost, c->s_mc));
+    HIP_TRY(c, hipStreamSynchronize(c->s_mc));
     return RH_OK;
 }
 
@@ -542,6 +459,13 @@ int scan_candidates(rh_ctx* c, const LocalScan& V, rh_cand* out, int cap, double
     return (int)found;
 }
 
+// the rows 1..n1 of an hp result as a scan
+LocalScan hp_scan(const LocalHp& R, float threshold)
+{
+    const int hp_ld = R.D.P2.n + 1;
+    return LocalScan{R.hp.as<const double>() + hp_ld, R.D.P1.n, hp_ld, hp_ld, 1, 0x3fffffff, kScanHp, threshold};
+}
+
 }  // namespace
 
 extern "C" {
@@ -557,10 +481,14 @@ int rh_set_local_chunk(rh_ctx* c, int windows)
 int rh_local_fold(rh_ctx* c, const char* seq, int n, int window, int step)
 {
     if (!c) return RH_ERR_ARG;
-    LocalPlan P;
+    LocalWalk w;
     std::string why;
-    if (int rc = local_check(seq, n, window, step, &P, &why)) return fail(c, rc, "%s", why.c_str());
-    return local_run(c, P, seq, nullptr, nullptr);
+    if (int rc = local_check(seq, n, window, step, &w.D.P1, &why)) return fail(c, rc, "%s", why.c_str());
+    w.s1 = seq;
+    w.rows = chunk_windows(c, w.D.P1, nullptr);
+    w.band = 1;
+    w.ms = c->loc_ms;
+    return local_walk(c, w);
 }
 
 int rh_local_duplex(rh_ctx* c, const char* s1, int n1, const char* s2, int n2, int windowed, int window, int step)
@@ -569,17 +497,29 @@ int rh_local_duplex(rh_ctx* c, const char* s1, int n1, const char* s2, int n2, i
     LocalDuplexPlan D;
     std::string why;
     if (int rc = local_duplex_check(s1, n1, s2, n2, windowed, window, step, &D, &why)) return fail(c, rc, "%s", why.c_str());
-    return local_run(c, D.P, windowed == 1 ? s1 : s2, &D, windowed == 1 ? s2 : s1);
+    const int chunk = chunk_windows(c, D.P, &D);
+    LocalWalk w;
+    w.D = local_duplex_grid(D);
+    w.s1 = s1; w.s2 = s2;
+    w.rows = windowed == 1 ? chunk : 1; w.cols = windowed == 1 ? 1 : chunk;
+    w.band = windowed;
+    w.front = windowed == 1 ? 2 : 1;   // the query is sequence 0 of every chunk
+    w.out = &c->loc_hp;
+    w.ms = c->loc_ms;                  // band and hp kernels together
+    if (int rc = local_walk(c, w)) return rc;
+    c->loc_hp.windowed = windowed;
+    return RH_OK;
 }
 
 int rh_local_hp_layout(rh_ctx* c, int* n1, int* n2, int* windowed, int* nw)
 {
     if (!c) return RH_ERR_ARG;
     if (int rc = local_hp_ready(c)) return rc;
-    if (n1) *n1 = c->loc_hp.n1;
-    if (n2) *n2 = c->loc_hp.n2;
-    if (windowed) *windowed = c->loc_hp.windowed;
-    if (nw) *nw = c->loc_hp.P.nw;
+    const LocalHp& R = c->loc_hp;
+    if (n1) *n1 = R.D.P1.n;
+    if (n2) *n2 = R.D.P2.n;
+    if (windowed) *windowed = R.windowed;
+    if (nw) *nw = R.windowed == 1 ? R.D.P1.nw : R.D.P2.nw;
     return RH_OK;
 }
 
@@ -587,11 +527,7 @@ int rh_local_hp_results(rh_ctx* c, double* hp, double* logz_pair)
 {
     if (!c) return RH_ERR_ARG;
     if (int rc = local_hp_ready(c)) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (hp) HIP_TRY(c, hipMemcpyAsync(hp, c->d_loc_hp.p, sizeof(double) * local_hp_size(c->loc_hp), hipMemcpyDeviceToHost, c->s_mc));
-    if (logz_pair) HIP_TRY(c, hipMemcpyAsync(logz_pair, c->d_loc_logzp.p, sizeof(double) * c->loc_hp.P.nw, hipMemcpyDeviceToHost, c->s_mc));
-    HIP_TRY(c, hipStreamSynchronize(c->s_mc));
-    return RH_OK;
+    return fetch_hp(c, c->loc_hp, hp, logz_pair);
 }
 
 int rh_local_layout(rh_ctx* c, int* n, int* ld, int* nw, int* max_w, int* starts)
@@ -625,11 +561,9 @@ int rh_local_candidates(rh_ctx* c, int what, float threshold, rh_cand* out, int 
     if (what < 0 || what > 2 || cap < 0 || (cap > 0 && !out)) return fail(c, RH_ERR_ARG, "rh_local_candidates: bad what/cap");
     HIP_TRY(c, hipSetDevice(c->device));
     const LocalPlan& P = c->loc;
-    const int hp_ld = c->loc_hp.n2 + 1;
-    const int n = what == 2 ? c->loc_hp.n1 : P.n;   // rows of the scan
-    const LocalScan V = what == 0   ? LocalScan{c->d_loc_bp.as<const double>(), n, P.ld, P.ld, 1, n - 1, kScanBp, threshold}
-                        : what == 1 ? LocalScan{c->d_loc_up.as<const double>(), n, c->loc_max_w, c->loc_max_w, 0, n - 1 + c->loc_max_w, kScanUp, threshold}
-                                    : LocalScan{c->d_loc_hp.as<const double>() + hp_ld, n, hp_ld, hp_ld, 1, 0x3fffffff, kScanHp, threshold};
+    const LocalScan V = what == 0   ? LocalScan{c->d_loc_bp.as<const double>(), P.n, P.ld, P.ld, 1, P.n - 1, kScanBp, threshold}
+                        : what == 1 ? LocalScan{c->d_loc_up.as<const double>(), P.n, c->loc_max_w, c->loc_max_w, 0, P.n - 1 + c->loc_max_w, kScanUp, threshold}
+                                    : hp_scan(c->loc_hp, threshold);
     return scan_candidates(c, V, out, cap, &c->loc_ms[1], "rh_local_candidates");
 }
 
@@ -655,17 +589,23 @@ int rh_set_local_tile(rh_ctx* c, int rows, int cols)
 int rh_local_duplex2(rh_ctx* c, const char* s1, int n1, const char* s2, int n2, int window1, int step1, int window2, int step2)
 {
     if (!c) return RH_ERR_ARG;
-    LocalDuplex2Plan D;
+    LocalWalk w;
     std::string why;
-    if (int rc = local_duplex2_check(s1, n1, s2, n2, window1, step1, window2, step2, &D, &why)) return fail(c, rc, "%s", why.c_str());
-    return local2_run(c, D, s1, s2);
+    if (int rc = local_duplex2_check(s1, n1, s2, n2, window1, step1, window2, step2, &w.D, &why)) return fail(c, rc, "%s", why.c_str());
+    w.s1 = s1; w.s2 = s2;
+    w.rows = c->loc2_tile[0]; w.cols = c->loc2_tile[1];
+    if (w.rows <= 0 || w.cols <= 0) local_tile_auto(w.D, local_tables(c), &w.rows, &w.cols);
+    w.rows = std::min(w.rows, w.D.P1.nw); w.cols = std::min(w.cols, w.D.P2.nw);
+    w.out = &c->loc_hp2;
+    w.ms = c->loc_hp2.ms;
+    return local_walk(c, w);
 }
 
 int rh_local_hp2_layout(rh_ctx* c, int* n1, int* n2, int* nw1, int* nw2, int* starts1, int* starts2)
 {
     if (!c) return RH_ERR_ARG;
     if (int rc = local_hp2_ready(c)) return rc;
-    const LocalPlan &P1 = c->loc2.P1, &P2 = c->loc2.P2;
+    const LocalPlan &P1 = c->loc_hp2.D.P1, &P2 = c->loc_hp2.D.P2;
     if (n1) *n1 = P1.n;
     if (n2) *n2 = P2.n;
     if (nw1) *nw1 = P1.nw;
@@ -679,11 +619,7 @@ int rh_local_hp2_results(rh_ctx* c, double* hp, double* logz_pair)
 {
     if (!c) return RH_ERR_ARG;
     if (int rc = local_hp2_ready(c)) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (hp) HIP_TRY(c, hipMemcpyAsync(hp, c->d_loc2_hp.p, sizeof(double) * local_hp2_size(c->loc2), hipMemcpyDeviceToHost, c->s_mc));
-    if (logz_pair) HIP_TRY(c, hipMemcpyAsync(logz_pair, c->d_loc2_logz.p, sizeof(double) * local_hp2_logz_size(c->loc2), hipMemcpyDeviceToHost, c->s_mc));
-    HIP_TRY(c, hipStreamSynchronize(c->s_mc));
-    return RH_OK;
+    return fetch_hp(c, c->loc_hp2, hp, logz_pair);
 }
 
 int rh_local_hp2_candidates(rh_ctx* c, float threshold, rh_cand* out, int cap)
@@ -692,17 +628,15 @@ int rh_local_hp2_candidates(rh_ctx* c, float threshold, rh_cand* out, int cap)
     if (int rc = local_hp2_ready(c)) return rc;
     if (cap < 0 || (cap > 0 && !out)) return fail(c, RH_ERR_ARG, "rh_local_hp2_candidates: bad cap");
     HIP_TRY(c, hipSetDevice(c->device));
-    const int n1 = c->loc2.P1.n, hp_ld = c->loc2.P2.n + 1;
-    const LocalScan V{c->d_loc2_hp.as<const double>() + hp_ld, n1, hp_ld, hp_ld, 1, 0x3fffffff, kScanHp, threshold};
-    return scan_candidates(c, V, out, cap, &c->loc2_ms[1], "rh_local_hp2_candidates");
+    return scan_candidates(c, hp_scan(c->loc_hp2, threshold), out, cap, &c->loc_hp2.ms[1], "rh_local_hp2_candidates");
 }
 
 int rh_local_hp2_tile(rh_ctx* c, int* rows, int* cols)
 {
     if (!c) return RH_ERR_ARG;
     if (int rc = local_hp2_ready(c)) return rc;
-    if (rows) *rows = c->loc2_used[0];
-    if (cols) *cols = c->loc2_used[1];
+    if (rows) *rows = c->loc_hp2.tile[0];
+    if (cols) *cols = c->loc_hp2.tile[1];
     return RH_OK;
 }
 
@@ -710,7 +644,7 @@ int rh_local_hp2_times(rh_ctx* c, double ms[2])
 {
     if (!c || !ms) return RH_ERR_ARG;
     if (int rc = local_hp2_ready(c)) return rc;
-    ms[0] = c->loc2_ms[0]; ms[1] = c->loc2_ms[1];
+    ms[0] = c->loc_hp2.ms[0]; ms[1] = c->loc_hp2.ms[1];
     return RH_OK;
 }
 

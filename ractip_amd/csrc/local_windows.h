@@ -105,6 +105,17 @@ struct LocalDuplex2Plan {
 // more window pairs than an int indexes (logz_pair[k*nw2 + l]); the product is taken in 64 bits.
 int local_duplex2_check(const char* s1, int n1, const char* s2, int n2, int window1, int step1, int window2, int step2, LocalDuplex2Plan* D,
                         std::string* why);
+// rh_local_duplex as a grid of window pairs: the query is the one window of its side (start 0, every letter of it in window 0; not
+// a plan local_check would give, a query may have one letter), and hp_loc has the layout of hp_loc2
+inline LocalDuplex2Plan local_duplex_grid(const LocalDuplexPlan& D)
+{
+    LocalPlan Q;
+    Q.n = Q.W = Q.We = Q.ld = D.nq; Q.S = 1; Q.nw = 1;
+    LocalDuplex2Plan G;
+    G.P1 = D.windowed == 1 ? D.P : Q;
+    G.P2 = D.windowed == 1 ? Q : D.P;
+    return G;
+}
 // doubles of hp_loc2: (n1+1) x (n2+1), row-major, 1-based (n1 = n2 = 1e5: 1e10 doubles) ...
 inline size_t local_hp2_size(const LocalDuplex2Plan& D) { return ((size_t)D.P1.n + 1) * ((size_t)D.P2.n + 1); }
 // ... of logz_pair [nw1][nw2] ...
@@ -119,10 +130,11 @@ inline size_t local_hp2_rowbuf_size(const LocalDuplex2Plan& D, int rows) { retur
 // with the actual rows and cols still fits.  Throughout rows + cols <= kLocalChunkMax (the sequences of a batch) and rows x cols <=
 // kLocalChunkMax - 1 (the pairs a chunk of rh_local_duplex reaches); (1, 1) when nothing fits.
 struct LocalTile { int kA = 0, kB = 0, lA = 0, lB = 0; };   // windows kA .. kB-1 of s1 with lA .. lB-1 of s2
-// tile t of the walk under (rows, cols), both already clipped to nw1 / nw2; false behind the last one
+// tile t of the walk under (rows, cols), both already clipped to nw1 / nw2; false behind the last one.  Without a second molecule
+// (P2.nw = 0, cols = 0: the chunks of rh_local_fold) a row block is one tile with lA = lB = 0.
 inline bool local_tile_at(const LocalDuplex2Plan& D, int rows, int cols, size_t t, LocalTile* out)
 {
-    const size_t per_block = ((size_t)D.P2.nw + cols - 1) / cols, kA = t / per_block * rows, lA = t % per_block * cols;
+    const size_t per_block = D.P2.nw > 0 ? ((size_t)D.P2.nw + cols - 1) / cols : 1, kA = t / per_block * rows, lA = t % per_block * cols;
     if (kA >= (size_t)D.P1.nw) return false;
     out->kA = (int)kA; out->kB = D.P1.nw - (int)kA < rows ? D.P1.nw : (int)kA + rows;
     out->lA = (int)lA; out->lB = D.P2.nw - (int)lA < cols ? D.P2.nw : (int)lA + cols;

@@ -207,12 +207,12 @@ def simulate(shape, h, tiles):
     acc = np.full((n1 + 1, n2 + 1), np.nan)
     for kA, kB, lA, lB in tiles:
         for k in range(kA, kB):
-            for l in range(lA, lB):                             # local_hp2_rows: per column its windows of the tile in increasing l
+            for l in range(lA, lB):                             # local_hp_col_gather: per column its windows of the tile in increasing l
                 sl = slice(b[l] + 1, b[l] + We2 + 1)
                 lo = first2[b[l]:b[l] + We2]
                 starts_here = (lo >= lA) & (np.maximum(lo, lA) == l)
                 R[k - kA][:, sl] = np.where(starts_here[None, :], 0.0, R[k - kA][:, sl]) + h[k][l]
-        if lB == len(b):                                        # local_hp2_add_rows: per row its windows of the block in increasing k
+        if lB == len(b):                                        # local_hp_row_gather: per row its windows of the block in increasing k
             for k in range(kA, kB):
                 sl = slice(a[k] + 1, a[k] + We1 + 1)
                 lo = first1[a[k]:a[k] + We1]

@@ -1,7 +1,7 @@
 """CPU suite: the window arithmetic of local folding (ractip_amd/csrc/local_windows.{h,cpp}) through the stand-alone program
 tools/local_windows_check.cpp built with the host sanitizers: the starts and the window count against the definition restated
-here, every rejection with its code and exact text, the windows that contain a run against a brute-force loop over the starts, and
-the band sizes of a sequence of a million letters as size_t."""
+here, every rejection with its code and exact text, the windows that contain a run against a brute-force loop over the starts,
+the band sizes of a sequence of a million letters as size_t, and the chunks of the tile walk when there is no second molecule."""
 import os
 import subprocess
 
@@ -109,6 +109,16 @@ def test_uncovered_runs_exist_only_with_a_step_above_one(exe):
             assert not uncovered
         else:
             assert uncovered and min(uncovered) > We - S + 1
+
+
+@pytest.mark.parametrize("n,W,S,chunk", [(41, 16, 1, 8), (41, 16, 1, 7), (43, 16, 5, 3), (43, 16, 5, 1), (43, 16, 5, 7), (43, 16, 5, 100), (9, 16, 1, 4)])
+def test_the_chunks_of_a_walk_without_a_second_molecule(exe, n, W, S, chunk):
+    """local_tile_at with P2.nw = 0: the chunks of rh_local_fold, first and last, with a ragged last one, one chunk, one window"""
+    nw = len(starts_restated(n, W, S))
+    chunk = min(chunk, nw)
+    want = [(k0, min(nw, k0 + chunk), 0, 0) for k0 in range(0, nw, chunk)]
+    got = [tuple(int(x) for x in line.split()) for line in run(exe, "chunks", n, W, S, chunk).splitlines()]
+    assert got == want and got[0][0] == 0 and got[-1][1] == nw
 
 
 def test_band_sizes_of_a_million_letters_are_size_t(exe):
