@@ -407,6 +407,31 @@ int rh_set_local_chunk(rh_ctx* ctx, int windows);
  * the accumulate and finish kernels, plus the scan kernels of the rh_local_candidates calls since. */
 int rh_local_times(rh_ctx* ctx, double ms[2]);
 
+/* ---- span-limited folding: the whole long sequence, pairs within max_span letters ----
+ * Inputs: n letters, max_span = L >= 2, Le = min(L, n).
+ * Ensemble: that of rh_fold under the context's Vienna-BL model (1.8 semantics, BL* tables or a parameter file), the treatment of
+ * unknown letters and of the end letters included.  Letters a < b (1-based) may pair only if b - a < L; nothing else changes.  With
+ * L >= n it is the ensemble of rh_fold.  Unlike rh_local_fold, which averages windows folded as if the molecule ended at their
+ * borders, this is one consistent ensemble of the whole molecule with one partition function (ViennaRNA's --maxBPspan; RNAplfold at
+ * W = n), in O(n L) memory and O(n L^2) time.  The exterior sums are kept as logarithms, so the length of the sequence cannot take
+ * the call out of the double range (ractip_amd/csrc/span_fold.h).
+ * Results, in the local-fold layouts: bp_band[i*ld + d] = P(i, i+d), i 0-based, ld = Le, column 0 and every entry with i + d >= n
+ * hold 0; up[i] (width 1) = 1 - sum_j P(i, j); logz_win[0] = log Z of the whole sequence.  They are fetched through rh_local_layout
+ * (which reports nw = 1, starts = {0}, ld = Le, max_w = 1 whatever the context's max_w is), rh_local_results and
+ * rh_local_candidates.  A span fold replaces the previous local-fold result exactly as an rh_local_fold would: it drops the hp part
+ * of an rh_local_duplex and leaves the result of rh_local_duplex2 alone.  The context's batch is neither read nor changed.
+ * Refusals.  RH_ERR_ARG: NULL sequence, n < 1, L < 2, sizes that overflow.  RH_ERR_UNSUPPORTED: CONTRAfold contexts, 2.x-semantics
+ * contexts, contexts in RH_MODE_LOG (there is no log-space version).  Both leave the previous local result and the batch in place;
+ * rh_last_error names the reason.  Structure constraints do not apply.
+ * A band cell that leaves the double range under the context's scale exponent sends the call through the exponent ladder; when no
+ * exponent holds it returns RH_ERR_UNSUPPORTED and leaves no local result, as RH_ERR_OOM does (buffers grow only and go with the
+ * context).
+ * Not covered yet: region accessibility for widths above one, the CONTRAfold model, batches of long sequences. */
+int rh_span_fold(rh_ctx* ctx, const char* seq, int n, int max_span);
+/* Measurement aid: device time (ms, HIP event pairs) of the last rh_span_fold: ms[0] the inside and outside sweeps (2 Le launches),
+ * ms[1] the two exterior passes and the finish kernel. */
+int rh_span_times(rh_ctx* ctx, double ms[2]);
+
 /* ---- local hybridization: window-averaged hp of a query on a long target ----
  * Two molecules s1 (n1 letters) and s2 (n2 letters).  `windowed` (1 or 2) names the one that is cut into the windows of rh_local_fold
  * (same W, S, We, starts); the other one, the query, is always whole.  For window k the engine computes hp_k of the pair

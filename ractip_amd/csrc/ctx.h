@@ -18,6 +18,7 @@
 #include "lin_model.h"
 #include "vienna_model.h"
 #include "scale_order.h"
+#include "span_fold.h"
 
 struct rh_ctx;
 
@@ -374,6 +375,11 @@ struct Ctx {   // (the fields of rh_ctx, below)
     LocalHp loc_hp2;
     int loc2_tile[2] = {0, 0};     // rh_set_local_tile: rows, cols of a tile (0, 0: local_tile_auto)
     DevBuf d_loc_rows;             // the row buffer of one row block of a walk with several windows on both sides (grow-only)
+    // rh_span_fold only (mccaskill_span.hip): the band tables, the exterior logarithms with the hairpin length weights behind them, the
+    // letters and the flag (grow-only); its result is the local result above.  span_ms: the sweeps; the exterior passes and the finish
+    DevBuf d_span_tab, d_span_ext, d_span_seq, d_span_bad;
+    double span_ms[2] = {0, 0};
+    bool span_timed = false;       // a span fold has run on this context
     std::vector<hipEvent_t> tev;   // event pool of the timed class (pairs), tev_n used by the last compute
     size_t tev_n = 0;
     Ctx() = default;

@@ -1,0 +1,423 @@
+// mccaskill_span.hip -- span-limited folding (rh_span_fold): the McCaskill ensemble of a whole long sequence under the Vienna-BL model,
+// restricted to pairs (a, b) with b - a < L.  Definition, table layout and the exterior representation: span_fold.h.
+//
+// The recurrences are those of mccaskill_vlin.hip for one molecule (hairpins, the interior loops within kMaxSingle, FM2 = sum FM1 x FM,
+// FM1 / FMS / FM, the pull-form outside and the posterior) on band tables of Le rows: every term whose enclosing or enclosed pair
+// would lie in a row d >= Le is dropped, and the exterior sums are logarithms (span_ext_pass).  One launch per diagonal, one lane per
+// cell, 64 consecutive cells of a diagonal per wavefront: every operand is a contiguous row segment.  The sums of a cell are plain
+// loops of at most Le terms.  Every launch writes its whole row, zeros where no cell exists, so nothing is cleared and a read only
+// needs its row and column inside the tables.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "ctx.h"
+#include "constraint_prepass.h"
+#include "dev_util.h"
+#include "vienna_model.h"
+
+using namespace rh;
+using namespace rh::host;
+
+namespace {
+
+constexpr int kSpanThreads = 256;
+constexpr double kSpanHuge = 1e280, kSpanTiny = 1e-280;   // a band cell outside them raises the flag
+enum SpanTable { SP_FC = 0, SP_FCX, SP_FCB, SP_FCA, SP_FM1, SP_FMS, SP_FM, SP_FCO, SP_FCOX, SP_FCOB, SP_FMSO, SP_FM1O, SP_FM2O, SP_COUNT };
+static_assert(SP_COUNT == kSpanInside + kSpanOutside);
+
+struct SpanArgs {
+    double* tab;           // SP_COUNT band tables of ts doubles, [d * ldn + i]
+    size_t ldn, ts;
+    const uint8_t* s;      // letters 1..n, code 0 at 0 and n+1
+    int n, Le, L;
+    const double* hplen;   // hairpin length weight x lam^d, d < Le
+    double* gi;            // log F5i [n+1]
+    double* go;            // log F5o [n+1]
+    double* band;          // bp_band [n][Le]
+    double* up;            // [n]
+    double* logz;          // [1]
+    int* bad;
+    double sc;             // the scale exponent s of the model
+};
+
+// the seven tabulated loop shapes (as mccaskill_vlin.hip): outer pair type t1, inner pair type t2, letters si1/sj1 next to the outer
+// pair inside the loop, sp1/sq1 next to the inner pair
+__device__ __forceinline__ double span_small_w(const VLinModel* L, int l1, int l2, int t1, int t2, int si1, int sj1, int sp1, int sq1)
+{
+    const int r2 = vienna_rtype(t2);
+    const int tt = t1 * 8 + r2;
+    if (l1 == 0 && l2 == 0) return L->E_stack[tt];
+    if (l1 + l2 == 1) return L->E_bulge1[tt];
+    if (l1 == 1 && l2 == 1) return L->E_int11[tt * 25 + si1 * 5 + sj1];
+    if (l1 == 1 && l2 == 2) return L->E_int21[tt * 125 + (si1 * 5 + sq1) * 5 + sj1];
+    if (l1 == 2 && l2 == 1) return L->E_int21[(r2 * 8 + t1) * 125 + (sq1 * 5 + si1) * 5 + sp1];
+    return L->E_int22[tt * 625 + ((si1 * 5 + sp1) * 5 + sq1) * 5 + sj1];
+}
+__device__ __forceinline__ int small_l1(int k) { return (k == 2 || k == 3 || k == 4) ? 1 : (k >= 5 ? 2 : 0); }
+__device__ __forceinline__ int small_l2(int k) { return (k == 1 || k == 3 || k == 5) ? 1 : ((k == 4 || k == 6) ? 2 : 0); }
+
+// ---- inside, diagonal d: grid over the ldn columns of the row
+__global__ __launch_bounds__(kSpanThreads) void span_inside_diag(SpanArgs A, const VLinModel* __restrict__ M, int d)
+{
+    const size_t col = (size_t)blockIdx.x * kSpanThreads + threadIdx.x;
+    if (col >= A.ldn) return;
+    const int i = (int)col, n = A.n, j = i + d;
+    const size_t ldn = A.ldn, ts = A.ts, at = (size_t)d * ldn + i;
+    double* __restrict__ tab = A.tab;
+    const bool valid = i >= 1 && i <= n - 1 - d;
+    double fc = 0.0, e_txi = 0.0, e_tau = 1.0, e_tsa = 0.0, fm1v = 0.0, fmsv = 0.0, fmv = 0.0;
+    bool bad = false;
+    if (valid) {
+        const uint8_t* __restrict__ s = A.s;
+        const int s_im1 = s[i - 1], s_i = s[i], s_ip1 = s[i + 1], s_j = s[j], s_jp1 = s[j + 1], s_jp2 = s[j + 2];
+        const int type = d + 1 < A.L ? vienna_ptype(s_i, s_jp1) : 0;   // the pair (i, j+1) spans d + 1 letters
+        double fm2 = 0.0;
+        {   // FM2[i,d] = sum_{m=1}^{d-1} FM1[m][i] * FM[d-m][i+m]
+            const double* __restrict__ fm1 = tab + SP_FM1 * ts + i;
+            const double* __restrict__ fm = tab + SP_FM * ts + i;
+            for (int m = 1; m <= d - 1; m++) fm2 = fma(fm1[(size_t)m * ldn], fm[(size_t)(d - m) * ldn + m], fm2);
+        }
+        if (type) {
+            const int idx = 25 * (5 * s_i + s_ip1) + 5 * s_jp1 + s_j;           // (i, j+1) seen from inside
+            const int idx_raw = 25 * (5 * s_jp1 + s_jp2) + 5 * s_i + s_im1;     // seen from outside
+            const double e_txo = M->TXO[idx], e_tmc = M->TMC[idx];
+            e_tau = M->E_tau[type]; e_txi = M->TXI[idx_raw]; e_tsa = M->TSA[idx_raw];
+            const int b_ip2 = s[i + 2 <= n + 1 ? i + 2 : n + 1], b_ip3 = s[i + 3 <= n + 1 ? i + 3 : n + 1];
+            const int b_jm1 = s[j - 1 >= 0 ? j - 1 : 0], b_jm2 = s[j - 2 >= 0 ? j - 2 : 0];
+            double hp = 0.0;
+            if (d == 3) hp = A.hplen[d] * e_tau;
+            else if (d > 3) {
+                double tet = 1.0;
+                if (d == 4 && s_i != 0 && s_ip1 != 0 && b_ip2 != 0 && b_ip3 != 0 && s_j != 0 && s_jp1 != 0)
+                    tet = M->E_tetra[(((((s_i - 1) * 4 + (s_ip1 - 1)) * 4 + (b_ip2 - 1)) * 4 + (b_ip3 - 1)) * 4 + (s_j - 1)) * 4 + (s_jp1 - 1)];
+                hp = A.hplen[d] * M->TMH[idx] * tet;
+            }
+            // loops with one enclosed pair (p, q) = (i+1+l1, j-l2), cell (p, d-2-t), t = l1 + l2: generic interior loops over FCX, bulges
+            // of two letters and more over FCB, the seven tabulated shapes over FC
+            double g = 0.0, gb = 0.0, sm = 0.0;
+            const int tmax = d - 2 < kMaxSingle ? d - 2 : kMaxSingle;
+            for (int t = 2; t <= tmax; t++) {
+                const size_t row = (size_t)(d - 2 - t) * ldn + i + 1;
+                if (t >= 4) {
+                    const double* __restrict__ w = M->shape_w + t * (t + 1) / 2;
+                    const double* __restrict__ x = tab + SP_FCX * ts + row;
+                    for (int l1 = 1; l1 < t; l1++) g = fma(w[l1], x[l1], g);
+                }
+                const double* __restrict__ xb = tab + SP_FCB * ts + row;
+                gb = fma(M->WB[t], xb[0] + xb[t], gb);
+            }
+#pragma unroll
+            for (int k = 0; k < 7; k++) {
+                const int l1 = small_l1(k), l2 = small_l2(k), t = l1 + l2;
+                if (d - 2 - t < 0) continue;
+                const double v = tab[SP_FC * ts + (size_t)(d - 2 - t) * ldn + i + 1 + l1];
+                if (v == 0.0) continue;
+                const int sp = l1 == 0 ? s_ip1 : (l1 == 1 ? b_ip2 : b_ip3), spm = l1 == 0 ? s_i : (l1 == 1 ? s_ip1 : b_ip2);
+                const int sq = l2 == 0 ? s_j : (l2 == 1 ? b_jm1 : b_jm2), sqp = l2 == 0 ? s_jp1 : (l2 == 1 ? s_j : b_jm1);
+                sm = fma(v, span_small_w(M, l1, l2, type, vienna_ptype(sp, sq), s_ip1, s_j, spm, sqp), sm);
+            }
+            fc = e_txo * g + e_tau * gb + sm + hp + fm2 * e_tmc;
+            if (!(fc == fc) || fc > kSpanHuge || (fc != 0.0 && fc < kSpanTiny)) bad = true;
+        }
+        if (d >= 2) {
+            fm1v = tab[SP_FCA * ts + (size_t)(d - 2) * ldn + i + 1] * M->w_mp2 + tab[SP_FM1 * ts + (size_t)(d - 1) * ldn + i + 1] * M->w_mu;
+            fmsv = fm1v + tab[SP_FMS * ts + (size_t)(d - 1) * ldn + i] * M->w_mu;
+            fmv = fm2 + fmsv;
+            if (!(fmv == fmv) || fmv > kSpanHuge) bad = true;
+        }
+    }
+    if (bad) { atomicOr(A.bad, 1); fc = fm1v = fmsv = fmv = 0.0; }
+    tab[SP_FC * ts + at] = fc;
+    tab[SP_FCX * ts + at] = fc * e_txi;
+    tab[SP_FCB * ts + at] = fc * e_tau;
+    tab[SP_FCA * ts + at] = fc * e_tsa;
+    tab[SP_FM1 * ts + at] = fm1v;
+    tab[SP_FMS * ts + at] = fmsv;
+    tab[SP_FM * ts + at] = fmv;
+}
+
+// ---- the exterior logarithms, one workgroup of kSpanWaves wavefronts: dir 0 writes gi[0..n] ascending, dir 1 go[n..0] descending
+// (span_fold.h).  Phase A of a block is spread over the wavefronts -- wavefront w takes the rows d = w, w + kSpanWaves, .. of every
+// entry, four loads in flight per lane -- as is the fill of T; phase B runs on wavefront 0.  An entry is read by the blocks behind
+// the one that wrote it: the barriers of a block order them.
+__global__ __launch_bounds__(kSpanBlock * kSpanWaves) void span_ext_pass(SpanArgs A, int dir)
+{
+    __shared__ double T[kSpanBlock][kSpanBlock];      // T[l][m]: the term of entry l whose other end is entry m of the block
+    __shared__ double part[kSpanWaves][kSpanBlock];   // phase-A sums per wavefront
+    __shared__ double esd[kSpanBlock];                // exp(s d)
+    __shared__ double ref_s;
+    const int w = threadIdx.x / kSpanBlock, lane = threadIdx.x % kSpanBlock, n = A.n, Le = A.Le;
+    const size_t ldn = A.ldn;
+    const double* __restrict__ fca = A.tab + SP_FCA * A.ts;
+    double* g = dir == 0 ? A.gi : A.go;
+    const double s = A.sc;
+    double g_ref = 0.0;
+    if (w == 0) esd[lane] = exp(s * (double)lane);
+    if (threadIdx.x == 0) g[dir == 0 ? 0 : n] = 0.0;
+    __syncthreads();
+    const int nb = span_ext_blocks(n);
+    for (int b = 0; b < nb; b++) {
+        const int at = span_ext_entry(dir, n, b, lane);
+        const bool on = at >= 0 && at <= n;
+        // A: the terms whose other end lies in front of the block, ascending d within a wavefront
+        double a = 0.0;
+        if (on) {
+            const int dmax = span_ext_dmax(dir, n, Le, at);
+            for (int d = span_ext_first(lane, w); d <= dmax; d += 4 * kSpanWaves) {
+                double gk[4], f[4];
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    const int du = d + u * kSpanWaves <= dmax ? d + u * kSpanWaves : d;
+                    gk[u] = g[span_ext_other(dir, at, du)];
+                    f[u] = fca[(size_t)du * ldn + span_ext_col(dir, at, du)];
+                }
+#pragma unroll
+                for (int u = 0; u < 4; u++)
+                    if (d + u * kSpanWaves <= dmax) a += span_ext_term(gk[u], g_ref, s * (double)(d + u * kSpanWaves), f[u]);
+            }
+        }
+        part[w][lane] = a;
+        // the terms inside the block: lane m fills its column, rows l = m+2 .. 63; for a row d the lanes read neighbouring cells
+        for (int d = w; d < kSpanBlock; d += kSpanWaves) {
+            const int l = lane + 2 + d;
+            if (l >= kSpanBlock) continue;
+            const int atl = span_ext_entry(dir, n, b, l);
+            const bool cell = d < Le && atl >= 0 && atl <= n;
+            T[l][lane] = cell ? fca[(size_t)d * ldn + span_ext_col(dir, atl, d)] * esd[d] : 0.0;
+        }
+        __syncthreads();
+        if (w == 0) {
+            a = part[0][lane];
+            for (int k = 1; k < kSpanWaves; k++) a += part[k][lane];
+            // B: the entries one after the other; every lane carries the running ratio, lane l keeps its own
+            double r = 1.0, mine = 0.0;
+            const int count = min(kSpanBlock, n - b * kSpanBlock);   // entries of this block
+            for (int l = 0; l < count; l++) {
+                const double inner = wsum(lane <= l - 2 ? mine * T[l][lane] : 0.0);
+                r = span_ext_ratio(r, __shfl(a, l, kSpanBlock), inner);
+                if (lane == l) mine = r;
+            }
+            if (on) g[at] = span_ext_log(g_ref, mine);
+            if (lane == 0) ref_s = span_ext_log(g_ref, r);
+        }
+        __syncthreads();   // the entries are read by the blocks behind this one; T and part are refilled
+        g_ref = ref_s;
+    }
+    if (threadIdx.x == 0 && !(g_ref == g_ref && g_ref < 1e300 && g_ref > -1e300)) atomicOr(A.bad, 1);
+}
+
+// ---- outside (pull form) and posterior, diagonal d
+__global__ __launch_bounds__(kSpanThreads) void span_outside_diag(SpanArgs A, const VLinModel* __restrict__ M, int d)
+{
+    const size_t col = (size_t)blockIdx.x * kSpanThreads + threadIdx.x;
+    if (col >= A.ldn) return;
+    const int i = (int)col, n = A.n, j = i + d, Le = A.Le;
+    const size_t ldn = A.ldn, ts = A.ts, at = (size_t)d * ldn + i;
+    double* __restrict__ tab = A.tab;
+    const bool valid = i >= 1 && i <= n - 1 - d;
+    double fco = 0.0, e_txo = 0.0, e_tau = 1.0, fmso = 0.0, fm1o = 0.0, fm2o = 0.0, p = 0.0;
+    bool bad = false;
+    if (valid) {
+        const uint8_t* __restrict__ s = A.s;
+        const int s_im1 = s[i - 1], s_i = s[i], s_ip1 = s[i + 1], s_j = s[j], s_jp1 = s[j + 1], s_jp2 = s[j + 2];
+        const int type = d + 1 < A.L ? vienna_ptype(s_i, s_jp1) : 0;
+        double fmo = 0.0;
+        if (d >= 2) {
+            const int emax = Le - 1 - d;
+            double s1 = 0.0;
+            {   // FMo[i,d] = sum_e FM2o[d+e][i-e] * FM1[e][i-e]: the part (i-e .. i] in front of this one
+                const int e1 = i - 1 < emax ? i - 1 : emax;
+                const double* __restrict__ x = tab + SP_FM2O * ts + (size_t)d * ldn + i;
+                const double* __restrict__ y = tab + SP_FM1 * ts + i;
+                for (int e = 1; e <= e1; e++) fmo = fma(x[(size_t)e * ldn - e], y[(size_t)e * ldn - e], fmo);
+            }
+            {   // FM1o[i,d] += sum_e FM2o[d+e][i] * FM[e][j]: the part (j .. j+e] behind this one
+                const int e1 = n - 1 - j < emax ? n - 1 - j : emax;
+                const double* __restrict__ x = tab + SP_FM2O * ts + (size_t)d * ldn + i;
+                const double* __restrict__ y = tab + SP_FM * ts + j;
+                for (int e = 1; e <= e1; e++) s1 = fma(x[(size_t)e * ldn], y[(size_t)e * ldn], s1);
+            }
+            const bool up = d + 1 < Le;
+            fmso = fmo + (up ? tab[SP_FMSO * ts + (size_t)(d + 1) * ldn + i] : 0.0) * M->w_mu;
+            fm1o = s1 + fmso + (up ? tab[SP_FM1O * ts + (size_t)(d + 1) * ldn + i - 1] : 0.0) * M->w_mu;
+        }
+        double e_tmc = 0.0;
+        if (type) {
+            const int idx = 25 * (5 * s_i + s_ip1) + 5 * s_jp1 + s_j;
+            const int idx_raw = 25 * (5 * s_jp1 + s_jp2) + 5 * s_i + s_im1;
+            e_txo = M->TXO[idx]; e_tmc = M->TMC[idx]; e_tau = M->E_tau[type];
+            const double e_txi = M->TXI[idx_raw], e_tsa = M->TSA[idx_raw];
+            const double ext = span_ext_outer(A.gi[i - 1], A.go[j + 1], A.gi[n], A.sc * (double)d);
+            const double multi = d + 2 < Le ? tab[SP_FM1O * ts + (size_t)(d + 2) * ldn + i - 1] * M->w_mp2 : 0.0;
+            // enclosing pairs (io, jo+1) = (i-1-l1, j+2+l2), cell (io, d+2+t); a cell that does not exist holds 0, column 0 included
+            double g = 0.0, gb = 0.0, sm = 0.0;
+            for (int t = 2; t <= kMaxSingle && d + 2 + t < Le; t++) {
+                const size_t base = (size_t)(d + 2 + t) * ldn + i - 1;
+                if (t >= 4) {
+                    const double* __restrict__ w = M->shape_w + t * (t + 1) / 2;
+                    const double* __restrict__ x = tab + SP_FCOX * ts + base;
+                    const int l1e = t - 1 < i - 1 ? t - 1 : i - 1;
+                    for (int l1 = 1; l1 <= l1e; l1++) g = fma(w[l1], x[-l1], g);
+                }
+                const double* __restrict__ xb = tab + SP_FCOB * ts + base;
+                gb = fma(M->WB[t], xb[0] + (t <= i - 1 ? xb[-t] : 0.0), gb);
+            }
+#pragma unroll
+            for (int k = 0; k < 7; k++) {
+                const int l1 = small_l1(k), l2 = small_l2(k), io = i - 1 - l1, jo = j + 1 + l2;
+                if (d + 2 + l1 + l2 >= Le || io < 1 || jo > n - 1) continue;
+                const double v = tab[SP_FCO * ts + (size_t)(jo - io) * ldn + io];
+                if (v == 0.0) continue;
+                const int to = vienna_ptype(s[io], s[jo + 1]);
+                sm = fma(v, span_small_w(M, l1, l2, to, type, s[io + 1], s[jo], s_im1, s_jp2), sm);
+            }
+            fco = e_tsa * (ext + multi) + e_txi * g + e_tau * gb + sm;
+            p = d >= kMinHairpin ? fco * tab[SP_FC * ts + at] : 0.0;
+            if (!(p == p) || !(fco == fco) || p > 1e300 || fco > 1e300) { bad = true; p = 0.0; fco = 0.0; }
+            p = p > 1.0 ? 1.0 : (p < 0.0 ? 0.0 : p);
+        }
+        fm2o = fmo + fco * e_tmc;
+        if (!(fm2o == fm2o) || fm2o > 1e300 || !(fm1o == fm1o) || fm1o > 1e300) { bad = true; fm2o = fm1o = fmso = 0.0; }
+    }
+    if (bad) atomicOr(A.bad, 1);
+    tab[SP_FCO * ts + at] = fco;
+    tab[SP_FCOX * ts + at] = fco * e_txo;
+    tab[SP_FCOB * ts + at] = fco * e_tau;
+    tab[SP_FMSO * ts + at] = fmso;
+    tab[SP_FM1O * ts + at] = fm1o;
+    tab[SP_FM2O * ts + at] = fm2o;
+    // bp_band[(i-1) * Le + d+1] = P(i, i+d+1); the lanes 1..n cover every row of the band, 0 where the pair runs off the end
+    if (i >= 1 && i <= n && d + 1 < Le) A.band[(size_t)(i - 1) * Le + d + 1] = p;
+}
+
+// ---- finish: up[i] = 1 - sum_j P(i, j), column 0 of the band, log Z.  grid (n), one wavefront per letter
+__global__ __launch_bounds__(kSpanBlock) void span_finish(SpanArgs A)
+{
+    const int i0 = blockIdx.x, lane = threadIdx.x, n = A.n, Le = A.Le;
+    double acc = 0.0;
+    for (int dd = 1 + lane; dd < Le; dd += kSpanBlock) {
+        if (i0 + dd < n) acc += A.band[(size_t)i0 * Le + dd];
+        if (i0 - dd >= 0) acc += A.band[(size_t)(i0 - dd) * Le + dd];
+    }
+    acc = wsum(acc);
+    if (lane == 0) {
+        const double u = 1.0 - acc;
+        A.up[i0] = u < 0.0 ? 0.0 : u;
+        A.band[(size_t)i0 * Le] = 0.0;
+        if (i0 == 0) A.logz[0] = A.gi[n];
+    }
+}
+
+// the events of one call, gone with their scope
+struct SpanEvents {
+    hipEvent_t e[5] = {};
+    hipError_t create()
+    {
+        for (auto& x : e) { hipError_t r = hipEventCreate(&x); if (r != hipSuccess) return r; }
+        return hipSuccess;
+    }
+    ~SpanEvents() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
+};
+
+// one attempt on the model selected now: inside sweep, exterior passes, outside sweep, finish; *flag = the device flag behind them
+int span_attempt(rh_ctx* c, SpanArgs A, const SpanEvents& ev, int* flag)
+{
+    const VLinModel* M = c->d_vlin;
+    hipStream_t st = c->s_mc;
+    std::vector<double> hplen((size_t)A.Le);
+    hairpin_length_weights(*c->h_vlin, A.Le, hplen.data());
+    A.sc = c->h_vlin->s;
+    HIP_TRY(c, hipMemcpyAsync(const_cast<double*>(A.hplen), hplen.data(), sizeof(double) * hplen.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemsetAsync(A.bad, 0, sizeof(int), st));
+    const dim3 grid((unsigned)((A.ldn + kSpanThreads - 1) / kSpanThreads)), block(kSpanThreads);
+    HIP_TRY(c, hipEventRecord(ev.e[0], st));
+    for (int d = 0; d < A.Le; d++) hipLaunchKernelGGL(span_inside_diag, grid, block, 0, st, A, M, d);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(ev.e[1], st));
+    hipLaunchKernelGGL(span_ext_pass, dim3(1), dim3(kSpanBlock * kSpanWaves), 0, st, A, 0);
+    hipLaunchKernelGGL(span_ext_pass, dim3(1), dim3(kSpanBlock * kSpanWaves), 0, st, A, 1);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(ev.e[2], st));
+    for (int d = A.Le - 1; d >= 0; d--) hipLaunchKernelGGL(span_outside_diag, grid, block, 0, st, A, M, d);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(ev.e[3], st));
+    hipLaunchKernelGGL(span_finish, dim3(A.n), dim3(kSpanBlock), 0, st, A);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(ev.e[4], st));
+    HIP_TRY(c, hipMemcpyAsync(flag, A.bad, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    float t[4] = {};
+    for (int k = 0; k < 4; k++) HIP_TRY(c, hipEventElapsedTime(&t[k], ev.e[k], ev.e[k + 1]));
+    c->span_ms[0] = (double)t[0] + t[2];
+    c->span_ms[1] = (double)t[1] + t[3];
+    return RH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rh_span_fold(rh_ctx* c, const char* seq, int n, int max_span)
+{
+    if (!c) return RH_ERR_ARG;
+    SpanPlan P;
+    std::string why;
+    if (int rc = span_check(seq, n, max_span, &P, &why)) return fail(c, rc, "%s", why.c_str());
+    if (c->model != RH_MODEL_VIENNA_BL) return fail(c, RH_ERR_UNSUPPORTED, "span fold: the CONTRAfold model has no span-limited kernels (Vienna-BL contexts only)");
+    if (c->vienna_sem == kViennaSem20) return fail(c, RH_ERR_UNSUPPORTED, "span fold: ViennaRNA-2.x semantics have no span-limited kernels (1.8 semantics only)");
+    if (c->mode == RH_MODE_LOG) return fail(c, RH_ERR_UNSUPPORTED, "span fold: there is no log-space version (the context is in RH_MODE_LOG)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->loc_valid = c->loc_hp.valid = false;   // (the hp result of rh_local_duplex goes with the band it came with)
+    int rc;
+    const size_t seq_bytes = ((size_t)n + 2 + 15) & ~(size_t)15;
+    if ((rc = ensure(c, c->d_span_tab, sizeof(double) * P.tables, false))) return rc;
+    if ((rc = ensure(c, c->d_span_ext, sizeof(double) * (P.ext + (size_t)P.Le), false))) return rc;
+    if ((rc = ensure(c, c->d_span_seq, seq_bytes, false))) return rc;
+    if ((rc = ensure(c, c->d_span_bad, sizeof(int), false))) return rc;
+    if ((rc = ensure(c, c->d_loc_bp, sizeof(double) * P.band, false))) return rc;
+    if ((rc = ensure(c, c->d_loc_up, sizeof(double) * (size_t)n, false))) return rc;
+    if ((rc = ensure(c, c->d_loc_logz, sizeof(double), false))) return rc;
+    SpanEvents ev;
+    HIP_TRY(c, ev.create());
+    std::vector<uint8_t> codes(seq_bytes, 0);
+    for (int i = 0; i < n; i++) codes[(size_t)i + 1] = vienna_code(seq[i]);
+    HIP_TRY(c, hipMemcpyAsync(c->d_span_seq.p, codes.data(), seq_bytes, hipMemcpyHostToDevice, c->s_mc));
+    SpanArgs A{};
+    A.tab = c->d_span_tab.as<double>(); A.ldn = P.ldn; A.ts = P.table;
+    A.s = c->d_span_seq.as<const uint8_t>();
+    A.n = n; A.Le = P.Le; A.L = max_span;
+    A.gi = c->d_span_ext.as<double>(); A.go = A.gi + (n + 1); A.hplen = A.go + (n + 1);
+    A.band = c->d_loc_bp.as<double>(); A.up = c->d_loc_up.as<double>(); A.logz = c->d_loc_logz.as<double>();
+    A.bad = c->d_span_bad.as<int>();
+    // the context's exponent first, then its ladder in exponent_order's order, while a band cell leaves the double range
+    std::vector<int> order = {c->vlin_primary};
+    for (int model : exponent_order(c->vlin_primary, c->vlin_m[0].h->s, kVRungS, rh_ctx::kVRungs)) order.push_back(model);
+    int flag = 1;
+    for (size_t a = 0; a < order.size() && flag; a++) {
+        if ((rc = select_vlin(c, order[a]))) break;
+        if ((rc = span_attempt(c, A, ev, &flag))) break;
+    }
+    const int back = select_vlin(c, c->vlin_primary);
+    if (rc) return rc;
+    if (back) return back;
+    if (flag) return fail(c, RH_ERR_UNSUPPORTED, "span fold: no scale exponent of the ladder keeps the band tables of max_span %d in the double range", max_span);
+    LocalPlan R;
+    R.n = n; R.W = max_span; R.S = 1; R.We = n; R.nw = 1; R.ld = P.Le;   // one window at 0 with the band pitch Le
+    c->loc = R; c->loc_max_w = 1; c->loc_valid = true;
+    c->loc_ms[0] = c->span_ms[0]; c->loc_ms[1] = c->span_ms[1];
+    c->span_timed = true;
+    return RH_OK;
+}
+
+int rh_span_times(rh_ctx* c, double ms[2])
+{
+    if (!c || !ms) return RH_ERR_ARG;
+    if (!c->span_timed) return fail(c, RH_ERR_ARG, "no span fold result");
+    ms[0] = c->span_ms[0]; ms[1] = c->span_ms[1];
+    return RH_OK;
+}
+
+}  // extern "C"

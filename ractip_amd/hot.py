@@ -30,6 +30,7 @@ EXPORTS = [
     "rh_local_duplex", "rh_local_hp_layout", "rh_local_hp_results",
     "rh_local_duplex2", "rh_local_hp2_layout", "rh_local_hp2_results", "rh_local_hp2_candidates", "rh_set_local_tile", "rh_local_hp2_tile",
     "rh_local_hp2_times",
+    "rh_span_fold", "rh_span_times",
     "rh_debug_vienna_cell", "rh_debug_vienna_value",   # loader inspection (host only; used by the CPU tests of the loader)
 ]
 
@@ -146,6 +147,10 @@ def load_library():
     L.rh_set_local_chunk.restype = ci
     L.rh_local_times.argtypes = [vp, vp]
     L.rh_local_times.restype = ci
+    L.rh_span_fold.argtypes = [vp, cp, ci, ci]
+    L.rh_span_fold.restype = ci
+    L.rh_span_times.argtypes = [vp, vp]
+    L.rh_span_times.restype = ci
     L.rh_local_duplex.argtypes = [vp, cp, ci, cp, ci, ci, ci, ci]
     L.rh_local_duplex.restype = ci
     L.rh_local_hp_layout.argtypes = [vp, vp, vp, vp, vp]
@@ -414,6 +419,22 @@ class Context:
         """Device time (ms) of the last local_fold: (folds, accumulate + finish + the scans since)."""
         ms = (ctypes.c_double * 2)()
         self._check(self.L.rh_local_times(self.h, ms))
+        return ms[0], ms[1]
+
+    # ---- span-limited folding
+    def span_fold(self, seq, max_span):
+        """The McCaskill ensemble of the whole sequence restricted to pairs (a, b) with b - a < max_span (rh_span_fold; Vienna-BL
+        contexts, 1.8 semantics): one partition function, O(n L) memory.  Returns (bp_band, up, logz): bp_band (n, ld) with
+        bp_band[i, d] = P(i, i + d), 0-based, ld = min(max_span, n); up (n, 1); log Z of the whole sequence.  The result is the
+        context's local result (local_results, local_candidates); band_to_tri gives the triangular layout."""
+        self._check(self.L.rh_span_fold(self.h, seq.encode(), len(seq), max_span))
+        band, up, logz, _ = self.local_results()
+        return band, up, float(logz[0])
+
+    def span_times(self):
+        """Device time (ms) of the last span_fold: (inside + outside sweeps, exterior passes + finish)."""
+        ms = (ctypes.c_double * 2)()
+        self._check(self.L.rh_span_times(self.h, ms))
         return ms[0], ms[1]
 
     # ---- local hybridization of two windowed molecules

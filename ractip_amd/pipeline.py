@@ -13,6 +13,12 @@ shorter one (Context.local_duplex), so nothing is computed over the whole pair.
 --local-hp-both (with --window): both molecules are windowed and every window of one is hybridized with every window of the other
 (Context.local_duplex2): the route for two long molecules, where not even one of them is folded whole.
 --write-rip FILE: also write bp1, bp2, hp as RIP tables (ractip_amd/rip.py) for a stock `ractip --rip FILE --min-w 0`.
+
+  python -m ractip_amd.pipeline --max-span L [--threshold T] a.fa
+
+--max-span L: span-limited folding of ONE sequence (Context.span_fold): the McCaskill ensemble of the whole sequence under the
+Vienna-BL model with pairs (a, b) only where b - a < L.  Prints ">name logZ <log Z>" and one line "i j p" per pair whose probability
+exceeds T (default 0.5), 1-based, row-major, scanned on the device (Context.local_candidates).
 """
 import sys
 
@@ -228,6 +234,44 @@ def predict(s1, s2, model="vienna", duplex=False, device=0, options=None, ctx=No
             ctx.close()
 
 
+def span_fold(seq, max_span, device=0, ctx=None):
+    """Span-limited folding of a whole long sequence (Context.span_fold): dict(n, max_span, bp_band (n, min(max_span, n)) with
+    bp_band[i, d] = P(i, i + d), up (n, 1), logZ).  ctx: a Vienna-BL context to run on (its local result becomes this one); by default
+    one is made for the call.  The joint programme of predict() is not run: it wants accessibilities of wider regions."""
+    own = ctx is None
+    if own:
+        ctx = hot.Context(device=device, model=hot.RH_MODEL_VIENNA_BL)
+    try:
+        band, up, logz = ctx.span_fold(seq, max_span)
+        return dict(n=len(seq), max_span=max_span, bp_band=band, up=up, logZ=logz)
+    finally:
+        if own:
+            ctx.close()
+
+
+def _main_span(argv, max_span):
+    threshold = 0.5
+    if "--threshold" in argv:
+        k = argv.index("--threshold")
+        threshold = float(argv[k + 1])
+        argv = argv[:k] + argv[k + 2:]
+    files = [a for a in argv if not a.startswith("--")]
+    if len(files) != 1 or len(files) != len(argv):
+        raise SystemExit("--max-span takes one FASTA file (and --threshold T)")
+    name, seq = read_fasta(files[0])
+    ctx = hot.Context(device=0, model=hot.RH_MODEL_VIENNA_BL)
+    try:
+        _, _, logz = ctx.span_fold(seq, max_span)
+        rec, total = ctx.local_candidates(0, threshold, cap=max(1, len(seq)))   # a letter has at most one pair above 0.5 ...
+        if total > len(rec):
+            rec, total = ctx.local_candidates(0, threshold, cap=total)            # ... below it the count says how many there are
+    finally:
+        ctx.close()
+    print(">%s logZ %.9f" % (name, logz))
+    for r in rec:
+        print("%d %d %.6g" % (r["i"], r["j"], r["p"]))
+
+
 def screen(queries, targets, model="vienna", duplex=False, device=0, options=None, ctx=None, query_structures=None, target_structures=None,
            accessibility=False):
     """The joint structures of the cross product queries x targets from ONE indexed batch: every distinct string is uploaded and
@@ -350,6 +394,9 @@ def main(argv):
         k = argv.index("--write-rip")
         rip_path = argv[k + 1]
         argv = argv[:k] + argv[k + 2:]
+    if "--max-span" in argv:
+        k = argv.index("--max-span")
+        return _main_span(argv[:k] + argv[k + 2:], int(argv[k + 1]))
     window, step = None, 1
     for flag in ("--window", "--step"):
         if flag in argv:

@@ -1,0 +1,76 @@
+"""Timing of span-limited folding (Context.span_fold) on the GPU, next to the window route for the same sequence on the same
+context: local_fold(W = L, S = 1), which folds n - W + 1 windows of W letters where the span fold fills one band of n x L cells.
+
+  python tools/span_fold_timing.py [--out FILE.json] [--n 5000,20000,100000] [--span 200] [--repeat 5] [--no-windows]
+
+Per n, the median and the range of --repeat runs behind one warm-up run (which allocates): wall time of rh_span_fold alone and of
+the fetch of band, up and log Z; device time of the sweeps and of the exterior passes + finish (rh_span_times); the launches of the
+sweeps (2 Le) and the device time per launch that gives; the same for local_fold (wall with its fetch, rh_local_times)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import ractip_amd                      # noqa: E402
+from ractip_amd import hot             # noqa: E402
+
+
+def spread(values):
+    """[median, min, max]"""
+    v = sorted(values)
+    return [v[len(v) // 2], v[0], v[-1]]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--n", default="5000,20000,100000")
+    ap.add_argument("--span", type=int, default=200)
+    ap.add_argument("--repeat", type=int, default=5)
+    ap.add_argument("--no-windows", action="store_true")
+    args = ap.parse_args()
+    L = args.span
+    rows = []
+    c = ractip_amd.Context(device=0, model=hot.RH_MODEL_VIENNA_BL)
+    for n in [int(x) for x in args.n.split(",")]:
+        seq = "".join(np.random.RandomState(n).choice(list("ACGU"), n))
+        enc = seq.encode()
+        runs = []
+        for _ in range(1 + args.repeat):
+            t0 = time.perf_counter()
+            c._check(c.L.rh_span_fold(c.h, enc, n, L))
+            t1 = time.perf_counter()
+            band, up, logz, _ = c.local_results()
+            t2 = time.perf_counter()
+            runs.append((1e3 * (t1 - t0), 1e3 * (t2 - t1)) + c.span_times())
+        call_ms, fetch_ms, sweep_ms, ext_ms = (spread(col) for col in zip(*runs[1:]))
+        launches = 2 * min(L, n)
+        row = dict(n=n, L=L, logZ=float(logz[0]), span_call_ms=call_ms, span_fetch_ms=fetch_ms, span_sweeps_ms=sweep_ms, span_exterior_finish_ms=ext_ms,
+                   sweep_launches=launches, sweep_us_per_launch=1e3 * sweep_ms[0] / launches, result_bytes=8 * (band.size + up.size + 1),
+                   pairs_above_half=int((band > 0.5).sum()))
+        if not args.no_windows:
+            runs = []
+            for _ in range(1 + args.repeat):
+                t0 = time.perf_counter()
+                wband, wup, wlogz, starts = c.local_fold(seq, L, 1)
+                runs.append((1e3 * (time.perf_counter() - t0),) + c.local_times())
+            wall_ms, fold_ms, acc_ms = (spread(col) for col in zip(*runs[1:]))
+            row.update(windows=len(starts), window_wall_ms=wall_ms, window_folds_ms=fold_ms, window_accumulate_ms=acc_ms,
+                       window_over_span_device=(fold_ms[0] + acc_ms[0]) / (sweep_ms[0] + ext_ms[0]),
+                       max_abs_band_difference=float(np.abs(wband - band).max()))
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    c.close()
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        json.dump(rows, open(args.out, "w"), indent=1)
+
+
+if __name__ == "__main__":
+    main()
