@@ -86,7 +86,10 @@ struct GraphSlot {   // one captured launch sequence (see run_graphed)
 // rh_batch_kernels reports it; nothing else reads the organisation switches.
 struct SweepPlan {
     enum Org { kNone, kStrips, kPairs, kLookahead, kDiagonals, kDxStrip8, kDxSweep4, kDxSweepW };
-    enum Far { kFarNone, kFarLds, kFarGather, kFarPacked };   // block products: LDS/FMA kernel, MFMA with gathered or packed operand tiles
+    // block products: LDS/FMA kernel, MFMA with gathered operand tiles, MFMA on packed tiles with one wavefront per tile or (kFarPacked4)
+    // split-K over the four wavefronts of a workgroup per tile
+    enum Far { kFarNone, kFarLds, kFarGather, kFarPacked, kFarPacked4 };
+    bool packed() const { return far == kFarPacked || far == kFarPacked4; }
     Org org = kNone;
     int W = 0;              // wavefronts per 64-cell group (strips: per workgroup)
     int BS = 0;             // block size of the far/near split of the O(n^3) terms (0: no block products)
@@ -265,6 +268,8 @@ struct Ctx {   // (the fields of rh_ctx, below)
     int f5_pass = 1;               // exterior sums of the strip sweeps in one pass per direction; RH_F5_PASS=0: lin_f5i_tail / lin_f5o_head over the same
                                    // ranges, one entry at a time (slow, the same bits: the reference of tests/test_gpu_f5_pass.py)
     int far_pk = 1;                // ... on packed operand tiles (lin_pack_tiles + lin_far_*_pk); RH_FAR_PK=0: gather per product
+    int far_wave = 1;              // 16-tile products on packed tiles: one wavefront per tile; RH_FAR_WAVE=0: lin_far_*_pk4, a workgroup per tile with
+                                   // split-K over its four wavefronts (the same bits: the reference of tests/test_gpu_far_wave.py)
     int use_graphs = 1;            // RH_NO_GRAPH=1 launches every kernel from the host instead
     GraphSlot g_in, g_out, g_dx;
     int mode = RH_MODE_AUTO;       // which McCaskill path rh_batch_compute takes

@@ -55,6 +55,8 @@ __global__ void lin_f5o_head(McBatch B, const LinModel* __restrict__ L, int khi,
 __global__ void lin_f5o_pass(McBatch B, const LinModel* __restrict__ L);
 __global__ void lin_far_inside_pk(McBatch B, int D, int l2);
 __global__ void lin_far_outside_pk(McBatch B, int D, int l2);
+__global__ void lin_far_inside_pk4(McBatch B, int D, int l2);
+__global__ void lin_far_outside_pk4(McBatch B, int D, int l2);
 __global__ void lin_far2_inside(McBatch B, int D2, int l2);
 __global__ void lin_far2_outside(McBatch B, int D2, int l2);
 __global__ void lin_finish(McBatch B, const LinModel* __restrict__ L, double* __restrict__ logz, int* __restrict__ bad);

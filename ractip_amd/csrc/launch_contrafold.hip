@@ -11,6 +11,7 @@
 #include "ctx.h"
 #include "f5_stage.h"
 #include "kernels.h"
+#include "pk_layout.h"
 
 // log-space path: logZ = F5i[n] (InferenceEngine.ipp:4089-4094)
 __global__ void log_finish(rh::McBatch B, double* __restrict__ logz)
@@ -105,7 +106,8 @@ const StripKernels kStrip[] = {STRIP(4, 0), STRIP(8, 1), STRIP(8, 0)};
 struct LdsKernels { int BS; Named<decltype(&lin_far_inside<16>)> in, out; };
 const LdsKernels kLds[] = {{16, NAMED(lin_far_inside<16>), NAMED(lin_far_outside<16>)}, {32, NAMED(lin_far_inside<32>), NAMED(lin_far_outside<32>)}};
 const Named<decltype(&lin_far_inside_mfma)> kFarGather[2] = {NAMED(lin_far_inside_mfma), NAMED(lin_far_outside_mfma)};
-const Named<decltype(&lin_far_inside_pk)> kFarPacked[2] = {NAMED(lin_far_inside_pk), NAMED(lin_far_outside_pk)};
+const Named<decltype(&lin_far_inside_pk)> kFarPacked[2] = {NAMED(lin_far_inside_pk), NAMED(lin_far_outside_pk)};      // a wavefront per tile
+const Named<decltype(&lin_far_inside_pk)> kFarPacked4[2] = {NAMED(lin_far_inside_pk4), NAMED(lin_far_outside_pk4)};   // a workgroup per tile
 #undef DIAG
 #undef STRIP
 static const DiagKernels& diag_kernels(int W, int BS) { return row_of(kDiag, [&](const DiagKernels& r) { return r.W == W && r.BS == BS; }); }
@@ -128,6 +130,7 @@ const char* far_name(SweepPlan::Far far, int BS, int phase)
         case SweepPlan::kFarLds: return phase == 0 ? lds_kernels(BS).in.name : lds_kernels(BS).out.name;
         case SweepPlan::kFarGather: return kFarGather[phase].name;
         case SweepPlan::kFarPacked: return kFarPacked[phase].name;
+        case SweepPlan::kFarPacked4: return kFarPacked4[phase].name;
         default: return "";
     }
 }
@@ -135,14 +138,23 @@ const char* far_name(SweepPlan::Far far, int BS, int phase)
 void far_products(const rh_ctx* c, int phase, int nmax, bool mfma, SweepPlan* P)
 {
     const int from = c->far2 >= 0 ? (c->far2 ? 1 : 0) : 384;
-    P->far = P->BS == 0 ? SweepPlan::kFarNone : !mfma ? SweepPlan::kFarLds : c->far_pk ? SweepPlan::kFarPacked : SweepPlan::kFarGather;
-    P->far2_from = P->far == SweepPlan::kFarPacked && from > 0 && nmax >= from ? from : 0;
+    P->far = P->BS == 0 ? SweepPlan::kFarNone : !mfma ? SweepPlan::kFarLds : !c->far_pk ? SweepPlan::kFarGather : c->far_wave ? SweepPlan::kFarPacked : SweepPlan::kFarPacked4;
+    P->far2_from = P->packed() && from > 0 && nmax >= from ? from : 0;
     P->far_name = far_name(P->far, P->BS, phase);
 }
 
 // schedule of the block products (BS > 0) against the fine diagonals:
 //   inside : far(D) right after fine diagonal (D-1)*BS-1  (its operands are final, tile (I,I+D) starts at (D-1)*BS+1)
 //   outside: far(D) right before fine diagonal (D+1)*BS-1 (operands: spans >= (D+1)*BS+1, already final)
+// the 16-tile products of block diagonal D on packed tiles: four tiles per workgroup (one per wavefront) or one
+static void far_packed_launch(const SweepPass& S, int phase, int D, int l2)
+{
+    rh_ctx* c = S.c;
+    const bool wave = S.P.far == SweepPlan::kFarPacked;
+    const int tiles = S.last_block() - D + 1;
+    const dim3 grid(wave ? (tiles + 3) / 4 : tiles, S.B.ns, phase == 0 ? 1 : 2);
+    KLAUNCH(c, phase == 0 ? 1 : 3, ((wave ? kFarPacked : kFarPacked4)[phase].kern), grid, dim3(256), S.st, S.B, D, l2);
+}
 void far_inside_after(const SweepPass& S, int done)   // done: the fine diagonals 0 .. done-1 are final
 {
     rh_ctx* c = S.c;
@@ -152,12 +164,12 @@ void far_inside_after(const SweepPass& S, int done)   // done: the fine diagonal
     if (S.P.far == SweepPlan::kFarLds) KLAUNCH(c, 1, (lds_kernels(S.P.BS).in.kern), dim3(last_block - D + 1, B.ns), dim3(256), S.st, B, D);
     else if (S.P.far == SweepPlan::kFarGather) KLAUNCH(c, 1, (kFarGather[0].kern), dim3(last_block - D + 1, B.ns), dim3(256), S.st, B, D);
     else {
-        KLAUNCH(c, 1, lin_pack_tiles<0>, dim3(B.nb - (D - 2), B.ns, 2), dim3(256), S.st, B, D - 2, 0, (int)S.P.banded);
+        KLAUNCH(c, 1, lin_pack_tiles<0>, dim3(pk_run_groups(B.nb - (D - 2)), B.ns, 2), dim3(256), S.st, B, D - 2, 0, (int)S.P.banded);
         if (l2 && (D + 3) % 4 == 0) {   // D = 4*D2-3: every operand tile of macro block diagonal D2 is packed now
             const int D2 = (D + 3) / 4, last2 = (B.nmax - 1) / 64;
             if (D2 >= 4 && D2 <= last2) KLAUNCH(c, 1, lin_far2_inside, dim3(last2 - D2 + 1, B.ns), dim3(256), S.st, B, D2, l2);
         }
-        KLAUNCH(c, 1, (kFarPacked[0].kern), dim3(last_block - D + 1, B.ns), dim3(256), S.st, B, D, l2);
+        far_packed_launch(S, 0, D, l2);
     }
     c->n_launch[S.k]++;
     c->n_far[S.k]++;
@@ -171,13 +183,13 @@ void far_outside_before(SweepPass& S, int d)
     if (S.P.far == SweepPlan::kFarLds) KLAUNCH(c, 3, (lds_kernels(S.P.BS).out.kern), dim3(last_block - D + 1, B.ns, 2), dim3(256), S.st, B, D);
     else if (S.P.far == SweepPlan::kFarGather) KLAUNCH(c, 3, (kFarGather[1].kern), dim3(last_block - D + 1, B.ns, 2), dim3(256), S.st, B, D);
     else {
-        if (D + 2 <= last_block) KLAUNCH(c, 3, lin_pack_tiles<1>, dim3(B.nb - (D + 2), B.ns, 1), dim3(256), S.st, B, D + 2, 1, 0);
+        if (D + 2 <= last_block) KLAUNCH(c, 3, lin_pack_tiles<1>, dim3(pk_run_groups(B.nb - (D + 2)), B.ns, 1), dim3(256), S.st, B, D + 2, 1, 0);
         if (l2) {   // macro block diagonal D2 holds tile block diagonals 4*D2-3 .. 4*D2+3: its products go first, their FM2o tiles (block diagonals >= 4*D2+5) are packed
             const int last2 = (B.nmax - 1) / 64;
             for (; S.far2_next >= 0 && 4 * S.far2_next + 3 >= D; S.far2_next--)
                 KLAUNCH(c, 3, lin_far2_outside, dim3(last2 - S.far2_next + 1, B.ns, 2), dim3(256), S.st, B, S.far2_next, l2);
         }
-        KLAUNCH(c, 3, (kFarPacked[1].kern), dim3(last_block - D + 1, B.ns, 2), dim3(256), S.st, B, D, l2);
+        far_packed_launch(S, 1, D, l2);
     }
     c->n_launch[S.k]++;
     c->n_far[S.k]++;
@@ -190,11 +202,11 @@ void far_outside_begin(SweepPass& S, int top)
     rh_ctx* c = S.c;
     const McBatch& B = S.B;
     const int last_block = S.last_block(), banded = S.P.banded;
-    if (S.P.far == SweepPlan::kFarPacked) {
+    if (S.P.packed()) {
         S.far2_next = (B.nmax - 1) / 64;   // macro block diagonals whose 64-block products are still to be launched (descending)
-        if (S.P.repack2 && last_block - 1 > 2) KLAUNCH(c, 3, lin_pack_tiles<1>, dim3(B.nb - 2, B.ns, 2), dim3(256), S.st, B, 2, 0, banded);
+        if (S.P.repack2 && last_block - 1 > 2) KLAUNCH(c, 3, lin_pack_tiles<1>, dim3(pk_run_groups(B.nb - 2), B.ns, 2), dim3(256), S.st, B, 2, 0, banded);
         for (int Dblk = std::max(2, last_block - 1); Dblk <= last_block; Dblk++)
-            KLAUNCH(c, 3, lin_pack_tiles<1>, dim3(B.nb - Dblk, B.ns, 2), dim3(256), S.st, B, Dblk, 0, banded);
+            KLAUNCH(c, 3, lin_pack_tiles<1>, dim3(pk_run_groups(B.nb - Dblk), B.ns, 2), dim3(256), S.st, B, Dblk, 0, banded);
     }
     for (int d = (last_block + 1) * S.P.BS - 1; d > top; d -= S.P.BS) far_outside_before(S, d);
 }

@@ -122,6 +122,7 @@ const EnvSwitch kEnvSwitches[] = {
     {"RH_NO_GRAPH", ENV_NOT, &Ctx::use_graphs},
     {"RH_FAR_MFMA", ENV_FLAG, &Ctx::far_mfma},
     {"RH_FAR_PK", ENV_FLAG, &Ctx::far_pk},
+    {"RH_FAR_WAVE", ENV_FLAG, &Ctx::far_wave},
     {"RH_LOOKAHEAD", ENV_INT, &Ctx::lookahead},
     {"RH_STRIP", ENV_INT, &Ctx::strip},
     {"RH_STRIP_W", ENV_4OR8, &Ctx::strip_w},
