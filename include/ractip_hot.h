@@ -426,11 +426,28 @@ int rh_local_times(rh_ctx* ctx, double ms[2]);
  * A band cell that leaves the double range under the context's scale exponent sends the call through the exponent ladder; when no
  * exponent holds it returns RH_ERR_UNSUPPORTED and leaves no local result, as RH_ERR_OOM does (buffers grow only and go with the
  * context).
- * Not covered yet: region accessibility for widths above one, the CONTRAfold model, batches of long sequences. */
+ * Not covered yet: the CONTRAfold model, batches of long sequences. */
 int rh_span_fold(rh_ctx* ctx, const char* seq, int n, int max_span);
 /* Measurement aid: device time (ms, HIP event pairs) of the last rh_span_fold: ms[0] the inside and outside sweeps (2 Le launches),
  * ms[1] the two exterior passes and the finish kernel. */
 int rh_span_times(rh_ctx* ctx, double ms[2]);
+/* The same ensemble with region accessibilities, what RactIP's integer programme takes under the default model:
+ *   up[i*max_w + w] = P(letters i+1 .. i+1+w all unpaired), i 0-based, 0 <= w < max_w, and 0 where the run passes letter n.
+ * max_w in 1..64 (the range of rh_set_max_w; anything else: RH_ERR_ARG, rh_last_error names it).  The context's own max_w setting is
+ * neither read nor changed.  Checks, refusals and the exponent ladder are those of rh_span_fold; bp_band and logz_win[0] are its
+ * bits.  rh_local_layout reports this max_w, rh_local_results and rh_local_candidates (what = 1: all n * max_w entries) serve the
+ * result as after an rh_local_fold at that max_w.
+ * max_w = 1 is rh_span_fold, bit for bit (1 - the row sums of the band).  For max_w > 1 EVERY column, column 0 included, is the sum
+ * over where the run can lie -- the exterior, a hairpin loop, a gap of a loop with one enclosed pair, a run of a multiloop -- taken
+ * on the band tables behind the outside sweep and clamped to at most 1, as rh_fold does for whole sequences at max_w > 1.  The
+ * exterior part is a difference of the exterior logarithms.  The stage runs inside the ladder attempt that kept the band in range;
+ * a value that is not finite sends the call to the next exponent.  Every sum has a fixed order: the bits depend on the letters, L,
+ * max_w and the context's model only. */
+int rh_span_fold_acc(rh_ctx* ctx, const char* seq, int n, int max_span, int max_w);
+/* Measurement aid: device time (ms, HIP event pairs) of the accessibility stage of the last rh_span_fold_acc at max_w > 1: ms[0] the
+ * hairpin part (suffix sums and their sums per run), ms[1] the gap sums of the loops with one enclosed pair, ms[2] the final kernel
+ * (exterior, gap and multiloop parts).  RH_ERR_ARG where the last span fold ran at width 1. */
+int rh_span_acc_times(rh_ctx* ctx, double ms[3]);
 
 /* ---- local hybridization: window-averaged hp of a query on a long target ----
  * Two molecules s1 (n1 letters) and s2 (n2 letters).  `windowed` (1 or 2) names the one that is cut into the windows of rh_local_fold

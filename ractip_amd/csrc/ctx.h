@@ -385,6 +385,11 @@ struct Ctx {   // (the fields of rh_ctx, below)
     DevBuf d_span_tab, d_span_ext, d_span_seq, d_span_bad;
     double span_ms[2] = {0, 0};
     bool span_timed = false;       // a span fold has run on this context
+    // rh_span_fold_acc at max_w > 1: the gap sums GL, GR [2][kSpanGapRows][ldn] (grow-only) and the device times of the last
+    // accessibility stage: the hairpin part, the gap sums, the final kernel
+    DevBuf d_span_gaps;
+    double span_acc_ms[3] = {0, 0, 0};
+    bool span_acc_timed = false;   // the last span fold ran the accessibility stage
     std::vector<hipEvent_t> tev;   // event pool of the timed class (pairs), tev_n used by the last compute
     size_t tev_n = 0;
     Ctx() = default;

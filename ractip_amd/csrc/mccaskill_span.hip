@@ -7,6 +7,7 @@
 // cell, 64 consecutive cells of a diagonal per wavefront: every operand is a contiguous row segment.  The sums of a cell are plain
 // loops of at most Le terms.  Every launch writes its whole row, zeros where no cell exists, so nothing is cleared and a read only
 // needs its row and column inside the tables.
+// rh_span_fold_acc adds the region accessibilities up[i][w] of the same ensemble: the span_acc_* kernels behind the outside sweep.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -37,10 +38,12 @@ struct SpanArgs {
     double* gi;            // log F5i [n+1]
     double* go;            // log F5o [n+1]
     double* band;          // bp_band [n][Le]
-    double* up;            // [n]
+    double* up;            // [n][max_w]
     double* logz;          // [1]
     int* bad;
     double sc;             // the scale exponent s of the model
+    double* gaps;          // GL, GR [2][kSpanGapRows][ldn] (max_w > 1)
+    int max_w;             // widths of up: [n][max_w]
 };
 
 // the seven tabulated loop shapes (as mccaskill_vlin.hip): outer pair type t1, inner pair type t2, letters si1/sj1 next to the outer
@@ -305,15 +308,226 @@ __global__ __launch_bounds__(kSpanBlock) void span_finish(SpanArgs A)
     acc = wsum(acc);
     if (lane == 0) {
         const double u = 1.0 - acc;
-        A.up[i0] = u < 0.0 ? 0.0 : u;
+        if (A.max_w == 1) A.up[i0] = u < 0.0 ? 0.0 : u;   // (wider: span_acc_final writes every column)
         A.band[(size_t)i0 * Le] = 0.0;
         if (i0 == 0) A.logz[0] = A.gi[n];
     }
 }
 
+// =================================================================================
+// Region accessibility up[i][w] = P(letters i+1 .. i+1+w unpaired) on the band tables behind the outside sweep (rh_span_fold_acc, max_w > 1):
+// the decomposition of the vlin_acc_* family in mccaskill_vlin.hip -- a run a..b lies in the exterior (E), in a hairpin loop (H), in a
+// gap of a loop with one enclosed pair (I) or in a run of a multiloop (M).  The outside tables are stored divided by Z and times
+// lam^-len, the inside tables times lam^len, so every outside x inside product is a probability up to the weights of the run's own
+// unpaired letters (w_mu^len in M; the loop weights carry them in H and I), and E is a difference of logarithms.  A cell that does
+// not exist holds 0 in every table and every row is ldn wide, so a read needs only its row below Le and its column inside 0..ldn-1.
+constexpr int SP_ACC_R = SP_FM;   // FM is dead behind the outside sweep: the hairpin suffix sums R take its place
+
+// R[d][p] = sum_{d' >= d} Hp(p, p+d'+1), Hp(p, q) = P(letters p, q close a hairpin loop) = FCo^(p, d) x the hairpin weight of
+// span_inside_diag.  One lane per column p, rows in descending order.
+__global__ __launch_bounds__(kSpanThreads) void span_acc_hp(SpanArgs A, const VLinModel* __restrict__ M)
+{
+    const size_t col = (size_t)blockIdx.x * kSpanThreads + threadIdx.x;
+    if (col >= A.ldn) return;
+    const int p = (int)col, n = A.n;
+    const size_t ldn = A.ldn;
+    const uint8_t* __restrict__ s = A.s;
+    const double* __restrict__ fco = A.tab + SP_FCO * A.ts + p;
+    double* __restrict__ R = A.tab + SP_ACC_R * A.ts + p;
+    int lt[6];   // letters p .. p+5 (the tetraloop's), code 0 past the end
+#pragma unroll
+    for (int k = 0; k < 6; k++) lt[k] = s[p + k <= n + 1 ? p + k : n + 1];
+    double run = 0.0;
+    for (int d = A.Le - 1; d >= 0; d--) {
+        const int q = p + d + 1;
+        if (d >= kMinHairpin && p >= 1 && q <= n) {
+            const double o = fco[(size_t)d * ldn];
+            if (o != 0.0) {   // (a pair that cannot form has FCo^ = 0)
+                const int sq = s[q], sqm = s[q - 1];
+                double e = A.hplen[d];
+                if (d == 3) e *= M->E_tau[vienna_ptype(lt[0], sq)];
+                else {
+                    e *= M->TMH[25 * (5 * lt[0] + lt[1]) + 5 * sq + sqm];
+                    if (d == 4 && lt[0] != 0 && lt[1] != 0 && lt[2] != 0 && lt[3] != 0 && lt[4] != 0 && lt[5] != 0)
+                        e *= M->E_tetra[(((((lt[0] - 1) * 4 + (lt[1] - 1)) * 4 + (lt[2] - 1)) * 4 + (lt[3] - 1)) * 4 + (lt[4] - 1)) * 4 + (lt[5] - 1)];
+                }
+                run = fma(o, e, run);
+            }
+        }
+        R[(size_t)d * ldn] = run;
+    }
+}
+
+// the H part: up[(a-1)*max_w + w] = H(a, b) = sum_{p < a} R[b-p][p], b = a + w <= n.  One wavefront per b: the widths share the terms
+// p <= b - max_w (at most Le of them, lane-strided and added by wsum), then lane 0 adds one term per narrower width.
+__global__ __launch_bounds__(256) void span_acc_hsum(SpanArgs A)
+{
+    const int b = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) + 1, lane = threadIdx.x & 63;
+    const int n = A.n, Le = A.Le, mw = A.max_w;
+    if (b > n) return;                                        // wave-uniform
+    const size_t ldn = A.ldn;
+    const double* __restrict__ R = A.tab + SP_ACC_R * A.ts;
+    double tail = 0.0;
+    for (int p = (b - Le + 1 > 1 ? b - Le + 1 : 1) + lane; p <= b - mw; p += 64) tail += R[(size_t)(b - p) * ldn + p];
+    tail = wsum(tail);
+    if (lane == 0) {
+        double run = tail;
+        for (int w = mw - 1; w >= 0; w--) {
+            const int a = b - w;
+            if (a < 1) continue;
+            A.up[(size_t)(a - 1) * mw + w] = run;
+            if (w >= 1 && w < Le) run += R[(size_t)w * ldn + a];   // width w-1 also counts p = a
+        }
+    }
+}
+
+// Gap sums of the loops with one enclosed pair, one THREAD per (letter, own gap length g = 1..30), lanes over the letter (as
+// vlin_acc_gaps; blockIdx.y = side * 30 + g - 1):
+//   GL[p][g] = sum over the loops with outer 5' letter p whose 5' gap is the g letters p+1..p+g
+//   GR[q][g] = the same for the 3' gap q-g..q-1 of the outer 3' letter q
+// A thread's inner 5' letter k = p+1+g (left) resp. inner 3' letter l = q-1-g (right) is fixed; its loops are (inner span r, other gap
+// o): inner cell (k, r) resp. (l-1-r, r), outer span D = r+2+g+o, outer cell (p, D) resp. (q-1-D, D), only rows D < Le.  The outer
+// values of inner span r+1 are those of r shifted by one o: a register window of 31 + UR - 1 entries that slides by UR per batch of
+// UR inner spans, one new load per span; the generic weights w(g, o) are uniform over the workgroup.  Bulges and the tabulated shapes
+// are a handful of (g, o) and are added with direct loads.  Every load of a lane's neighbours is a contiguous row segment.
+__global__ __launch_bounds__(256) void span_acc_gaps(SpanArgs A, const VLinModel* __restrict__ M)
+{
+    constexpr int NW = kMaxSingle + 1, UR = 2;
+    const int g = (int)blockIdx.y % kMaxSingle + 1;
+    const bool right = (int)blockIdx.y >= kMaxSingle;
+    const int pos = blockIdx.x * blockDim.x + threadIdx.x + 1;   // p (left) or q (right)
+    const int n = A.n, Le = A.Le;
+    const bool live = pos <= n;
+    const size_t ldn = A.ldn, ts = A.ts;
+    const uint8_t* __restrict__ s = A.s;
+    const double* __restrict__ FCO = A.tab + SP_FCO * ts;
+    const double* __restrict__ FCOX = A.tab + SP_FCOX * ts;
+    const double* __restrict__ FCOB = A.tab + SP_FCOB * ts;
+    const double* __restrict__ FC = A.tab + SP_FC * ts;
+    const double* __restrict__ FCX = A.tab + SP_FCX * ts;
+    const double* __restrict__ FCB = A.tab + SP_FCB * ts;
+    // generic weights of (own gap g, other gap o); 0 for bulges, tabulated shapes and o beyond the loop budget
+    double wt[NW];
+#pragma unroll
+    for (int o = 0; o < NW; o++) {
+        const int t = g + o;
+        wt[o] = t <= kMaxSingle ? M->shape_w[t * (t + 1) / 2 + (right ? o : g)] : 0.0;
+    }
+    const double wb = g >= 2 ? M->WB[g] : 0.0;
+    // outer cell of span D: column p (left) resp. q-1-D (right); 0 beyond the band and in front of letter 1
+    const auto outer_at = [&](const double* __restrict__ T, int D) -> double {
+        const int pc = right ? pos - 1 - D : pos;
+        return (live && D < Le && pc >= 1) ? T[(size_t)D * ldn + pc] : 0.0;
+    };
+    const int kl = right ? pos - 1 - g : pos + 1 + g;   // inner 3' letter l (right) resp. inner 5' letter k (left)
+    const int rmax = right ? kl - 2 : n - 1 - kl;       // inner spans 0..rmax exist
+    const int r_end = Le - 3 - g;                       // the last inner span whose outer pair (other gap 0) lies in the band
+    double win[NW + UR - 1];
+#pragma unroll
+    for (int o = 0; o < NW + UR - 1; o++) win[o] = outer_at(FCOX, 2 + g + o);
+    double acc = 0.0;
+    for (int r0 = 0; r0 <= r_end; r0 += UR) {
+        double xs[UR], wn[UR], bo[UR], bi[UR];
+        bool ok[UR];
+        size_t ics[UR];
+#pragma unroll
+        for (int u = 0; u < UR; u++) {
+            const int r = r0 + u;                             // (r <= r_end + 1 < Le)
+            ok[u] = live && kl >= 1 && r <= rmax;
+            ics[u] = (size_t)r * ldn + (ok[u] ? (right ? kl - 1 - r : kl) : 1);
+            xs[u] = ok[u] ? FCX[ics[u]] : 0.0;
+            wn[u] = outer_at(FCOX, r0 + UR + 2 + g + (NW - 1) + u);   // enters the window of the next batch at index NW-1+u
+            bo[u] = ok[u] ? outer_at(FCOB, r + 2 + g) : 0.0;          // bulge: own gap g >= 2, other gap 0
+            bi[u] = ok[u] ? FCB[ics[u]] : 0.0;
+        }
+#pragma unroll
+        for (int u = 0; u < UR; u++) {
+            const int r = r0 + u;
+            double sum = 0.0;
+#pragma unroll
+            for (int o = 0; o < NW; o++) sum = fma(wt[o], win[u + o], sum);
+            acc = fma(xs[u], sum, acc);
+            acc = fma(bo[u] * wb, bi[u], acc);
+            if (g <= 2 && ok[u]) {   // the tabulated shapes with this gap length (four of the sixty slices)
+                const int k = right ? kl - 1 - r : kl, l = k + r + 1;   // inner pair (k, l)
+                const double fc = FC[ics[u]];
+                if (fc != 0.0) {
+                    const int ti = vienna_ptype(s[k], s[l]);
+                    for (int o = 0; o <= 2; o++) {
+                        const int l1 = right ? o : g, l2 = right ? g : o;
+                        if (l1 + l2 == 2 && (l1 == 0 || l2 == 0)) continue;   // 0x2 / 2x0 are bulges
+                        const int D = r + 2 + g + o, p = k - 1 - l1, q = l + 1 + l2;
+                        if (D >= Le || p < 1 || q > n) continue;
+                        const double fo = FCO[(size_t)D * ldn + p];
+                        if (fo == 0.0) continue;
+                        acc = fma(fo * span_small_w(M, l1, l2, vienna_ptype(s[p], s[q]), ti, s[p + 1], s[q - 1], s[k - 1], s[l + 1]), fc, acc);
+                    }
+                }
+            }
+        }
+        // slide the window by the batch
+#pragma unroll
+        for (int o = 0; o + 1 < NW; o++) win[o] = win[o + UR];
+#pragma unroll
+        for (int u = 0; u < UR; u++) win[NW - 1 + u] = wn[u];
+    }
+    if (live) A.gaps[((size_t)(right ? 1 : 0) * kSpanGapRows + g) * ldn + pos] = acc;
+}
+
+// gap sums -> suffix sums over the gap length: S[g][pos] = sum_{l >= g} G[l][pos]; one thread per (letter, side = blockIdx.y)
+__global__ __launch_bounds__(256) void span_acc_gsuf(SpanArgs A)
+{
+    const int pos = blockIdx.x * blockDim.x + threadIdx.x + 1;
+    if (pos > A.n) return;
+    double* __restrict__ G = A.gaps + (size_t)blockIdx.y * kSpanGapRows * A.ldn + pos;
+    double run = 0.0;
+    for (int g = kMaxSingle; g >= 1; g--) { run += G[(size_t)g * A.ldn]; G[(size_t)g * A.ldn] = run; }
+}
+
+// adds E, I and M to the H part and clamps; one THREAD per (letter a, width w = blockIdx.y), lanes over a.  A run that passes letter n
+// holds 0; a value that is not finite raises the flag.
+__global__ __launch_bounds__(256) void span_acc_final(SpanArgs A, const VLinModel* __restrict__ M)
+{
+    const int a = blockIdx.x * blockDim.x + threadIdx.x + 1, w = blockIdx.y;
+    const int n = A.n, Le = A.Le;
+    if (a > n) return;
+    const int b = a + w, len = w + 1;
+    double* __restrict__ up = A.up + (size_t)(a - 1) * A.max_w + w;
+    if (b > n) { *up = 0.0; return; }
+    const size_t ldn = A.ldn, ts = A.ts;
+    const double* __restrict__ gl = A.gaps;                                   // suffix sums over the gap length, [g][pos]
+    const double* __restrict__ gr = A.gaps + (size_t)kSpanGapRows * ldn;
+    double mu_len = 1.0;
+    for (int k = 0; k < len; k++) mu_len *= M->w_mu;
+    double acc = exp(A.gi[a - 1] + A.go[b] - A.gi[n]);                        // E, in logarithms
+    // I: the run lies in the 5' gap of the loop whose outer 5' letter is p < a when that gap reaches b: length >= b-p
+    for (int p = a - 1; p >= 1 && p >= b - kMaxSingle; p--) acc += gl[(size_t)(b - p) * ldn + p];
+    for (int q = b + 1; q <= n && q <= a + kMaxSingle; q++) acc += gr[(size_t)(q - a) * ldn + q];   // ... 3' gaps
+    double m = 0.0;
+    if (a >= 2 && b <= n - 3) {     // M, run before a branch: FM1o(a-1, e+1) x FM1(b, e-w), the part ends at letter a+e; rows e+1 < Le
+        const double* __restrict__ x = A.tab + SP_FM1O * ts + (a - 1);
+        const double* __restrict__ y = A.tab + SP_FM1 * ts + b;
+        const int e1 = n - 1 - a < Le - 2 ? n - 1 - a : Le - 2;
+        for (int e = w + 2; e <= e1; e++) m = fma(x[(size_t)(e + 1) * ldn], y[(size_t)(e - w) * ldn], m);
+    }
+    if (a >= 4 && b <= n - 1) {     // M, run after the last branch: FMSo(i, e+len) x FMS(i, e), i = a-1-e; rows e+len < Le
+        const double* __restrict__ x = A.tab + SP_FMSO * ts;
+        const double* __restrict__ y = A.tab + SP_FMS * ts;
+        const int e1 = a - 2 < Le - 1 - len ? a - 2 : Le - 1 - len;
+        for (int e = 2; e <= e1; e++) {
+            const int i = a - 1 - e;
+            m = fma(x[(size_t)(e + len) * ldn + i], y[(size_t)e * ldn + i], m);
+        }
+    }
+    acc += m * mu_len;
+    acc += *up;                                                               // H (span_acc_hsum)
+    if (!(acc <= 1e300)) atomicOr(A.bad, 1);
+    *up = acc > 1.0 ? 1.0 : acc;
+}
+
 // the events of one call, gone with their scope
 struct SpanEvents {
-    hipEvent_t e[5] = {};
+    hipEvent_t e[9] = {};
     hipError_t create()
     {
         for (auto& x : e) { hipError_t r = hipEventCreate(&x); if (r != hipSuccess) return r; }
@@ -322,7 +536,8 @@ struct SpanEvents {
     ~SpanEvents() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
 };
 
-// one attempt on the model selected now: inside sweep, exterior passes, outside sweep, finish; *flag = the device flag behind them
+// one attempt on the model selected now: inside sweep, exterior passes, outside sweep, finish and, where they came back unflagged
+// and widths above one are asked for, the accessibility stage; *flag = the device flag behind them
 int span_attempt(rh_ctx* c, SpanArgs A, const SpanEvents& ev, int* flag)
 {
     const VLinModel* M = c->d_vlin;
@@ -353,19 +568,40 @@ int span_attempt(rh_ctx* c, SpanArgs A, const SpanEvents& ev, int* flag)
     for (int k = 0; k < 4; k++) HIP_TRY(c, hipEventElapsedTime(&t[k], ev.e[k], ev.e[k + 1]));
     c->span_ms[0] = (double)t[0] + t[2];
     c->span_ms[1] = (double)t[1] + t[3];
+    if (*flag || A.max_w == 1) return RH_OK;
+    // the accessibility stage, on this attempt's model and hairpin weights: the hairpin part, the gap sums, the final kernel
+    const unsigned letters = (unsigned)((A.n + 255) / 256);
+    HIP_TRY(c, hipEventRecord(ev.e[5], st));
+    hipLaunchKernelGGL(span_acc_hp, grid, block, 0, st, A, M);
+    hipLaunchKernelGGL(span_acc_hsum, dim3((unsigned)((A.n + 3) / 4)), dim3(256), 0, st, A);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(ev.e[6], st));
+    hipLaunchKernelGGL(span_acc_gaps, dim3(letters, 2 * kMaxSingle), dim3(256), 0, st, A, M);
+    hipLaunchKernelGGL(span_acc_gsuf, dim3(letters, 2), dim3(256), 0, st, A);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(ev.e[7], st));
+    hipLaunchKernelGGL(span_acc_final, dim3(letters, (unsigned)A.max_w), dim3(256), 0, st, A, M);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(ev.e[8], st));
+    HIP_TRY(c, hipMemcpyAsync(flag, A.bad, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    for (int k = 0; k < 3; k++) {
+        float ta = 0.f;
+        HIP_TRY(c, hipEventElapsedTime(&ta, ev.e[5 + k], ev.e[6 + k]));
+        c->span_acc_ms[k] = (double)ta;
+    }
     return RH_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int rh_span_fold(rh_ctx* c, const char* seq, int n, int max_span)
+// rh_span_fold (max_w = 1) and rh_span_fold_acc
+int span_run(rh_ctx* c, const char* seq, int n, int max_span, int max_w)
 {
     if (!c) return RH_ERR_ARG;
     SpanPlan P;
+    SpanAccPlan Q;
     std::string why;
     if (int rc = span_check(seq, n, max_span, &P, &why)) return fail(c, rc, "%s", why.c_str());
+    if (int rc = span_acc_check(P, max_w, &Q, &why)) return fail(c, rc, "%s", why.c_str());
     if (c->model != RH_MODEL_VIENNA_BL) return fail(c, RH_ERR_UNSUPPORTED, "span fold: the CONTRAfold model has no span-limited kernels (Vienna-BL contexts only)");
     if (c->vienna_sem == kViennaSem20) return fail(c, RH_ERR_UNSUPPORTED, "span fold: ViennaRNA-2.x semantics have no span-limited kernels (1.8 semantics only)");
     if (c->mode == RH_MODE_LOG) return fail(c, RH_ERR_UNSUPPORTED, "span fold: there is no log-space version (the context is in RH_MODE_LOG)");
@@ -378,7 +614,8 @@ int rh_span_fold(rh_ctx* c, const char* seq, int n, int max_span)
     if ((rc = ensure(c, c->d_span_seq, seq_bytes, false))) return rc;
     if ((rc = ensure(c, c->d_span_bad, sizeof(int), false))) return rc;
     if ((rc = ensure(c, c->d_loc_bp, sizeof(double) * P.band, false))) return rc;
-    if ((rc = ensure(c, c->d_loc_up, sizeof(double) * (size_t)n, false))) return rc;
+    if ((rc = ensure(c, c->d_loc_up, sizeof(double) * Q.up, false))) return rc;
+    if (Q.gaps && (rc = ensure(c, c->d_span_gaps, sizeof(double) * Q.gaps, false))) return rc;
     if ((rc = ensure(c, c->d_loc_logz, sizeof(double), false))) return rc;
     SpanEvents ev;
     HIP_TRY(c, ev.create());
@@ -392,6 +629,7 @@ int rh_span_fold(rh_ctx* c, const char* seq, int n, int max_span)
     A.gi = c->d_span_ext.as<double>(); A.go = A.gi + (n + 1); A.hplen = A.go + (n + 1);
     A.band = c->d_loc_bp.as<double>(); A.up = c->d_loc_up.as<double>(); A.logz = c->d_loc_logz.as<double>();
     A.bad = c->d_span_bad.as<int>();
+    A.gaps = Q.gaps ? c->d_span_gaps.as<double>() : nullptr; A.max_w = max_w;
     // the context's exponent first, then its ladder in exponent_order's order, while a band cell leaves the double range
     std::vector<int> order = {c->vlin_primary};
     for (int model : exponent_order(c->vlin_primary, c->vlin_m[0].h->s, kVRungS, rh_ctx::kVRungs)) order.push_back(model);
@@ -406,9 +644,27 @@ int rh_span_fold(rh_ctx* c, const char* seq, int n, int max_span)
     if (flag) return fail(c, RH_ERR_UNSUPPORTED, "span fold: no scale exponent of the ladder keeps the band tables of max_span %d in the double range", max_span);
     LocalPlan R;
     R.n = n; R.W = max_span; R.S = 1; R.We = n; R.nw = 1; R.ld = P.Le;   // one window at 0 with the band pitch Le
-    c->loc = R; c->loc_max_w = 1; c->loc_valid = true;
+    c->loc = R; c->loc_max_w = max_w; c->loc_valid = true;
+    c->span_acc_timed = max_w > 1;
     c->loc_ms[0] = c->span_ms[0]; c->loc_ms[1] = c->span_ms[1];
+    if (c->span_acc_timed) c->loc_ms[1] += c->span_acc_ms[0] + c->span_acc_ms[1] + c->span_acc_ms[2];
     c->span_timed = true;
+    return RH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rh_span_fold(rh_ctx* c, const char* seq, int n, int max_span) { return span_run(c, seq, n, max_span, 1); }
+
+int rh_span_fold_acc(rh_ctx* c, const char* seq, int n, int max_span, int max_w) { return span_run(c, seq, n, max_span, max_w); }
+
+int rh_span_acc_times(rh_ctx* c, double ms[3])
+{
+    if (!c || !ms) return RH_ERR_ARG;
+    if (!c->span_timed || !c->span_acc_timed) return fail(c, RH_ERR_ARG, "no span fold result with widths above one");
+    for (int k = 0; k < 3; k++) ms[k] = c->span_acc_ms[k];
     return RH_OK;
 }
 

@@ -1,4 +1,4 @@
-// span_fold.cpp -- the argument checks and the sizes of rh_span_fold (span_fold.h).  Host only: no HIP, no context.
+// span_fold.cpp -- the argument checks and the sizes of rh_span_fold and rh_span_fold_acc (span_fold.h).  Host only: no HIP, no context.
 #include "span_fold.h"
 
 #include <limits>
@@ -33,6 +33,21 @@ int span_check(const char* seq, int n, int max_span, SpanPlan* P, std::string* w
                       mul((size_t)n, (size_t)S.Le, &S.band) && mul(S.band, sizeof(double), &bytes);
     if (!fits) return reject(why, "span fold: the tables of " + std::to_string(n) + " letters at max_span " + std::to_string(max_span) + " overflow size_t");
     *P = S;
+    return RH_OK;
+}
+
+int span_acc_check(const SpanPlan& P, int max_w, SpanAccPlan* A, std::string* why)
+{
+    if (max_w < 1 || max_w > kSpanAccMaxW)
+        return reject(why, "span fold: max_w " + std::to_string(max_w) + " (must be 1.." + std::to_string(kSpanAccMaxW) + ")");
+    SpanAccPlan S;
+    S.max_w = max_w;
+    size_t bytes = 0;
+    const bool fits = mul((size_t)P.n, (size_t)max_w, &S.up) && mul(S.up, sizeof(double), &bytes) &&
+                      mul(P.ldn, (size_t)(2 * kSpanGapRows), &S.gaps) && mul(S.gaps, sizeof(double), &bytes);
+    if (!fits) return reject(why, "span fold: the accessibilities of " + std::to_string(P.n) + " letters at max_w " + std::to_string(max_w) + " overflow size_t");
+    if (max_w == 1) S.gaps = 0;
+    *A = S;
     return RH_OK;
 }
 

@@ -1,4 +1,5 @@
-// span_fold.h -- the host plan and the exterior recurrence of span-limited folding (rh_span_fold; kernels in mccaskill_span.hip).
+// span_fold.h -- the host plan and the exterior recurrence of span-limited folding (rh_span_fold, rh_span_fold_acc; kernels in
+// mccaskill_span.hip).
 // Plain C++ (no HIP needed): tools/span_fold_check.cpp runs both on the CPU.
 //
 // Definition.  Inputs: n letters, max_span = L >= 2, Le = min(L, n).  The ensemble is that of rh_fold under the context's Vienna-BL
@@ -56,6 +57,19 @@ struct SpanPlan {
 // RH_OK with *P filled, or RH_ERR_ARG with the reason in *why; reads nothing of seq but whether it is NULL.  Sizes are size_t
 // throughout (n = 1e6, L = 1000: 1e9 doubles per table); a size that does not fit is rejected.
 int span_check(const char* seq, int n, int max_span, SpanPlan* P, std::string* why);
+
+// ---- region accessibility up[i][w] on the same ensemble (rh_span_fold_acc; kernels in mccaskill_span.hip)
+constexpr int kSpanAccMaxW = 64;      // widest region, the range of rh_set_max_w
+constexpr int kSpanGapRows = 32;      // rows of one side of the gap-sum buffer: gap lengths 1..30 at their own index
+
+struct SpanAccPlan {
+    int max_w = 0;             // as asked for
+    size_t up = 0;             // doubles of up = n * max_w
+    size_t gaps = 0;           // doubles of the gap sums GL and GR = 2 * kSpanGapRows * ldn; 0 at max_w = 1, which needs none
+};
+
+// The sizes of the accessibility stage over a checked plan: RH_OK with *A filled, or RH_ERR_ARG with the reason in *why.
+int span_acc_check(const SpanPlan& P, int max_w, SpanAccPlan* A, std::string* why);
 
 // ---- the exterior passes: what the kernel and the CPU check share.  dir 0: gi, entries ascending from 1; dir 1: go, entries
 // descending from n-1.  Block b holds the entries span_ext_entry(dir, n, b, l), l = 0..63 (those inside 0..n).

@@ -30,7 +30,7 @@ EXPORTS = [
     "rh_local_duplex", "rh_local_hp_layout", "rh_local_hp_results",
     "rh_local_duplex2", "rh_local_hp2_layout", "rh_local_hp2_results", "rh_local_hp2_candidates", "rh_set_local_tile", "rh_local_hp2_tile",
     "rh_local_hp2_times",
-    "rh_span_fold", "rh_span_times",
+    "rh_span_fold", "rh_span_times", "rh_span_fold_acc", "rh_span_acc_times",
     "rh_debug_vienna_cell", "rh_debug_vienna_value",   # loader inspection (host only; used by the CPU tests of the loader)
 ]
 
@@ -151,6 +151,10 @@ def load_library():
     L.rh_span_fold.restype = ci
     L.rh_span_times.argtypes = [vp, vp]
     L.rh_span_times.restype = ci
+    L.rh_span_fold_acc.argtypes = [vp, cp, ci, ci, ci]
+    L.rh_span_fold_acc.restype = ci
+    L.rh_span_acc_times.argtypes = [vp, vp]
+    L.rh_span_acc_times.restype = ci
     L.rh_local_duplex.argtypes = [vp, cp, ci, cp, ci, ci, ci, ci]
     L.rh_local_duplex.restype = ci
     L.rh_local_hp_layout.argtypes = [vp, vp, vp, vp, vp]
@@ -422,12 +426,13 @@ class Context:
         return ms[0], ms[1]
 
     # ---- span-limited folding
-    def span_fold(self, seq, max_span):
-        """The McCaskill ensemble of the whole sequence restricted to pairs (a, b) with b - a < max_span (rh_span_fold; Vienna-BL
+    def span_fold(self, seq, max_span, max_w=1):
+        """The McCaskill ensemble of the whole sequence restricted to pairs (a, b) with b - a < max_span (rh_span_fold_acc; Vienna-BL
         contexts, 1.8 semantics): one partition function, O(n L) memory.  Returns (bp_band, up, logz): bp_band (n, ld) with
-        bp_band[i, d] = P(i, i + d), 0-based, ld = min(max_span, n); up (n, 1); log Z of the whole sequence.  The result is the
-        context's local result (local_results, local_candidates); band_to_tri gives the triangular layout."""
-        self._check(self.L.rh_span_fold(self.h, seq.encode(), len(seq), max_span))
+        bp_band[i, d] = P(i, i + d), 0-based, ld = min(max_span, n); up (n, max_w) with up[i, w] = P(letters i .. i + w unpaired),
+        0-based, 0 where the run passes the end (max_w in 1..64; the context's own max_w is not used); log Z of the whole sequence.
+        The result is the context's local result (local_results, local_candidates); band_to_tri gives the triangular layout."""
+        self._check(self.L.rh_span_fold_acc(self.h, seq.encode(), len(seq), max_span, max_w))
         band, up, logz, _ = self.local_results()
         return band, up, float(logz[0])
 
@@ -436,6 +441,12 @@ class Context:
         ms = (ctypes.c_double * 2)()
         self._check(self.L.rh_span_times(self.h, ms))
         return ms[0], ms[1]
+
+    def span_acc_times(self):
+        """Device time (ms) of the accessibility stage of the last span_fold at max_w > 1: (hairpin part, gap sums, final kernel)."""
+        ms = (ctypes.c_double * 3)()
+        self._check(self.L.rh_span_acc_times(self.h, ms))
+        return ms[0], ms[1], ms[2]
 
     # ---- local hybridization of two windowed molecules
     def local_duplex2(self, s1, s2, window1, step1=1, window2=None, step2=None):

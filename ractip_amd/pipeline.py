@@ -14,6 +14,12 @@ shorter one (Context.local_duplex), so nothing is computed over the whole pair.
 (Context.local_duplex2): the route for two long molecules, where not even one of them is folded whole.
 --write-rip FILE: also write bp1, bp2, hp as RIP tables (ractip_amd/rip.py) for a stock `ractip --rip FILE --min-w 0`.
 
+  python -m ractip_amd.pipeline --max-span L [--window W [--step S] --local-hp | --local-hp-both] [--duplex] [--write-rip FILE] a.fa b.fa
+
+--max-span L with two files: bp and up[i][w] of both molecules come from span-limited folds (Context.span_fold at the programme's
+max_w: one ensemble per molecule, pairs within L letters), hp from the pair as before or, with --window and --local-hp /
+--local-hp-both, from the window averages above.  Default (Vienna-BL) model only, no --use-constraint.
+
   python -m ractip_amd.pipeline --max-span L [--threshold T] a.fa
 
 --max-span L: span-limited folding of ONE sequence (Context.span_fold): the McCaskill ensemble of the whole sequence under the
@@ -180,8 +186,28 @@ def _predict_local(ctx, s1, s2, model, duplex, opt, default_options, rip_path, a
     return ilp.solve(s1, s2, bp[0], bp[1], hp, None, None, ilp.Options(min_w=0) if default_options else opt)
 
 
+def _predict_span(ctx, s1, s2, duplex, opt, rip_path, max_span, window, step, local_hp, local_hp_both):
+    """predict with bp and up of both molecules from span folds at the programme's max_w; hp from the pair path, or from local_duplex
+    (the longer molecule windowed, s2 on a tie) / local_duplex2, fetched before the span folds replace the local result"""
+    _set_up(ctx, "vienna", opt, duplex, False)
+    if local_hp_both:
+        hp = ctx.local_duplex2(s1, s2, window, step)[0]
+    elif local_hp:
+        hp = ctx.local_duplex(s1, s2, window, step, 1 if len(s1) > len(s2) else 2)[0]
+    else:
+        hp = probabilities(ctx, s1, s2)["hp"]
+    bp, up = [], []
+    for s in (s1, s2):
+        band, u, _ = ctx.span_fold(s, max_span, max(1, opt.max_w))
+        bp.append(hot.band_to_tri(band))
+        up.append(u)
+    if rip_path:
+        rip.write_rip(rip_path, s1, s2, bp[0], bp[1], hp)
+    return ilp.solve(s1, s2, bp[0], bp[1], hp, up[0], up[1], opt)
+
+
 def predict(s1, s2, model="vienna", duplex=False, device=0, options=None, ctx=None, rip_path=None, structures=None, accessibility=False,
-            window=None, step=1, local_hp=False, local_hp_both=False):
+            window=None, step=1, local_hp=False, local_hp_both=False, max_span=None):
     """model "vienna": RactIP's default path (rnafold + rnaduplex; duplex=True = --duplex, else co_pf_fold), parity
     unpinned; model "contrafold": the --contrafold path (bp from the CONTRAfold engine, width-1 up, accessibility off as
     src/ractip.cpp:1511-1517 demands), hp from the CONTRAfold duplex engine.  structures = (str1, str2): the FASTA structure
@@ -193,7 +219,11 @@ def predict(s1, s2, model="vienna", duplex=False, device=0, options=None, ctx=No
     average, from one Context.local_duplex call that windows the longer molecule (s2 on a tie) against the whole shorter one and
     also yields the windowed molecule's bp and up; the other molecule's come from local_fold as before.  local_hp_both=True (needs
     window, excludes local_hp): hp is the window average of Context.local_duplex2 with (window, step) on BOTH molecules -- the route
-    for two long molecules, where no whole molecule is folded anywhere; bp and up of both come from local_fold."""
+    for two long molecules, where no whole molecule is folded anywhere; bp and up of both come from local_fold.  max_span=L (model
+    "vienna" only, no structure constraints): bp and up[i][w], widths 1..options.max_w, of both molecules come from span-limited
+    folds (Context.span_fold: one ensemble of each whole molecule with pairs within L letters) instead; hp comes from the pair path,
+    or with window= and local_hp / local_hp_both from the window averages (a window alone has nothing to do here and is refused).
+    With L no smaller than either molecule the ensembles, and so the structures, are those of the whole-sequence folds."""
     if local_hp_both and window is None:
         raise ValueError("local_hp_both needs a window")
     if local_hp_both and local_hp:
@@ -204,11 +234,19 @@ def predict(s1, s2, model="vienna", duplex=False, device=0, options=None, ctx=No
         raise ValueError("structure constraints apply to the default (Vienna-BL) path only")
     if structures is not None and window is not None:
         raise ValueError("local folding takes no structure constraints")
+    if max_span is not None and model != "vienna":
+        raise ValueError("span-limited folding runs on the default (Vienna-BL) path only")
+    if max_span is not None and structures is not None:
+        raise ValueError("span-limited folding takes no structure constraints")
+    if max_span is not None and window is not None and not (local_hp or local_hp_both):
+        raise ValueError("max_span with a window needs local_hp or local_hp_both: bp and up come from the span folds")
     own = ctx is None
     if own:
         ctx = hot.Context(device=device, model=hot.RH_MODEL_VIENNA_BL if model == "vienna" else hot.RH_MODEL_CONTRAFOLD)
     try:
         opt = options or ilp.Options()
+        if max_span is not None:
+            return _predict_span(ctx, s1, s2, duplex, opt, rip_path, max_span, window, step, local_hp, local_hp_both)
         if window is not None:
             return _predict_local(ctx, s1, s2, model, duplex, opt, options is None, rip_path, accessibility, window, step, local_hp, local_hp_both)
         if model == "vienna":
@@ -234,15 +272,16 @@ def predict(s1, s2, model="vienna", duplex=False, device=0, options=None, ctx=No
             ctx.close()
 
 
-def span_fold(seq, max_span, device=0, ctx=None):
+def span_fold(seq, max_span, max_w=1, device=0, ctx=None):
     """Span-limited folding of a whole long sequence (Context.span_fold): dict(n, max_span, bp_band (n, min(max_span, n)) with
-    bp_band[i, d] = P(i, i + d), up (n, 1), logZ).  ctx: a Vienna-BL context to run on (its local result becomes this one); by default
-    one is made for the call.  The joint programme of predict() is not run: it wants accessibilities of wider regions."""
+    bp_band[i, d] = P(i, i + d), up (n, max_w) with up[i, w] = P(letters i .. i + w unpaired), logZ).  ctx: a Vienna-BL context to
+    run on (its local result becomes this one; its max_w setting is not used); by default one is made for the call.
+    predict(max_span=L) runs the joint programme on two of these."""
     own = ctx is None
     if own:
         ctx = hot.Context(device=device, model=hot.RH_MODEL_VIENNA_BL)
     try:
-        band, up, logz = ctx.span_fold(seq, max_span)
+        band, up, logz = ctx.span_fold(seq, max_span, max_w)
         return dict(n=len(seq), max_span=max_span, bp_band=band, up=up, logZ=logz)
     finally:
         if own:
@@ -394,9 +433,13 @@ def main(argv):
         k = argv.index("--write-rip")
         rip_path = argv[k + 1]
         argv = argv[:k] + argv[k + 2:]
+    max_span = None
     if "--max-span" in argv:
         k = argv.index("--max-span")
-        return _main_span(argv[:k] + argv[k + 2:], int(argv[k + 1]))
+        max_span, argv = int(argv[k + 1]), argv[:k] + argv[k + 2:]
+        valued = {i + 1 for i, a in enumerate(argv) if a in ("--threshold", "--window", "--step")}
+        if sum(1 for i, a in enumerate(argv) if not a.startswith("--") and i not in valued) != 2:
+            return _main_span(argv, max_span)      # the one-file form
     window, step = None, 1
     for flag in ("--window", "--step"):
         if flag in argv:
@@ -418,7 +461,7 @@ def main(argv):
     structures = (t1, t2) if "--use-constraint" in flags else None
     r1, r2, _ = predict(s1, s2, model="contrafold" if "--contrafold" in flags else "vienna", duplex="--duplex" in flags, rip_path=rip_path,
                         structures=structures, window=window, step=step, local_hp="--local-hp" in flags,
-                        local_hp_both="--local-hp-both" in flags)
+                        local_hp_both="--local-hp-both" in flags, max_span=max_span)
     print(">%s\n%s\n%s\n>%s\n%s\n%s" % (n1, s1, r1, n2, s2, r2))   # src/ractip.cpp:1607-1610
 
 

@@ -5,6 +5,7 @@
 //       ractip_amd/csrc/span_fold.cpp -o span_fold_check
 //
 //   span_fold_check plan N L [null]    "ok n L Le ldn table tables band ext" or "err CODE TEXT" as span_check answers
+//   span_fold_check acc N L MAX_W      "ok n L max_w up gaps" (the sizes of the accessibility stage, span_acc_check) or "err CODE TEXT"
 //   span_fold_check exterior N L       both exterior passes on the CPU in the kernel's order (span_ext_pass_host: blocks of 64 entries, lane
 //                                      by lane, the butterfly) over a synthetic FCA band whose free energy is front-loaded: the first quarter
 //                                      of the letters carries 3.5 nats each, the rest 0.01.  Compared with a long-double recurrence in
@@ -32,6 +33,19 @@ int plan(int n, int L, bool null)
     const int rc = span_check(null ? nullptr : seq.c_str(), n, L, &P, &why);
     if (rc) { std::printf("err %d %s\n", rc, why.c_str()); return 0; }
     std::printf("ok %d %d %d %zu %zu %zu %zu %zu\n", P.n, P.L, P.Le, P.ldn, P.table, P.tables, P.band, P.ext);
+    return 0;
+}
+
+int acc(int n, int L, int max_w)
+{
+    SpanPlan P;
+    SpanAccPlan A;
+    std::string why;
+    const std::string seq(1, 'A');
+    int rc = span_check(seq.c_str(), n, L, &P, &why);
+    if (!rc) rc = span_acc_check(P, max_w, &A, &why);
+    if (rc) { std::printf("err %d %s\n", rc, why.c_str()); return 0; }
+    std::printf("ok %d %d %d %zu %zu\n", P.n, P.L, A.max_w, A.up, A.gaps);
     return 0;
 }
 
@@ -98,6 +112,7 @@ int main(int argc, char** argv)
 {
     if (argc >= 4 && !std::strcmp(argv[1], "plan")) return plan(std::atoi(argv[2]), std::atoi(argv[3]), argc >= 5 && !std::strcmp(argv[4], "null"));
     if (argc >= 4 && !std::strcmp(argv[1], "exterior")) return exterior(std::atoi(argv[2]), std::atoi(argv[3]));
-    std::fprintf(stderr, "usage: span_fold_check plan N L [null] | exterior N L\n");
+    if (argc >= 5 && !std::strcmp(argv[1], "acc")) return acc(std::atoi(argv[2]), std::atoi(argv[3]), std::atoi(argv[4]));
+    std::fprintf(stderr, "usage: span_fold_check plan N L [null] | exterior N L | acc N L MAX_W\n");
     return 2;
 }

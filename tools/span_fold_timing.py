@@ -1,11 +1,14 @@
 """Timing of span-limited folding (Context.span_fold) on the GPU, next to the window route for the same sequence on the same
 context: local_fold(W = L, S = 1), which folds n - W + 1 windows of W letters where the span fold fills one band of n x L cells.
 
-  python tools/span_fold_timing.py [--out FILE.json] [--n 5000,20000,100000] [--span 200] [--repeat 5] [--no-windows]
+  python tools/span_fold_timing.py [--out FILE.json] [--n 5000,20000,100000] [--span 200] [--repeat 5] [--no-windows] [--max-w W]
 
 Per n, the median and the range of --repeat runs behind one warm-up run (which allocates): wall time of rh_span_fold alone and of
 the fetch of band, up and log Z; device time of the sweeps and of the exterior passes + finish (rh_span_times); the launches of the
-sweeps (2 Le) and the device time per launch that gives; the same for local_fold (wall with its fetch, rh_local_times)."""
+sweeps (2 Le) and the device time per launch that gives; the same for local_fold (wall with its fetch, rh_local_times).
+--max-w W (default 1): the span fold with region accessibilities up[i][w] of W widths (rh_span_fold_acc); for W > 1 also the device
+time of the three parts of the accessibility stage (rh_span_acc_times: hairpin part, gap sums, final kernel), and local_fold runs
+on the same context at max_w = W, the route to wide accessibilities that the stage replaces."""
 import argparse
 import json
 import os
@@ -34,26 +37,32 @@ def main():
     ap.add_argument("--span", type=int, default=200)
     ap.add_argument("--repeat", type=int, default=5)
     ap.add_argument("--no-windows", action="store_true")
+    ap.add_argument("--max-w", type=int, default=1)
     args = ap.parse_args()
-    L = args.span
+    L, W = args.span, args.max_w
     rows = []
     c = ractip_amd.Context(device=0, model=hot.RH_MODEL_VIENNA_BL)
+    c.set_max_w(W)                     # for local_fold; the span fold takes its widths as an argument
     for n in [int(x) for x in args.n.split(",")]:
         seq = "".join(np.random.RandomState(n).choice(list("ACGU"), n))
         enc = seq.encode()
         runs = []
         for _ in range(1 + args.repeat):
             t0 = time.perf_counter()
-            c._check(c.L.rh_span_fold(c.h, enc, n, L))
+            c._check(c.L.rh_span_fold_acc(c.h, enc, n, L, W))
             t1 = time.perf_counter()
             band, up, logz, _ = c.local_results()
             t2 = time.perf_counter()
-            runs.append((1e3 * (t1 - t0), 1e3 * (t2 - t1)) + c.span_times())
-        call_ms, fetch_ms, sweep_ms, ext_ms = (spread(col) for col in zip(*runs[1:]))
+            runs.append((1e3 * (t1 - t0), 1e3 * (t2 - t1)) + c.span_times() + (c.span_acc_times() if W > 1 else ()))
+        call_ms, fetch_ms, sweep_ms, ext_ms = (spread(col) for col in list(zip(*runs[1:]))[:4])
         launches = 2 * min(L, n)
-        row = dict(n=n, L=L, logZ=float(logz[0]), span_call_ms=call_ms, span_fetch_ms=fetch_ms, span_sweeps_ms=sweep_ms, span_exterior_finish_ms=ext_ms,
+        row = dict(n=n, L=L, max_w=W, logZ=float(logz[0]), span_call_ms=call_ms, span_fetch_ms=fetch_ms, span_sweeps_ms=sweep_ms, span_exterior_finish_ms=ext_ms,
                    sweep_launches=launches, sweep_us_per_launch=1e3 * sweep_ms[0] / launches, result_bytes=8 * (band.size + up.size + 1),
                    pairs_above_half=int((band > 0.5).sum()))
+        if W > 1:
+            hp_ms, gap_ms, final_ms = (spread(col) for col in list(zip(*runs[1:]))[4:])
+            row.update(acc_hairpin_ms=hp_ms, acc_gaps_ms=gap_ms, acc_final_ms=final_ms,
+                       acc_over_sweeps=(hp_ms[0] + gap_ms[0] + final_ms[0]) / sweep_ms[0])
         if not args.no_windows:
             runs = []
             for _ in range(1 + args.repeat):
@@ -62,7 +71,7 @@ def main():
                 runs.append((1e3 * (time.perf_counter() - t0),) + c.local_times())
             wall_ms, fold_ms, acc_ms = (spread(col) for col in zip(*runs[1:]))
             row.update(windows=len(starts), window_wall_ms=wall_ms, window_folds_ms=fold_ms, window_accumulate_ms=acc_ms,
-                       window_over_span_device=(fold_ms[0] + acc_ms[0]) / (sweep_ms[0] + ext_ms[0]),
+                       window_over_span_device=(fold_ms[0] + acc_ms[0]) / (sweep_ms[0] + ext_ms[0] + (hp_ms[0] + gap_ms[0] + final_ms[0] if W > 1 else 0.0)),
                        max_abs_band_difference=float(np.abs(wband - band).max()))
         rows.append(row)
         print(json.dumps(row), flush=True)
