@@ -426,7 +426,7 @@ int rh_local_times(rh_ctx* ctx, double ms[2]);
  * A band cell that leaves the double range under the context's scale exponent sends the call through the exponent ladder; when no
  * exponent holds it returns RH_ERR_UNSUPPORTED and leaves no local result, as RH_ERR_OOM does (buffers grow only and go with the
  * context).
- * Not covered yet: the CONTRAfold model, batches of long sequences. */
+ * Not covered yet: the CONTRAfold model. */
 int rh_span_fold(rh_ctx* ctx, const char* seq, int n, int max_span);
 /* Measurement aid: device time (ms, HIP event pairs) of the last rh_span_fold: ms[0] the inside and outside sweeps (2 Le launches),
  * ms[1] the two exterior passes and the finish kernel. */
@@ -448,6 +448,33 @@ int rh_span_fold_acc(rh_ctx* ctx, const char* seq, int n, int max_span, int max_
  * hairpin part (suffix sums and their sums per run), ms[1] the gap sums of the loops with one enclosed pair, ms[2] the final kernel
  * (exterior, gap and multiloop parts).  RH_ERR_ARG where the last span fold ran at width 1. */
 int rh_span_acc_times(rh_ctx* ctx, double ms[3]);
+/* Span folds in batches: `count` sequences of ragged lengths n[k] through one set of launches, at one max_span and one max_w.
+ * Item k is rh_span_fold_acc(ctx, seqs[k], n[k], max_span, max_w): the same ensemble, layouts (ld = min(max_span, n[k]),
+ * up[i*max_w + w]) and clamping, and the bits of that single call made on this context.  The single calls run the same kernels as a
+ * batch of one.  The item is a dimension of every launch: one launch per diagonal below the largest min(max_span, n[k]), and one
+ * workgroup per item in the exterior passes.  The exponent ladder runs per item: the items of an attempt that stayed in range are
+ * finished on that attempt's exponent, the others form the next attempt, so every item ends on the exponent its single call ends on.
+ * An item for which no exponent holds gets status RH_ERR_UNSUPPORTED, which its fetches return; the call still returns RH_OK and
+ * serves the other items.
+ * The batch is cut into chunks of consecutive items whose band tables and gap sums fit rh_set_span_batch_bytes (0, the default: 16 GiB,
+ * a setting that has not been tuned; a chunk holds at least one item); chunks run one after the other and change no bit.
+ * The result lives in buffers of its own until the next rh_span_fold_batch: it neither reads nor changes the context's batch, the
+ * local result (rh_local_*, the single span calls) or the result of rh_local_duplex2, and these calls leave it alone.
+ * Refusals.  RH_ERR_ARG: count < 1, a NULL array, a NULL sequence, n[k] < 1, max_span < 2, max_w outside 1..64, sizes that overflow
+ * (rh_last_error names the item).  RH_ERR_UNSUPPORTED: as rh_span_fold.  Both leave the previous batch result in place. */
+int rh_span_fold_batch(rh_ctx* ctx, const char* const* seqs, const int* n, int count, int max_span, int max_w);
+int rh_span_batch_layout(rh_ctx* ctx, int* count, int* max_span, int* max_w);
+/* n, ld = min(max_span, n) and the status of one item; RH_ERR_ARG for an item outside the batch */
+int rh_span_batch_item(rh_ctx* ctx, int item, int* n, int* ld, int* status);
+/* bp_band [n][ld], up [n][max_w] and log Z (one double) of one item; any pointer may be NULL */
+int rh_span_batch_results(rh_ctx* ctx, int item, double* bp_band, double* up, double* logz);
+/* Thresholded list of one item, by the scan kernels of rh_local_candidates: what = 0 the band, 1 up; same records, order and return */
+int rh_span_batch_candidates(rh_ctx* ctx, int item, int what, float threshold, rh_cand* out, int cap);
+/* Table memory (band tables + gap sums, bytes) one chunk of a span batch may take; 0: the default */
+int rh_set_span_batch_bytes(rh_ctx* ctx, size_t bytes);
+/* Measurement aid: device time (ms, HIP event pairs) of the last rh_span_fold_batch, summed over its chunks and ladder attempts: ms[0]
+ * the inside and outside sweeps, ms[1] the exterior passes and the finish kernels, ms[2] the accessibility stage. */
+int rh_span_batch_times(rh_ctx* ctx, double ms[3]);
 
 /* ---- local hybridization: window-averaged hp of a query on a long target ----
  * Two molecules s1 (n1 letters) and s2 (n2 letters).  `windowed` (1 or 2) names the one that is cut into the windows of rh_local_fold

@@ -390,6 +390,17 @@ struct Ctx {   // (the fields of rh_ctx, below)
     DevBuf d_span_gaps;
     double span_acc_ms[3] = {0, 0, 0};
     bool span_acc_timed = false;   // the last span fold ran the accessibility stage
+    // every span fold: the per-item descriptors of the launches (grow-only)
+    DevBuf d_span_desc;
+    // rh_span_fold_batch only: the last batch result -- its plan, the status of every item, the bands, up tables and log Z of all
+    // items one behind the other (grow-only, kept until the next rh_span_fold_batch), the chunk budget and the device times
+    SpanBatchPlan sb;
+    std::vector<int> sb_status;
+    bool sb_valid = false;
+    DevBuf d_sb_bp, d_sb_up, d_sb_logz;
+    size_t sb_bytes = 0;           // rh_set_span_batch_bytes (0: kSpanBatchBytes)
+    double sb_ms[3] = {0, 0, 0};   // sweeps; exterior passes + finish; accessibility stage
+    double sb_scan_ms = 0;         // the scan kernels of rh_span_batch_candidates since
     std::vector<hipEvent_t> tev;   // event pool of the timed class (pairs), tev_n used by the last compute
     size_t tev_n = 0;
     Ctx() = default;
@@ -499,6 +510,8 @@ int compute(rh_ctx* c);
 McLinArgs mc_lin_args(const rh_ctx* c, int phase, const McBatch& B, const LinSet* lin, bool routed);
 DxLinArgs dx_lin_args(const rh_ctx* c);
 int flagged(rh_ctx* c, const int* d_flags, int n, hipStream_t st, std::vector<int>* set);
+// local_fold.hip: the scan of rh_local_candidates (what = 0: a band [n][pitch]; 1: an up table [n][pitch]) on any such table
+int local_scan_table(rh_ctx* c, const double* table, int n, int pitch, int what, float threshold, rh_cand* out, int cap, double* ms, const char* who);
 
 }  // namespace rh::host
 

@@ -468,6 +468,13 @@ LocalScan hp_scan(const LocalHp& R, float threshold)
 
 }  // namespace
 
+int rh::host::local_scan_table(rh_ctx* c, const double* table, int n, int pitch, int what, float threshold, rh_cand* out, int cap, double* ms, const char* who)
+{
+    const LocalScan V = what == 0 ? LocalScan{table, n, pitch, pitch, 1, n - 1, kScanBp, threshold}
+                                  : LocalScan{table, n, pitch, pitch, 0, n - 1 + pitch, kScanUp, threshold};
+    return scan_candidates(c, V, out, cap, ms, who);
+}
+
 extern "C" {
 
 int rh_set_local_chunk(rh_ctx* c, int windows)
@@ -561,10 +568,9 @@ int rh_local_candidates(rh_ctx* c, int what, float threshold, rh_cand* out, int 
     if (what < 0 || what > 2 || cap < 0 || (cap > 0 && !out)) return fail(c, RH_ERR_ARG, "rh_local_candidates: bad what/cap");
     HIP_TRY(c, hipSetDevice(c->device));
     const LocalPlan& P = c->loc;
-    const LocalScan V = what == 0   ? LocalScan{c->d_loc_bp.as<const double>(), P.n, P.ld, P.ld, 1, P.n - 1, kScanBp, threshold}
-                        : what == 1 ? LocalScan{c->d_loc_up.as<const double>(), P.n, c->loc_max_w, c->loc_max_w, 0, P.n - 1 + c->loc_max_w, kScanUp, threshold}
-                                    : hp_scan(c->loc_hp, threshold);
-    return scan_candidates(c, V, out, cap, &c->loc_ms[1], "rh_local_candidates");
+    if (what == 2) return scan_candidates(c, hp_scan(c->loc_hp, threshold), out, cap, &c->loc_ms[1], "rh_local_candidates");
+    return local_scan_table(c, what == 0 ? c->d_loc_bp.as<const double>() : c->d_loc_up.as<const double>(), P.n, what == 0 ? P.ld : c->loc_max_w, what, threshold,
+                            out, cap, &c->loc_ms[1], "rh_local_candidates");
 }
 
 int rh_local_times(rh_ctx* c, double ms[2])

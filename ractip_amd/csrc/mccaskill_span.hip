@@ -8,6 +8,8 @@
 // loops of at most Le terms.  Every launch writes its whole row, zeros where no cell exists, so nothing is cleared and a read only
 // needs its row and column inside the tables.
 // rh_span_fold_acc adds the region accessibilities up[i][w] of the same ensemble: the span_acc_* kernels behind the outside sweep.
+// rh_span_fold_batch runs many sequences through the same launches: every kernel takes per-item descriptors and the item as a grid
+// dimension (span_item), the exponent ladder runs per item, and the single calls are batches of one.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -45,6 +47,29 @@ struct SpanArgs {
     double* gaps;          // GL, GR [2][kSpanGapRows][ldn] (max_w > 1)
     int max_w;             // widths of up: [n][max_w]
 };
+static_assert(sizeof(SpanArgs) % 8 == 0);
+
+// Every kernel runs a batch of items, a single call a batch of one: the launch hands over a device array with one SpanArgs per item
+// and the item is a grid dimension (y, or z where the kernel's own grid has two), so a workgroup belongs to ONE item.  The grid spans
+// the widest item of the launch; a workgroup with nothing to do for its item leaves before its first load or store besides this
+// one.  The address is uniform over the workgroup and the load is the kernel's first access: the descriptor arrives by scalar loads
+// and stays in scalar registers.
+// A pointer that comes out of memory could point anywhere as far as the compiler knows, and every access through it would be a flat
+// one (which also waits on the LDS counter); all of these point to device memory, and saying so makes the accesses global ones.
+template <class T> __device__ __forceinline__ T* span_global(T* p)
+{
+    typedef __attribute__((address_space(1))) T* G;
+    return (T*)(G)(uintptr_t)p;   // (through the integer: a pointer cast there and back would fold away)
+}
+__device__ __forceinline__ SpanArgs span_item(const SpanArgs* __restrict__ items, unsigned item)
+{
+    SpanArgs A = items[item];
+    A.tab = span_global(A.tab); A.s = span_global(A.s); A.hplen = span_global(A.hplen);
+    A.gi = span_global(A.gi); A.go = span_global(A.go);
+    A.band = span_global(A.band); A.up = span_global(A.up); A.logz = span_global(A.logz);
+    A.bad = span_global(A.bad); A.gaps = span_global(A.gaps);
+    return A;
+}
 
 // the seven tabulated loop shapes (as mccaskill_vlin.hip): outer pair type t1, inner pair type t2, letters si1/sj1 next to the outer
 // pair inside the loop, sp1/sq1 next to the inner pair
@@ -63,8 +88,10 @@ __device__ __forceinline__ int small_l1(int k) { return (k == 2 || k == 3 || k =
 __device__ __forceinline__ int small_l2(int k) { return (k == 1 || k == 3 || k == 5) ? 1 : ((k == 4 || k == 6) ? 2 : 0); }
 
 // ---- inside, diagonal d: grid over the ldn columns of the row
-__global__ __launch_bounds__(kSpanThreads) void span_inside_diag(SpanArgs A, const VLinModel* __restrict__ M, int d)
+__global__ __launch_bounds__(kSpanThreads) void span_inside_diag(const SpanArgs* __restrict__ items, const VLinModel* __restrict__ M, int d)
 {
+    const SpanArgs A = span_item(items, blockIdx.y);
+    if (d >= A.Le || (size_t)blockIdx.x * kSpanThreads >= A.ldn) return;   // the item has no such row, or no such columns
     const size_t col = (size_t)blockIdx.x * kSpanThreads + threadIdx.x;
     if (col >= A.ldn) return;
     const int i = (int)col, n = A.n, j = i + d;
@@ -146,8 +173,9 @@ __global__ __launch_bounds__(kSpanThreads) void span_inside_diag(SpanArgs A, con
 // (span_fold.h).  Phase A of a block is spread over the wavefronts -- wavefront w takes the rows d = w, w + kSpanWaves, .. of every
 // entry, four loads in flight per lane -- as is the fill of T; phase B runs on wavefront 0.  An entry is read by the blocks behind
 // the one that wrote it: the barriers of a block order them.
-__global__ __launch_bounds__(kSpanBlock * kSpanWaves) void span_ext_pass(SpanArgs A, int dir)
+__global__ __launch_bounds__(kSpanBlock * kSpanWaves) void span_ext_pass(const SpanArgs* __restrict__ items, int dir)
 {
+    const SpanArgs A = span_item(items, blockIdx.y);
     __shared__ double T[kSpanBlock][kSpanBlock];      // T[l][m]: the term of entry l whose other end is entry m of the block
     __shared__ double part[kSpanWaves][kSpanBlock];   // phase-A sums per wavefront
     __shared__ double esd[kSpanBlock];                // exp(s d)
@@ -213,8 +241,10 @@ __global__ __launch_bounds__(kSpanBlock * kSpanWaves) void span_ext_pass(SpanArg
 }
 
 // ---- outside (pull form) and posterior, diagonal d
-__global__ __launch_bounds__(kSpanThreads) void span_outside_diag(SpanArgs A, const VLinModel* __restrict__ M, int d)
+__global__ __launch_bounds__(kSpanThreads) void span_outside_diag(const SpanArgs* __restrict__ items, const VLinModel* __restrict__ M, int d)
 {
+    const SpanArgs A = span_item(items, blockIdx.y);
+    if (d >= A.Le || (size_t)blockIdx.x * kSpanThreads >= A.ldn) return;
     const size_t col = (size_t)blockIdx.x * kSpanThreads + threadIdx.x;
     if (col >= A.ldn) return;
     const int i = (int)col, n = A.n, j = i + d, Le = A.Le;
@@ -297,9 +327,11 @@ __global__ __launch_bounds__(kSpanThreads) void span_outside_diag(SpanArgs A, co
 }
 
 // ---- finish: up[i] = 1 - sum_j P(i, j), column 0 of the band, log Z.  grid (n), one wavefront per letter
-__global__ __launch_bounds__(kSpanBlock) void span_finish(SpanArgs A)
+__global__ __launch_bounds__(kSpanBlock) void span_finish(const SpanArgs* __restrict__ items)
 {
+    const SpanArgs A = span_item(items, blockIdx.y);
     const int i0 = blockIdx.x, lane = threadIdx.x, n = A.n, Le = A.Le;
+    if (i0 >= n) return;
     double acc = 0.0;
     for (int dd = 1 + lane; dd < Le; dd += kSpanBlock) {
         if (i0 + dd < n) acc += A.band[(size_t)i0 * Le + dd];
@@ -325,8 +357,10 @@ constexpr int SP_ACC_R = SP_FM;   // FM is dead behind the outside sweep: the ha
 
 // R[d][p] = sum_{d' >= d} Hp(p, p+d'+1), Hp(p, q) = P(letters p, q close a hairpin loop) = FCo^(p, d) x the hairpin weight of
 // span_inside_diag.  One lane per column p, rows in descending order.
-__global__ __launch_bounds__(kSpanThreads) void span_acc_hp(SpanArgs A, const VLinModel* __restrict__ M)
+__global__ __launch_bounds__(kSpanThreads) void span_acc_hp(const SpanArgs* __restrict__ items, const VLinModel* __restrict__ M)
 {
+    const SpanArgs A = span_item(items, blockIdx.y);
+    if ((size_t)blockIdx.x * kSpanThreads >= A.ldn) return;
     const size_t col = (size_t)blockIdx.x * kSpanThreads + threadIdx.x;
     if (col >= A.ldn) return;
     const int p = (int)col, n = A.n;
@@ -360,8 +394,10 @@ __global__ __launch_bounds__(kSpanThreads) void span_acc_hp(SpanArgs A, const VL
 
 // the H part: up[(a-1)*max_w + w] = H(a, b) = sum_{p < a} R[b-p][p], b = a + w <= n.  One wavefront per b: the widths share the terms
 // p <= b - max_w (at most Le of them, lane-strided and added by wsum), then lane 0 adds one term per narrower width.
-__global__ __launch_bounds__(256) void span_acc_hsum(SpanArgs A)
+__global__ __launch_bounds__(256) void span_acc_hsum(const SpanArgs* __restrict__ items)
 {
+    const SpanArgs A = span_item(items, blockIdx.y);
+    if ((int)blockIdx.x * 4 + 1 > A.n) return;
     const int b = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) + 1, lane = threadIdx.x & 63;
     const int n = A.n, Le = A.Le, mw = A.max_w;
     if (b > n) return;                                        // wave-uniform
@@ -390,9 +426,11 @@ __global__ __launch_bounds__(256) void span_acc_hsum(SpanArgs A)
 // values of inner span r+1 are those of r shifted by one o: a register window of 31 + UR - 1 entries that slides by UR per batch of
 // UR inner spans, one new load per span; the generic weights w(g, o) are uniform over the workgroup.  Bulges and the tabulated shapes
 // are a handful of (g, o) and are added with direct loads.  Every load of a lane's neighbours is a contiguous row segment.
-__global__ __launch_bounds__(256) void span_acc_gaps(SpanArgs A, const VLinModel* __restrict__ M)
+__global__ __launch_bounds__(256) void span_acc_gaps(const SpanArgs* __restrict__ items, const VLinModel* __restrict__ M)
 {
     constexpr int NW = kMaxSingle + 1, UR = 2;
+    const SpanArgs A = span_item(items, blockIdx.z);
+    if ((int)(blockIdx.x * blockDim.x) + 1 > A.n) return;   // no letter of the item in this workgroup
     const int g = (int)blockIdx.y % kMaxSingle + 1;
     const bool right = (int)blockIdx.y >= kMaxSingle;
     const int pos = blockIdx.x * blockDim.x + threadIdx.x + 1;   // p (left) or q (right)
@@ -475,8 +513,10 @@ __global__ __launch_bounds__(256) void span_acc_gaps(SpanArgs A, const VLinModel
 }
 
 // gap sums -> suffix sums over the gap length: S[g][pos] = sum_{l >= g} G[l][pos]; one thread per (letter, side = blockIdx.y)
-__global__ __launch_bounds__(256) void span_acc_gsuf(SpanArgs A)
+__global__ __launch_bounds__(256) void span_acc_gsuf(const SpanArgs* __restrict__ items)
 {
+    const SpanArgs A = span_item(items, blockIdx.z);
+    if ((int)(blockIdx.x * blockDim.x) + 1 > A.n) return;
     const int pos = blockIdx.x * blockDim.x + threadIdx.x + 1;
     if (pos > A.n) return;
     double* __restrict__ G = A.gaps + (size_t)blockIdx.y * kSpanGapRows * A.ldn + pos;
@@ -486,8 +526,10 @@ __global__ __launch_bounds__(256) void span_acc_gsuf(SpanArgs A)
 
 // adds E, I and M to the H part and clamps; one THREAD per (letter a, width w = blockIdx.y), lanes over a.  A run that passes letter n
 // holds 0; a value that is not finite raises the flag.
-__global__ __launch_bounds__(256) void span_acc_final(SpanArgs A, const VLinModel* __restrict__ M)
+__global__ __launch_bounds__(256) void span_acc_final(const SpanArgs* __restrict__ items, const VLinModel* __restrict__ M)
 {
+    const SpanArgs A = span_item(items, blockIdx.z);
+    if ((int)(blockIdx.x * blockDim.x) + 1 > A.n) return;
     const int a = blockIdx.x * blockDim.x + threadIdx.x + 1, w = blockIdx.y;
     const int n = A.n, Le = A.Le;
     if (a > n) return;
@@ -536,64 +578,137 @@ struct SpanEvents {
     ~SpanEvents() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
 };
 
-// one attempt on the model selected now: inside sweep, exterior passes, outside sweep, finish and, where they came back unflagged
-// and widths above one are asked for, the accessibility stage; *flag = the device flag behind them
-int span_attempt(rh_ctx* c, SpanArgs A, const SpanEvents& ev, int* flag)
+// device times (ms) of the attempts of one ladder: the sweeps; the exterior passes and the finish; the three steps of the accessibility stage
+struct SpanTimes {
+    double sweeps = 0, ext = 0, acc[3] = {0, 0, 0};
+};
+
+// One attempt on the model selected now over the items `run` (a single call: one): inside sweeps, exterior passes, outside sweeps,
+// finish and, for the items that came back unflagged where widths above one are asked for, the accessibility stage on the same model
+// and hairpin weights.  One launch per diagonal below the largest Le, over the widest ldn; the exterior passes have a workgroup per
+// item.  The items share one hplen (it depends on the exponent only and item k reads the rows below its own Le); item k of `run`
+// gets the flag bad[k], and (*flags)[k] is that flag behind everything that ran for it.  `sum`: the times are added to *T.
+int span_attempt(rh_ctx* c, std::vector<SpanArgs>& run, int* bad, const SpanEvents& ev, std::vector<int>* flags, SpanTimes* T, bool sum)
 {
     const VLinModel* M = c->d_vlin;
     hipStream_t st = c->s_mc;
-    std::vector<double> hplen((size_t)A.Le);
-    hairpin_length_weights(*c->h_vlin, A.Le, hplen.data());
-    A.sc = c->h_vlin->s;
-    HIP_TRY(c, hipMemcpyAsync(const_cast<double*>(A.hplen), hplen.data(), sizeof(double) * hplen.size(), hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemsetAsync(A.bad, 0, sizeof(int), st));
-    const dim3 grid((unsigned)((A.ldn + kSpanThreads - 1) / kSpanThreads)), block(kSpanThreads);
+    const unsigned K = (unsigned)run.size();
+    const int max_w = run[0].max_w;
+    int Le = 0, n = 0;
+    size_t ldn = 0;
+    for (unsigned k = 0; k < K; k++) {
+        SpanArgs& A = run[k];
+        Le = std::max(Le, A.Le); n = std::max(n, A.n); ldn = std::max(ldn, A.ldn);
+        A.sc = c->h_vlin->s;
+        A.bad = bad + k;
+    }
+    std::vector<double> hplen((size_t)Le);
+    hairpin_length_weights(*c->h_vlin, Le, hplen.data());
+    int rc;
+    if ((rc = ensure(c, c->d_span_desc, sizeof(SpanArgs) * K, false))) return rc;
+    const SpanArgs* items = c->d_span_desc.as<const SpanArgs>();
+    HIP_TRY(c, hipMemcpyAsync(const_cast<double*>(run[0].hplen), hplen.data(), sizeof(double) * hplen.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(c->d_span_desc.p, run.data(), sizeof(SpanArgs) * K, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemsetAsync(bad, 0, sizeof(int) * K, st));
+    const dim3 grid((unsigned)((ldn + kSpanThreads - 1) / kSpanThreads), K), block(kSpanThreads);
     HIP_TRY(c, hipEventRecord(ev.e[0], st));
-    for (int d = 0; d < A.Le; d++) hipLaunchKernelGGL(span_inside_diag, grid, block, 0, st, A, M, d);
+    for (int d = 0; d < Le; d++) hipLaunchKernelGGL(span_inside_diag, grid, block, 0, st, items, M, d);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(ev.e[1], st));
-    hipLaunchKernelGGL(span_ext_pass, dim3(1), dim3(kSpanBlock * kSpanWaves), 0, st, A, 0);
-    hipLaunchKernelGGL(span_ext_pass, dim3(1), dim3(kSpanBlock * kSpanWaves), 0, st, A, 1);
+    hipLaunchKernelGGL(span_ext_pass, dim3(1, K), dim3(kSpanBlock * kSpanWaves), 0, st, items, 0);
+    hipLaunchKernelGGL(span_ext_pass, dim3(1, K), dim3(kSpanBlock * kSpanWaves), 0, st, items, 1);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(ev.e[2], st));
-    for (int d = A.Le - 1; d >= 0; d--) hipLaunchKernelGGL(span_outside_diag, grid, block, 0, st, A, M, d);
+    for (int d = Le - 1; d >= 0; d--) hipLaunchKernelGGL(span_outside_diag, grid, block, 0, st, items, M, d);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(ev.e[3], st));
-    hipLaunchKernelGGL(span_finish, dim3(A.n), dim3(kSpanBlock), 0, st, A);
+    hipLaunchKernelGGL(span_finish, dim3((unsigned)n, K), dim3(kSpanBlock), 0, st, items);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(ev.e[4], st));
-    HIP_TRY(c, hipMemcpyAsync(flag, A.bad, sizeof(int), hipMemcpyDeviceToHost, st));
+    flags->assign(K, 1);
+    HIP_TRY(c, hipMemcpyAsync(flags->data(), bad, sizeof(int) * K, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
     float t[4] = {};
     for (int k = 0; k < 4; k++) HIP_TRY(c, hipEventElapsedTime(&t[k], ev.e[k], ev.e[k + 1]));
-    c->span_ms[0] = (double)t[0] + t[2];
-    c->span_ms[1] = (double)t[1] + t[3];
-    if (*flag || A.max_w == 1) return RH_OK;
-    // the accessibility stage, on this attempt's model and hairpin weights: the hairpin part, the gap sums, the final kernel
-    const unsigned letters = (unsigned)((A.n + 255) / 256);
+    T->sweeps = (sum ? T->sweeps : 0.0) + (double)t[0] + t[2];
+    T->ext = (sum ? T->ext : 0.0) + (double)t[1] + t[3];
+    if (max_w == 1) return RH_OK;
+    // the accessibility stage for the unflagged items: the hairpin part, the gap sums, the final kernel
+    std::vector<SpanArgs> acc;
+    for (unsigned k = 0; k < K; k++) if (!(*flags)[k]) acc.push_back(run[k]);
+    if (acc.empty()) return RH_OK;
+    const unsigned Ka = (unsigned)acc.size();
+    n = 0; ldn = 0;
+    for (const SpanArgs& A : acc) { n = std::max(n, A.n); ldn = std::max(ldn, A.ldn); }
+    HIP_TRY(c, hipMemcpyAsync(c->d_span_desc.p, acc.data(), sizeof(SpanArgs) * Ka, hipMemcpyHostToDevice, st));   // (the sweeps are done with it)
+    const unsigned letters = (unsigned)((n + 255) / 256);
     HIP_TRY(c, hipEventRecord(ev.e[5], st));
-    hipLaunchKernelGGL(span_acc_hp, grid, block, 0, st, A, M);
-    hipLaunchKernelGGL(span_acc_hsum, dim3((unsigned)((A.n + 3) / 4)), dim3(256), 0, st, A);
+    hipLaunchKernelGGL(span_acc_hp, dim3((unsigned)((ldn + kSpanThreads - 1) / kSpanThreads), Ka), block, 0, st, items, M);
+    hipLaunchKernelGGL(span_acc_hsum, dim3((unsigned)((n + 3) / 4), Ka), dim3(256), 0, st, items);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(ev.e[6], st));
-    hipLaunchKernelGGL(span_acc_gaps, dim3(letters, 2 * kMaxSingle), dim3(256), 0, st, A, M);
-    hipLaunchKernelGGL(span_acc_gsuf, dim3(letters, 2), dim3(256), 0, st, A);
+    hipLaunchKernelGGL(span_acc_gaps, dim3(letters, 2 * kMaxSingle, Ka), dim3(256), 0, st, items, M);
+    hipLaunchKernelGGL(span_acc_gsuf, dim3(letters, 2, Ka), dim3(256), 0, st, items);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(ev.e[7], st));
-    hipLaunchKernelGGL(span_acc_final, dim3(letters, (unsigned)A.max_w), dim3(256), 0, st, A, M);
+    hipLaunchKernelGGL(span_acc_final, dim3(letters, (unsigned)max_w, Ka), dim3(256), 0, st, items, M);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(ev.e[8], st));
-    HIP_TRY(c, hipMemcpyAsync(flag, A.bad, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(flags->data(), bad, sizeof(int) * K, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
     for (int k = 0; k < 3; k++) {
         float ta = 0.f;
         HIP_TRY(c, hipEventElapsedTime(&ta, ev.e[5 + k], ev.e[6 + k]));
-        c->span_acc_ms[k] = (double)ta;
+        T->acc[k] = (sum ? T->acc[k] : 0.0) + (double)ta;
     }
     return RH_OK;
 }
 
-// rh_span_fold (max_w = 1) and rh_span_fold_acc
+// The exponent ladder over the items of one set of launches: the context's exponent first, then its ladder in exponent_order's order,
+// while a band cell of an item leaves the double range.  The flagged items of an attempt are the next attempt's items, on their own
+// tables, so every item ends on the exponent its single call ends on.  (*status)[k]: RH_OK, or RH_ERR_UNSUPPORTED where no exponent
+// holds for item k.
+int span_ladder(rh_ctx* c, const std::vector<SpanArgs>& items, int* bad, std::vector<int>* status, SpanTimes* T, bool sum)
+{
+    SpanEvents ev;
+    HIP_TRY(c, ev.create());
+    std::vector<int> order = {c->vlin_primary};
+    for (int model : exponent_order(c->vlin_primary, c->vlin_m[0].h->s, kVRungS, rh_ctx::kVRungs)) order.push_back(model);
+    std::vector<int> left(items.size()), flags;
+    for (size_t k = 0; k < left.size(); k++) left[k] = (int)k;
+    int rc = RH_OK;
+    for (size_t a = 0; a < order.size() && !left.empty(); a++) {
+        if ((rc = select_vlin(c, order[a]))) break;
+        std::vector<SpanArgs> run;
+        for (int k : left) run.push_back(items[(size_t)k]);
+        if ((rc = span_attempt(c, run, bad, ev, &flags, T, sum))) break;
+        std::vector<int> next;
+        for (size_t k = 0; k < left.size(); k++) if (flags[k]) next.push_back(left[k]);
+        left.swap(next);
+    }
+    const int back = select_vlin(c, c->vlin_primary);
+    if (rc) return rc;
+    if (back) return back;
+    status->assign(items.size(), RH_OK);
+    for (int k : left) (*status)[(size_t)k] = RH_ERR_UNSUPPORTED;
+    return RH_OK;
+}
+
+int span_refusals(rh_ctx* c)
+{
+    if (c->model != RH_MODEL_VIENNA_BL) return fail(c, RH_ERR_UNSUPPORTED, "span fold: the CONTRAfold model has no span-limited kernels (Vienna-BL contexts only)");
+    if (c->vienna_sem == kViennaSem20) return fail(c, RH_ERR_UNSUPPORTED, "span fold: ViennaRNA-2.x semantics have no span-limited kernels (1.8 semantics only)");
+    if (c->mode == RH_MODE_LOG) return fail(c, RH_ERR_UNSUPPORTED, "span fold: there is no log-space version (the context is in RH_MODE_LOG)");
+    return RH_OK;
+}
+
+// the letter codes of one item: code 0 at 0 and behind the last letter
+void span_codes(const char* seq, int n, uint8_t* codes)
+{
+    for (int i = 0; i < n; i++) codes[(size_t)i + 1] = vienna_code(seq[i]);
+}
+
+// rh_span_fold (max_w = 1) and rh_span_fold_acc: a batch of one whose result is the context's local result
 int span_run(rh_ctx* c, const char* seq, int n, int max_span, int max_w)
 {
     if (!c) return RH_ERR_ARG;
@@ -602,9 +717,7 @@ int span_run(rh_ctx* c, const char* seq, int n, int max_span, int max_w)
     std::string why;
     if (int rc = span_check(seq, n, max_span, &P, &why)) return fail(c, rc, "%s", why.c_str());
     if (int rc = span_acc_check(P, max_w, &Q, &why)) return fail(c, rc, "%s", why.c_str());
-    if (c->model != RH_MODEL_VIENNA_BL) return fail(c, RH_ERR_UNSUPPORTED, "span fold: the CONTRAfold model has no span-limited kernels (Vienna-BL contexts only)");
-    if (c->vienna_sem == kViennaSem20) return fail(c, RH_ERR_UNSUPPORTED, "span fold: ViennaRNA-2.x semantics have no span-limited kernels (1.8 semantics only)");
-    if (c->mode == RH_MODE_LOG) return fail(c, RH_ERR_UNSUPPORTED, "span fold: there is no log-space version (the context is in RH_MODE_LOG)");
+    if (int rc = span_refusals(c)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     c->loc_valid = c->loc_hp.valid = false;   // (the hp result of rh_local_duplex goes with the band it came with)
     int rc;
@@ -617,10 +730,8 @@ int span_run(rh_ctx* c, const char* seq, int n, int max_span, int max_w)
     if ((rc = ensure(c, c->d_loc_up, sizeof(double) * Q.up, false))) return rc;
     if (Q.gaps && (rc = ensure(c, c->d_span_gaps, sizeof(double) * Q.gaps, false))) return rc;
     if ((rc = ensure(c, c->d_loc_logz, sizeof(double), false))) return rc;
-    SpanEvents ev;
-    HIP_TRY(c, ev.create());
     std::vector<uint8_t> codes(seq_bytes, 0);
-    for (int i = 0; i < n; i++) codes[(size_t)i + 1] = vienna_code(seq[i]);
+    span_codes(seq, n, codes.data());
     HIP_TRY(c, hipMemcpyAsync(c->d_span_seq.p, codes.data(), seq_bytes, hipMemcpyHostToDevice, c->s_mc));
     SpanArgs A{};
     A.tab = c->d_span_tab.as<double>(); A.ldn = P.ldn; A.ts = P.table;
@@ -628,20 +739,13 @@ int span_run(rh_ctx* c, const char* seq, int n, int max_span, int max_w)
     A.n = n; A.Le = P.Le; A.L = max_span;
     A.gi = c->d_span_ext.as<double>(); A.go = A.gi + (n + 1); A.hplen = A.go + (n + 1);
     A.band = c->d_loc_bp.as<double>(); A.up = c->d_loc_up.as<double>(); A.logz = c->d_loc_logz.as<double>();
-    A.bad = c->d_span_bad.as<int>();
     A.gaps = Q.gaps ? c->d_span_gaps.as<double>() : nullptr; A.max_w = max_w;
-    // the context's exponent first, then its ladder in exponent_order's order, while a band cell leaves the double range
-    std::vector<int> order = {c->vlin_primary};
-    for (int model : exponent_order(c->vlin_primary, c->vlin_m[0].h->s, kVRungS, rh_ctx::kVRungs)) order.push_back(model);
-    int flag = 1;
-    for (size_t a = 0; a < order.size() && flag; a++) {
-        if ((rc = select_vlin(c, order[a]))) break;
-        if ((rc = span_attempt(c, A, ev, &flag))) break;
-    }
-    const int back = select_vlin(c, c->vlin_primary);
-    if (rc) return rc;
-    if (back) return back;
-    if (flag) return fail(c, RH_ERR_UNSUPPORTED, "span fold: no scale exponent of the ladder keeps the band tables of max_span %d in the double range", max_span);
+    std::vector<int> status;
+    SpanTimes T;
+    if ((rc = span_ladder(c, {A}, c->d_span_bad.as<int>(), &status, &T, false))) return rc;   // (the times of the last attempt)
+    if (status[0]) return fail(c, RH_ERR_UNSUPPORTED, "span fold: no scale exponent of the ladder keeps the band tables of max_span %d in the double range", max_span);
+    c->span_ms[0] = T.sweeps; c->span_ms[1] = T.ext;
+    for (int k = 0; k < 3; k++) c->span_acc_ms[k] = T.acc[k];
     LocalPlan R;
     R.n = n; R.W = max_span; R.S = 1; R.We = n; R.nw = 1; R.ld = P.Le;   // one window at 0 with the band pitch Le
     c->loc = R; c->loc_max_w = max_w; c->loc_valid = true;
@@ -649,6 +753,75 @@ int span_run(rh_ctx* c, const char* seq, int n, int max_span, int max_w)
     c->loc_ms[0] = c->span_ms[0]; c->loc_ms[1] = c->span_ms[1];
     if (c->span_acc_timed) c->loc_ms[1] += c->span_acc_ms[0] + c->span_acc_ms[1] + c->span_acc_ms[2];
     c->span_timed = true;
+    return RH_OK;
+}
+
+// rh_span_fold_batch: chunk after chunk on the grow-only scratch of the single calls; the results go to the batch's own buffers
+int span_batch_run(rh_ctx* c, const char* const* seqs, const int* n, int count, int max_span, int max_w)
+{
+    if (!c) return RH_ERR_ARG;
+    SpanBatchPlan B;
+    std::string why;
+    if (int rc = span_batch_plan(seqs, n, count, max_span, max_w, c->sb_bytes, &B, &why)) return fail(c, rc, "%s", why.c_str());
+    if (int rc = span_refusals(c)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->sb_valid = false;
+    size_t tables = 0, gaps = 0, ext = 0, letters = 0;
+    int items = 0;
+    for (const SpanChunk& C : B.chunks) {
+        tables = std::max(tables, C.tables); gaps = std::max(gaps, C.gaps); ext = std::max(ext, C.ext + (size_t)C.max_Le);
+        letters = std::max(letters, C.letters); items = std::max(items, C.count);
+    }
+    int rc;
+    if ((rc = ensure(c, c->d_span_tab, sizeof(double) * tables, false))) return rc;
+    if ((rc = ensure(c, c->d_span_ext, sizeof(double) * ext, false))) return rc;
+    if ((rc = ensure(c, c->d_span_seq, letters, false))) return rc;
+    if ((rc = ensure(c, c->d_span_bad, sizeof(int) * (size_t)items, false))) return rc;
+    if (gaps && (rc = ensure(c, c->d_span_gaps, sizeof(double) * gaps, false))) return rc;
+    if ((rc = ensure(c, c->d_sb_bp, sizeof(double) * B.band, false))) return rc;
+    if ((rc = ensure(c, c->d_sb_up, sizeof(double) * B.up, false))) return rc;
+    if ((rc = ensure(c, c->d_sb_logz, sizeof(double) * (size_t)count, false))) return rc;
+    std::vector<int> status((size_t)count, RH_OK), part;
+    SpanTimes T;
+    for (const SpanChunk& C : B.chunks) {
+        std::vector<uint8_t> codes(C.letters, 0);
+        std::vector<SpanArgs> args((size_t)C.count);
+        size_t tab_at = 0, gaps_at = 0, ext_at = 0, seq_at = 0;
+        double* hplen = c->d_span_ext.as<double>() + C.ext;   // behind the chunk's gi and go
+        for (int j = 0; j < C.count; j++) {
+            const int k = C.first + j;
+            const SpanBatchItem& I = B.items[(size_t)k];
+            span_codes(seqs[k], I.P.n, codes.data() + seq_at);
+            SpanArgs& A = args[(size_t)j];
+            A = SpanArgs{};
+            A.tab = c->d_span_tab.as<double>() + tab_at; A.ldn = I.P.ldn; A.ts = I.P.table;
+            A.s = c->d_span_seq.as<const uint8_t>() + seq_at;
+            A.n = I.P.n; A.Le = I.P.Le; A.L = max_span;
+            A.gi = c->d_span_ext.as<double>() + ext_at; A.go = A.gi + (I.P.n + 1); A.hplen = hplen;
+            A.band = c->d_sb_bp.as<double>() + I.band_at; A.up = c->d_sb_up.as<double>() + I.up_at; A.logz = c->d_sb_logz.as<double>() + k;
+            A.gaps = I.Q.gaps ? c->d_span_gaps.as<double>() + gaps_at : nullptr; A.max_w = max_w;
+            tab_at += I.P.tables; gaps_at += I.Q.gaps; ext_at += I.P.ext; seq_at += ((size_t)I.P.n + 2 + 15) & ~(size_t)15;
+        }
+        HIP_TRY(c, hipMemcpyAsync(c->d_span_seq.p, codes.data(), C.letters, hipMemcpyHostToDevice, c->s_mc));
+        if ((rc = span_ladder(c, args, c->d_span_bad.as<int>(), &part, &T, true))) return rc;   // (synchronised: the next chunk reuses the scratch)
+        for (int j = 0; j < C.count; j++) status[(size_t)(C.first + j)] = part[(size_t)j];
+    }
+    c->sb = std::move(B);
+    c->sb_status.swap(status);
+    c->sb_ms[0] = T.sweeps; c->sb_ms[1] = T.ext; c->sb_ms[2] = T.acc[0] + T.acc[1] + T.acc[2];
+    c->sb_scan_ms = 0;
+    c->sb_valid = true;
+    return RH_OK;
+}
+
+// a fetch of item `item` of the batch result: RH_OK, or the failure recorded in the context
+int span_batch_ready(rh_ctx* c, int item, const char* who, bool served)
+{
+    if (!c->sb_valid) return fail(c, RH_ERR_ARG, "%s: no span batch result", who);
+    if (item < 0 || item >= c->sb.count) return fail(c, RH_ERR_ARG, "%s: item %d outside the batch of %d", who, item, c->sb.count);
+    if (served && c->sb_status[(size_t)item])
+        return fail(c, c->sb_status[(size_t)item], "%s: item %d: no scale exponent of the ladder keeps the band tables of max_span %d in the double range", who, item,
+                    c->sb.L);
     return RH_OK;
 }
 
@@ -673,6 +846,70 @@ int rh_span_times(rh_ctx* c, double ms[2])
     if (!c || !ms) return RH_ERR_ARG;
     if (!c->span_timed) return fail(c, RH_ERR_ARG, "no span fold result");
     ms[0] = c->span_ms[0]; ms[1] = c->span_ms[1];
+    return RH_OK;
+}
+
+int rh_span_fold_batch(rh_ctx* c, const char* const* seqs, const int* n, int count, int max_span, int max_w)
+{
+    return span_batch_run(c, seqs, n, count, max_span, max_w);
+}
+
+int rh_span_batch_layout(rh_ctx* c, int* count, int* max_span, int* max_w)
+{
+    if (!c) return RH_ERR_ARG;
+    if (!c->sb_valid) return fail(c, RH_ERR_ARG, "rh_span_batch_layout: no span batch result");
+    if (count) *count = c->sb.count;
+    if (max_span) *max_span = c->sb.L;
+    if (max_w) *max_w = c->sb.max_w;
+    return RH_OK;
+}
+
+int rh_span_batch_item(rh_ctx* c, int item, int* n, int* ld, int* status)
+{
+    if (!c) return RH_ERR_ARG;
+    if (int rc = span_batch_ready(c, item, "rh_span_batch_item", false)) return rc;
+    if (n) *n = c->sb.items[(size_t)item].P.n;
+    if (ld) *ld = c->sb.items[(size_t)item].P.Le;
+    if (status) *status = c->sb_status[(size_t)item];
+    return RH_OK;
+}
+
+int rh_span_batch_results(rh_ctx* c, int item, double* bp_band, double* up, double* logz)
+{
+    if (!c) return RH_ERR_ARG;
+    if (int rc = span_batch_ready(c, item, "rh_span_batch_results", true)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const SpanBatchItem& I = c->sb.items[(size_t)item];
+    if (bp_band) HIP_TRY(c, hipMemcpyAsync(bp_band, c->d_sb_bp.as<const double>() + I.band_at, sizeof(double) * I.P.band, hipMemcpyDeviceToHost, c->s_mc));
+    if (up) HIP_TRY(c, hipMemcpyAsync(up, c->d_sb_up.as<const double>() + I.up_at, sizeof(double) * I.Q.up, hipMemcpyDeviceToHost, c->s_mc));
+    if (logz) HIP_TRY(c, hipMemcpyAsync(logz, c->d_sb_logz.as<const double>() + item, sizeof(double), hipMemcpyDeviceToHost, c->s_mc));
+    HIP_TRY(c, hipStreamSynchronize(c->s_mc));
+    return RH_OK;
+}
+
+int rh_span_batch_candidates(rh_ctx* c, int item, int what, float threshold, rh_cand* out, int cap)
+{
+    if (!c) return RH_ERR_ARG;
+    if (int rc = span_batch_ready(c, item, "rh_span_batch_candidates", true)) return rc;
+    if (what < 0 || what > 1 || cap < 0 || (cap > 0 && !out)) return fail(c, RH_ERR_ARG, "rh_span_batch_candidates: bad what/cap");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const SpanBatchItem& I = c->sb.items[(size_t)item];
+    const double* table = what == 0 ? c->d_sb_bp.as<const double>() + I.band_at : c->d_sb_up.as<const double>() + I.up_at;
+    return local_scan_table(c, table, I.P.n, what == 0 ? I.P.Le : c->sb.max_w, what, threshold, out, cap, &c->sb_scan_ms, "rh_span_batch_candidates");
+}
+
+int rh_set_span_batch_bytes(rh_ctx* c, size_t bytes)
+{
+    if (!c) return RH_ERR_ARG;
+    c->sb_bytes = bytes;
+    return RH_OK;
+}
+
+int rh_span_batch_times(rh_ctx* c, double ms[3])
+{
+    if (!c || !ms) return RH_ERR_ARG;
+    if (!c->sb_valid) return fail(c, RH_ERR_ARG, "rh_span_batch_times: no span batch result");
+    for (int k = 0; k < 3; k++) ms[k] = c->sb_ms[k];
     return RH_OK;
 }
 

@@ -1,4 +1,4 @@
-// span_fold.cpp -- the argument checks and the sizes of rh_span_fold and rh_span_fold_acc (span_fold.h).  Host only: no HIP, no context.
+// span_fold.cpp -- the argument checks and the sizes of rh_span_fold, rh_span_fold_acc and rh_span_fold_batch (span_fold.h).  Host only: no HIP, no context.
 #include "span_fold.h"
 
 #include <limits>
@@ -48,6 +48,59 @@ int span_acc_check(const SpanPlan& P, int max_w, SpanAccPlan* A, std::string* wh
     if (!fits) return reject(why, "span fold: the accessibilities of " + std::to_string(P.n) + " letters at max_w " + std::to_string(max_w) + " overflow size_t");
     if (max_w == 1) S.gaps = 0;
     *A = S;
+    return RH_OK;
+}
+
+// a + b into *out, false where the sum does not fit a size_t
+static bool add(size_t a, size_t b, size_t* out)
+{
+    if (b > std::numeric_limits<size_t>::max() - a) return false;
+    *out = a + b;
+    return true;
+}
+
+int span_batch_plan(const char* const* seqs, const int* n, int count, int max_span, int max_w, size_t budget, SpanBatchPlan* B, std::string* why)
+{
+    const std::string who = "span fold batch: ";
+    if (count < 1) return reject(why, who + "the batch has " + std::to_string(count) + " items (must be >= 1)");
+    if (!seqs) return reject(why, who + "the array of sequences is NULL");
+    if (!n) return reject(why, who + "the array of lengths is NULL");
+    if (max_span < 2) return reject(why, who + "max_span " + std::to_string(max_span) + " (must be >= 2)");
+    if (max_w < 1 || max_w > kSpanAccMaxW) return reject(why, who + "max_w " + std::to_string(max_w) + " (must be 1.." + std::to_string(kSpanAccMaxW) + ")");
+    if (budget == 0) budget = kSpanBatchBytes;
+    SpanBatchPlan S;
+    S.count = count; S.L = max_span; S.max_w = max_w;
+    S.items.resize((size_t)count);
+    for (int k = 0; k < count; k++) {
+        SpanBatchItem& I = S.items[(size_t)k];
+        std::string text;
+        int rc = span_check(seqs[k], n[k], max_span, &I.P, &text);
+        if (!rc) rc = span_acc_check(I.P, max_w, &I.Q, &text);
+        // (the single call's reason behind its "span fold: ")
+        if (rc) return reject(why, who + "item " + std::to_string(k) + ": " + text.substr(text.rfind("span fold: ", 0) == 0 ? 11 : 0));
+        I.band_at = S.band; I.up_at = S.up;
+        size_t doubles = 0, bytes = 0;
+        const bool fits = add(S.band, I.P.band, &S.band) && mul(S.band, sizeof(double), &bytes) && add(S.up, I.Q.up, &S.up) && mul(S.up, sizeof(double), &bytes) &&
+                          add(I.P.tables, I.Q.gaps, &doubles) && mul(doubles, sizeof(double), &I.bytes);
+        if (!fits) return reject(why, who + "item " + std::to_string(k) + ": the results of the items up to it overflow size_t");
+    }
+    size_t used = 0;   // bytes of the open chunk
+    for (int k = 0; k < count; k++) {
+        const SpanBatchItem& I = S.items[(size_t)k];
+        size_t with = 0;
+        const bool open = !S.chunks.empty() && S.chunks.back().count < kSpanChunkItems && add(used, I.bytes, &with) && with <= budget;
+        if (!open) { S.chunks.emplace_back(); S.chunks.back().first = k; with = I.bytes; }
+        used = with;
+        SpanChunk& C = S.chunks.back();
+        C.count++;
+        C.tables += I.P.tables; C.gaps += I.Q.gaps;   // (below `used`, which fits)
+        C.ext += I.P.ext;
+        C.letters += ((size_t)I.P.n + 2 + 15) & ~(size_t)15;
+        if (I.P.Le > C.max_Le) C.max_Le = I.P.Le;
+        if (I.P.n > C.max_n) C.max_n = I.P.n;
+        if (I.P.ldn > C.max_ldn) C.max_ldn = I.P.ldn;
+    }
+    *B = std::move(S);
     return RH_OK;
 }
 

@@ -29,6 +29,7 @@
 #include <cmath>
 #include <cstddef>
 #include <string>
+#include <vector>
 
 #if defined(__HIPCC__)
 #define RH_SF_HD __host__ __device__ inline
@@ -70,6 +71,39 @@ struct SpanAccPlan {
 
 // The sizes of the accessibility stage over a checked plan: RH_OK with *A filled, or RH_ERR_ARG with the reason in *why.
 int span_acc_check(const SpanPlan& P, int max_w, SpanAccPlan* A, std::string* why);
+
+// ---- batches of span folds (rh_span_fold_batch): item k is the single call on (seqs[k], n[k]) at the batch's one max_span and max_w.
+// The results of all items lie one behind the other in the batch's own buffers (band_at, up_at; log Z at the item's index); the band
+// tables and gap sums are scratch and are laid out per CHUNK: greedy runs of consecutive items whose tables and gap sums together
+// fit the byte budget (a chunk always holds at least one item, however large), at most kSpanChunkItems of them (a grid dimension).
+constexpr size_t kSpanBatchBytes = (size_t)16 << 30;   // default budget of a chunk: a setting, not a tuned value
+constexpr int kSpanChunkItems = 65535;
+
+struct SpanBatchItem {
+    SpanPlan P;
+    SpanAccPlan Q;
+    size_t band_at = 0, up_at = 0;   // doubles in front of the item in the batch's bp_band and up buffers
+    size_t bytes = 0;                // of its tables and gap sums: what the budget counts
+};
+
+struct SpanChunk {
+    int first = 0, count = 0;        // items first .. first + count - 1
+    size_t tables = 0, gaps = 0;     // doubles of the chunk's tables and gap sums, item after item
+    size_t ext = 0;                  // doubles of its gi and go
+    size_t letters = 0;              // bytes of its letter codes: n + 2 per item, padded to 16
+    int max_Le = 0, max_n = 0;
+    size_t max_ldn = 0;
+};
+
+struct SpanBatchPlan {
+    int count = 0, L = 0, max_w = 0;
+    std::vector<SpanBatchItem> items;
+    std::vector<SpanChunk> chunks;
+    size_t band = 0, up = 0;         // doubles of all bands and of all up tables
+};
+
+// RH_OK with *B filled, or RH_ERR_ARG with the reason in *why (an item's reason names the item).  budget = 0: kSpanBatchBytes.
+int span_batch_plan(const char* const* seqs, const int* n, int count, int max_span, int max_w, size_t budget, SpanBatchPlan* B, std::string* why);
 
 // ---- the exterior passes: what the kernel and the CPU check share.  dir 0: gi, entries ascending from 1; dir 1: go, entries
 // descending from n-1.  Block b holds the entries span_ext_entry(dir, n, b, l), l = 0..63 (those inside 0..n).

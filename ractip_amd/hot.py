@@ -31,6 +31,8 @@ EXPORTS = [
     "rh_local_duplex2", "rh_local_hp2_layout", "rh_local_hp2_results", "rh_local_hp2_candidates", "rh_set_local_tile", "rh_local_hp2_tile",
     "rh_local_hp2_times",
     "rh_span_fold", "rh_span_times", "rh_span_fold_acc", "rh_span_acc_times",
+    "rh_span_fold_batch", "rh_span_batch_layout", "rh_span_batch_item", "rh_span_batch_results", "rh_span_batch_candidates",
+    "rh_set_span_batch_bytes", "rh_span_batch_times",
     "rh_debug_vienna_cell", "rh_debug_vienna_value",   # loader inspection (host only; used by the CPU tests of the loader)
 ]
 
@@ -155,6 +157,20 @@ def load_library():
     L.rh_span_fold_acc.restype = ci
     L.rh_span_acc_times.argtypes = [vp, vp]
     L.rh_span_acc_times.restype = ci
+    L.rh_span_fold_batch.argtypes = [vp, vp, vp, ci, ci, ci]
+    L.rh_span_fold_batch.restype = ci
+    L.rh_span_batch_layout.argtypes = [vp, vp, vp, vp]
+    L.rh_span_batch_layout.restype = ci
+    L.rh_span_batch_item.argtypes = [vp, ci, vp, vp, vp]
+    L.rh_span_batch_item.restype = ci
+    L.rh_span_batch_results.argtypes = [vp, ci, vp, vp, vp]
+    L.rh_span_batch_results.restype = ci
+    L.rh_span_batch_candidates.argtypes = [vp, ci, ci, ctypes.c_float, vp, ci]
+    L.rh_span_batch_candidates.restype = ci
+    L.rh_set_span_batch_bytes.argtypes = [vp, ctypes.c_size_t]
+    L.rh_set_span_batch_bytes.restype = ci
+    L.rh_span_batch_times.argtypes = [vp, vp]
+    L.rh_span_batch_times.restype = ci
     L.rh_local_duplex.argtypes = [vp, cp, ci, cp, ci, ci, ci, ci]
     L.rh_local_duplex.restype = ci
     L.rh_local_hp_layout.argtypes = [vp, vp, vp, vp, vp]
@@ -446,6 +462,44 @@ class Context:
         """Device time (ms) of the accessibility stage of the last span_fold at max_w > 1: (hairpin part, gap sums, final kernel)."""
         ms = (ctypes.c_double * 3)()
         self._check(self.L.rh_span_acc_times(self.h, ms))
+        return ms[0], ms[1], ms[2]
+
+    def span_fold_batch(self, seqs, max_span, max_w=1):
+        """span_fold of every sequence of `seqs` (ragged lengths) through one set of launches (rh_span_fold_batch): a list of
+        (bp_band, up, logz), item k with the bits of span_fold(seqs[k], max_span, max_w) on this context.  The result lives beside the
+        local result until the next span_fold_batch (span_batch_results, span_batch_candidates).  Raises for an item for which no
+        scale exponent of the ladder holds, and names it."""
+        enc = [s.encode() for s in seqs]
+        arr = (ctypes.c_char_p * max(len(enc), 1))(*enc)
+        lens = (ctypes.c_int * max(len(enc), 1))(*[len(s) for s in seqs])
+        self._check(self.L.rh_span_fold_batch(self.h, arr, lens, len(enc), max_span, max_w))
+        return [self.span_batch_results(k) for k in range(len(enc))]
+
+    def span_batch_results(self, item):
+        """(bp_band, up, logz) of one item of the last span_fold_batch (rh_span_batch_item, rh_span_batch_results)."""
+        n, ld, status, w = (ctypes.c_int() for _ in range(4))
+        self._check(self.L.rh_span_batch_layout(self.h, None, None, ctypes.byref(w)))
+        self._check(self.L.rh_span_batch_item(self.h, item, ctypes.byref(n), ctypes.byref(ld), ctypes.byref(status)))
+        band, up, logz = np.empty((n.value, ld.value)), np.empty((n.value, w.value)), np.empty(1)
+        self._check(self.L.rh_span_batch_results(self.h, item, band.ctypes.data, up.ctypes.data, logz.ctypes.data))
+        return band, up, float(logz[0])
+
+    def span_batch_candidates(self, item, what, threshold, cap=1 << 22):
+        """Thresholded list of one item of the last span_fold_batch (rh_span_batch_candidates): what = 0 the pairs, 1 the
+        accessibilities; (records, total) as local_candidates returns them after the item's single span_fold."""
+        buf = np.empty(max(cap, 1), dtype=self.CAND_DTYPE)
+        k = self._check(self.L.rh_span_batch_candidates(self.h, item, what, ctypes.c_float(threshold), buf.ctypes.data, cap))
+        return buf[:min(k, cap)], k
+
+    def set_span_batch_bytes(self, b):
+        """Table memory (bytes) one chunk of a span_fold_batch may take (0: the default, 16 GiB); results are unchanged."""
+        self._check(self.L.rh_set_span_batch_bytes(self.h, b))
+
+    def span_batch_times(self):
+        """Device time (ms) of the last span_fold_batch, summed over chunks and ladder attempts: (sweeps, exterior passes + finish,
+        accessibility stage)."""
+        ms = (ctypes.c_double * 3)()
+        self._check(self.L.rh_span_batch_times(self.h, ms))
         return ms[0], ms[1], ms[2]
 
     # ---- local hybridization of two windowed molecules

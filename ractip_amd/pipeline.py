@@ -25,6 +25,11 @@ max_w: one ensemble per molecule, pairs within L letters), hp from the pair as b
 --max-span L: span-limited folding of ONE sequence (Context.span_fold): the McCaskill ensemble of the whole sequence under the
 Vienna-BL model with pairs (a, b) only where b - a < L.  Prints ">name logZ <log Z>" and one line "i j p" per pair whose probability
 exceeds T (default 0.5), 1-based, row-major, scanned on the device (Context.local_candidates).
+
+  python -m ractip_amd.pipeline --max-span L --all-records [--threshold T] many.fa
+
+--all-records: every record of the file is folded, all of them as ONE batch (Context.span_fold_batch), and the lines above are
+printed for each record in the file's order.
 """
 import sys
 
@@ -197,8 +202,7 @@ def _predict_span(ctx, s1, s2, duplex, opt, rip_path, max_span, window, step, lo
     else:
         hp = probabilities(ctx, s1, s2)["hp"]
     bp, up = [], []
-    for s in (s1, s2):
-        band, u, _ = ctx.span_fold(s, max_span, max(1, opt.max_w))
+    for band, u, _ in ctx.span_fold_batch([s1, s2], max_span, max(1, opt.max_w)):   # one batch of two: the bits of two span_fold calls
         bp.append(hot.band_to_tri(band))
         up.append(u)
     if rip_path:
@@ -288,15 +292,68 @@ def span_fold(seq, max_span, max_w=1, device=0, ctx=None):
             ctx.close()
 
 
+def span_fold_batch(seqs, max_span, max_w=1, device=0, ctx=None):
+    """span_fold of several long sequences as one batch (Context.span_fold_batch: the item is a dimension of every launch, the
+    lengths may differ): a list with the dict of span_fold for every sequence, bit for bit what span_fold gives on the same context.
+    ctx: a Vienna-BL context to run on (its local result stays; the batch result becomes this one)."""
+    own = ctx is None
+    if own:
+        ctx = hot.Context(device=device, model=hot.RH_MODEL_VIENNA_BL)
+    try:
+        res = ctx.span_fold_batch(list(seqs), max_span, max_w)
+        return [dict(n=len(s), max_span=max_span, bp_band=band, up=up, logZ=logz) for s, (band, up, logz) in zip(seqs, res)]
+    finally:
+        if own:
+            ctx.close()
+
+
+def read_fasta_records(path):
+    """every record of a FASTA file: a list of (name, sequence)"""
+    records = []
+    for line in open(path):
+        line = line.strip()
+        if line.startswith(">"):
+            records.append([line[1:], ""])
+        elif line and records:
+            records[-1][1] += line
+    return [(name, seq) for name, seq in records]
+
+
+def _main_span_records(path, max_span, threshold):
+    """--all-records: every record of the file folded as one batch; per record what the one-file form prints"""
+    records = read_fasta_records(path)
+    if not records:
+        raise SystemExit("%s holds no FASTA record" % path)
+    ctx = hot.Context(device=0, model=hot.RH_MODEL_VIENNA_BL)
+    try:
+        res = ctx.span_fold_batch([seq for _, seq in records], max_span)
+        lists = []
+        for k, (_, seq) in enumerate(records):
+            rec, total = ctx.span_batch_candidates(k, 0, threshold, cap=max(1, len(seq)))
+            if total > len(rec):
+                rec, total = ctx.span_batch_candidates(k, 0, threshold, cap=total)
+            lists.append(rec.copy())
+    finally:
+        ctx.close()
+    for (name, _), (_, _, logz), rec in zip(records, res, lists):
+        print(">%s logZ %.9f" % (name, logz))
+        for r in rec:
+            print("%d %d %.6g" % (r["i"], r["j"], r["p"]))
+
+
 def _main_span(argv, max_span):
     threshold = 0.5
     if "--threshold" in argv:
         k = argv.index("--threshold")
         threshold = float(argv[k + 1])
         argv = argv[:k] + argv[k + 2:]
+    all_records = "--all-records" in argv
+    argv = [a for a in argv if a != "--all-records"]
     files = [a for a in argv if not a.startswith("--")]
     if len(files) != 1 or len(files) != len(argv):
-        raise SystemExit("--max-span takes one FASTA file (and --threshold T)")
+        raise SystemExit("--max-span takes one FASTA file (and --threshold T, --all-records)")
+    if all_records:
+        return _main_span_records(files[0], max_span, threshold)
     name, seq = read_fasta(files[0])
     ctx = hot.Context(device=0, model=hot.RH_MODEL_VIENNA_BL)
     try:
