@@ -11,6 +11,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ORACLE_DIR = os.path.join(ROOT, "oracle")
 PARAMS = os.path.join(ROOT, "ractip_amd", "data", "contrafold_complementary.params")
+VIENNA_BL_PARAMS = os.path.join(ROOT, "ractip_amd", "data", "vienna_bl_star.params")
 NEG = -2e20
 
 
@@ -172,9 +173,10 @@ def constraint_mask(constraint, n, turn=3):
 
 
 class ViennaOracle:
-    """BL*/ViennaRNA-1.8-semantics pf_duplex restatement (oracle/vienna_oracle.c) -- PARITY UNPINNED."""
+    """BL*/ViennaRNA-1.8-semantics pf_duplex restatement (oracle/vienna_oracle.c) -- PARITY UNPINNED.
+    params: a flat table dump (tests/_vienna18_tables.py writes them); None is the bundled BL* file."""
 
-    def __init__(self):
+    def __init__(self, params=None):
         so = os.path.join(ORACLE_DIR, "libvienna_oracle.so")
         src = os.path.join(ORACLE_DIR, "vienna_oracle.c")
         if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
@@ -199,8 +201,9 @@ class ViennaOracle:
         L.vo_set_allow_mask.argtypes = [ctypes.c_void_p]
         L.vo_set_allow_mask.restype = None
         self.L = L
-        self.m = L.vo_load(os.path.join(ROOT, "ractip_amd", "data", "vienna_bl_star.params").encode())
-        assert self.m
+        self.params = params or VIENNA_BL_PARAMS
+        self.m = L.vo_load(self.params.encode())
+        assert self.m, "oracle could not load " + self.params
 
     def mccaskill(self, seq, max_w=0, tables=False, constraint=None):
         """pf_fold / pf_unstru semantics: logZ, bp (triangular, reference layout), up[n][max_w].
@@ -343,11 +346,12 @@ class OraclePool:
     """Memoised oracle calls on a small thread pool.  The ctypes calls release the GIL, so up to `workers` of them run at once.
     Every method returns a Future, keyed by its inputs (a sequence, or a pair for the two-sequence calls): asking twice costs one
     call, and asking early lets the oracle run while the GPU computes.  Only unconstrained Vienna calls go to the threads:
-    vienna_oracle.c keeps the allowed-pair mask in one global (vo_allow_mask)."""
+    vienna_oracle.c keeps the allowed-pair mask in one global (vo_allow_mask).  params: the table file of the Vienna calls (None: BL*);
+    a pool has one, so its keys need not name it."""
 
-    def __init__(self, workers=ORACLE_WORKERS):
+    def __init__(self, workers=ORACLE_WORKERS, params=None):
         self.cf = Oracle()
-        self.vo = ViennaOracle()
+        self.vo = ViennaOracle(params)
         self.pool = ThreadPoolExecutor(max_workers=min(workers, ORACLE_WORKERS))
         self.cache = {}
         self.constrained_cache = {}

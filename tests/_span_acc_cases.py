@@ -10,11 +10,11 @@ import _span_cases as sc
 _refs = {}
 
 
-def masked_acc(seq, L, max_w, bruteforce=False):
-    """dict(logZ, band (n, min(L, n)), up (n, max_w)) of the oracle under the band mask; L = None: no mask"""
-    key = (seq, L, max_w, bruteforce)
+def masked_acc(seq, L, max_w, bruteforce=False, params=None):
+    """dict(logZ, band (n, min(L, n)), up (n, max_w)) of the oracle under the band mask; L = None: no mask; params: the table file"""
+    key = (seq, L, max_w, bruteforce, sc.file_key(params))
     if key not in _refs:
-        vo, n = sc.oracle(), len(seq)
+        vo, n = sc.oracle(params), len(seq)
         mask = sc.band_mask(n, L) if L is not None else None
         vo.L.vo_set_allow_mask(mask.ctypes.data if mask is not None else None)
         try:

@@ -3,18 +3,31 @@ once per (sequence, L), and the long factorising sequence.
 
 oracle/vienna_oracle.c applies vo_set_allow_mask to every pair test of its DP and of its brute-force enumeration, so the mask
 allow[a][b] = 1 iff b - a < L (1-based a < b) makes both the ensemble of rh_span_fold."""
+import hashlib
+
 import numpy as np
 
 from _oracle import ViennaOracle, tri_offset
 
-_vo = []
+_vo = {}
 _refs = {}
 
 
-def oracle():
-    if not _vo:
-        _vo.append(ViennaOracle())
-    return _vo[0]
+def file_key(params):
+    """what the caches name a table file by: its path and a digest of what it holds now, so that a file written again under the same
+    name is another file (None: the bundled BL* file)"""
+    if params is None:
+        return None
+    with open(params, "rb") as f:
+        return params, hashlib.sha1(f.read()).hexdigest()
+
+
+def oracle(params=None):
+    """the oracle on a table file (None: the bundled BL* file), one per file and content"""
+    key = file_key(params)
+    if key not in _vo:
+        _vo[key] = ViennaOracle(params)
+    return _vo[key]
 
 
 def band_mask(n, L):
@@ -35,11 +48,11 @@ def tri_to_band(tri, n, ld):
     return band
 
 
-def masked(seq, L, bruteforce=False):
-    """dict(logZ, band (n, min(L, n)), up (n, 1), post) of the oracle under the band mask; L = None: no mask"""
-    key = (seq, L, bruteforce)
+def masked(seq, L, bruteforce=False, params=None):
+    """dict(logZ, band (n, min(L, n)), up (n, 1), post) of the oracle under the band mask; L = None: no mask; params: the table file"""
+    key = (seq, L, bruteforce, file_key(params))
     if key not in _refs:
-        vo, n = oracle(), len(seq)
+        vo, n = oracle(params), len(seq)
         mask = band_mask(n, L) if L is not None else None
         vo.L.vo_set_allow_mask(mask.ctypes.data if mask is not None else None)
         try:
