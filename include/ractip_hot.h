@@ -422,7 +422,7 @@ int rh_local_times(rh_ctx* ctx, double ms[2]);
  * of an rh_local_duplex and leaves the result of rh_local_duplex2 alone.  The context's batch is neither read nor changed.
  * Refusals.  RH_ERR_ARG: NULL sequence, n < 1, L < 2, sizes that overflow.  RH_ERR_UNSUPPORTED: CONTRAfold contexts, 2.x-semantics
  * contexts, contexts in RH_MODE_LOG (there is no log-space version).  Both leave the previous local result and the batch in place;
- * rh_last_error names the reason.  Structure constraints do not apply.
+ * rh_last_error names the reason.  Structure constraints: rh_span_fold_constrained below.
  * A band cell that leaves the double range under the context's scale exponent sends the call through the exponent ladder; when no
  * exponent holds it returns RH_ERR_UNSUPPORTED and leaves no local result, as RH_ERR_OOM does (buffers grow only and go with the
  * context).
@@ -461,7 +461,8 @@ int rh_span_acc_times(rh_ctx* ctx, double ms[3]);
  * The result lives in buffers of its own until the next rh_span_fold_batch: it neither reads nor changes the context's batch, the
  * local result (rh_local_*, the single span calls) or the result of rh_local_duplex2, and these calls leave it alone.
  * Refusals.  RH_ERR_ARG: count < 1, a NULL array, a NULL sequence, n[k] < 1, max_span < 2, max_w outside 1..64, sizes that overflow
- * (rh_last_error names the item).  RH_ERR_UNSUPPORTED: as rh_span_fold.  Both leave the previous batch result in place. */
+ * (rh_last_error names the item).  RH_ERR_UNSUPPORTED: as rh_span_fold.  Both leave the previous batch result in place.
+ * Structure constraints: rh_span_fold_batch_constrained below. */
 int rh_span_fold_batch(rh_ctx* ctx, const char* const* seqs, const int* n, int count, int max_span, int max_w);
 int rh_span_batch_layout(rh_ctx* ctx, int* count, int* max_span, int* max_w);
 /* n, ld = min(max_span, n) and the status of one item; RH_ERR_ARG for an item outside the batch */
@@ -475,6 +476,23 @@ int rh_set_span_batch_bytes(rh_ctx* ctx, size_t bytes);
 /* Measurement aid: device time (ms, HIP event pairs) of the last rh_span_fold_batch, summed over its chunks and ladder attempts: ms[0]
  * the inside and outside sweeps, ms[1] the exterior passes and the finish kernels, ms[2] the accessibility stage. */
 int rh_span_batch_times(rh_ctx* ctx, double ms[3]);
+/* Span folds under a structure constraint.  `constraint`: a string in the fold_constrained alphabet of rh_bpp (or NULL); shorter than
+ * n it is padded with '.', longer the surplus is ignored.  The ensemble is that of rh_span_fold_acc with one more restriction: letters
+ * a < b may pair only if b - a < max_span AND the constraint allows the pair, by the rule of rh_fold_constrained -- 'x' never pairs,
+ * '<' only with a later letter, '>' only with an earlier one, a matched '(' ')' removes every pair that conflicts with it (it does not
+ * force the pair itself), '|' and '.' restrict nothing.  With max_span >= n it is the ensemble of rh_fold_constrained.  Model, unknown
+ * letters, end letters, layouts, the exponent ladder and the local-result slots are those of rh_span_fold_acc; a NULL constraint, or
+ * one that restricts nothing, gives rh_span_fold_acc bit for bit.  No n x n mask is built: the constraint costs 8 bytes per letter.
+ * Refusals, each leaving the previous local result in place.  RH_ERR_ARG: those of rh_span_fold_acc; unbalanced brackets or a bracket
+ * pair of non-complementary letters, with the reason rh_fold_constrained gives; a matched bracket pair (a, b) with b - a >= max_span
+ * (rh_last_error names a, b and max_span); a constraint over 2^30 letters or more.  RH_ERR_UNSUPPORTED: as rh_span_fold. */
+int rh_span_fold_constrained(rh_ctx* ctx, const char* seq, int n, const char* constraint, int max_span, int max_w);
+/* rh_span_fold_batch under constraints: item k is rh_span_fold_constrained(ctx, seqs[k], n[k], constraints[k], max_span, max_w), bit
+ * for bit.  `constraints`, and any entry of it, may be NULL.  The result goes to the span-batch slots (rh_span_batch_*).  The per-letter
+ * records are not counted in the chunk budget, so the chunks do not depend on the constraints.  Refusals: those of rh_span_fold_batch
+ * and, per item, of rh_span_fold_constrained (rh_last_error names the item); every check of every item runs before anything is
+ * staged, and a refused call leaves the previous batch result in place. */
+int rh_span_fold_batch_constrained(rh_ctx* ctx, const char* const* seqs, const int* n, int count, const char* const* constraints, int max_span, int max_w);
 
 /* ---- local hybridization: window-averaged hp of a query on a long target ----
  * Two molecules s1 (n1 letters) and s2 (n2 letters).  `windowed` (1 or 2) names the one that is cut into the windows of rh_local_fold

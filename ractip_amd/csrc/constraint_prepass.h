@@ -8,7 +8,8 @@
 //   ch[k]   the constraint character ('.' beyond the string's end)
 //   P[k]    the forced partner of a matched bracket, 0 if none
 //   enc[k]  the opening letter of the innermost matched bracket pair that strictly encloses k, 0 if none
-// allow_pair below is the one statement of the rule: the kernel evaluates it per byte.
+// allow_pair_values below is the one statement of the rule; allow_pair reads it off the three arrays (the mask kernel evaluates it per
+// byte), allow_pair_rec off two packed records (the span kernels, which have no mask).
 // Second half of this file: the same three values for a joint string that is given as two shares (indexed batches).
 #pragma once
 #include <cstdint>
@@ -23,14 +24,46 @@
 
 namespace rh::host {
 
+// The two facts the rule takes from a constraint character
+RH_HOST_DEVICE inline bool cons_no_downstream(uint8_t c) { return c == 'x' || c == ')' || c == '>'; }   // the letter pairs with no later letter
+RH_HOST_DEVICE inline bool cons_no_upstream(uint8_t c) { return c == 'x' || c == '(' || c == '<'; }     // ... with no earlier letter
+
+// The rule on the values of the two letters alone: a_down = cons_no_downstream(ch[a]), b_up = cons_no_upstream(ch[b]), P and enc of both.
+RH_HOST_DEVICE inline bool allow_pair_values(int a, int b, int n, bool a_down, bool b_up, int Pa, int Pb, int enca, int encb)
+{
+    if (a < 1 || b <= a || b > n) return false;
+    if (a_down || b_up) return false;
+    return Pa == b || (Pa == 0 && Pb == 0 && enca == encb);   // the forced pair itself, or two free letters of one loop
+}
+
 // May letters a and b pair?  a, b index the three arrays (0 .. their length - 1); n = the sequence's length.
 RH_HOST_DEVICE inline bool allow_pair(int a, int b, int n, const uint8_t* ch, const int* P, const int* enc)
 {
-    if (a < 1 || b <= a || b > n) return false;
-    const uint8_t ca = ch[a], cb = ch[b];
-    if (ca == 'x' || ca == ')' || ca == '>') return false;   // a does not pair downstream
-    if (cb == 'x' || cb == '(' || cb == '<') return false;   // b does not pair upstream
-    return P[a] == b || (P[a] == 0 && P[b] == 0 && enc[a] == enc[b]);   // the forced pair itself, or two free letters of one loop
+    if (a < 1 || b <= a || b > n) return false;   // (before the arrays are read)
+    return allow_pair_values(a, b, n, cons_no_downstream(ch[a]), cons_no_upstream(ch[b]), P[a], P[b], enc[a], enc[b]);
+}
+
+// ---- per-letter records: ch / P / enc of one letter in 8 bytes, for the kernels that cannot afford the n x n byte mask (span folds
+// under a constraint, mccaskill_span.hip).  A pair test is two records and allow_pair_values.  P and enc are letters of the sequence,
+// below 2^30 (span_cons_records, span_fold.h, refuses longer ones), so the two facts of ch sit beside P.
+struct alignas(8) ConsRec {
+    uint32_t p;   // P | kConsRecDown | kConsRecUp
+    uint32_t e;   // enc
+};
+static_assert(sizeof(ConsRec) == 8);
+constexpr uint32_t kConsRecIndex = (1u << 30) - 1, kConsRecDown = 1u << 30, kConsRecUp = 1u << 31;
+constexpr int kConsRecMaxN = (int)kConsRecIndex;
+
+RH_HOST_DEVICE inline ConsRec cons_rec_pack(uint8_t ch, int P, int enc)
+{
+    return ConsRec{(uint32_t)P | (cons_no_downstream(ch) ? kConsRecDown : 0u) | (cons_no_upstream(ch) ? kConsRecUp : 0u), (uint32_t)enc};
+}
+RH_HOST_DEVICE inline int cons_rec_partner(ConsRec r) { return (int)(r.p & kConsRecIndex); }
+RH_HOST_DEVICE inline int cons_rec_enc(ConsRec r) { return (int)r.e; }
+// allow_pair on the records of letters a and b
+RH_HOST_DEVICE inline bool allow_pair_rec(int a, int b, int n, ConsRec ra, ConsRec rb)
+{
+    return allow_pair_values(a, b, n, (ra.p & kConsRecDown) != 0, (rb.p & kConsRecUp) != 0, cons_rec_partner(ra), cons_rec_partner(rb), cons_rec_enc(ra), cons_rec_enc(rb));
 }
 
 uint8_t nuc_code(char ch);      // CONTRAfold model: A,C,G,U -> 0..3 in either case, anything else (T and N included) 4; host only, here so that a CPU program can call it

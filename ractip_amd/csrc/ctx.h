@@ -392,6 +392,8 @@ struct Ctx {   // (the fields of rh_ctx, below)
     bool span_acc_timed = false;   // the last span fold ran the accessibility stage
     // every span fold: the per-item descriptors of the launches (grow-only)
     DevBuf d_span_desc;
+    // span folds under a constraint: the per-letter records of the items of one chunk, laid out like the letters (grow-only)
+    DevBuf d_span_cons;
     // rh_span_fold_batch only: the last batch result -- its plan, the status of every item, the bands, up tables and log Z of all
     // items one behind the other (grow-only, kept until the next rh_span_fold_batch), the chunk budget and the device times
     SpanBatchPlan sb;

@@ -10,6 +10,9 @@
 // rh_span_fold_acc adds the region accessibilities up[i][w] of the same ensemble: the span_acc_* kernels behind the outside sweep.
 // rh_span_fold_batch runs many sequences through the same launches: every kernel takes per-item descriptors and the item as a grid
 // dimension (span_item), the exponent ladder runs per item, and the single calls are batches of one.
+// rh_span_fold_constrained / rh_span_fold_batch_constrained restrict the pairs further by a structure constraint: an item's descriptor
+// points to the packed per-letter records of its constraint (ConsRec, constraint_prepass.h), and the two sweeps -- the only kernels
+// that decide whether a pair exists -- test a pair on the records of its two letters.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -36,6 +39,7 @@ struct SpanArgs {
     size_t ldn, ts;
     const uint8_t* s;      // letters 1..n, code 0 at 0 and n+1
     int n, Le, L;
+    int max_w;             // widths of up: [n][max_w]
     const double* hplen;   // hairpin length weight x lam^d, d < Le
     double* gi;            // log F5i [n+1]
     double* go;            // log F5o [n+1]
@@ -45,9 +49,9 @@ struct SpanArgs {
     int* bad;
     double sc;             // the scale exponent s of the model
     double* gaps;          // GL, GR [2][kSpanGapRows][ldn] (max_w > 1)
-    int max_w;             // widths of up: [n][max_w]
+    const ConsRec* cons;   // the constraint's records of letters 0..n+1; null: the item has no constraint
 };
-static_assert(sizeof(SpanArgs) % 8 == 0);
+static_assert(sizeof(SpanArgs) == 128);   // two scalar loads of 16 dwords
 
 // Every kernel runs a batch of items, a single call a batch of one: the launch hands over a device array with one SpanArgs per item
 // and the item is a grid dimension (y, or z where the kernel's own grid has two), so a workgroup belongs to ONE item.  The grid spans
@@ -68,7 +72,22 @@ __device__ __forceinline__ SpanArgs span_item(const SpanArgs* __restrict__ items
     A.gi = span_global(A.gi); A.go = span_global(A.go);
     A.band = span_global(A.band); A.up = span_global(A.up); A.logz = span_global(A.logz);
     A.bad = span_global(A.bad); A.gaps = span_global(A.gaps);
+    if (A.cons) A.cons = span_global(A.cons);
     return A;
+}
+
+// The pair type of cell (i, d), the pair of letters (i, j1 = i + d + 1): 0 where the span limit or the item's constraint excludes the
+// pair.  Every other kernel reaches a pair through an FC / FCo^ cell, which is 0 where the type is: the tabulated shapes skip v == 0
+// and fo == 0, FCX / FCB / FCA and their outside copies are FC / FCo^ times a weight, the exterior passes read FCA, span_acc_hp skips
+// FCo^ == 0, the gap sums are products of an inside and an outside cell, and the multiloop tables are sums over FCA and FCo^.
+// The null test is uniform over the workgroup (the descriptor sits in scalar registers); the two 8-byte loads are contiguous along
+// the diagonal.  kCons = false, the sweeps of a launch none of whose items has a constraint, compiles the test away: those sweeps
+// are the code they were before constraints existed.
+template <bool kCons> __device__ __forceinline__ int span_pair_type(const SpanArgs& A, int i, int j1, int d, int s_i, int s_j1)
+{
+    int type = d + 1 < A.L ? vienna_ptype(s_i, s_j1) : 0;   // the pair (i, j1) spans d + 1 letters
+    if (kCons && A.cons && type && !allow_pair_rec(i, j1, A.n, A.cons[i], A.cons[j1])) type = 0;
+    return type;
 }
 
 // the seven tabulated loop shapes (as mccaskill_vlin.hip): outer pair type t1, inner pair type t2, letters si1/sj1 next to the outer
@@ -88,7 +107,7 @@ __device__ __forceinline__ int small_l1(int k) { return (k == 2 || k == 3 || k =
 __device__ __forceinline__ int small_l2(int k) { return (k == 1 || k == 3 || k == 5) ? 1 : ((k == 4 || k == 6) ? 2 : 0); }
 
 // ---- inside, diagonal d: grid over the ldn columns of the row
-__global__ __launch_bounds__(kSpanThreads) void span_inside_diag(const SpanArgs* __restrict__ items, const VLinModel* __restrict__ M, int d)
+template <bool kCons> __global__ __launch_bounds__(kSpanThreads) void span_inside_diag(const SpanArgs* __restrict__ items, const VLinModel* __restrict__ M, int d)
 {
     const SpanArgs A = span_item(items, blockIdx.y);
     if (d >= A.Le || (size_t)blockIdx.x * kSpanThreads >= A.ldn) return;   // the item has no such row, or no such columns
@@ -103,7 +122,7 @@ __global__ __launch_bounds__(kSpanThreads) void span_inside_diag(const SpanArgs*
     if (valid) {
         const uint8_t* __restrict__ s = A.s;
         const int s_im1 = s[i - 1], s_i = s[i], s_ip1 = s[i + 1], s_j = s[j], s_jp1 = s[j + 1], s_jp2 = s[j + 2];
-        const int type = d + 1 < A.L ? vienna_ptype(s_i, s_jp1) : 0;   // the pair (i, j+1) spans d + 1 letters
+        const int type = span_pair_type<kCons>(A, i, j + 1, d, s_i, s_jp1);
         double fm2 = 0.0;
         {   // FM2[i,d] = sum_{m=1}^{d-1} FM1[m][i] * FM[d-m][i+m]
             const double* __restrict__ fm1 = tab + SP_FM1 * ts + i;
@@ -241,7 +260,7 @@ __global__ __launch_bounds__(kSpanBlock * kSpanWaves) void span_ext_pass(const S
 }
 
 // ---- outside (pull form) and posterior, diagonal d
-__global__ __launch_bounds__(kSpanThreads) void span_outside_diag(const SpanArgs* __restrict__ items, const VLinModel* __restrict__ M, int d)
+template <bool kCons> __global__ __launch_bounds__(kSpanThreads) void span_outside_diag(const SpanArgs* __restrict__ items, const VLinModel* __restrict__ M, int d)
 {
     const SpanArgs A = span_item(items, blockIdx.y);
     if (d >= A.Le || (size_t)blockIdx.x * kSpanThreads >= A.ldn) return;
@@ -256,7 +275,7 @@ __global__ __launch_bounds__(kSpanThreads) void span_outside_diag(const SpanArgs
     if (valid) {
         const uint8_t* __restrict__ s = A.s;
         const int s_im1 = s[i - 1], s_i = s[i], s_ip1 = s[i + 1], s_j = s[j], s_jp1 = s[j + 1], s_jp2 = s[j + 2];
-        const int type = d + 1 < A.L ? vienna_ptype(s_i, s_jp1) : 0;
+        const int type = span_pair_type<kCons>(A, i, j + 1, d, s_i, s_jp1);
         double fmo = 0.0;
         if (d >= 2) {
             const int emax = Le - 1 - d;
@@ -596,9 +615,11 @@ int span_attempt(rh_ctx* c, std::vector<SpanArgs>& run, int* bad, const SpanEven
     const int max_w = run[0].max_w;
     int Le = 0, n = 0;
     size_t ldn = 0;
+    bool cons = false;   // an item of the launches has a constraint: the sweeps that test pairs on the records
     for (unsigned k = 0; k < K; k++) {
         SpanArgs& A = run[k];
         Le = std::max(Le, A.Le); n = std::max(n, A.n); ldn = std::max(ldn, A.ldn);
+        cons = cons || A.cons != nullptr;
         A.sc = c->h_vlin->s;
         A.bad = bad + k;
     }
@@ -612,14 +633,16 @@ int span_attempt(rh_ctx* c, std::vector<SpanArgs>& run, int* bad, const SpanEven
     HIP_TRY(c, hipMemsetAsync(bad, 0, sizeof(int) * K, st));
     const dim3 grid((unsigned)((ldn + kSpanThreads - 1) / kSpanThreads), K), block(kSpanThreads);
     HIP_TRY(c, hipEventRecord(ev.e[0], st));
-    for (int d = 0; d < Le; d++) hipLaunchKernelGGL(span_inside_diag, grid, block, 0, st, items, M, d);
+    const auto inside = cons ? span_inside_diag<true> : span_inside_diag<false>;
+    const auto outside = cons ? span_outside_diag<true> : span_outside_diag<false>;
+    for (int d = 0; d < Le; d++) hipLaunchKernelGGL(inside, grid, block, 0, st, items, M, d);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(ev.e[1], st));
     hipLaunchKernelGGL(span_ext_pass, dim3(1, K), dim3(kSpanBlock * kSpanWaves), 0, st, items, 0);
     hipLaunchKernelGGL(span_ext_pass, dim3(1, K), dim3(kSpanBlock * kSpanWaves), 0, st, items, 1);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(ev.e[2], st));
-    for (int d = Le - 1; d >= 0; d--) hipLaunchKernelGGL(span_outside_diag, grid, block, 0, st, items, M, d);
+    for (int d = Le - 1; d >= 0; d--) hipLaunchKernelGGL(outside, grid, block, 0, st, items, M, d);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(ev.e[3], st));
     hipLaunchKernelGGL(span_finish, dim3((unsigned)n, K), dim3(kSpanBlock), 0, st, items);
@@ -708,15 +731,19 @@ void span_codes(const char* seq, int n, uint8_t* codes)
     for (int i = 0; i < n; i++) codes[(size_t)i + 1] = vienna_code(seq[i]);
 }
 
-// rh_span_fold (max_w = 1) and rh_span_fold_acc: a batch of one whose result is the context's local result
-int span_run(rh_ctx* c, const char* seq, int n, int max_span, int max_w)
+// rh_span_fold (max_w = 1), rh_span_fold_acc and rh_span_fold_constrained (cons, which may be NULL): a batch of one whose result is
+// the context's local result
+int span_run(rh_ctx* c, const char* seq, int n, const char* cons, int max_span, int max_w)
 {
     if (!c) return RH_ERR_ARG;
     SpanPlan P;
     SpanAccPlan Q;
     std::string why;
+    std::vector<ConsRec> rec;   // empty: nothing restricts the band
+    bool restricts = false;
     if (int rc = span_check(seq, n, max_span, &P, &why)) return fail(c, rc, "%s", why.c_str());
     if (int rc = span_acc_check(P, max_w, &Q, &why)) return fail(c, rc, "%s", why.c_str());
+    if (int rc = span_cons_records(seq, n, cons, max_span, &rec, &restricts, &why)) return fail(c, rc, "%s", why.c_str());
     if (int rc = span_refusals(c)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     c->loc_valid = c->loc_hp.valid = false;   // (the hp result of rh_local_duplex goes with the band it came with)
@@ -730,9 +757,11 @@ int span_run(rh_ctx* c, const char* seq, int n, int max_span, int max_w)
     if ((rc = ensure(c, c->d_loc_up, sizeof(double) * Q.up, false))) return rc;
     if (Q.gaps && (rc = ensure(c, c->d_span_gaps, sizeof(double) * Q.gaps, false))) return rc;
     if ((rc = ensure(c, c->d_loc_logz, sizeof(double), false))) return rc;
+    if (restricts && (rc = ensure(c, c->d_span_cons, sizeof(ConsRec) * rec.size(), false))) return rc;
     std::vector<uint8_t> codes(seq_bytes, 0);
     span_codes(seq, n, codes.data());
     HIP_TRY(c, hipMemcpyAsync(c->d_span_seq.p, codes.data(), seq_bytes, hipMemcpyHostToDevice, c->s_mc));
+    if (restricts) HIP_TRY(c, hipMemcpyAsync(c->d_span_cons.p, rec.data(), sizeof(ConsRec) * rec.size(), hipMemcpyHostToDevice, c->s_mc));
     SpanArgs A{};
     A.tab = c->d_span_tab.as<double>(); A.ldn = P.ldn; A.ts = P.table;
     A.s = c->d_span_seq.as<const uint8_t>();
@@ -740,6 +769,7 @@ int span_run(rh_ctx* c, const char* seq, int n, int max_span, int max_w)
     A.gi = c->d_span_ext.as<double>(); A.go = A.gi + (n + 1); A.hplen = A.go + (n + 1);
     A.band = c->d_loc_bp.as<double>(); A.up = c->d_loc_up.as<double>(); A.logz = c->d_loc_logz.as<double>();
     A.gaps = Q.gaps ? c->d_span_gaps.as<double>() : nullptr; A.max_w = max_w;
+    A.cons = restricts ? c->d_span_cons.as<const ConsRec>() : nullptr;
     std::vector<int> status;
     SpanTimes T;
     if ((rc = span_ladder(c, {A}, c->d_span_bad.as<int>(), &status, &T, false))) return rc;   // (the times of the last attempt)
@@ -756,21 +786,27 @@ int span_run(rh_ctx* c, const char* seq, int n, int max_span, int max_w)
     return RH_OK;
 }
 
-// rh_span_fold_batch: chunk after chunk on the grow-only scratch of the single calls; the results go to the batch's own buffers
-int span_batch_run(rh_ctx* c, const char* const* seqs, const int* n, int count, int max_span, int max_w)
+// rh_span_fold_batch and rh_span_fold_batch_constrained (cons, or any entry of it, may be NULL): chunk after chunk on the grow-only
+// scratch of the single calls; the results go to the batch's own buffers.  The records of a chunk lie item after item like its letter
+// codes, a record per code, and are not part of the chunk budget, as the letters are not: the chunks do not depend on the constraints.
+int span_batch_run(rh_ctx* c, const char* const* seqs, const int* n, int count, const char* const* cons, int max_span, int max_w)
 {
     if (!c) return RH_ERR_ARG;
     SpanBatchPlan B;
     std::string why;
+    std::vector<std::vector<ConsRec>> recs;   // per item; empty: nothing restricts its band
     if (int rc = span_batch_plan(seqs, n, count, max_span, max_w, c->sb_bytes, &B, &why)) return fail(c, rc, "%s", why.c_str());
+    if (int rc = span_cons_batch(seqs, n, count, cons, max_span, &recs, &why)) return fail(c, rc, "%s", why.c_str());
     if (int rc = span_refusals(c)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     c->sb_valid = false;
-    size_t tables = 0, gaps = 0, ext = 0, letters = 0;
+    size_t tables = 0, gaps = 0, ext = 0, letters = 0, records = 0;
     int items = 0;
     for (const SpanChunk& C : B.chunks) {
         tables = std::max(tables, C.tables); gaps = std::max(gaps, C.gaps); ext = std::max(ext, C.ext + (size_t)C.max_Le);
         letters = std::max(letters, C.letters); items = std::max(items, C.count);
+        for (int j = 0; j < C.count; j++)
+            if (!recs[(size_t)(C.first + j)].empty()) records = std::max(records, C.letters);
     }
     int rc;
     if ((rc = ensure(c, c->d_span_tab, sizeof(double) * tables, false))) return rc;
@@ -781,10 +817,12 @@ int span_batch_run(rh_ctx* c, const char* const* seqs, const int* n, int count, 
     if ((rc = ensure(c, c->d_sb_bp, sizeof(double) * B.band, false))) return rc;
     if ((rc = ensure(c, c->d_sb_up, sizeof(double) * B.up, false))) return rc;
     if ((rc = ensure(c, c->d_sb_logz, sizeof(double) * (size_t)count, false))) return rc;
+    if (records && (rc = ensure(c, c->d_span_cons, sizeof(ConsRec) * records, false))) return rc;
     std::vector<int> status((size_t)count, RH_OK), part;
     SpanTimes T;
     for (const SpanChunk& C : B.chunks) {
         std::vector<uint8_t> codes(C.letters, 0);
+        std::vector<ConsRec> crec;   // the chunk's records, as many as letter codes, where an item of the chunk has some
         std::vector<SpanArgs> args((size_t)C.count);
         size_t tab_at = 0, gaps_at = 0, ext_at = 0, seq_at = 0;
         double* hplen = c->d_span_ext.as<double>() + C.ext;   // behind the chunk's gi and go
@@ -800,9 +838,16 @@ int span_batch_run(rh_ctx* c, const char* const* seqs, const int* n, int count, 
             A.gi = c->d_span_ext.as<double>() + ext_at; A.go = A.gi + (I.P.n + 1); A.hplen = hplen;
             A.band = c->d_sb_bp.as<double>() + I.band_at; A.up = c->d_sb_up.as<double>() + I.up_at; A.logz = c->d_sb_logz.as<double>() + k;
             A.gaps = I.Q.gaps ? c->d_span_gaps.as<double>() + gaps_at : nullptr; A.max_w = max_w;
+            const std::vector<ConsRec>& R = recs[(size_t)k];
+            if (!R.empty()) {   // (n + 2 records behind seq_at, inside the C.letters the chunk's codes take)
+                if (crec.empty()) crec.assign(C.letters, ConsRec{0, 0});
+                std::copy(R.begin(), R.end(), crec.begin() + (ptrdiff_t)seq_at);
+                A.cons = c->d_span_cons.as<const ConsRec>() + seq_at;
+            }
             tab_at += I.P.tables; gaps_at += I.Q.gaps; ext_at += I.P.ext; seq_at += ((size_t)I.P.n + 2 + 15) & ~(size_t)15;
         }
         HIP_TRY(c, hipMemcpyAsync(c->d_span_seq.p, codes.data(), C.letters, hipMemcpyHostToDevice, c->s_mc));
+        if (!crec.empty()) HIP_TRY(c, hipMemcpyAsync(c->d_span_cons.p, crec.data(), sizeof(ConsRec) * crec.size(), hipMemcpyHostToDevice, c->s_mc));
         if ((rc = span_ladder(c, args, c->d_span_bad.as<int>(), &part, &T, true))) return rc;   // (synchronised: the next chunk reuses the scratch)
         for (int j = 0; j < C.count; j++) status[(size_t)(C.first + j)] = part[(size_t)j];
     }
@@ -829,9 +874,14 @@ int span_batch_ready(rh_ctx* c, int item, const char* who, bool served)
 
 extern "C" {
 
-int rh_span_fold(rh_ctx* c, const char* seq, int n, int max_span) { return span_run(c, seq, n, max_span, 1); }
+int rh_span_fold(rh_ctx* c, const char* seq, int n, int max_span) { return span_run(c, seq, n, nullptr, max_span, 1); }
 
-int rh_span_fold_acc(rh_ctx* c, const char* seq, int n, int max_span, int max_w) { return span_run(c, seq, n, max_span, max_w); }
+int rh_span_fold_acc(rh_ctx* c, const char* seq, int n, int max_span, int max_w) { return span_run(c, seq, n, nullptr, max_span, max_w); }
+
+int rh_span_fold_constrained(rh_ctx* c, const char* seq, int n, const char* constraint, int max_span, int max_w)
+{
+    return span_run(c, seq, n, constraint, max_span, max_w);
+}
 
 int rh_span_acc_times(rh_ctx* c, double ms[3])
 {
@@ -851,7 +901,12 @@ int rh_span_times(rh_ctx* c, double ms[2])
 
 int rh_span_fold_batch(rh_ctx* c, const char* const* seqs, const int* n, int count, int max_span, int max_w)
 {
-    return span_batch_run(c, seqs, n, count, max_span, max_w);
+    return span_batch_run(c, seqs, n, count, nullptr, max_span, max_w);
+}
+
+int rh_span_fold_batch_constrained(rh_ctx* c, const char* const* seqs, const int* n, int count, const char* const* constraints, int max_span, int max_w)
+{
+    return span_batch_run(c, seqs, n, count, constraints, max_span, max_w);
 }
 
 int rh_span_batch_layout(rh_ctx* c, int* count, int* max_span, int* max_w)

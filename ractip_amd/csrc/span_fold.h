@@ -31,6 +31,8 @@
 #include <string>
 #include <vector>
 
+#include "constraint_prepass.h"
+
 #if defined(__HIPCC__)
 #define RH_SF_HD __host__ __device__ inline
 #else
@@ -104,6 +106,21 @@ struct SpanBatchPlan {
 
 // RH_OK with *B filled, or RH_ERR_ARG with the reason in *why (an item's reason names the item).  budget = 0: kSpanBatchBytes.
 int span_batch_plan(const char* const* seqs, const int* n, int count, int max_span, int max_w, size_t budget, SpanBatchPlan* B, std::string* why);
+
+// ---- structure constraints (rh_span_fold_constrained, rh_span_fold_batch_constrained): letters a < b may pair only if b - a < L AND
+// allow_pair(a, b, n, ch, P, enc) of constraint_prepass.h holds.  There is no n x n mask: the sweeps test a pair on the packed records
+// of its two letters (ConsRec, allow_pair_rec).  Both functions are in span_cons.cpp, which needs constraint_prepass.cpp.
+//
+// One item's constraint: the pre-pass, the forced pairs against L, the records.  RH_OK with rec holding n + 2 records (letters
+// 0 .. n+1; those of 0 and n+1 restrict nothing) and *restricts saying whether any pair of the band is excluded at all -- a NULL
+// constraint, or one of '.' and '|' only, restricts nothing and the caller runs the unconstrained kernels' path on it.
+// RH_ERR_ARG with the reason in *why: the pre-pass's own (unbalanced brackets, a bracket pair of non-complementary letters), a
+// matched bracket pair (a, b) with b - a >= L, a sequence of 2^30 letters or more.  seq, n and max_span have passed span_check.
+int span_cons_records(const char* seq, int n, const char* cons, int max_span, std::vector<ConsRec>* rec, bool* restricts, std::string* why);
+
+// The constraints of a batch over a plan that span_batch_plan accepted: recs[k] as above for item k, left empty where the item's
+// constraint restricts nothing (cons or cons[k] NULL included).  An item's reason names the item.
+int span_cons_batch(const char* const* seqs, const int* n, int count, const char* const* cons, int max_span, std::vector<std::vector<ConsRec>>* recs, std::string* why);
 
 // ---- the exterior passes: what the kernel and the CPU check share.  dir 0: gi, entries ascending from 1; dir 1: go, entries
 // descending from n-1.  Block b holds the entries span_ext_entry(dir, n, b, l), l = 0..63 (those inside 0..n).

@@ -33,6 +33,7 @@ EXPORTS = [
     "rh_span_fold", "rh_span_times", "rh_span_fold_acc", "rh_span_acc_times",
     "rh_span_fold_batch", "rh_span_batch_layout", "rh_span_batch_item", "rh_span_batch_results", "rh_span_batch_candidates",
     "rh_set_span_batch_bytes", "rh_span_batch_times",
+    "rh_span_fold_constrained", "rh_span_fold_batch_constrained",
     "rh_debug_vienna_cell", "rh_debug_vienna_value",   # loader inspection (host only; used by the CPU tests of the loader)
 ]
 
@@ -171,6 +172,10 @@ def load_library():
     L.rh_set_span_batch_bytes.restype = ci
     L.rh_span_batch_times.argtypes = [vp, vp]
     L.rh_span_batch_times.restype = ci
+    L.rh_span_fold_constrained.argtypes = [vp, cp, ci, cp, ci, ci]
+    L.rh_span_fold_constrained.restype = ci
+    L.rh_span_fold_batch_constrained.argtypes = [vp, vp, vp, ci, vp, ci, ci]
+    L.rh_span_fold_batch_constrained.restype = ci
     L.rh_local_duplex.argtypes = [vp, cp, ci, cp, ci, ci, ci, ci]
     L.rh_local_duplex.restype = ci
     L.rh_local_hp_layout.argtypes = [vp, vp, vp, vp, vp]
@@ -442,13 +447,18 @@ class Context:
         return ms[0], ms[1]
 
     # ---- span-limited folding
-    def span_fold(self, seq, max_span, max_w=1):
+    def span_fold(self, seq, max_span, max_w=1, constraint=None):
         """The McCaskill ensemble of the whole sequence restricted to pairs (a, b) with b - a < max_span (rh_span_fold_acc; Vienna-BL
         contexts, 1.8 semantics): one partition function, O(n L) memory.  Returns (bp_band, up, logz): bp_band (n, ld) with
         bp_band[i, d] = P(i, i + d), 0-based, ld = min(max_span, n); up (n, max_w) with up[i, w] = P(letters i .. i + w unpaired),
         0-based, 0 where the run passes the end (max_w in 1..64; the context's own max_w is not used); log Z of the whole sequence.
-        The result is the context's local result (local_results, local_candidates); band_to_tri gives the triangular layout."""
-        self._check(self.L.rh_span_fold_acc(self.h, seq.encode(), len(seq), max_span, max_w))
+        The result is the context's local result (local_results, local_candidates); band_to_tri gives the triangular layout.
+        constraint: a string in the fold_constrained alphabet of bpp, which restricts the pairs further (rh_span_fold_constrained);
+        a matched bracket pair must lie within max_span."""
+        if constraint is not None:
+            self._check(self.L.rh_span_fold_constrained(self.h, seq.encode(), len(seq), constraint.encode(), max_span, max_w))
+        else:
+            self._check(self.L.rh_span_fold_acc(self.h, seq.encode(), len(seq), max_span, max_w))
         band, up, logz, _ = self.local_results()
         return band, up, float(logz[0])
 
@@ -464,15 +474,23 @@ class Context:
         self._check(self.L.rh_span_acc_times(self.h, ms))
         return ms[0], ms[1], ms[2]
 
-    def span_fold_batch(self, seqs, max_span, max_w=1):
+    def span_fold_batch(self, seqs, max_span, max_w=1, constraints=None):
         """span_fold of every sequence of `seqs` (ragged lengths) through one set of launches (rh_span_fold_batch): a list of
         (bp_band, up, logz), item k with the bits of span_fold(seqs[k], max_span, max_w) on this context.  The result lives beside the
         local result until the next span_fold_batch (span_batch_results, span_batch_candidates).  Raises for an item for which no
-        scale exponent of the ladder holds, and names it."""
+        scale exponent of the ladder holds, and names it.
+        constraints: one string or None per sequence (rh_span_fold_batch_constrained); item k then has the bits of
+        span_fold(seqs[k], max_span, max_w, constraints[k])."""
         enc = [s.encode() for s in seqs]
         arr = (ctypes.c_char_p * max(len(enc), 1))(*enc)
         lens = (ctypes.c_int * max(len(enc), 1))(*[len(s) for s in seqs])
-        self._check(self.L.rh_span_fold_batch(self.h, arr, lens, len(enc), max_span, max_w))
+        if constraints is not None:
+            if len(constraints) != len(enc):
+                raise RhError("%d constraints for %d sequences" % (len(constraints), len(enc)))
+            cons = (ctypes.c_char_p * max(len(enc), 1))(*[None if x is None else x.encode() for x in constraints])
+            self._check(self.L.rh_span_fold_batch_constrained(self.h, arr, lens, len(enc), cons, max_span, max_w))
+        else:
+            self._check(self.L.rh_span_fold_batch(self.h, arr, lens, len(enc), max_span, max_w))
         return [self.span_batch_results(k) for k in range(len(enc))]
 
     def span_batch_results(self, item):

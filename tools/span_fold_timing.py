@@ -1,14 +1,16 @@
 """Timing of span-limited folding (Context.span_fold) on the GPU, next to the window route for the same sequence on the same
 context: local_fold(W = L, S = 1), which folds n - W + 1 windows of W letters where the span fold fills one band of n x L cells.
 
-  python tools/span_fold_timing.py [--out FILE.json] [--n 5000,20000,100000] [--span 200] [--repeat 5] [--no-windows] [--max-w W]
+  python tools/span_fold_timing.py [--out FILE.json] [--n 5000,20000,100000] [--span 200] [--repeat 5] [--no-windows] [--max-w W] [--constraint]
 
 Per n, the median and the range of --repeat runs behind one warm-up run (which allocates): wall time of rh_span_fold alone and of
 the fetch of band, up and log Z; device time of the sweeps and of the exterior passes + finish (rh_span_times); the launches of the
 sweeps (2 Le) and the device time per launch that gives; the same for local_fold (wall with its fetch, rh_local_times).
 --max-w W (default 1): the span fold with region accessibilities up[i][w] of W widths (rh_span_fold_acc); for W > 1 also the device
 time of the three parts of the accessibility stage (rh_span_acc_times: hairpin part, gap sums, final kernel), and local_fold runs
-on the same context at max_w = W, the route to wide accessibilities that the stage replaces."""
+on the same context at max_w = W, the route to wide accessibilities that the stage replaces.
+--constraint: also the same sequence under a structure constraint of scattered helices and x runs (rh_span_fold_constrained,
+scattered_constraint below): its wall and device times next to the unconstrained ones, and the ratio of the sweeps."""
 import argparse
 import json
 import os
@@ -30,6 +32,28 @@ def spread(values):
     return [v[len(v) // 2], v[0], v[-1]]
 
 
+PAIRS = {"GC", "CG", "AU", "UA", "GU", "UG"}
+
+
+def scattered_constraint(seq, L, every=300):
+    """a constraint over seq as it is: every `every` letters a helix -- the first (a, b) from there with 10 <= b - a <= min(40, L - 1)
+    whose letters are complementary, grown inwards while they stay so, six brackets at the most -- and, half a period on, eight 'x'"""
+    n, c = len(seq), ["."] * len(seq)
+    for at in range(20, n - 60, every):
+        found = next(((a, a + d) for a in range(at, at + 10) for d in range(min(40, L - 1), 9, -1) if seq[a] + seq[a + d] in PAIRS), None)
+        if found:
+            a, b = found
+            for k in range(6):
+                if b - a < 5 or seq[a] + seq[b] not in PAIRS:
+                    break
+                c[a], c[b] = "(", ")"
+                a, b = a + 1, b - 1
+        x = at + every // 2
+        if x + 8 < n:
+            c[x:x + 8] = "x" * 8
+    return "".join(c)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -38,6 +62,7 @@ def main():
     ap.add_argument("--repeat", type=int, default=5)
     ap.add_argument("--no-windows", action="store_true")
     ap.add_argument("--max-w", type=int, default=1)
+    ap.add_argument("--constraint", action="store_true")
     args = ap.parse_args()
     L, W = args.span, args.max_w
     rows = []
@@ -63,6 +88,20 @@ def main():
             hp_ms, gap_ms, final_ms = (spread(col) for col in list(zip(*runs[1:]))[4:])
             row.update(acc_hairpin_ms=hp_ms, acc_gaps_ms=gap_ms, acc_final_ms=final_ms,
                        acc_over_sweeps=(hp_ms[0] + gap_ms[0] + final_ms[0]) / sweep_ms[0])
+        if args.constraint:
+            cons = scattered_constraint(seq, L)
+            cenc, runs = cons.encode(), []
+            for _ in range(1 + args.repeat):
+                t0 = time.perf_counter()
+                c._check(c.L.rh_span_fold_constrained(c.h, enc, n, cenc, L, W))
+                t1 = time.perf_counter()
+                _, _, clogz, _ = c.local_results()
+                runs.append((1e3 * (t1 - t0),) + c.span_times() + (c.span_acc_times() if W > 1 else ()))
+            cols = [spread(col) for col in zip(*runs[1:])]
+            row.update(cons_brackets=cons.count("("), cons_x=cons.count("x"), cons_logZ=float(clogz[0]), cons_call_ms=cols[0], cons_sweeps_ms=cols[1],
+                       cons_exterior_finish_ms=cols[2], cons_sweeps_over_plain=cols[1][0] / sweep_ms[0], cons_call_over_plain=cols[0][0] / call_ms[0])
+            if W > 1:
+                row.update(cons_acc_ms=[sum(x) for x in zip(*cols[3:6])])
         if not args.no_windows:
             runs = []
             for _ in range(1 + args.repeat):
