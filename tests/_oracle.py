@@ -24,7 +24,9 @@ def tri_offset(n, i):
 
 
 class Oracle:
-    def __init__(self):
+    """params: a CONTRAfold "name value" weight file (tests/_contrafold_weights.py writes them); None is the bundled file."""
+
+    def __init__(self, params=None):
         so = os.path.join(ORACLE_DIR, "libcf_oracle.so")
         src = os.path.join(ORACLE_DIR, "cf_oracle.c")
         if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
@@ -43,8 +45,9 @@ class Oracle:
         L.cfo_count_loads.restype = ctypes.c_ulonglong
         L.cfo_count_stores.restype = ctypes.c_ulonglong
         self.L = L
-        self.m = L.cfo_load_params(PARAMS.encode())
-        assert self.m, "oracle could not load " + PARAMS
+        self.params = params or PARAMS
+        self.m = L.cfo_load_params(self.params.encode())
+        assert self.m, "oracle could not load " + self.params
 
     def inference(self, seq, tables=False):
         n = len(seq)
@@ -347,10 +350,10 @@ class OraclePool:
     Every method returns a Future, keyed by its inputs (a sequence, or a pair for the two-sequence calls): asking twice costs one
     call, and asking early lets the oracle run while the GPU computes.  Only unconstrained Vienna calls go to the threads:
     vienna_oracle.c keeps the allowed-pair mask in one global (vo_allow_mask).  params: the table file of the Vienna calls (None: BL*);
-    a pool has one, so its keys need not name it."""
+    a pool has one, so its keys need not name it.  cf_params: the weight file of the CONTRAfold calls (None: the bundled one)."""
 
-    def __init__(self, workers=ORACLE_WORKERS, params=None):
-        self.cf = Oracle()
+    def __init__(self, workers=ORACLE_WORKERS, params=None, cf_params=None):
+        self.cf = Oracle(cf_params)
         self.vo = ViennaOracle(params)
         self.pool = ThreadPoolExecutor(max_workers=min(workers, ORACLE_WORKERS))
         self.cache = {}
