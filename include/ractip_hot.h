@@ -426,8 +426,20 @@ int rh_local_times(rh_ctx* ctx, double ms[2]);
  * A band cell that leaves the double range under the context's scale exponent sends the call through the exponent ladder; when no
  * exponent holds it returns RH_ERR_UNSUPPORTED and leaves no local result, as RH_ERR_OOM does (buffers grow only and go with the
  * context).
- * Not covered yet: the CONTRAfold model. */
+ * The CONTRAfold model: rh_set_span_contrafold below; a CONTRAfold context that did not ask is refused. */
 int rh_span_fold(rh_ctx* ctx, const char* seq, int n, int max_span);
+/* Span folds under the CONTRAfold model, opt-in per context (default off: a CONTRAfold context refuses every span call as above).  On
+ * a RH_MODEL_VIENNA_BL context the call is accepted and changes nothing.  On, for a RH_MODEL_CONTRAFOLD context, rh_span_fold,
+ * rh_span_fold_acc and rh_span_fold_batch with max_w == 1 and their constrained forms with a NULL constraint (every entry NULL for a
+ * batch) compute the span-limited ensemble under the context's CONTRAfold weights: the ensemble of rh_fold on that context (the
+ * derivations the inside recurrences of InferenceEngine.ipp count) restricted to the derivations in which letters a < b pair only if
+ * they are complementary and b - a < L; with L >= n it is the ensemble of rh_fold.  Unknown letters are encoded as in the batch path.
+ * bp_band, up (width 1, max(0, 1 - sum_j bp(i, j))) and log Z come back through the same fetches, batches and candidates included.
+ * The exponent ladder is the CONTRAfold one (0.12 per unit span, then 0.45, 1.5, 0); the context's batch, rh_fold's bits and the batch
+ * path's state are untouched.  Still RH_ERR_UNSUPPORTED with the switch on, each leaving the previous result in place: max_w > 1, a
+ * constraint that is not NULL (the model takes none), a context in RH_MODE_LOG. */
+int rh_set_span_contrafold(rh_ctx* ctx, int on);
+int rh_get_span_contrafold(const rh_ctx* ctx);
 /* Measurement aid: device time (ms, HIP event pairs) of the last rh_span_fold: ms[0] the inside and outside sweeps (2 Le launches),
  * ms[1] the two exterior passes and the finish kernel. */
 int rh_span_times(rh_ctx* ctx, double ms[2]);

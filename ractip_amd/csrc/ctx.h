@@ -385,6 +385,7 @@ struct Ctx {   // (the fields of rh_ctx, below)
     DevBuf d_span_tab, d_span_ext, d_span_seq, d_span_bad;
     double span_ms[2] = {0, 0};
     bool span_timed = false;       // a span fold has run on this context
+    int span_cf = 0;               // rh_set_span_contrafold: a CONTRAfold context answers the span calls (mccaskill_span_cf.hip) instead of refusing them
     // rh_span_fold_acc at max_w > 1: the gap sums GL, GR [2][kSpanGapRows][ldn] (grow-only) and the device times of the last
     // accessibility stage: the hairpin part, the gap sums, the final kernel
     DevBuf d_span_gaps;
@@ -502,6 +503,8 @@ int launch_dx_lin(rh_ctx* c, const DxLinArgs& A);
 int launch_dx_vlin(rh_ctx* c, const DxLinArgs& A);
 int launch_dx_vlog(rh_ctx* c);
 // fallbacks.hip
+int ensure_rungs(rh_ctx* c);   // builds lin_r, the CONTRAfold models at the exponents kRungS, on first use
+extern const double kRungS[Ctx::kRungs];
 int retry_mc_lin_rungs(rh_ctx* c, int first_model, std::vector<int>* rest, int (&rescued_by)[Ctx::kRungs + 1]);
 int recompute_mc_subset_log(rh_ctx* c, const std::vector<int>& F);
 int retry_dx_lin_rungs(rh_ctx* c, std::vector<int>* rest);

@@ -128,7 +128,7 @@ int recompute_mc_subset_log(rh_ctx* c, const std::vector<int>& F)
 // goes to the log-space kernels (3x slower).  An exponent costs dynamic range only, never accuracy: a cell that underflows to 0
 // while Z~ stays inside (1e-200, 1e200) is below 1e-100 of the terms that make up Z.  Flagged sequences are compacted into a
 // sub-batch that reuses the (dead) tables of the main pass; results are scattered back into their slots.
-constexpr double kRungS[rh_ctx::kRungs] = {0.45, 1.5, 0.0};
+const double kRungS[rh_ctx::kRungs] = {0.45, 1.5, 0.0};
 
 int ensure_rungs(rh_ctx* c)
 {

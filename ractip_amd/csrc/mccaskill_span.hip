@@ -13,6 +13,8 @@
 // rh_span_fold_constrained / rh_span_fold_batch_constrained restrict the pairs further by a structure constraint: an item's descriptor
 // points to the packed per-letter records of its constraint (ConsRec, constraint_prepass.h), and the two sweeps -- the only kernels
 // that decide whether a pair exists -- test a pair on the records of its two letters.
+// rh_set_span_contrafold turns the same calls on for a CONTRAfold context: the launcher runs the sweeps of mccaskill_span_cf.hip between
+// the exterior passes and the finish of this file, over the context's own exponent ladder (lin0, then kRungS).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -22,6 +24,7 @@
 #include "ctx.h"
 #include "constraint_prepass.h"
 #include "dev_util.h"
+#include "span_kernels.h"
 #include "vienna_model.h"
 
 using namespace rh;
@@ -29,52 +32,10 @@ using namespace rh::host;
 
 namespace {
 
-constexpr int kSpanThreads = 256;
-constexpr double kSpanHuge = 1e280, kSpanTiny = 1e-280;   // a band cell outside them raises the flag
 enum SpanTable { SP_FC = 0, SP_FCX, SP_FCB, SP_FCA, SP_FM1, SP_FMS, SP_FM, SP_FCO, SP_FCOX, SP_FCOB, SP_FMSO, SP_FM1O, SP_FM2O, SP_COUNT };
-static_assert(SP_COUNT == kSpanInside + kSpanOutside);
+static_assert(SP_COUNT == kSpanTables && SP_FCA == kSpanExtTable);
 
-struct SpanArgs {
-    double* tab;           // SP_COUNT band tables of ts doubles, [d * ldn + i]
-    size_t ldn, ts;
-    const uint8_t* s;      // letters 1..n, code 0 at 0 and n+1
-    int n, Le, L;
-    int max_w;             // widths of up: [n][max_w]
-    const double* hplen;   // hairpin length weight x lam^d, d < Le
-    double* gi;            // log F5i [n+1]
-    double* go;            // log F5o [n+1]
-    double* band;          // bp_band [n][Le]
-    double* up;            // [n][max_w]
-    double* logz;          // [1]
-    int* bad;
-    double sc;             // the scale exponent s of the model
-    double* gaps;          // GL, GR [2][kSpanGapRows][ldn] (max_w > 1)
-    const ConsRec* cons;   // the constraint's records of letters 0..n+1; null: the item has no constraint
-};
-static_assert(sizeof(SpanArgs) == 128);   // two scalar loads of 16 dwords
-
-// Every kernel runs a batch of items, a single call a batch of one: the launch hands over a device array with one SpanArgs per item
-// and the item is a grid dimension (y, or z where the kernel's own grid has two), so a workgroup belongs to ONE item.  The grid spans
-// the widest item of the launch; a workgroup with nothing to do for its item leaves before its first load or store besides this
-// one.  The address is uniform over the workgroup and the load is the kernel's first access: the descriptor arrives by scalar loads
-// and stays in scalar registers.
-// A pointer that comes out of memory could point anywhere as far as the compiler knows, and every access through it would be a flat
-// one (which also waits on the LDS counter); all of these point to device memory, and saying so makes the accesses global ones.
-template <class T> __device__ __forceinline__ T* span_global(T* p)
-{
-    typedef __attribute__((address_space(1))) T* G;
-    return (T*)(G)(uintptr_t)p;   // (through the integer: a pointer cast there and back would fold away)
-}
-__device__ __forceinline__ SpanArgs span_item(const SpanArgs* __restrict__ items, unsigned item)
-{
-    SpanArgs A = items[item];
-    A.tab = span_global(A.tab); A.s = span_global(A.s); A.hplen = span_global(A.hplen);
-    A.gi = span_global(A.gi); A.go = span_global(A.go);
-    A.band = span_global(A.band); A.up = span_global(A.up); A.logz = span_global(A.logz);
-    A.bad = span_global(A.bad); A.gaps = span_global(A.gaps);
-    if (A.cons) A.cons = span_global(A.cons);
-    return A;
-}
+// (SpanArgs, the per-item descriptor of every kernel, and span_item, which fetches it: span_kernels.h)
 
 // The pair type of cell (i, d), the pair of letters (i, j1 = i + d + 1): 0 where the span limit or the item's constraint excludes the
 // pair.  Every other kernel reaches a pair through an FC / FCo^ cell, which is 0 where the type is: the tabulated shapes skip v == 0
@@ -607,7 +568,9 @@ struct SpanTimes {
 // and hairpin weights.  One launch per diagonal below the largest Le, over the widest ldn; the exterior passes have a workgroup per
 // item.  The items share one hplen (it depends on the exponent only and item k reads the rows below its own Le); item k of `run`
 // gets the flag bad[k], and (*flags)[k] is that flag behind everything that ran for it.  `sum`: the times are added to *T.
-int span_attempt(rh_ctx* c, std::vector<SpanArgs>& run, int* bad, const SpanEvents& ev, std::vector<int>* flags, SpanTimes* T, bool sum)
+// A CONTRAfold context (`cf`: the model of this attempt, lin0 or a rung) runs the sweeps of mccaskill_span_cf.hip between the same
+// exterior passes and finish, and has no accessibility stage.
+int span_attempt(rh_ctx* c, const LinSet* cf, std::vector<SpanArgs>& run, int* bad, const SpanEvents& ev, std::vector<int>* flags, SpanTimes* T, bool sum)
 {
     const VLinModel* M = c->d_vlin;
     hipStream_t st = c->s_mc;
@@ -620,11 +583,15 @@ int span_attempt(rh_ctx* c, std::vector<SpanArgs>& run, int* bad, const SpanEven
         SpanArgs& A = run[k];
         Le = std::max(Le, A.Le); n = std::max(n, A.n); ldn = std::max(ldn, A.ldn);
         cons = cons || A.cons != nullptr;
-        A.sc = c->h_vlin->s;
+        A.sc = cf ? cf->h.s : c->h_vlin->s;
         A.bad = bad + k;
     }
     std::vector<double> hplen((size_t)Le);
-    hairpin_length_weights(*c->h_vlin, Le, hplen.data());
+    if (cf) for (int d = 0; d < Le; d++) hplen[(size_t)d] = cf->h.E_hairpin[d < 30 ? d : 30] * std::exp(-cf->h.s * (double)d);
+    else hairpin_length_weights(*c->h_vlin, Le, hplen.data());
+    // CONTRAfold: the exterior's factor of row d, exp(external_paired - external_unpaired (d + 2)) (span_fold.h)
+    const double eu = cf ? c->h_score->external_unpaired : 0.0, ep = cf ? c->h_score->external_paired : 0.0;
+    const auto ext_w = [&](int d) { return std::exp(ep - eu * (double)(d + 2)); };
     int rc;
     if ((rc = ensure(c, c->d_span_desc, sizeof(SpanArgs) * K, false))) return rc;
     const SpanArgs* items = c->d_span_desc.as<const SpanArgs>();
@@ -635,17 +602,20 @@ int span_attempt(rh_ctx* c, std::vector<SpanArgs>& run, int* bad, const SpanEven
     HIP_TRY(c, hipEventRecord(ev.e[0], st));
     const auto inside = cons ? span_inside_diag<true> : span_inside_diag<false>;
     const auto outside = cons ? span_outside_diag<true> : span_outside_diag<false>;
-    for (int d = 0; d < Le; d++) hipLaunchKernelGGL(inside, grid, block, 0, st, items, M, d);
+    if (cf) for (int d = 0; d < Le; d++) hipLaunchKernelGGL(span_cf_inside_diag, grid, block, 0, st, items, cf->d.as<const LinModel>(), d, ext_w(d));
+    else for (int d = 0; d < Le; d++) hipLaunchKernelGGL(inside, grid, block, 0, st, items, M, d);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(ev.e[1], st));
     hipLaunchKernelGGL(span_ext_pass, dim3(1, K), dim3(kSpanBlock * kSpanWaves), 0, st, items, 0);
     hipLaunchKernelGGL(span_ext_pass, dim3(1, K), dim3(kSpanBlock * kSpanWaves), 0, st, items, 1);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(ev.e[2], st));
-    for (int d = Le - 1; d >= 0; d--) hipLaunchKernelGGL(outside, grid, block, 0, st, items, M, d);
+    if (cf) for (int d = Le - 1; d >= 0; d--) hipLaunchKernelGGL(span_cf_outside_diag, grid, block, 0, st, items, cf->d.as<const LinModel>(), d, ext_w(d));
+    else for (int d = Le - 1; d >= 0; d--) hipLaunchKernelGGL(outside, grid, block, 0, st, items, M, d);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(ev.e[3], st));
     hipLaunchKernelGGL(span_finish, dim3((unsigned)n, K), dim3(kSpanBlock), 0, st, items);
+    if (cf) hipLaunchKernelGGL(span_cf_logz, dim3((K + 63) / 64), dim3(64), 0, st, items, (int)K, eu);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(ev.e[4], st));
     flags->assign(K, 1);
@@ -655,7 +625,7 @@ int span_attempt(rh_ctx* c, std::vector<SpanArgs>& run, int* bad, const SpanEven
     for (int k = 0; k < 4; k++) HIP_TRY(c, hipEventElapsedTime(&t[k], ev.e[k], ev.e[k + 1]));
     T->sweeps = (sum ? T->sweeps : 0.0) + (double)t[0] + t[2];
     T->ext = (sum ? T->ext : 0.0) + (double)t[1] + t[3];
-    if (max_w == 1) return RH_OK;
+    if (max_w == 1 || cf) return RH_OK;
     // the accessibility stage for the unflagged items: the hairpin part, the gap sums, the final kernel
     std::vector<SpanArgs> acc;
     for (unsigned k = 0; k < K; k++) if (!(*flags)[k]) acc.push_back(run[k]);
@@ -691,25 +661,31 @@ int span_attempt(rh_ctx* c, std::vector<SpanArgs>& run, int* bad, const SpanEven
 // while a band cell of an item leaves the double range.  The flagged items of an attempt are the next attempt's items, on their own
 // tables, so every item ends on the exponent its single call ends on.  (*status)[k]: RH_OK, or RH_ERR_UNSUPPORTED where no exponent
 // holds for item k.
+// A CONTRAfold context starts on lin0 (s = 0.12) whatever the batch path remembers (lin_primary: a span fold's bits depend on its
+// letters only) and goes on over kRungS; the rung models are the batch path's, built on first use, and nothing is selected.
 int span_ladder(rh_ctx* c, const std::vector<SpanArgs>& items, int* bad, std::vector<int>* status, SpanTimes* T, bool sum)
 {
     SpanEvents ev;
     HIP_TRY(c, ev.create());
-    std::vector<int> order = {c->vlin_primary};
-    for (int model : exponent_order(c->vlin_primary, c->vlin_m[0].h->s, kVRungS, rh_ctx::kVRungs)) order.push_back(model);
+    const bool cf = c->model == RH_MODEL_CONTRAFOLD;
+    const int first = cf ? -1 : c->vlin_primary;
+    std::vector<int> order = {first};
+    for (int model : cf ? exponent_order(first, c->lin0.h.s, kRungS, rh_ctx::kRungs) : exponent_order(first, c->vlin_m[0].h->s, kVRungS, rh_ctx::kVRungs))
+        order.push_back(model);
     std::vector<int> left(items.size()), flags;
     for (size_t k = 0; k < left.size(); k++) left[k] = (int)k;
     int rc = RH_OK;
     for (size_t a = 0; a < order.size() && !left.empty(); a++) {
-        if ((rc = select_vlin(c, order[a]))) break;
+        if ((rc = cf ? (order[a] >= 0 ? ensure_rungs(c) : RH_OK) : select_vlin(c, order[a]))) break;
+        const LinSet* lin = !cf ? nullptr : order[a] < 0 ? &c->lin0 : &c->lin_r[order[a]];
         std::vector<SpanArgs> run;
         for (int k : left) run.push_back(items[(size_t)k]);
-        if ((rc = span_attempt(c, run, bad, ev, &flags, T, sum))) break;
+        if ((rc = span_attempt(c, lin, run, bad, ev, &flags, T, sum))) break;
         std::vector<int> next;
         for (size_t k = 0; k < left.size(); k++) if (flags[k]) next.push_back(left[k]);
         left.swap(next);
     }
-    const int back = select_vlin(c, c->vlin_primary);
+    const int back = cf ? RH_OK : select_vlin(c, c->vlin_primary);
     if (rc) return rc;
     if (back) return back;
     status->assign(items.size(), RH_OK);
@@ -717,19 +693,31 @@ int span_ladder(rh_ctx* c, const std::vector<SpanArgs>& items, int* bad, std::ve
     return RH_OK;
 }
 
-int span_refusals(rh_ctx* c)
+// has_cons: the call came with a constraint (an entry of a batch's is not NULL)
+int span_refusals(rh_ctx* c, int max_w, bool has_cons)
 {
+    if (c->model == RH_MODEL_CONTRAFOLD && c->span_cf) {   // rh_set_span_contrafold: what the CONTRAfold sweeps do not cover
+        if (c->mode == RH_MODE_LOG) return fail(c, RH_ERR_UNSUPPORTED, "span fold: there is no log-space version (the context is in RH_MODE_LOG)");
+        if (max_w > 1)
+            return fail(c, RH_ERR_UNSUPPORTED, "span fold: the CONTRAfold model has no span region accessibility yet (max_w %d: width 1 only)", max_w);
+        if (has_cons) return fail(c, RH_ERR_UNSUPPORTED, "span fold: the CONTRAfold model takes no structure constraint (pass NULL)");
+        return RH_OK;
+    }
     if (c->model != RH_MODEL_VIENNA_BL) return fail(c, RH_ERR_UNSUPPORTED, "span fold: the CONTRAfold model has no span-limited kernels (Vienna-BL contexts only)");
     if (c->vienna_sem == kViennaSem20) return fail(c, RH_ERR_UNSUPPORTED, "span fold: ViennaRNA-2.x semantics have no span-limited kernels (1.8 semantics only)");
     if (c->mode == RH_MODE_LOG) return fail(c, RH_ERR_UNSUPPORTED, "span fold: there is no log-space version (the context is in RH_MODE_LOG)");
     return RH_OK;
 }
 
-// the letter codes of one item: code 0 at 0 and behind the last letter
-void span_codes(const char* seq, int n, uint8_t* codes)
+// the letter codes of one item as the model's batch path encodes them; the model's "no nucleotide" code (span_no_letter) stays at 0
+// and behind the last letter
+void span_codes(const rh_ctx* c, const char* seq, int n, uint8_t* codes)
 {
-    for (int i = 0; i < n; i++) codes[(size_t)i + 1] = vienna_code(seq[i]);
+    const bool cf = c->model == RH_MODEL_CONTRAFOLD;
+    for (int i = 0; i < n; i++) codes[(size_t)i + 1] = cf ? nuc_code(seq[i]) : vienna_code(seq[i]);
 }
+uint8_t span_no_letter(const rh_ctx* c) { return c->model == RH_MODEL_CONTRAFOLD ? 4 : 0; }
+int span_tables(const rh_ctx* c) { return c->model == RH_MODEL_CONTRAFOLD ? kSpanCfTables : kSpanTables; }
 
 // rh_span_fold (max_w = 1), rh_span_fold_acc and rh_span_fold_constrained (cons, which may be NULL): a batch of one whose result is
 // the context's local result
@@ -741,10 +729,10 @@ int span_run(rh_ctx* c, const char* seq, int n, const char* cons, int max_span, 
     std::string why;
     std::vector<ConsRec> rec;   // empty: nothing restricts the band
     bool restricts = false;
-    if (int rc = span_check(seq, n, max_span, &P, &why)) return fail(c, rc, "%s", why.c_str());
+    if (int rc = span_check(seq, n, max_span, &P, &why, span_tables(c))) return fail(c, rc, "%s", why.c_str());
     if (int rc = span_acc_check(P, max_w, &Q, &why)) return fail(c, rc, "%s", why.c_str());
     if (int rc = span_cons_records(seq, n, cons, max_span, &rec, &restricts, &why)) return fail(c, rc, "%s", why.c_str());
-    if (int rc = span_refusals(c)) return rc;
+    if (int rc = span_refusals(c, max_w, cons != nullptr)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     c->loc_valid = c->loc_hp.valid = false;   // (the hp result of rh_local_duplex goes with the band it came with)
     int rc;
@@ -758,8 +746,8 @@ int span_run(rh_ctx* c, const char* seq, int n, const char* cons, int max_span, 
     if (Q.gaps && (rc = ensure(c, c->d_span_gaps, sizeof(double) * Q.gaps, false))) return rc;
     if ((rc = ensure(c, c->d_loc_logz, sizeof(double), false))) return rc;
     if (restricts && (rc = ensure(c, c->d_span_cons, sizeof(ConsRec) * rec.size(), false))) return rc;
-    std::vector<uint8_t> codes(seq_bytes, 0);
-    span_codes(seq, n, codes.data());
+    std::vector<uint8_t> codes(seq_bytes, span_no_letter(c));
+    span_codes(c, seq, n, codes.data());
     HIP_TRY(c, hipMemcpyAsync(c->d_span_seq.p, codes.data(), seq_bytes, hipMemcpyHostToDevice, c->s_mc));
     if (restricts) HIP_TRY(c, hipMemcpyAsync(c->d_span_cons.p, rec.data(), sizeof(ConsRec) * rec.size(), hipMemcpyHostToDevice, c->s_mc));
     SpanArgs A{};
@@ -795,9 +783,11 @@ int span_batch_run(rh_ctx* c, const char* const* seqs, const int* n, int count, 
     SpanBatchPlan B;
     std::string why;
     std::vector<std::vector<ConsRec>> recs;   // per item; empty: nothing restricts its band
-    if (int rc = span_batch_plan(seqs, n, count, max_span, max_w, c->sb_bytes, &B, &why)) return fail(c, rc, "%s", why.c_str());
+    if (int rc = span_batch_plan(seqs, n, count, max_span, max_w, c->sb_bytes, &B, &why, span_tables(c))) return fail(c, rc, "%s", why.c_str());
     if (int rc = span_cons_batch(seqs, n, count, cons, max_span, &recs, &why)) return fail(c, rc, "%s", why.c_str());
-    if (int rc = span_refusals(c)) return rc;
+    bool has_cons = false;
+    for (int k = 0; cons && k < count; k++) has_cons = has_cons || cons[k] != nullptr;
+    if (int rc = span_refusals(c, max_w, has_cons)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     c->sb_valid = false;
     size_t tables = 0, gaps = 0, ext = 0, letters = 0, records = 0;
@@ -821,7 +811,7 @@ int span_batch_run(rh_ctx* c, const char* const* seqs, const int* n, int count, 
     std::vector<int> status((size_t)count, RH_OK), part;
     SpanTimes T;
     for (const SpanChunk& C : B.chunks) {
-        std::vector<uint8_t> codes(C.letters, 0);
+        std::vector<uint8_t> codes(C.letters, span_no_letter(c));
         std::vector<ConsRec> crec;   // the chunk's records, as many as letter codes, where an item of the chunk has some
         std::vector<SpanArgs> args((size_t)C.count);
         size_t tab_at = 0, gaps_at = 0, ext_at = 0, seq_at = 0;
@@ -829,7 +819,7 @@ int span_batch_run(rh_ctx* c, const char* const* seqs, const int* n, int count, 
         for (int j = 0; j < C.count; j++) {
             const int k = C.first + j;
             const SpanBatchItem& I = B.items[(size_t)k];
-            span_codes(seqs[k], I.P.n, codes.data() + seq_at);
+            span_codes(c, seqs[k], I.P.n, codes.data() + seq_at);
             SpanArgs& A = args[(size_t)j];
             A = SpanArgs{};
             A.tab = c->d_span_tab.as<double>() + tab_at; A.ldn = I.P.ldn; A.ts = I.P.table;
@@ -873,6 +863,14 @@ int span_batch_ready(rh_ctx* c, int item, const char* who, bool served)
 }  // namespace
 
 extern "C" {
+
+int rh_set_span_contrafold(rh_ctx* c, int on)
+{
+    if (!c) return RH_ERR_ARG;
+    if (c->model == RH_MODEL_CONTRAFOLD) c->span_cf = on != 0;   // (a Vienna-BL context has its span folds anyway: accepted, changes nothing)
+    return RH_OK;
+}
+int rh_get_span_contrafold(const rh_ctx* c) { return c ? c->span_cf : RH_ERR_ARG; }
 
 int rh_span_fold(rh_ctx* c, const char* seq, int n, int max_span) { return span_run(c, seq, n, nullptr, max_span, 1); }
 

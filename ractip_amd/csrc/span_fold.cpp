@@ -17,7 +17,7 @@ static bool mul(size_t a, size_t b, size_t* out)
     return true;
 }
 
-int span_check(const char* seq, int n, int max_span, SpanPlan* P, std::string* why)
+int span_check(const char* seq, int n, int max_span, SpanPlan* P, std::string* why, int n_tables)
 {
     if (!seq) return reject(why, "span fold: the sequence is NULL");
     if (n < 1) return reject(why, "span fold: the sequence has length " + std::to_string(n) + " (must be >= 1)");
@@ -29,7 +29,7 @@ int span_check(const char* seq, int n, int max_span, SpanPlan* P, std::string* w
     S.ldn = ((size_t)n + 1 + kSpanLine - 1) / kSpanLine * kSpanLine;
     S.ext = 2 * ((size_t)n + 1);
     size_t bytes = 0;
-    const bool fits = mul((size_t)S.Le, S.ldn, &S.table) && mul(S.table, (size_t)(kSpanInside + kSpanOutside), &S.tables) && mul(S.tables, sizeof(double), &bytes) &&
+    const bool fits = mul((size_t)S.Le, S.ldn, &S.table) && mul(S.table, (size_t)n_tables, &S.tables) && mul(S.tables, sizeof(double), &bytes) &&
                       mul((size_t)n, (size_t)S.Le, &S.band) && mul(S.band, sizeof(double), &bytes);
     if (!fits) return reject(why, "span fold: the tables of " + std::to_string(n) + " letters at max_span " + std::to_string(max_span) + " overflow size_t");
     *P = S;
@@ -59,7 +59,7 @@ static bool add(size_t a, size_t b, size_t* out)
     return true;
 }
 
-int span_batch_plan(const char* const* seqs, const int* n, int count, int max_span, int max_w, size_t budget, SpanBatchPlan* B, std::string* why)
+int span_batch_plan(const char* const* seqs, const int* n, int count, int max_span, int max_w, size_t budget, SpanBatchPlan* B, std::string* why, int n_tables)
 {
     const std::string who = "span fold batch: ";
     if (count < 1) return reject(why, who + "the batch has " + std::to_string(count) + " items (must be >= 1)");
@@ -74,7 +74,7 @@ int span_batch_plan(const char* const* seqs, const int* n, int count, int max_sp
     for (int k = 0; k < count; k++) {
         SpanBatchItem& I = S.items[(size_t)k];
         std::string text;
-        int rc = span_check(seqs[k], n[k], max_span, &I.P, &text);
+        int rc = span_check(seqs[k], n[k], max_span, &I.P, &text, n_tables);
         if (!rc) rc = span_acc_check(I.P, max_w, &I.Q, &text);
         // (the single call's reason behind its "span fold: ")
         if (rc) return reject(why, who + "item " + std::to_string(k) + ": " + text.substr(text.rfind("span fold: ", 0) == 0 ? 11 : 0));

@@ -25,6 +25,17 @@
 //      terms R_m FCA inside the block (m <= l-2), which lane m holds and the butterfly of wsum (dev_util.h) adds; g = g_ref + log R_l.
 // A ratio stays below Z of 64 letters.  log Z = gi[n].  The exterior term of FCo^(i, d) is exp(gi[i-1] + go[i+d+1] - log Z + s d)
 // times the stem weight.
+//
+// The CONTRAfold model (rh_set_span_contrafold; kernels in mccaskill_span_cf.hip).  The same definition over the ensemble of rh_fold on
+// a CONTRAfold context (the derivations the inside recurrences of InferenceEngine.ipp count), a pair needing complementary letters and
+// b - a < L; unknown letters are code 4, as in the batch path.  Band tables as above with the weights of LinModel (lin_model.h):
+// FC FCX FCM FCA FM1 FM and FCO FCOX FMO FM1O FM2O, kSpanCfTables in all.  The exterior passes above take an unpaired step of
+// weight 1, CONTRAfold's carries exp(eu), eu = external_unpaired.  With F5i'[j] = F5i[j] exp(-eu j) and F5o'[k] = F5o[k] exp(-eu (n-k))
+// the factor moves into the cell: both recurrences hold for F5' over the table
+//     FCA(k+1, d) = FC x base_pair x junction_a x exp(external_paired - eu (d + 2))        (FCM, the multiloop's stem, times ext_w(d))
+// which is what the CONTRAfold inside sweep writes where the passes read (kSpanExtTable), so the passes run unchanged on gi = log F5i',
+// go = log F5o'.  log Z = gi[n] + n eu.  F5i[i-1] F5o[j+1] / Z = exp(gi[i-1] + go[j+1] - gi[n]) exp(-eu (d + 2)): the exterior term of
+// FCo^(i, d) is span_ext_outer times the same ext_w(d).
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -45,6 +56,8 @@ constexpr int kSpanBlock = 64;        // entries per block of an exterior pass =
 constexpr int kSpanWaves = 16;        // wavefronts of an exterior pass: phase A row d belongs to wavefront d % kSpanWaves
 constexpr int kSpanInside = 7;        // band tables of the inside sweep: FC FCX FCB FCA FM1 FMS FM
 constexpr int kSpanOutside = 6;       // ... of the outside sweep: FCO FCOX FCOB FMSO FM1O FM2O
+constexpr int kSpanTables = kSpanInside + kSpanOutside;   // band tables of an item under the Vienna-BL model
+constexpr int kSpanCfTables = 11;     // ... under the CONTRAfold model: FC FCX FCM FCA FM1 FM, FCO FCOX FMO FM1O FM2O
 constexpr int kSpanLine = 16;         // doubles per 128-byte line
 
 struct SpanPlan {
@@ -52,14 +65,15 @@ struct SpanPlan {
     int Le = 0;                // min(L, n): rows of the band tables, row pitch of bp_band
     size_t ldn = 0;            // row pitch of the band tables
     size_t table = 0;          // doubles of one band table = Le * ldn
-    size_t tables = 0;         // doubles of all of them
+    size_t tables = 0;         // doubles of all of them: n_tables of the model's sweeps
     size_t band = 0;           // doubles of bp_band = n * Le
     size_t ext = 0;            // doubles of gi and go together = 2 (n + 1)
 };
 
 // RH_OK with *P filled, or RH_ERR_ARG with the reason in *why; reads nothing of seq but whether it is NULL.  Sizes are size_t
-// throughout (n = 1e6, L = 1000: 1e9 doubles per table); a size that does not fit is rejected.
-int span_check(const char* seq, int n, int max_span, SpanPlan* P, std::string* why);
+// throughout (n = 1e6, L = 1000: 1e9 doubles per table); a size that does not fit is rejected.  n_tables: the band tables of the
+// model's sweeps (kSpanTables, kSpanCfTables), so that an item is sized, and a batch chunked, by the bytes its model really uses.
+int span_check(const char* seq, int n, int max_span, SpanPlan* P, std::string* why, int n_tables = kSpanTables);
 
 // ---- region accessibility up[i][w] on the same ensemble (rh_span_fold_acc; kernels in mccaskill_span.hip)
 constexpr int kSpanAccMaxW = 64;      // widest region, the range of rh_set_max_w
@@ -105,7 +119,8 @@ struct SpanBatchPlan {
 };
 
 // RH_OK with *B filled, or RH_ERR_ARG with the reason in *why (an item's reason names the item).  budget = 0: kSpanBatchBytes.
-int span_batch_plan(const char* const* seqs, const int* n, int count, int max_span, int max_w, size_t budget, SpanBatchPlan* B, std::string* why);
+int span_batch_plan(const char* const* seqs, const int* n, int count, int max_span, int max_w, size_t budget, SpanBatchPlan* B, std::string* why,
+                    int n_tables = kSpanTables);
 
 // ---- structure constraints (rh_span_fold_constrained, rh_span_fold_batch_constrained): letters a < b may pair only if b - a < L AND
 // allow_pair(a, b, n, ch, P, enc) of constraint_prepass.h holds.  There is no n x n mask: the sweeps test a pair on the packed records

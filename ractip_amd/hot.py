@@ -34,6 +34,7 @@ EXPORTS = [
     "rh_span_fold_batch", "rh_span_batch_layout", "rh_span_batch_item", "rh_span_batch_results", "rh_span_batch_candidates",
     "rh_set_span_batch_bytes", "rh_span_batch_times",
     "rh_span_fold_constrained", "rh_span_fold_batch_constrained",
+    "rh_set_span_contrafold", "rh_get_span_contrafold",
     "rh_debug_vienna_cell", "rh_debug_vienna_value",   # loader inspection (host only; used by the CPU tests of the loader)
 ]
 
@@ -176,6 +177,10 @@ def load_library():
     L.rh_span_fold_constrained.restype = ci
     L.rh_span_fold_batch_constrained.argtypes = [vp, vp, vp, ci, vp, ci, ci]
     L.rh_span_fold_batch_constrained.restype = ci
+    L.rh_set_span_contrafold.argtypes = [vp, ci]
+    L.rh_set_span_contrafold.restype = ci
+    L.rh_get_span_contrafold.argtypes = [vp]
+    L.rh_get_span_contrafold.restype = ci
     L.rh_local_duplex.argtypes = [vp, cp, ci, cp, ci, ci, ci, ci]
     L.rh_local_duplex.restype = ci
     L.rh_local_hp_layout.argtypes = [vp, vp, vp, vp, vp]
@@ -447,9 +452,18 @@ class Context:
         return ms[0], ms[1]
 
     # ---- span-limited folding
+    def set_span_contrafold(self, on):
+        """CONTRAfold model: span_fold and span_fold_batch on this context (off by default, when a CONTRAfold context refuses them;
+        see rh_set_span_contrafold).  Accepted on a Vienna-BL context, where it changes nothing."""
+        self._check(self.L.rh_set_span_contrafold(self.h, 1 if on else 0))
+
+    def get_span_contrafold(self):
+        return bool(self.L.rh_get_span_contrafold(self.h))
+
     def span_fold(self, seq, max_span, max_w=1, constraint=None):
         """The McCaskill ensemble of the whole sequence restricted to pairs (a, b) with b - a < max_span (rh_span_fold_acc; Vienna-BL
-        contexts, 1.8 semantics): one partition function, O(n L) memory.  Returns (bp_band, up, logz): bp_band (n, ld) with
+        contexts, 1.8 semantics, and CONTRAfold contexts after set_span_contrafold(True), there with max_w = 1 and no constraint,
+        pairs of complementary letters): one partition function, O(n L) memory.  Returns (bp_band, up, logz): bp_band (n, ld) with
         bp_band[i, d] = P(i, i + d), 0-based, ld = min(max_span, n); up (n, max_w) with up[i, w] = P(letters i .. i + w unpaired),
         0-based, 0 where the run passes the end (max_w in 1..64; the context's own max_w is not used); log Z of the whole sequence.
         The result is the context's local result (local_results, local_candidates); band_to_tri gives the triangular layout.
@@ -478,7 +492,8 @@ class Context:
         """span_fold of every sequence of `seqs` (ragged lengths) through one set of launches (rh_span_fold_batch): a list of
         (bp_band, up, logz), item k with the bits of span_fold(seqs[k], max_span, max_w) on this context.  The result lives beside the
         local result until the next span_fold_batch (span_batch_results, span_batch_candidates).  Raises for an item for which no
-        scale exponent of the ladder holds, and names it.
+        scale exponent of the ladder holds, and names it.  Contexts as for span_fold: a CONTRAfold context needs
+        set_span_contrafold(True), max_w = 1 and no constraints.
         constraints: one string or None per sequence (rh_span_fold_batch_constrained); item k then has the bits of
         span_fold(seqs[k], max_span, max_w, constraints[k])."""
         enc = [s.encode() for s in seqs]

@@ -32,6 +32,12 @@ the whole-sequence folds (fold_constraint); a matched bracket pair must lie with
 
 --all-records: every record of the file is folded, all of them as ONE batch (Context.span_fold_batch), and the lines above are
 printed for each record in the file's order.  With --use-constraint every record is folded under its own structure line.
+
+  python -m ractip_amd.pipeline --max-span L --contrafold [--all-records] [--threshold T] one.fa
+
+--contrafold with the one-file forms: the same ensemble and output under the CONTRAfold model (a CONTRAfold context with its span
+folds switched on, Context.set_span_contrafold).  The model takes no constraint: with --use-constraint the command exits with a
+message.  With two files --max-span --contrafold still raises (the joint programme on CONTRAfold span folds is the follow-up).
 """
 import sys
 
@@ -278,16 +284,30 @@ def predict(s1, s2, model="vienna", duplex=False, device=0, options=None, ctx=No
             ctx.close()
 
 
-def span_fold(seq, max_span, max_w=1, device=0, ctx=None, structure=None):
+def _span_context(device, model):
+    """a context for the span calls: Vienna-BL, or CONTRAfold with its span folds switched on (Context.set_span_contrafold)"""
+    if model not in ("vienna", "contrafold"):
+        raise ValueError("model %r (\"vienna\" or \"contrafold\")" % (model,))
+    ctx = hot.Context(device=device, model=hot.RH_MODEL_VIENNA_BL if model == "vienna" else hot.RH_MODEL_CONTRAFOLD)
+    if model == "contrafold":
+        ctx.set_span_contrafold(True)
+    return ctx
+
+
+def span_fold(seq, max_span, max_w=1, device=0, ctx=None, structure=None, model="vienna"):
     """Span-limited folding of a whole long sequence (Context.span_fold): dict(n, max_span, bp_band (n, min(max_span, n)) with
     bp_band[i, d] = P(i, i + d), up (n, max_w) with up[i, w] = P(letters i .. i + w unpaired), logZ).  ctx: a Vienna-BL context to
     run on (its local result becomes this one; its max_w setting is not used); by default one is made for the call.
     structure: the sequence's FASTA structure line, used as a constraint after the translation of fold_constraint.
+    model "contrafold": the same ensemble under the CONTRAfold model (pairs of complementary letters), on a CONTRAfold context with
+    its span folds switched on; max_w = 1 only, and structure= raises ValueError: the model takes no constraint.
     predict(max_span=L) runs the joint programme on two of these, without constraints: predict(max_span=, structures=) and the
     two-file --max-span --use-constraint still raise (the open follow-up)."""
+    if model == "contrafold" and structure is not None:
+        raise ValueError("span-limited folding under the CONTRAfold model takes no structure constraint")
     own = ctx is None
     if own:
-        ctx = hot.Context(device=device, model=hot.RH_MODEL_VIENNA_BL)
+        ctx = _span_context(device, model)
     try:
         band, up, logz = ctx.span_fold(seq, max_span, max_w, None if structure is None else fold_constraint(structure, len(seq)))
         return dict(n=len(seq), max_span=max_span, bp_band=band, up=up, logZ=logz)
@@ -296,20 +316,23 @@ def span_fold(seq, max_span, max_w=1, device=0, ctx=None, structure=None):
             ctx.close()
 
 
-def span_fold_batch(seqs, max_span, max_w=1, device=0, ctx=None, structures=None):
+def span_fold_batch(seqs, max_span, max_w=1, device=0, ctx=None, structures=None, model="vienna"):
     """span_fold of several long sequences as one batch (Context.span_fold_batch: the item is a dimension of every launch, the
     lengths may differ): a list with the dict of span_fold for every sequence, bit for bit what span_fold gives on the same context.
     ctx: a Vienna-BL context to run on (its local result stays; the batch result becomes this one).
-    structures: one FASTA structure line or None per sequence, each used as span_fold uses structure=."""
+    structures: one FASTA structure line or None per sequence, each used as span_fold uses structure=.
+    model "contrafold": as for span_fold; structures= raises ValueError."""
     seqs = list(seqs)
     cons = None
+    if model == "contrafold" and structures is not None:
+        raise ValueError("span-limited folding under the CONTRAfold model takes no structure constraints")
     if structures is not None:
         if len(structures) != len(seqs):
             raise ValueError("%d structure lines for %d sequences" % (len(structures), len(seqs)))
         cons = [None if t is None else fold_constraint(t, len(s)) for s, t in zip(seqs, structures)]
     own = ctx is None
     if own:
-        ctx = hot.Context(device=device, model=hot.RH_MODEL_VIENNA_BL)
+        ctx = _span_context(device, model)
     try:
         res = ctx.span_fold_batch(seqs, max_span, max_w, cons)
         return [dict(n=len(s), max_span=max_span, bp_band=band, up=up, logZ=logz) for s, (band, up, logz) in zip(seqs, res)]
@@ -347,7 +370,7 @@ def read_fasta_records_with_structure(path):
     return [(name, seq, structure or "") for name, seq, structure in records]
 
 
-def _main_span_records(path, max_span, threshold, use_constraint=False):
+def _main_span_records(path, max_span, threshold, use_constraint=False, model="vienna"):
     """--all-records: every record of the file folded as one batch; per record what the one-file form prints"""
     cons = None
     if use_constraint:
@@ -358,7 +381,7 @@ def _main_span_records(path, max_span, threshold, use_constraint=False):
         records = read_fasta_records(path)
     if not records:
         raise SystemExit("%s holds no FASTA record" % path)
-    ctx = hot.Context(device=0, model=hot.RH_MODEL_VIENNA_BL)
+    ctx = _span_context(0, model)
     try:
         res = ctx.span_fold_batch([seq for _, seq in records], max_span, 1, cons)
         lists = []
@@ -383,17 +406,20 @@ def _main_span(argv, max_span):
         argv = argv[:k] + argv[k + 2:]
     all_records = "--all-records" in argv
     use_constraint = "--use-constraint" in argv
-    argv = [a for a in argv if a not in ("--all-records", "--use-constraint")]
+    model = "contrafold" if "--contrafold" in argv else "vienna"
+    argv = [a for a in argv if a not in ("--all-records", "--use-constraint", "--contrafold")]
     files = [a for a in argv if not a.startswith("--")]
     if len(files) != 1 or len(files) != len(argv):
-        raise SystemExit("--max-span takes one FASTA file (and --threshold T, --all-records, --use-constraint)")
+        raise SystemExit("--max-span takes one FASTA file (and --threshold T, --all-records, --use-constraint, --contrafold)")
+    if model == "contrafold" and use_constraint:
+        raise SystemExit("--max-span --contrafold takes no --use-constraint: the CONTRAfold model takes no structure constraint")
     if all_records:
-        return _main_span_records(files[0], max_span, threshold, use_constraint)
+        return _main_span_records(files[0], max_span, threshold, use_constraint, model)
     if use_constraint:
         name, seq, structure = read_fasta_with_structure(files[0])
     else:
         (name, seq), structure = read_fasta(files[0]), None
-    ctx = hot.Context(device=0, model=hot.RH_MODEL_VIENNA_BL)
+    ctx = _span_context(0, model)
     try:
         _, _, logz = ctx.span_fold(seq, max_span, 1, None if structure is None else fold_constraint(structure, len(seq)))
         rec, total = ctx.local_candidates(0, threshold, cap=max(1, len(seq)))   # a letter has at most one pair above 0.5 ...

@@ -2,13 +2,14 @@
 same sequences on the same context.
 
   python tools/span_batch_timing.py [--out FILE.json] [--shapes 5000x1,5000x2,5000x8,5000x32,20000x2,20000x8,100000x1,100000x4]
-                                    [--span 200] [--max-w 15] [--repeat 5]
+                                    [--span 200] [--max-w 15] [--repeat 5] [--model vienna|contrafold]
 
 Per shape n x K (K random ACGU sequences of n letters), the median and the range of --repeat runs behind one warm-up run (which
 allocates).  The batch and the loop run interleaved: in every repetition first the batch, then the K single calls.  Wall time of the
 compute calls alone (no fetch); device time of the batch (rh_span_batch_times: sweeps, exterior passes + finish, accessibility
 stage) and of the K single calls (rh_span_times + rh_span_acc_times, summed over the loop); the ratios batch / loop; and whether
-every item of the batch had the bits of its single call."""
+every item of the batch had the bits of its single call.
+--model contrafold: on a CONTRAfold context with its span folds switched on (Context.set_span_contrafold), which takes --max-w 1."""
 import argparse
 import ctypes
 import json
@@ -38,10 +39,17 @@ def main():
     ap.add_argument("--span", type=int, default=200)
     ap.add_argument("--max-w", type=int, default=15)
     ap.add_argument("--repeat", type=int, default=5)
+    ap.add_argument("--model", default="vienna", choices=["vienna", "contrafold"])
     args = ap.parse_args()
     L, W = args.span, args.max_w
     rows = []
-    c = ractip_amd.Context(device=0, model=hot.RH_MODEL_VIENNA_BL)
+    if args.model == "contrafold":
+        if W != 1:
+            ap.error("--model contrafold takes --max-w 1")
+        c = ractip_amd.Context(device=0, model=hot.RH_MODEL_CONTRAFOLD)
+        c.set_span_contrafold(True)
+    else:
+        c = ractip_amd.Context(device=0, model=hot.RH_MODEL_VIENNA_BL)
     for shape in args.shapes.split(","):
         n, K = (int(x) for x in shape.split("x"))
         enc = ["".join(np.random.RandomState(n + 7919 * k).choice(list("ACGU"), n)).encode() for k in range(K)]
@@ -68,7 +76,7 @@ def main():
                     same = same and bool((one[0] == got[0]).all() and (one[1] == got[1]).all() and one[2][0] == got[2])
             runs.append((1e3 * (t1 - t0), 1e3 * loop_wall, sum(batch_dev), sum(loop_dev)) + tuple(batch_dev) + tuple(loop_dev))
         cols = [spread(col) for col in zip(*runs[1:])]
-        row = dict(n=n, K=K, L=L, max_w=W, same_bits=same, batch_wall_ms=cols[0], loop_wall_ms=cols[1], batch_device_ms=cols[2], loop_device_ms=cols[3],
+        row = dict(model=args.model, n=n, K=K, L=L, max_w=W, same_bits=same, batch_wall_ms=cols[0], loop_wall_ms=cols[1], batch_device_ms=cols[2], loop_device_ms=cols[3],
                    wall_ratio=cols[0][0] / cols[1][0], device_ratio=cols[2][0] / cols[3][0],
                    batch_sweeps_ms=cols[4], batch_exterior_finish_ms=cols[5], batch_acc_ms=cols[6],
                    loop_sweeps_ms=cols[7], loop_exterior_finish_ms=cols[8], loop_acc_ms=cols[9])

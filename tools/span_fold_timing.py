@@ -2,6 +2,7 @@
 context: local_fold(W = L, S = 1), which folds n - W + 1 windows of W letters where the span fold fills one band of n x L cells.
 
   python tools/span_fold_timing.py [--out FILE.json] [--n 5000,20000,100000] [--span 200] [--repeat 5] [--no-windows] [--max-w W] [--constraint]
+                                   [--model vienna|contrafold]
 
 Per n, the median and the range of --repeat runs behind one warm-up run (which allocates): wall time of rh_span_fold alone and of
 the fetch of band, up and log Z; device time of the sweeps and of the exterior passes + finish (rh_span_times); the launches of the
@@ -10,7 +11,9 @@ sweeps (2 Le) and the device time per launch that gives; the same for local_fold
 time of the three parts of the accessibility stage (rh_span_acc_times: hairpin part, gap sums, final kernel), and local_fold runs
 on the same context at max_w = W, the route to wide accessibilities that the stage replaces.
 --constraint: also the same sequence under a structure constraint of scattered helices and x runs (rh_span_fold_constrained,
-scattered_constraint below): its wall and device times next to the unconstrained ones, and the ratio of the sweeps."""
+scattered_constraint below): its wall and device times next to the unconstrained ones, and the ratio of the sweeps.
+--model contrafold: the same on a CONTRAfold context with its span folds switched on (Context.set_span_contrafold; --max-w 1 and no
+--constraint there), local_fold(W = L, S = 1) on that same context included."""
 import argparse
 import json
 import os
@@ -63,11 +66,18 @@ def main():
     ap.add_argument("--no-windows", action="store_true")
     ap.add_argument("--max-w", type=int, default=1)
     ap.add_argument("--constraint", action="store_true")
+    ap.add_argument("--model", default="vienna", choices=["vienna", "contrafold"])
     args = ap.parse_args()
     L, W = args.span, args.max_w
     rows = []
-    c = ractip_amd.Context(device=0, model=hot.RH_MODEL_VIENNA_BL)
-    c.set_max_w(W)                     # for local_fold; the span fold takes its widths as an argument
+    if args.model == "contrafold":
+        if W != 1 or args.constraint:
+            ap.error("--model contrafold takes --max-w 1 and no --constraint")
+        c = ractip_amd.Context(device=0, model=hot.RH_MODEL_CONTRAFOLD)
+        c.set_span_contrafold(True)
+    else:
+        c = ractip_amd.Context(device=0, model=hot.RH_MODEL_VIENNA_BL)
+        c.set_max_w(W)                 # for local_fold; the span fold takes its widths as an argument
     for n in [int(x) for x in args.n.split(",")]:
         seq = "".join(np.random.RandomState(n).choice(list("ACGU"), n))
         enc = seq.encode()
@@ -81,7 +91,7 @@ def main():
             runs.append((1e3 * (t1 - t0), 1e3 * (t2 - t1)) + c.span_times() + (c.span_acc_times() if W > 1 else ()))
         call_ms, fetch_ms, sweep_ms, ext_ms = (spread(col) for col in list(zip(*runs[1:]))[:4])
         launches = 2 * min(L, n)
-        row = dict(n=n, L=L, max_w=W, logZ=float(logz[0]), span_call_ms=call_ms, span_fetch_ms=fetch_ms, span_sweeps_ms=sweep_ms, span_exterior_finish_ms=ext_ms,
+        row = dict(model=args.model, n=n, L=L, max_w=W, logZ=float(logz[0]), span_call_ms=call_ms, span_fetch_ms=fetch_ms, span_sweeps_ms=sweep_ms, span_exterior_finish_ms=ext_ms,
                    sweep_launches=launches, sweep_us_per_launch=1e3 * sweep_ms[0] / launches, result_bytes=8 * (band.size + up.size + 1),
                    pairs_above_half=int((band > 0.5).sum()))
         if W > 1:
