@@ -423,9 +423,13 @@ int rh_local_times(rh_ctx* ctx, double ms[2]);
  * Refusals.  RH_ERR_ARG: NULL sequence, n < 1, L < 2, sizes that overflow.  RH_ERR_UNSUPPORTED: CONTRAfold contexts, 2.x-semantics
  * contexts, contexts in RH_MODE_LOG (there is no log-space version).  Both leave the previous local result and the batch in place;
  * rh_last_error names the reason.  Structure constraints: rh_span_fold_constrained below.
- * A band cell that leaves the double range under the context's scale exponent sends the call through the exponent ladder; when no
- * exponent holds it returns RH_ERR_UNSUPPORTED and leaves no local result, as RH_ERR_OOM does (buffers grow only and go with the
- * context).
+ * A band cell that leaves the double range under the context's scale exponent sends the call through the exponent ladder (0.28 per
+ * unit span, then 0.7, 1.8, 0): the closed value of a pair outside (1e-280, 1e280) or not a number, a multiloop sum above 1e280, an
+ * outside value or a posterior above 1e300, an exterior logarithm that is not finite.  A closed value that underflows to exactly 0 is
+ * not tested itself: it times the pair's outside value is the pair's probability, so the outside value passes 1e300 for every pair
+ * with a probability above 5e-24.  When no exponent holds, the call returns RH_ERR_UNSUPPORTED ("no scale exponent of the ladder
+ * ...") and leaves no local result, as RH_ERR_OOM does (buffers grow only and go with the context); everything else the context
+ * holds stays.
  * The CONTRAfold model: rh_set_span_contrafold below; a CONTRAfold context that did not ask is refused. */
 int rh_span_fold(rh_ctx* ctx, const char* seq, int n, int max_span);
 /* Span folds under the CONTRAfold model, opt-in per context (default off: a CONTRAfold context refuses every span call as above).  On
