@@ -440,8 +440,9 @@ int rh_span_fold(rh_ctx* ctx, const char* seq, int n, int max_span);
  * they are complementary and b - a < L; with L >= n it is the ensemble of rh_fold.  Unknown letters are encoded as in the batch path.
  * bp_band, up (width 1, max(0, 1 - sum_j bp(i, j))) and log Z come back through the same fetches, batches and candidates included.
  * The exponent ladder is the CONTRAfold one (0.12 per unit span, then 0.45, 1.5, 0); the context's batch, rh_fold's bits and the batch
- * path's state are untouched.  Still RH_ERR_UNSUPPORTED with the switch on, each leaving the previous result in place: max_w > 1, a
- * constraint that is not NULL (the model takes none), a context in RH_MODE_LOG. */
+ * path's state are untouched.  Still RH_ERR_UNSUPPORTED with the switch on, each leaving the previous result in place: max_w > 1
+ * unless rh_set_region_accessibility is on as well (see rh_span_fold_acc), a constraint that is not NULL (the model takes none), a
+ * context in RH_MODE_LOG. */
 int rh_set_span_contrafold(rh_ctx* ctx, int on);
 int rh_get_span_contrafold(const rh_ctx* ctx);
 /* Measurement aid: device time (ms, HIP event pairs) of the last rh_span_fold: ms[0] the inside and outside sweeps (2 Le launches),
@@ -458,11 +459,21 @@ int rh_span_times(rh_ctx* ctx, double ms[2]);
  * on the band tables behind the outside sweep and clamped to at most 1, as rh_fold does for whole sequences at max_w > 1.  The
  * exterior part is a difference of the exterior logarithms.  The stage runs inside the ladder attempt that kept the band in range;
  * a value that is not finite sends the call to the next exponent.  Every sum has a fixed order: the bits depend on the letters, L,
- * max_w and the context's model only. */
+ * max_w and the context's model only.
+ * The CONTRAfold model.  A context with rh_set_span_contrafold AND rh_set_region_accessibility on answers max_w 1..64 (this call, the
+ * batch, the constrained forms with NULL constraints); with region accessibility off max_w > 1 stays RH_ERR_UNSUPPORTED.  up is
+ * Z(the run's letters forbidden to pair) / Z over the derivations of the span ensemble.  Column 0 has the bits of the max_w = 1 call
+ * (1 - the row sums of the band), as rh_fold keeps it under this model; the columns w >= 1 are the sum of five terms on the band
+ * tables -- the exterior, a hairpin loop, a gap of a loop with one enclosed pair, the leading letters of a multiloop branch, and the
+ * trailing letters of a multiloop by the banded chain of products that counts every derivation -- clamped to at most
+ * 1.  bp_band and log Z have the bits of the max_w = 1 call.  An item then takes four more band tables of scratch. */
 int rh_span_fold_acc(rh_ctx* ctx, const char* seq, int n, int max_span, int max_w);
 /* Measurement aid: device time (ms, HIP event pairs) of the accessibility stage of the last rh_span_fold_acc at max_w > 1: ms[0] the
  * hairpin part (suffix sums and their sums per run), ms[1] the gap sums of the loops with one enclosed pair, ms[2] the final kernel
- * (exterior, gap and multiloop parts).  RH_ERR_ARG where the last span fold ran at width 1. */
+ * (exterior, gap and multiloop parts).  On a CONTRAfold context the split is: ms[0] everything but the multiloop chain (hairpin
+ * sums, gap sums, column 0, the kernel that adds the four direct terms), ms[1] the S build of the chain (one launch per diagonal),
+ * ms[2] the max_w - 1 links of the chain with the kernels that add each width's term.  RH_ERR_ARG where the last span fold ran at
+ * width 1. */
 int rh_span_acc_times(rh_ctx* ctx, double ms[3]);
 /* Span folds in batches: `count` sequences of ragged lengths n[k] through one set of launches, at one max_span and one max_w.
  * Item k is rh_span_fold_acc(ctx, seqs[k], n[k], max_span, max_w): the same ensemble, layouts (ld = min(max_span, n[k]),

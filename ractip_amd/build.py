@@ -13,7 +13,7 @@ import sys
 PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
-HOT_SOURCES = ["rh_api.hip", "staging.hip", "allow_mask.hip", "constraint_prepass.cpp", "batch_request.cpp", "local_windows.cpp", "local_fold.hip", "span_fold.cpp", "span_cons.cpp", "mccaskill_span.hip", "mccaskill_span_cf.hip", "launch_contrafold.hip", "launch_vienna.hip", "launch_duplex.hip", "fallbacks.hip", "compute.hip", "candidates.hip", "pair_index.hip", "pack_results.hip", "mccaskill.hip", "mccaskill_acc.hip", "mccaskill_lin.hip", "mccaskill_far.hip", "mccaskill_strip.hip", "mccaskill_small.hip", "duplex.hip", "duplex_lin.hip", "duplex_vienna.hip", "duplex_vlin.hip", "mccaskill_vienna.hip", "mccaskill_vlin.hip", "param_loader.cpp", "vienna_loader.cpp"]
+HOT_SOURCES = ["rh_api.hip", "staging.hip", "allow_mask.hip", "constraint_prepass.cpp", "batch_request.cpp", "local_windows.cpp", "local_fold.hip", "span_fold.cpp", "span_cons.cpp", "mccaskill_span.hip", "mccaskill_span_cf.hip", "mccaskill_span_cf_acc.hip", "launch_contrafold.hip", "launch_vienna.hip", "launch_duplex.hip", "fallbacks.hip", "compute.hip", "candidates.hip", "pair_index.hip", "pack_results.hip", "mccaskill.hip", "mccaskill_acc.hip", "mccaskill_lin.hip", "mccaskill_far.hip", "mccaskill_strip.hip", "mccaskill_small.hip", "duplex.hip", "duplex_lin.hip", "duplex_vienna.hip", "duplex_vlin.hip", "mccaskill_vienna.hip", "mccaskill_vlin.hip", "param_loader.cpp", "vienna_loader.cpp"]
 HOT_LIB = os.path.join(PKG, "libractip_hot.so")
 LAST_BUILD = {"compiled": [], "reused": [], "linked": False}   # what the last build_hot() did (reported by __graft_entry__.build)
 

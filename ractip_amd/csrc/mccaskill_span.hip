@@ -14,7 +14,8 @@
 // points to the packed per-letter records of its constraint (ConsRec, constraint_prepass.h), and the two sweeps -- the only kernels
 // that decide whether a pair exists -- test a pair on the records of its two letters.
 // rh_set_span_contrafold turns the same calls on for a CONTRAfold context: the launcher runs the sweeps of mccaskill_span_cf.hip between
-// the exterior passes and the finish of this file, over the context's own exponent ladder (lin0, then kRungS).
+// the exterior passes and the finish of this file, over the context's own exponent ladder (lin0, then kRungS); with
+// rh_set_region_accessibility on as well it answers max_w > 1 through the stage of mccaskill_span_cf_acc.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -569,7 +570,7 @@ struct SpanTimes {
 // item.  The items share one hplen (it depends on the exponent only and item k reads the rows below its own Le); item k of `run`
 // gets the flag bad[k], and (*flags)[k] is that flag behind everything that ran for it.  `sum`: the times are added to *T.
 // A CONTRAfold context (`cf`: the model of this attempt, lin0 or a rung) runs the sweeps of mccaskill_span_cf.hip between the same
-// exterior passes and finish, and has no accessibility stage.
+// exterior passes and finish, and the accessibility stage of mccaskill_span_cf_acc.hip.
 int span_attempt(rh_ctx* c, const LinSet* cf, std::vector<SpanArgs>& run, int* bad, const SpanEvents& ev, std::vector<int>* flags, SpanTimes* T, bool sum)
 {
     const VLinModel* M = c->d_vlin;
@@ -625,16 +626,49 @@ int span_attempt(rh_ctx* c, const LinSet* cf, std::vector<SpanArgs>& run, int* b
     for (int k = 0; k < 4; k++) HIP_TRY(c, hipEventElapsedTime(&t[k], ev.e[k], ev.e[k + 1]));
     T->sweeps = (sum ? T->sweeps : 0.0) + (double)t[0] + t[2];
     T->ext = (sum ? T->ext : 0.0) + (double)t[1] + t[3];
-    if (max_w == 1 || cf) return RH_OK;
+    if (max_w == 1) return RH_OK;
     // the accessibility stage for the unflagged items: the hairpin part, the gap sums, the final kernel
     std::vector<SpanArgs> acc;
     for (unsigned k = 0; k < K; k++) if (!(*flags)[k]) acc.push_back(run[k]);
     if (acc.empty()) return RH_OK;
     const unsigned Ka = (unsigned)acc.size();
-    n = 0; ldn = 0;
-    for (const SpanArgs& A : acc) { n = std::max(n, A.n); ldn = std::max(ldn, A.ldn); }
+    n = 0; ldn = 0; Le = 0;
+    for (const SpanArgs& A : acc) { n = std::max(n, A.n); ldn = std::max(ldn, A.ldn); Le = std::max(Le, A.Le); }
     HIP_TRY(c, hipMemcpyAsync(c->d_span_desc.p, acc.data(), sizeof(SpanArgs) * Ka, hipMemcpyHostToDevice, st));   // (the sweeps are done with it)
     const unsigned letters = (unsigned)((n + 255) / 256);
+    if (cf) {
+        // CONTRAfold (mccaskill_span_cf_acc.hip).  The three times: everything but the chain (hairpin sums, gap sums, column 0, the
+        // final kernel); the S build; the links with their closes.
+        const LinModel* Mc = cf->d.as<const LinModel>();
+        const unsigned cols = (unsigned)((ldn + kSpanThreads - 1) / kSpanThreads);
+        HIP_TRY(c, hipEventRecord(ev.e[5], st));
+        hipLaunchKernelGGL(span_cf_acc_hp, dim3(cols, Ka), block, 0, st, items);
+        hipLaunchKernelGGL(span_cf_acc_gaps, dim3((unsigned)((n + 127) / 128), 2 * kMaxSingle, Ka), dim3(128), 0, st, items, Mc);
+        hipLaunchKernelGGL(span_acc_gsuf, dim3(letters, 2, Ka), dim3(256), 0, st, items);
+        hipLaunchKernelGGL(span_cf_acc_col0, dim3((unsigned)n, Ka), dim3(kSpanBlock), 0, st, items);
+        hipLaunchKernelGGL(span_cf_acc_final, dim3(letters, (unsigned)(max_w - 1), Ka), dim3(256), 0, st, items, Mc);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipEventRecord(ev.e[6], st));
+        for (int d = 0; d < Le; d++) hipLaunchKernelGGL(span_cf_acc_sdiag, dim3(cols, Ka), block, 0, st, items, d);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipEventRecord(ev.e[7], st));
+        const unsigned rows = (unsigned)std::min(Le, 65535);
+        for (int j = 1; j < max_w; j++) {   // A_j into the table A_{j-1} did not come from
+            const int src = j == 1 ? (int)CF_FMO : (j % 2 ? (int)CFA_A1 : (int)CFA_A0), dst = j % 2 ? (int)CFA_A0 : (int)CFA_A1;
+            hipLaunchKernelGGL(span_cf_acc_link, dim3(cols, rows, Ka), block, 0, st, items, Mc, src, dst, j == 1 ? 1 : 0);
+            hipLaunchKernelGGL(span_cf_acc_close, dim3(letters, Ka), dim3(256), 0, st, items, j, dst);
+        }
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipEventRecord(ev.e[8], st));
+        HIP_TRY(c, hipMemcpyAsync(flags->data(), bad, sizeof(int) * K, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        for (int k = 0; k < 3; k++) {
+            float ta = 0.f;
+            HIP_TRY(c, hipEventElapsedTime(&ta, ev.e[5 + k], ev.e[6 + k]));
+            T->acc[k] = (sum ? T->acc[k] : 0.0) + (double)ta;
+        }
+        return RH_OK;
+    }
     HIP_TRY(c, hipEventRecord(ev.e[5], st));
     hipLaunchKernelGGL(span_acc_hp, dim3((unsigned)((ldn + kSpanThreads - 1) / kSpanThreads), Ka), block, 0, st, items, M);
     hipLaunchKernelGGL(span_acc_hsum, dim3((unsigned)((n + 3) / 4), Ka), dim3(256), 0, st, items);
@@ -698,8 +732,9 @@ int span_refusals(rh_ctx* c, int max_w, bool has_cons)
 {
     if (c->model == RH_MODEL_CONTRAFOLD && c->span_cf) {   // rh_set_span_contrafold: what the CONTRAfold sweeps do not cover
         if (c->mode == RH_MODE_LOG) return fail(c, RH_ERR_UNSUPPORTED, "span fold: there is no log-space version (the context is in RH_MODE_LOG)");
-        if (max_w > 1)
-            return fail(c, RH_ERR_UNSUPPORTED, "span fold: the CONTRAfold model has no span region accessibility yet (max_w %d: width 1 only)", max_w);
+        if (max_w > 1 && !c->region_acc)
+            return fail(c, RH_ERR_UNSUPPORTED,
+                        "span fold: the CONTRAfold model has no span region accessibility (max_w %d: width 1 only) unless rh_set_region_accessibility is on", max_w);
         if (has_cons) return fail(c, RH_ERR_UNSUPPORTED, "span fold: the CONTRAfold model takes no structure constraint (pass NULL)");
         return RH_OK;
     }
@@ -717,7 +752,11 @@ void span_codes(const rh_ctx* c, const char* seq, int n, uint8_t* codes)
     for (int i = 0; i < n; i++) codes[(size_t)i + 1] = cf ? nuc_code(seq[i]) : vienna_code(seq[i]);
 }
 uint8_t span_no_letter(const rh_ctx* c) { return c->model == RH_MODEL_CONTRAFOLD ? 4 : 0; }
-int span_tables(const rh_ctx* c) { return c->model == RH_MODEL_CONTRAFOLD ? kSpanCfTables : kSpanTables; }
+// the band tables of an item: the sweeps' and, under the CONTRAfold model at widths above one, the accessibility stage's own
+int span_tables(const rh_ctx* c, int max_w)
+{
+    return c->model == RH_MODEL_CONTRAFOLD ? span_cf_tables(max_w) : kSpanTables;
+}
 
 // rh_span_fold (max_w = 1), rh_span_fold_acc and rh_span_fold_constrained (cons, which may be NULL): a batch of one whose result is
 // the context's local result
@@ -729,7 +768,7 @@ int span_run(rh_ctx* c, const char* seq, int n, const char* cons, int max_span, 
     std::string why;
     std::vector<ConsRec> rec;   // empty: nothing restricts the band
     bool restricts = false;
-    if (int rc = span_check(seq, n, max_span, &P, &why, span_tables(c))) return fail(c, rc, "%s", why.c_str());
+    if (int rc = span_check(seq, n, max_span, &P, &why, span_tables(c, max_w))) return fail(c, rc, "%s", why.c_str());
     if (int rc = span_acc_check(P, max_w, &Q, &why)) return fail(c, rc, "%s", why.c_str());
     if (int rc = span_cons_records(seq, n, cons, max_span, &rec, &restricts, &why)) return fail(c, rc, "%s", why.c_str());
     if (int rc = span_refusals(c, max_w, cons != nullptr)) return rc;
@@ -783,7 +822,7 @@ int span_batch_run(rh_ctx* c, const char* const* seqs, const int* n, int count, 
     SpanBatchPlan B;
     std::string why;
     std::vector<std::vector<ConsRec>> recs;   // per item; empty: nothing restricts its band
-    if (int rc = span_batch_plan(seqs, n, count, max_span, max_w, c->sb_bytes, &B, &why, span_tables(c))) return fail(c, rc, "%s", why.c_str());
+    if (int rc = span_batch_plan(seqs, n, count, max_span, max_w, c->sb_bytes, &B, &why, span_tables(c, max_w))) return fail(c, rc, "%s", why.c_str());
     if (int rc = span_cons_batch(seqs, n, count, cons, max_span, &recs, &why)) return fail(c, rc, "%s", why.c_str());
     bool has_cons = false;
     for (int k = 0; cons && k < count; k++) has_cons = has_cons || cons[k] != nullptr;

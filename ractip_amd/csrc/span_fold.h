@@ -36,6 +36,10 @@
 // which is what the CONTRAfold inside sweep writes where the passes read (kSpanExtTable), so the passes run unchanged on gi = log F5i',
 // go = log F5o'.  log Z = gi[n] + n eu.  F5i[i-1] F5o[j+1] / Z = exp(gi[i-1] + go[j+1] - gi[n]) exp(-eu (d + 2)): the exterior term of
 // FCo^(i, d) is span_ext_outer times the same ext_w(d).
+// Region accessibility under the CONTRAfold model (max_w > 1 with rh_set_region_accessibility on; kernels in
+// mccaskill_span_cf_acc.hip): kSpanCfAccTables more band tables behind the eleven -- the hairpin suffix sums, the chain's S and its
+// two vectors -- so a call is sized with span_cf_tables(max_w) tables.  The exterior term of a run a..b is
+// exp(gi[a-1] + go[b] - gi[n]): F5i[a-1] exp(eu len) F5o[b] / Z with the three exp(eu ..) factors of F5' adding up to exp(eu n).
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -58,6 +62,8 @@ constexpr int kSpanInside = 7;        // band tables of the inside sweep: FC FCX
 constexpr int kSpanOutside = 6;       // ... of the outside sweep: FCO FCOX FCOB FMSO FM1O FM2O
 constexpr int kSpanTables = kSpanInside + kSpanOutside;   // band tables of an item under the Vienna-BL model
 constexpr int kSpanCfTables = 11;     // ... under the CONTRAfold model: FC FCX FCM FCA FM1 FM, FCO FCOX FMO FM1O FM2O
+constexpr int kSpanCfAccTables = 4;   // ... more for its region accessibility (max_w > 1): hairpin sums R, the chain's S, two A
+constexpr int span_cf_tables(int max_w) { return max_w > 1 ? kSpanCfTables + kSpanCfAccTables : kSpanCfTables; }   // of a call, for span_check
 constexpr int kSpanLine = 16;         // doubles per 128-byte line
 
 struct SpanPlan {

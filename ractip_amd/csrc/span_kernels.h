@@ -42,6 +42,10 @@ constexpr int kSpanExtTable = 3;
 // exterior's own factor of the row.
 enum SpanCfTable { CF_FC = 0, CF_FCX, CF_FCM, CF_FCA, CF_FM1, CF_FM, CF_FCO, CF_FCOX, CF_FMO, CF_FM1O, CF_FM2O, CF_COUNT };
 static_assert(CF_FCA == kSpanExtTable && CF_COUNT == host::kSpanCfTables);
+// ... and, behind them, the band tables of the CONTRAfold accessibility stage (max_w > 1): the hairpin suffix sums R, the chain's
+// S and its two vectors A in turn.
+enum SpanCfAccTable { CFA_R = CF_COUNT, CFA_S, CFA_A0, CFA_A1, CFA_END };
+static_assert(CFA_END == host::kSpanCfTables + host::kSpanCfAccTables);
 
 namespace {
 
@@ -76,5 +80,21 @@ __global__ void span_cf_inside_diag(const SpanArgs* __restrict__ items, const Li
 __global__ void span_cf_outside_diag(const SpanArgs* __restrict__ items, const LinModel* __restrict__ M, int d, double ext_w);
 // behind span_finish: log Z = gi[n] + n external_unpaired.  One thread per item.
 __global__ void span_cf_logz(const SpanArgs* __restrict__ items, int count, double eu);
+
+// ---- mccaskill_span_cf_acc.hip: the CONTRAfold accessibility stage (max_w > 1) on finished band tables; M is the attempt's model.
+// grid (columns / kSpanThreads, items): the hairpin suffix sums R
+__global__ void span_cf_acc_hp(const SpanArgs* __restrict__ items);
+// grid (letters / 128, 2 * kMaxSingle, items): the gap sums GL, GR of the loops with one enclosed pair (then span_acc_gsuf)
+__global__ void span_cf_acc_gaps(const SpanArgs* __restrict__ items, const LinModel* __restrict__ M);
+// grid (n, items), one wavefront: column 0 = 1 - the row sums of the band
+__global__ void span_cf_acc_col0(const SpanArgs* __restrict__ items);
+// grid (letters / 256, max_w - 1, items): exterior, hairpin, one enclosed pair, leading multiloop letters of widths 2..max_w
+__global__ void span_cf_acc_final(const SpanArgs* __restrict__ items, const LinModel* __restrict__ M);
+// one launch per diagonal d, grid (columns / kSpanThreads, items): S of the chain
+__global__ void span_cf_acc_sdiag(const SpanArgs* __restrict__ items, int d);
+// grid (columns / kSpanThreads, rows, items): table dst_t = w_mu x table src_t x S (first: src_t is FMO, the factor w_mu^2)
+__global__ void span_cf_acc_link(const SpanArgs* __restrict__ items, const LinModel* __restrict__ M, int src_t, int dst_t, int first);
+// grid (letters / 256, items): adds the chain's term of width j + 1 from table src_t = A_j to column j, flags and clamps it
+__global__ void span_cf_acc_close(const SpanArgs* __restrict__ items, int j, int src_t);
 
 }  // namespace rh

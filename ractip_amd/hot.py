@@ -462,8 +462,8 @@ class Context:
 
     def span_fold(self, seq, max_span, max_w=1, constraint=None):
         """The McCaskill ensemble of the whole sequence restricted to pairs (a, b) with b - a < max_span (rh_span_fold_acc; Vienna-BL
-        contexts, 1.8 semantics, and CONTRAfold contexts after set_span_contrafold(True), there with max_w = 1 and no constraint,
-        pairs of complementary letters): one partition function, O(n L) memory.  Returns (bp_band, up, logz): bp_band (n, ld) with
+        contexts, 1.8 semantics, and CONTRAfold contexts after set_span_contrafold(True), there without a constraint, pairs of
+        complementary letters, and max_w > 1 only after set_region_accessibility(True)): one partition function, O(n L) memory.  Returns (bp_band, up, logz): bp_band (n, ld) with
         bp_band[i, d] = P(i, i + d), 0-based, ld = min(max_span, n); up (n, max_w) with up[i, w] = P(letters i .. i + w unpaired),
         0-based, 0 where the run passes the end (max_w in 1..64; the context's own max_w is not used); log Z of the whole sequence.
         The result is the context's local result (local_results, local_candidates); band_to_tri gives the triangular layout.
@@ -483,7 +483,8 @@ class Context:
         return ms[0], ms[1]
 
     def span_acc_times(self):
-        """Device time (ms) of the accessibility stage of the last span_fold at max_w > 1: (hairpin part, gap sums, final kernel)."""
+        """Device time (ms) of the accessibility stage of the last span_fold at max_w > 1: (hairpin part, gap sums, final kernel);
+        on a CONTRAfold context (everything but the multiloop chain, the chain's S build, its links and closes)."""
         ms = (ctypes.c_double * 3)()
         self._check(self.L.rh_span_acc_times(self.h, ms))
         return ms[0], ms[1], ms[2]
@@ -493,7 +494,7 @@ class Context:
         (bp_band, up, logz), item k with the bits of span_fold(seqs[k], max_span, max_w) on this context.  The result lives beside the
         local result until the next span_fold_batch (span_batch_results, span_batch_candidates).  Raises for an item for which no
         scale exponent of the ladder holds, and names it.  Contexts as for span_fold: a CONTRAfold context needs
-        set_span_contrafold(True), max_w = 1 and no constraints.
+        set_span_contrafold(True), no constraints and, for max_w > 1, set_region_accessibility(True).
         constraints: one string or None per sequence (rh_span_fold_batch_constrained); item k then has the bits of
         span_fold(seqs[k], max_span, max_w, constraints[k])."""
         enc = [s.encode() for s in seqs]

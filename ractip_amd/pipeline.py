@@ -37,7 +37,14 @@ printed for each record in the file's order.  With --use-constraint every record
 
 --contrafold with the one-file forms: the same ensemble and output under the CONTRAfold model (a CONTRAfold context with its span
 folds switched on, Context.set_span_contrafold).  The model takes no constraint: with --use-constraint the command exits with a
-message.  With two files --max-span --contrafold still raises (the joint programme on CONTRAfold span folds is the follow-up).
+message.
+
+  python -m ractip_amd.pipeline --contrafold --accessibility [--max-span L [--window W [--step S] --local-hp | --local-hp-both]] a.fa b.fa
+
+--accessibility (two files, with --contrafold): predict(..., accessibility=True) -- the CONTRAfold model's region accessibility
+up[i][w], widths 1..max_w, goes into the joint programme.  With --max-span L, bp and up of both molecules come from span folds under
+the CONTRAfold model (one batch of two on a context with its span folds and region accessibility switched on), hp from the CONTRAfold
+pair path or the window averages.  Without --accessibility, two files with --max-span --contrafold raise as before.
 """
 import sys
 
@@ -199,10 +206,16 @@ def _predict_local(ctx, s1, s2, model, duplex, opt, default_options, rip_path, a
     return ilp.solve(s1, s2, bp[0], bp[1], hp, None, None, ilp.Options(min_w=0) if default_options else opt)
 
 
-def _predict_span(ctx, s1, s2, duplex, opt, rip_path, max_span, window, step, local_hp, local_hp_both):
+def _predict_span(ctx, s1, s2, duplex, opt, rip_path, max_span, window, step, local_hp, local_hp_both, model="vienna"):
     """predict with bp and up of both molecules from span folds at the programme's max_w; hp from the pair path, or from local_duplex
-    (the longer molecule windowed, s2 on a tie) / local_duplex2, fetched before the span folds replace the local result"""
-    _set_up(ctx, "vienna", opt, duplex, False)
+    (the longer molecule windowed, s2 on a tie) / local_duplex2, fetched before the span folds replace the local result.
+    model "contrafold": hp from the CONTRAfold pair path (width 1: the span batch brings its own widths), the span folds with the
+    context's span folds and region accessibility switched on"""
+    if model == "vienna":
+        _set_up(ctx, "vienna", opt, duplex, False)
+    else:
+        ctx.set_span_contrafold(True)
+        ctx.set_region_accessibility(True)
     if local_hp_both:
         hp = ctx.local_duplex2(s1, s2, window, step)[0]
     elif local_hp:
@@ -235,7 +248,10 @@ def predict(s1, s2, model="vienna", duplex=False, device=0, options=None, ctx=No
     "vienna" only, no structure constraints): bp and up[i][w], widths 1..options.max_w, of both molecules come from span-limited
     folds (Context.span_fold: one ensemble of each whole molecule with pairs within L letters) instead; hp comes from the pair path,
     or with window= and local_hp / local_hp_both from the window averages (a window alone has nothing to do here and is refused).
-    With L no smaller than either molecule the ensembles, and so the structures, are those of the whole-sequence folds."""
+    With L no smaller than either molecule the ensembles, and so the structures, are those of the whole-sequence folds.
+    max_span=L with model "contrafold" needs accessibility=True (without it the call raises): hp comes from the CONTRAfold pair path
+    (or the window averages), bp and up[i][w] of both molecules from one span batch of two on the context with its span folds and
+    region accessibility switched on."""
     if local_hp_both and window is None:
         raise ValueError("local_hp_both needs a window")
     if local_hp_both and local_hp:
@@ -246,8 +262,9 @@ def predict(s1, s2, model="vienna", duplex=False, device=0, options=None, ctx=No
         raise ValueError("structure constraints apply to the default (Vienna-BL) path only")
     if structures is not None and window is not None:
         raise ValueError("local folding takes no structure constraints")
-    if max_span is not None and model != "vienna":
-        raise ValueError("span-limited folding runs on the default (Vienna-BL) path only")
+    if max_span is not None and model != "vienna" and not accessibility:
+        raise ValueError("span-limited folding runs on the default (Vienna-BL) path only, or under the CONTRAfold model with accessibility=True "
+                         "(the joint programme takes up[i][w] of the span folds)")
     if max_span is not None and structures is not None:
         raise ValueError("span-limited folding takes no structure constraints")
     if max_span is not None and window is not None and not (local_hp or local_hp_both):
@@ -258,7 +275,7 @@ def predict(s1, s2, model="vienna", duplex=False, device=0, options=None, ctx=No
     try:
         opt = options or ilp.Options()
         if max_span is not None:
-            return _predict_span(ctx, s1, s2, duplex, opt, rip_path, max_span, window, step, local_hp, local_hp_both)
+            return _predict_span(ctx, s1, s2, duplex, opt, rip_path, max_span, window, step, local_hp, local_hp_both, model)
         if window is not None:
             return _predict_local(ctx, s1, s2, model, duplex, opt, options is None, rip_path, accessibility, window, step, local_hp, local_hp_both)
         if model == "vienna":
@@ -284,13 +301,16 @@ def predict(s1, s2, model="vienna", duplex=False, device=0, options=None, ctx=No
             ctx.close()
 
 
-def _span_context(device, model):
-    """a context for the span calls: Vienna-BL, or CONTRAfold with its span folds switched on (Context.set_span_contrafold)"""
+def _span_context(device, model, max_w=1):
+    """a context for the span calls: Vienna-BL, or CONTRAfold with its span folds switched on (Context.set_span_contrafold) and, for
+    widths above one, its region accessibility (Context.set_region_accessibility)"""
     if model not in ("vienna", "contrafold"):
         raise ValueError("model %r (\"vienna\" or \"contrafold\")" % (model,))
     ctx = hot.Context(device=device, model=hot.RH_MODEL_VIENNA_BL if model == "vienna" else hot.RH_MODEL_CONTRAFOLD)
     if model == "contrafold":
         ctx.set_span_contrafold(True)
+        if max_w > 1:
+            ctx.set_region_accessibility(True)
     return ctx
 
 
@@ -300,14 +320,15 @@ def span_fold(seq, max_span, max_w=1, device=0, ctx=None, structure=None, model=
     run on (its local result becomes this one; its max_w setting is not used); by default one is made for the call.
     structure: the sequence's FASTA structure line, used as a constraint after the translation of fold_constraint.
     model "contrafold": the same ensemble under the CONTRAfold model (pairs of complementary letters), on a CONTRAfold context with
-    its span folds switched on; max_w = 1 only, and structure= raises ValueError: the model takes no constraint.
+    its span folds switched on and, for max_w > 1, its region accessibility too; structure= raises ValueError: the model takes no
+    constraint.
     predict(max_span=L) runs the joint programme on two of these, without constraints: predict(max_span=, structures=) and the
     two-file --max-span --use-constraint still raise (the open follow-up)."""
     if model == "contrafold" and structure is not None:
         raise ValueError("span-limited folding under the CONTRAfold model takes no structure constraint")
     own = ctx is None
     if own:
-        ctx = _span_context(device, model)
+        ctx = _span_context(device, model, max_w)
     try:
         band, up, logz = ctx.span_fold(seq, max_span, max_w, None if structure is None else fold_constraint(structure, len(seq)))
         return dict(n=len(seq), max_span=max_span, bp_band=band, up=up, logZ=logz)
@@ -332,7 +353,7 @@ def span_fold_batch(seqs, max_span, max_w=1, device=0, ctx=None, structures=None
         cons = [None if t is None else fold_constraint(t, len(s)) for s, t in zip(seqs, structures)]
     own = ctx is None
     if own:
-        ctx = _span_context(device, model)
+        ctx = _span_context(device, model, max_w)
     try:
         res = ctx.span_fold_batch(seqs, max_span, max_w, cons)
         return [dict(n=len(s), max_span=max_span, bp_band=band, up=up, logZ=logz) for s, (band, up, logz) in zip(seqs, res)]
@@ -582,7 +603,7 @@ def main(argv):
     structures = (t1, t2) if "--use-constraint" in flags else None
     r1, r2, _ = predict(s1, s2, model="contrafold" if "--contrafold" in flags else "vienna", duplex="--duplex" in flags, rip_path=rip_path,
                         structures=structures, window=window, step=step, local_hp="--local-hp" in flags,
-                        local_hp_both="--local-hp-both" in flags, max_span=max_span)
+                        local_hp_both="--local-hp-both" in flags, max_span=max_span, accessibility="--accessibility" in flags)
     print(">%s\n%s\n%s\n>%s\n%s\n%s" % (n1, s1, r1, n2, s2, r2))   # src/ractip.cpp:1607-1610
 
 

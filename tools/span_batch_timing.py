@@ -9,7 +9,8 @@ allocates).  The batch and the loop run interleaved: in every repetition first t
 compute calls alone (no fetch); device time of the batch (rh_span_batch_times: sweeps, exterior passes + finish, accessibility
 stage) and of the K single calls (rh_span_times + rh_span_acc_times, summed over the loop); the ratios batch / loop; and whether
 every item of the batch had the bits of its single call.
---model contrafold: on a CONTRAfold context with its span folds switched on (Context.set_span_contrafold), which takes --max-w 1."""
+--model contrafold: on a CONTRAfold context with its span folds switched on (Context.set_span_contrafold) and, for
+--max-w above 1, its region accessibility (Context.set_region_accessibility)."""
 import argparse
 import ctypes
 import json
@@ -44,10 +45,10 @@ def main():
     L, W = args.span, args.max_w
     rows = []
     if args.model == "contrafold":
-        if W != 1:
-            ap.error("--model contrafold takes --max-w 1")
         c = ractip_amd.Context(device=0, model=hot.RH_MODEL_CONTRAFOLD)
         c.set_span_contrafold(True)
+        if W > 1:
+            c.set_region_accessibility(True)
     else:
         c = ractip_amd.Context(device=0, model=hot.RH_MODEL_VIENNA_BL)
     for shape in args.shapes.split(","):

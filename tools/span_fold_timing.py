@@ -2,7 +2,7 @@
 context: local_fold(W = L, S = 1), which folds n - W + 1 windows of W letters where the span fold fills one band of n x L cells.
 
   python tools/span_fold_timing.py [--out FILE.json] [--n 5000,20000,100000] [--span 200] [--repeat 5] [--no-windows] [--max-w W] [--constraint]
-                                   [--model vienna|contrafold]
+                                   [--model vienna|contrafold] [--window-fraction F]
 
 Per n, the median and the range of --repeat runs behind one warm-up run (which allocates): wall time of rh_span_fold alone and of
 the fetch of band, up and log Z; device time of the sweeps and of the exterior passes + finish (rh_span_times); the launches of the
@@ -12,8 +12,11 @@ time of the three parts of the accessibility stage (rh_span_acc_times: hairpin p
 on the same context at max_w = W, the route to wide accessibilities that the stage replaces.
 --constraint: also the same sequence under a structure constraint of scattered helices and x runs (rh_span_fold_constrained,
 scattered_constraint below): its wall and device times next to the unconstrained ones, and the ratio of the sweeps.
---model contrafold: the same on a CONTRAfold context with its span folds switched on (Context.set_span_contrafold; --max-w 1 and no
---constraint there), local_fold(W = L, S = 1) on that same context included."""
+--model contrafold: the same on a CONTRAfold context with its span folds switched on (Context.set_span_contrafold; no --constraint
+there) and, for --max-w above 1, its region accessibility (Context.set_region_accessibility), local_fold(W = L, S = 1) on that same
+context included.  The three parts of the stage are then: everything but the multiloop chain, the chain's S build, its links and
+closes (the JSON keys stay acc_hairpin_ms, acc_gaps_ms, acc_final_ms).
+--window-fraction F (default 1): local_fold runs on the first F n letters only and its times are scaled by 1 / F (stated in the row)."""
 import argparse
 import json
 import os
@@ -67,14 +70,18 @@ def main():
     ap.add_argument("--max-w", type=int, default=1)
     ap.add_argument("--constraint", action="store_true")
     ap.add_argument("--model", default="vienna", choices=["vienna", "contrafold"])
+    ap.add_argument("--window-fraction", type=float, default=1.0)
     args = ap.parse_args()
     L, W = args.span, args.max_w
     rows = []
     if args.model == "contrafold":
-        if W != 1 or args.constraint:
-            ap.error("--model contrafold takes --max-w 1 and no --constraint")
+        if args.constraint:
+            ap.error("--model contrafold takes no --constraint")
         c = ractip_amd.Context(device=0, model=hot.RH_MODEL_CONTRAFOLD)
         c.set_span_contrafold(True)
+        if W > 1:
+            c.set_region_accessibility(True)
+            c.set_max_w(W)             # for local_fold, as below
     else:
         c = ractip_amd.Context(device=0, model=hot.RH_MODEL_VIENNA_BL)
         c.set_max_w(W)                 # for local_fold; the span fold takes its widths as an argument
@@ -114,14 +121,18 @@ def main():
                 row.update(cons_acc_ms=[sum(x) for x in zip(*cols[3:6])])
         if not args.no_windows:
             runs = []
+            frac = args.window_fraction
+            cut = seq if frac >= 1.0 else seq[:max(L, int(n * frac))]
+            scale = (n - L + 1) / max(1, len(cut) - L + 1)     # windows of the whole sequence per window folded
             for _ in range(1 + args.repeat):
                 t0 = time.perf_counter()
-                wband, wup, wlogz, starts = c.local_fold(seq, L, 1)
-                runs.append((1e3 * (time.perf_counter() - t0),) + c.local_times())
+                wband, wup, wlogz, starts = c.local_fold(cut, L, 1)
+                runs.append(tuple(scale * t for t in (1e3 * (time.perf_counter() - t0),) + c.local_times()))
             wall_ms, fold_ms, acc_ms = (spread(col) for col in zip(*runs[1:]))
-            row.update(windows=len(starts), window_wall_ms=wall_ms, window_folds_ms=fold_ms, window_accumulate_ms=acc_ms,
-                       window_over_span_device=(fold_ms[0] + acc_ms[0]) / (sweep_ms[0] + ext_ms[0] + (hp_ms[0] + gap_ms[0] + final_ms[0] if W > 1 else 0.0)),
-                       max_abs_band_difference=float(np.abs(wband - band).max()))
+            row.update(windows=len(starts), window_scale=scale, window_wall_ms=wall_ms, window_folds_ms=fold_ms, window_accumulate_ms=acc_ms,
+                       window_over_span_device=(fold_ms[0] + acc_ms[0]) / (sweep_ms[0] + ext_ms[0] + (hp_ms[0] + gap_ms[0] + final_ms[0] if W > 1 else 0.0)))
+            if frac >= 1.0:
+                row.update(max_abs_band_difference=float(np.abs(wband - band).max()))
         rows.append(row)
         print(json.dumps(row), flush=True)
     c.close()
